@@ -1,6 +1,6 @@
 """bench.py -- GP log-marginal-likelihood evaluations per second (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--n 32768] [--d 8]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--n 32768] [--d 8] [--full] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path over one batch of synthetic input: one evaluation of
 theta -> log p(y | X, theta) (kernel-matrix build + Cholesky + log|K| + quadratic form) at
@@ -14,8 +14,14 @@ collective ("weak" scaling); torch.distributed (RCCL) is used only for the timin
 max-over-ranks reduction.
 
 One JSON line on rank 0, with `roofline` (dominant kernel = trailing SYRK on fp64 MFMA, timed
-with HIP events on the library's own stream, inside the timed region) and `cpu_baseline`
-(the CPU oracle = LU restatement of the reference algorithm, bounded sample, rank 0 at N=1 only).
+with HIP events on the library's own stream, inside the timed region).  A plain run does only what
+that line needs: set-up, warm-up, the timed steps, the line.  `--full` adds everything measured
+beside the headline, each outside the timed region: `roofline_syrk_alone`, the live PMC passes and
+clock probes, the store ceiling, `other_configs`, `cpu_baseline` (the CPU oracle = LU restatement
+of the reference algorithm, rank 0 at N=1 only) and, with N>1, the `strong` series.
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller (rank 0) as
+DIR/loglik.npy and DIR/info.npy (float64, shape (1,)); the inputs depend only on the arguments.
 """
 from __future__ import annotations
 
@@ -47,6 +53,13 @@ def _roof(cls: dict, peak: float, unit: str, what: str) -> dict:
     return {"kernel": what, "bound": "mfma" if unit == "TFLOP/s" else "hbm", "achieved": ach, "peak": peak, "unit": unit,
             "frac": ach / peak, "launches": int(cls["launches"]), "avg_launch_ms": cls["ms"] / cls["launches"],
             "algorithmic_per_launch": work / cls["launches"]}
+
+
+def dump_outputs(dirname: str, ll: float, info: int) -> None:
+    """What one evaluation hands its caller -- the log-likelihood and the status -- as float64 .npy files in `dirname`."""
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "loglik.npy"), np.array([ll], dtype=np.float64))
+    np.save(os.path.join(dirname, "info.npy"), np.array([info], dtype=np.float64))
 
 
 def cpu_baseline(n_full: int, d: int, max_full_s: float = 600.0) -> dict:
@@ -613,6 +626,12 @@ def main() -> None:
                          "the C ABI (gphip_create_rank), strong scaling.  cholesky-torch: the same schedule driven by "
                          "the Python harness (dist_cholesky.py, torch.distributed broadcasts).")
     ap.add_argument("--supertile", type=int, default=0, help="experiment: XCD-private 8x8 super-tile order")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline (outside the timed region): "
+                                                        "roofline_syrk_alone, live PMC passes and clock probes, store ceiling, "
+                                                        "other_configs, cpu_baseline and, with N>1, the strong-scaling series; "
+                                                        "the --no-* options below leave parts of it out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's results (rank 0) to "
+                                                                        "DIR/loglik.npy and DIR/info.npy, float64")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-alone", action="store_true", help="skip the extra look-ahead-off evaluation behind roofline_syrk_alone "
                                                             "(profiling runs: keeps the rocprof launch statistics those of the timed schedule)")
@@ -629,6 +648,9 @@ def main() -> None:
     ap.add_argument("--no-strong", action="store_true", help="N>1, mode theta: skip the short strong-scaling series (ONE "
                                                              "factorisation sharded over all ranks) printed as the `strong` sub-record")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    extras = args.full and not args.no_extras
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -726,11 +748,13 @@ def main() -> None:
     bad = [v for v in vals if v[1] != 0 or not np.isfinite(v[0])]
     if bad:
         raise SystemExit(f"bench: evaluation failed: {bad[:3]}")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *vals[-1])
     # Outside the timed region, rank 0 at N=1: the SAME kernel with the chip to itself.  In the timed region the
     # trailing SYRK shares the CUs with the look-ahead stream (LA update + potrf + panel solves of the next panel), so
     # its event time there includes that contention; one extra evaluation with look-ahead off times it alone.
     alone = None
-    if world == 1 and not sharded and not args.no_alone:
+    if args.full and world == 1 and not sharded and not args.no_alone:
         h.set_option("lookahead", 0)
         h.reset_profile()
         evaluate(thetas[0])
@@ -784,7 +808,7 @@ def main() -> None:
     # through gphip_create_rank).  Outside the timed region of the headline; reported as the `strong` sub-record.
     strong = None
     strong_failed = False
-    if dist is not None and not sharded and not args.no_strong:
+    if args.full and dist is not None and not sharded and not args.no_strong:
         # Watchdog: this is the only place where the bench waits inside RCCL collectives of the library (real multi-rank
         # RCCL has only ever been exercised here).  If one does not return, the headline measured above must not be lost:
         # after --strong-timeout seconds rank 0 prints the record with the failure noted (`strong.error`) and every rank leaves --
@@ -955,7 +979,7 @@ def main() -> None:
 
     if rank == 0:
         out = record(strong, alone)
-        if world > 1 and not sharded:
+        if args.full and world > 1 and not sharded:
             # the split north_star names, next to the weak (theta-sharded) `value`: top-level so that a reader of the line
             # does not mistake the by-construction weak number for it
             ok = strong is not None and "error" not in strong
@@ -967,7 +991,7 @@ def main() -> None:
             out["strong_best_variant"] = bv
             out["strong_best_speedup"] = (strong["variants"][bv]["speedup_vs_one_gpu_weak_step"] if ok and bv in strong.get("variants", {})
                                           else out["strong_speedup"])
-        if world == 1 and not args.no_extras and not args.no_live_pmc and args.mode == "theta":
+        if world == 1 and extras and not args.no_live_pmc and args.mode == "theta":
             live = live_pmc_traffic(n, d, local_rank)
             if live is not None:
                 committed = out["roofline"].get("traffic")
@@ -979,7 +1003,7 @@ def main() -> None:
                     f"measured in this run: two child processes of this bench (bench.py --pmc-probe, 2 evaluations each) under "
                     f"rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE, {live['launches']} launches averaged, {live['seconds']} s "
                     f"outside the timed region; committed profiles/ summary says {committed}")
-        if world == 1 and not args.no_extras and out.get("roofline_kbuild"):
+        if world == 1 and extras and out.get("roofline_kbuild"):
             # The build is a pure streaming WRITE of 4.3 GB: what the same box does with the plainest possible store stream of
             # the same size (the runtime's own fill kernel behind Tensor.zero_()), measured here with HIP events, is the
             # ceiling it runs against on THIS box -- the 8 TB/s of `peak` is the read-side headline figure.
@@ -1000,7 +1024,7 @@ def main() -> None:
                     "kbuild_frac_of_store_ceiling": out["roofline_kbuild"]["achieved"] / gbs}
             except Exception as exc:                                # never let an extra break the headline
                 out["roofline_kbuild"]["store_ceiling"] = {"error": repr(exc)}
-        if world == 1 and not args.no_extras and not args.no_live_pmc and args.mode == "theta" and out.get("roofline_kbuild"):
+        if world == 1 and extras and not args.no_live_pmc and args.mode == "theta" and out.get("roofline_kbuild"):
             clk = live_kbuild_clock(n, d, local_rank)
             if clk is not None:
                 syc = clk.pop("syrk", None)
@@ -1018,7 +1042,7 @@ def main() -> None:
                     if out.get("roofline_syrk_alone"):
                         syc["syrk_alone_frac_at_clock"] = out["roofline_syrk_alone"]["achieved"] / pk
                     out["roofline"]["clock_probe"] = syc
-        if world == 1 and not args.no_extras:
+        if world == 1 and extras:
             h.close()                                           # free the 8.7 GB workspace first
             out["other_configs"] = other_configs(local_rank)
             if not args.no_live_pmc:
@@ -1026,7 +1050,7 @@ def main() -> None:
                 for nm, v in (clocks or {}).items():
                     if nm in out["other_configs"]:
                         out["other_configs"][nm]["clock_probe"] = v
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(n, d)
         print(json.dumps(out), flush=True)
     h.close()

@@ -9,7 +9,7 @@ for name in names:
     env = dict(os.environ)
     if name != "default":
         env["GPHIP_LIB"] = os.path.join(ROOT, "bayesianinference_amd", "lib", "variants", f"libgphip_{name}.so")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "8", "--warmup", "2", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "8", "--warmup", "2", "--full", "--no-cpu-baseline"]
     if not extras:
         cmd.append("--no-extras")
     r = subprocess.run(cmd, env=env, capture_output=True, text=True)

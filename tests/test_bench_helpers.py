@@ -51,3 +51,11 @@ def test_bench_argument_names_survive_torchrun_parser():
     for opt in ours - {"--n", "--d"}:           # (--n / --d stay for direct use; under torchrun pass --npoints / --dim)
         assert not any(t.startswith(opt) and t != opt for t in torchrun), opt
     assert "--npoints" in ours and "--dim" in ours
+
+
+def test_dump_outputs_writes_float64_arrays(tmp_path):
+    import numpy as np
+    _bench().dump_outputs(str(tmp_path / "out"), -1234.5678901234567, 0)
+    ll, info = np.load(tmp_path / "out" / "loglik.npy"), np.load(tmp_path / "out" / "info.npy")
+    assert ll.dtype == np.float64 and ll.tolist() == [-1234.5678901234567]
+    assert info.dtype == np.float64 and info.tolist() == [0.0]

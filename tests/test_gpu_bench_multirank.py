@@ -30,7 +30,7 @@ def _run(tmp_name, extra, world=2, timeout=600, want_rc=0, npoints=4096):
                LD_LIBRARY_PATH="/opt/rocm/lib:" + os.environ.get("LD_LIBRARY_PATH", ""))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "2",
-           "--warmup", "1", "--npoints", str(npoints)] + extra
+           "--warmup", "1", "--npoints", str(npoints), "--full"] + extra
     p = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=timeout)
     assert (p.returncode == 0) == (want_rc == 0), (p.stdout + p.stderr)[-4000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
