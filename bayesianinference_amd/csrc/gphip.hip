@@ -169,6 +169,7 @@ struct gphip_ctx {
     int panel_wide = 1;                          // wider outer panels while the trailing matrix is large (queue_factor)
     int thin_tiles = 1;                          // gemm_nt: skip the zero rows of the rhs block-row and the unread upper quadrant of diagonal tiles
     int debug_fail_alloc = 0;                    // tests: make the n-th device allocation of the next slot (re)allocation fail
+    int debug_abort_word = 0;                    // tests: set the abort word in front of the next launch of a kind (abort_hook)
     int dataflow_tail = 64;                      // large N: the last <= dataflow_tail tile columns go to the dataflow kernel (0 = off)
     bool fused_eval = false;                     // eval_chunk: the whole evaluation is ONE dataflow launch (build + factor + results)
     bool theta_packed = false;                   // eval_chunk: hyper-parameters travel as kernel arguments (k_scale_theta)
@@ -177,6 +178,7 @@ struct gphip_ctx {
                                                  // kernel (U = L^-T into dV, see DfArgs::U); u_ready: it ran for the current factor
     int* dFlags = nullptr;                       // [slots][(Nt+1)^2] ready flags (value = epoch)
     unsigned long long* dTicket = nullptr;       // task ticket counter (+ abort flag in the next word)
+    const char* abort_unread = nullptr;          // a launch without a finalize behind it left the abort word to the call: its error text
     unsigned long long ticket_base = 0;
     int epoch = 0;
     // fitted state (slot 0)
@@ -283,6 +285,7 @@ void invalidate_fit(gphip_ctx* h) {
 }
 // ... and a successful fit stamps the factor with the workspace generation it lives in
 void stamp_fit(gphip_ctx* h);
+void record_fit(gphip_ctx* h, bool ok, const double* theta, int p, double logdet);
 bool has_fit(const gphip_ctx* h) { return h->fitted && h->fit_gen == h->ws_gen; }
 
 double pivot_tol_rel(const gphip_ctx* h) {
@@ -832,6 +835,15 @@ bool use_dataflow(const gphip_ctx* h, int nslots) {
     return tasks < (1l << 30);
 }
 
+// Test hook "debug_abort_word" (resolves only under GPHIP_TEST_HOOKS=1): 1 / 2 / 3 = in front of the next dataflow Cholesky /
+// dataflow substitution or inverse / single-vector substitution launch, set the abort word as a spin-limit hit would.  Every
+// wait of that launch falls through at its next look at the word; the call must report the void results.
+void abort_hook(gphip_ctx* h, int kind) {
+    if (h->debug_abort_word != kind) return;
+    h->debug_abort_word = 0;
+    (void)hipMemsetAsync(h->dTicket + 1, 1, 4, h->stream);
+}
+
 // c0 > 0 (128-tiles only): factor the trailing submatrix that starts at tile column c0 -- the tail of the
 // look-ahead schedule, already updated by every earlier panel.  No finalize here.
 template <typename T, int TBX, int OCC = 2, int NST = 2, bool BUILD = false>
@@ -896,6 +908,7 @@ void launch_dataflow(gphip_ctx* h, int nslots, int c0 = 0, double* part = nullpt
         // two workgroups per CU: the neighbour of a diagonal task steps aside while that task is on the chain
         if (lds <= 80 * 1024 && h->dataflow_park) g.park = reinterpret_cast<int*>(h->dTicket + 2);
     }
+    abort_hook(h, 1);
     hipLaunchKernelGGL((chol_dataflow_kernel<T, TBX, OCC, NST, BUILD>), dim3((unsigned)tasks), dim3(256), lds, h->stream, g, tp);
 }
 
@@ -934,8 +947,13 @@ void launch_dataflow_inverse(gphip_ctx* h, int64_t fwd_rows = 0, bool back = fal
     size_t lds = df_lds_bytes<T, TBX, NST>();
     if (TBX == 64 && OCC <= 2 && lds < DF_XXF_LDS) lds = DF_XXF_LDS;
     ThetaPack tp;
+    abort_hook(h, 2);
     hipLaunchKernelGGL((chol_dataflow_kernel<T, TBX, OCC, NST, false>), dim3((unsigned)tasks), dim3(256), lds, h->stream, g, tp);
     if (fwd_rows == 0) h->u_ready = true;
+    if (!h->abort_unread)
+        h->abort_unread = fwd_rows == 0 ? "dataflow inverse launch timed out (set option grad_potri=2 and report)"
+                          : back        ? "dataflow backward substitution timed out (set option predict_df=0 and report)"
+                                        : "dataflow forward substitution timed out (set option predict_df=0 and report)";
 }
 
 // a prediction of few test points against a factor that came from the 64-tile single launch (its 64-block inverses are still
@@ -994,20 +1012,47 @@ bool samples_forward_df(gphip_ctx* h, int nb, int64_t mpad) {
     return true;
 }
 
-// The forward / backward / inverse launches above have no finalize kernel behind them to export the abort word (a dependency
-// wait that hit its spin limit makes every later wait of the launch fall through: the results are void).  The caller queues
-// this copy behind them and asks for the verdict after its stream synchronisation.
+// The one place the abort word (and the park counters behind it) goes back to zero, once a call has read it: nothing is left
+// unread after this.
+int clear_abort_word(gphip_ctx* h) {
+    h->abort_unread = nullptr;
+    HIPCHK(hipMemsetAsync(h->dTicket + 1, 0, 8 + DF_PARK_SLOTS * 4, h->stream));
+    return GPHIP_OK;
+}
+
+// The forward / backward / inverse launches above and the single-vector substitutions (queue_trsv) have no finalize kernel
+// behind them to export the abort word (a dependency wait that hit its spin limit makes every later wait of the launch fall
+// through: the results are void); they leave h->abort_unread set instead.  complete_call copies the word in front of the call's
+// synchronisation and turns it into the call's error.
 int queue_abort_probe(gphip_ctx* h) {
     HIPCHK(hipMemcpyAsync(h->hInfo + h->slots + 1, reinterpret_cast<int*>(h->dTicket + 1), 4, hipMemcpyDeviceToHost, h->stream));
     return GPHIP_OK;
 }
-int abort_probe_verdict(gphip_ctx* h, const char* what) {
+int abort_probe_verdict(gphip_ctx* h) {
+    const char* what = h->abort_unread;
+    h->abort_unread = nullptr;
     if (h->hInfo[h->slots + 1] == 0) return GPHIP_OK;
     h->hInfo[h->slots + 1] = 0;
-    HIPCHK(hipMemsetAsync(h->dTicket + 1, 0, 8 + DF_PARK_SLOTS * 4, h->stream));
+    if (const int rc = clear_abort_word(h)) return rc;
     h->fitted = false;                         // the factor itself may be intact, but nothing derived from it in this call is
     h->u_ready = false;
     return fail(h, GPHIP_ERR_HIP, what);
+}
+
+// The tail of every call that substitutes with a factor: sync() is the call's own stream synchronisation (a download that
+// synchronises, by default hipStreamSynchronize); the abort probe goes in front of it when a launch of the call asked for one.
+template <typename Sync>
+int complete_call(gphip_ctx* h, Sync&& sync) {
+    const bool probe = h->abort_unread != nullptr;
+    int rc = probe ? queue_abort_probe(h) : GPHIP_OK;
+    if (!rc) rc = sync();
+    if (rc) return rc;
+    HIPCHK(hipGetLastError());
+    harvest(h);
+    return probe ? abort_probe_verdict(h) : GPHIP_OK;
+}
+int complete_call(gphip_ctx* h) {
+    return complete_call(h, [h]() -> int { HIPCHK(hipStreamSynchronize(h->stream)); return GPHIP_OK; });
 }
 
 template <typename T>
@@ -1469,7 +1514,7 @@ int eval_chunk(gphip_ctx* h, const double* Theta, int nb, double* out, double* p
         fprintf(stderr, "\n");
     }
     if (h->hInfo[nb] != 0) {                   // a dataflow dependency wait hit its spin limit: results are void
-        HIPCHK(hipMemsetAsync(h->dTicket + 1, 0, 8 + DF_PARK_SLOTS * 4, h->stream));
+        if (const int rc = clear_abort_word(h)) return rc;
         return fail(h, GPHIP_ERR_HIP, "dataflow Cholesky schedule timed out (set option dataflow=0 and report)");
     }
     for (int s = 0; s < nb; ++s) {
@@ -1594,6 +1639,22 @@ int ensure_vbuf(gphip_ctx* h, int64_t cap) {
     HIPCHK(hipMalloc(&h->dPwNugT, (size_t)cap * 8));
     h->vcap = cap;
     return GPHIP_OK;
+}
+
+// Rows of V (rows x Npad) per chunk of a substitution over the whole factor: as many as keep V within ~8 GiB -- every chunk
+// re-runs the substitution over all of L, and its per-block launches only fill the chip when the chunk has many row tiles --
+// at least 2048, at most cap (whole tiles); halved while V does not fit next to the factor.
+int ensure_vchunk(gphip_ctx* h, int64_t cap, int64_t* rows) {
+    int64_t mc = (int64_t)((8.0 * (1 << 30)) / ((double)h->Npad * h->es)) / TB * TB;
+    mc = std::min(std::max<int64_t>(mc, 2048), cap);
+    int rc = ensure_vbuf(h, mc);
+    while (rc == GPHIP_ERR_HIP && mc > 2048) {
+        (void)hipGetLastError();
+        mc = (mc / 2 + TB - 1) / TB * TB;
+        rc = ensure_vbuf(h, mc);
+    }
+    *rows = mc;
+    return rc;
 }
 
 // One outer panel [k0, k1) of the forward substitution below: solve its tile columns, update the rest of the panel after
@@ -1926,10 +1987,36 @@ int queue_trsv(gphip_ctx* h, const T* B, int pass, int nrhs, bool back, T** Xout
     const long ntasks = nt >= 5 ? (long)(nt - 4) * (nt - 3) / 2 : 0;                 // common ticket list: I >= K + 4
     const long grid = std::min<long>((long)h->ncu, 3 * TRSV_CHAIN + ntasks);         // chain pairs + feeders + tile role; one per CU: all resident
     ProfScope ps(h, 2, 0.0, (double)h->slot_elems * sizeof(T));
+    abort_hook(h, 3);
+    if (!h->abort_unread) h->abort_unread = "single-vector substitution timed out (set option trsv=0 and report)";
     if (back) hipLaunchKernelGGL((trsv_dataflow_kernel<T, true>), dim3((unsigned)grid), dim3(TRSV_THREADS), trsv_lds_bytes(sizeof(T)), h->stream, g);
     else hipLaunchKernelGGL((trsv_dataflow_kernel<T, false>), dim3((unsigned)grid), dim3(TRSV_THREADS), trsv_lds_bytes(sizeof(T)), h->stream, g);
     *Xout = g.X;
     return GPHIP_OK;
+}
+
+// gphip_solve, nr <= TRSV_MAXR right-hand sides (b: nr rows of Npad): upload, forward launch (input -> pass 0), backward launch
+// (pass 0 -> pass 1); *x = the solutions on the device.  No synchronisation: b and b32 (the fp32 copy) live until the caller's
+// download has synchronised the stream.
+template <typename T>
+int queue_trsv_solve(gphip_ctx* h, const std::vector<double>& b, std::vector<float>& b32, int nr, void** x) {
+    const void* src = b.data();
+    if constexpr (sizeof(T) == 4) { b32.assign(b.begin(), b.end()); src = b32.data(); }
+    HIPCHK(hipMemcpyAsync(h->dTrsvX, src, b.size() * sizeof(T), hipMemcpyHostToDevice, h->stream));
+    T *x0 = nullptr, *x1 = nullptr;
+    int rc = queue_trsv_fill<T>(h, nr, 2);
+    if (!rc) rc = queue_trsv<T>(h, trsv_input<T>(h), 0, nr, false, &x0);
+    if (!rc) rc = queue_trsv<T>(h, x0, 1, nr, true, &x1);
+    *x = x1;
+    return rc;
+}
+
+// gphip_solve, few vectors on the GEMM path: their compact rows (mc x Npad) into the 128-row block V (to_v) or back
+template <typename T>
+void queue_rows_vblock(gphip_ctx* h, void* rows, int64_t mc, int64_t mpad, bool to_v) {
+    const unsigned gx = (unsigned)((h->Npad + 255) / 256);
+    if (to_v) hipLaunchKernelGGL(rows_to_vblock_kernel<T>, dim3(gx), dim3(256), 0, h->stream, (const T*)rows, (int)mc, (long)h->Npad, (T*)h->dV, (long)mpad);
+    else hipLaunchKernelGGL(vblock_to_rows_kernel<T>, dim3(gx), dim3(256), 0, h->stream, (const T*)h->dV, (long)mpad, (int)mc, (long)h->Npad, (T*)rows);
 }
 
 // alpha = K^-1 r from the fitted factor (z = L^-1 r sits in the rhs row): one backward pass on a
@@ -2140,6 +2227,16 @@ namespace {
 void stamp_fit(gphip_ctx* h) {
     h->fit_gen = h->ws_gen;
     if (h->group && !h->in_group_call && !h->group->in_sharded_fit) h->fit_id = ++h->group->fit_id;
+}
+// the resident factor (slot 0, whole on this device) is theta's; ok: it may serve the calls that substitute with it
+void record_fit(gphip_ctx* h, bool ok, const double* theta, int p, double logdet) {
+    h->fitted = ok;
+    h->dist_fit = false;
+    stamp_fit(h);
+    h->theta_fit.assign(theta, theta + p);
+    h->logdet_fit = logdet;
+    h->mu_fit = h->hSlotp[2];
+    h->kappa_fit = h->hSlotp[SP_KXX] + h->hSlotp[1];
 }
 }  // namespace
 
@@ -2567,21 +2664,8 @@ int gphip_loglik_grad(gphip_handle h, const double* theta, int p, double* out, d
     const size_t ngacc = std::max((size_t)2 * d + 6, (size_t)h->ncp + 1);
     if (!h->dGacc) HIPCHK(hipMalloc(&h->dGacc, ngacc * 8));
     h->ngacc = ngacc;
-    int64_t MC = 0;
-    if (!potri) {
-        // rows of K^-1 per pass: as many as keep the scratch block within ~8 GiB (each pass runs a forward and a
-        // backward substitution over all of L; few, tall passes keep their launches chip-filling)
-        MC = (int64_t)((8.0 * (1 << 30)) / ((double)Npad * h->es)) / TB * TB;
-        if (MC < 2048) MC = 2048;
-        if (MC > Npad) MC = Npad;
-        rc = ensure_vbuf(h, MC);
-        while (rc == GPHIP_ERR_HIP && MC > 2048) {
-            (void)hipGetLastError();
-            MC = (MC / 2 + TB - 1) / TB * TB;
-            rc = ensure_vbuf(h, MC);
-        }
-        if (rc) return rc;
-    }
+    int64_t MC = 0;                            // rows of K^-1 per pass (each pass a forward and a backward substitution)
+    if (!potri && (rc = ensure_vchunk(h, Npad, &MC))) return rc;
     h->cs = h->stream;
     rc = (potri && h->u_ready) ? DISPATCH(h, queue_alpha_from_u, h) : DISPATCH(h, queue_alpha, h);
     if (rc) return rc;
@@ -2599,66 +2683,44 @@ int gphip_loglik_grad(gphip_handle h, const double* theta, int p, double* out, d
     }
     std::vector<double> gacc(ngacc), alpha;
     HIPCHK(hipMemcpyAsync(gacc.data(), h->dGacc, gacc.size() * 8, hipMemcpyDeviceToHost, h->stream));
-    const bool u_df = potri && h->u_ready;     // U = L^-T came from an inverse launch of the dataflow kernel
-    if (u_df) { rc = queue_abort_probe(h); if (rc) return rc; }
-    rc = DISPATCH(h, download, h, alpha, h->dAlpha, (size_t)N, h->stream);
+    rc = complete_call(h, [&] { return DISPATCH(h, download, h, alpha, h->dAlpha, (size_t)N, h->stream); });
     if (rc) return rc;
-    HIPCHK(hipGetLastError());
-    harvest(h);
-    if (u_df) { rc = abort_probe_verdict(h, "dataflow inverse launch timed out (set option grad_potri=2 and report)"); if (rc) return rc; }
     h->grad_analytic = 1;
+    int o = 0;                                                // (theta index of the next derivative)
     if (h->custom) {
         // theta = [p_0 .. p_{ncp-1}] sn [mu]  (accumulators: custom_grad_kernel)
         for (int m = 0; m < h->ncp; ++m) grad[m] = 0.5 * gacc[(size_t)m];
         grad[h->ncp] = gacc[(size_t)h->ncp] * theta[h->ncp];
-        if (h->mean_id == GPHIP_MEAN_CONST) {
-            double sum = 0.0;
-            for (double v : alpha) sum += v;
-            grad[h->ncp + 1] = sum;
+        o = h->ncp + 1;
+    } else {
+        // chain rule onto the theta layout [term 1: l.., (alpha), sf] [term 2] [c] sn [mu]  (accumulators: grad_reduce_*)
+        auto lengths = [&](int nl, size_t base) {
+            if (nl == 1) {
+                double sum = 0.0;
+                for (int64_t j = 0; j < d; ++j) sum += gacc[base + (size_t)j];
+                grad[o] = 0.5 * sum / theta[o];                   // even in l: d/dl of f(l^2)
+            } else {
+                for (int64_t j = 0; j < d; ++j) grad[o + j] = 0.5 * gacc[base + (size_t)j] / theta[o + j];
+            }
+            o += nl;
+        };
+        lengths(h->nl, 0);
+        if (h->has_a1) grad[o++] = 0.5 * gacc[(size_t)2 * d + 3];
+        grad[o] = gacc[(size_t)d] / theta[o]; ++o;                // sf1: 1/2 * sum w (dk/dk1) k1 * 2/sf
+        if (h->nl2 > 0) {
+            lengths(h->nl2, (size_t)d + 2);
+            if (h->has_a2) grad[o++] = 0.5 * gacc[(size_t)2 * d + 4];
+            grad[o] = gacc[(size_t)2 * d + 2] / theta[o]; ++o;
         }
-        h->fitted = true;
-        h->dist_fit = false;
-        stamp_fit(h);
-        h->theta_fit.assign(theta, theta + p);
-        h->logdet_fit = parts[0];
-        h->mu_fit = h->hSlotp[2];
-        h->kappa_fit = h->hSlotp[SP_KXX] + h->hSlotp[1];
-        return GPHIP_OK;
+        if (h->ks.offset) grad[o++] = 0.5 * gacc[(size_t)2 * d + 5];
+        grad[o] = gacc[(size_t)d + 1] * theta[o]; ++o;            // sn: 1/2 * tr(W) * 2 sn
     }
-    // chain rule onto the theta layout [term 1: l.., (alpha), sf] [term 2] [c] sn [mu]  (accumulators: grad_reduce_*)
-    int o = 0;
-    auto lengths = [&](int nl, size_t base) {
-        if (nl == 1) {
-            double sum = 0.0;
-            for (int64_t j = 0; j < d; ++j) sum += gacc[base + (size_t)j];
-            grad[o] = 0.5 * sum / theta[o];                   // even in l: d/dl of f(l^2)
-        } else {
-            for (int64_t j = 0; j < d; ++j) grad[o + j] = 0.5 * gacc[base + (size_t)j] / theta[o + j];
-        }
-        o += nl;
-    };
-    lengths(h->nl, 0);
-    if (h->has_a1) grad[o++] = 0.5 * gacc[(size_t)2 * d + 3];
-    grad[o] = gacc[(size_t)d] / theta[o]; ++o;                // sf1: 1/2 * sum w (dk/dk1) k1 * 2/sf
-    if (h->nl2 > 0) {
-        lengths(h->nl2, (size_t)d + 2);
-        if (h->has_a2) grad[o++] = 0.5 * gacc[(size_t)2 * d + 4];
-        grad[o] = gacc[(size_t)2 * d + 2] / theta[o]; ++o;
-    }
-    if (h->ks.offset) grad[o++] = 0.5 * gacc[(size_t)2 * d + 5];
-    grad[o] = gacc[(size_t)d + 1] * theta[o]; ++o;            // sn: 1/2 * tr(W) * 2 sn
     if (h->mean_id == GPHIP_MEAN_CONST) {
         double sum = 0.0;
         for (double v : alpha) sum += v;
-        grad[o++] = sum;
+        grad[o] = sum;
     }
-    h->fitted = true;                                         // the factor of theta is still resident (whole, on this device)
-    h->dist_fit = false;
-    stamp_fit(h);
-    h->theta_fit.assign(theta, theta + p);
-    h->logdet_fit = parts[0];
-    h->mu_fit = h->hSlotp[2];
-    h->kappa_fit = h->hSlotp[SP_KXX] + h->hSlotp[1];
+    record_fit(h, true, theta, p, parts[0]);                  // the factor of theta is still resident (whole, on this device)
     return GPHIP_OK;
 }
 
@@ -2697,17 +2759,12 @@ int gphip_fit(gphip_handle h, const double* theta, int p, int* info) {
     int rc = eval_batch(h, theta, 1, p, &out, parts, info);
     h->want_w = false;
     if (rc) return rc;
-    const bool sharded_fit = h->group && h->group->fit_id != id_before;     // group_eval_run stamped every member itself
+    const bool sharded_fit = h->group && h->group->fit_id != id_before;     // group_eval_run recorded every member itself
     if (h->dist_fit) {                         // (a later gphip_solve factors locally again: it needs the same K)
         h->fit_pw_mean.assign(h->pw_mean_host ? h->pw_mean_host : nullptr, h->pw_mean_host ? h->pw_mean_host + h->N : nullptr);
         h->fit_pw_nug.assign(h->pw_nug_host ? h->pw_nug_host : nullptr, h->pw_nug_host ? h->pw_nug_host + h->N : nullptr);
     }
-    h->fitted = (*info == 0);
-    if (!sharded_fit) stamp_fit(h);
-    h->theta_fit.assign(theta, theta + p);
-    h->logdet_fit = parts[0];
-    h->mu_fit = h->hSlotp[2];
-    h->kappa_fit = h->hSlotp[SP_KXX] + h->hSlotp[1];
+    if (!sharded_fit) record_fit(h, *info == 0, theta, p, parts[0]);
     return GPHIP_OK;
 }
 
@@ -2877,18 +2934,8 @@ static int predict_local(gphip_handle h, const void* Xs, int64_t M, double* mean
     HIPCHK(hipSetDevice(h->device));
     const double* X = static_cast<const double*>(Xs);
     const int64_t d = h->d;
-    // test points per chunk: as many as keep V (chunk x Npad) within ~8 GiB -- every chunk re-runs the whole
-    // substitution over L, and its per-block launches only fill the chip when the chunk has many row tiles
-    int64_t MC = (int64_t)((8.0 * (1 << 30)) / ((double)h->Npad * h->es)) / TB * TB;
-    if (MC < 2048) MC = 2048;
-    if (MC > 32768) MC = 32768;
-    if (M < MC) MC = (M + TB - 1) / TB * TB;
-    int rc = ensure_vbuf(h, MC);
-    while (rc == GPHIP_ERR_HIP && MC > 2048) {               // not enough free HBM next to the factor: smaller chunks
-        (void)hipGetLastError();
-        MC = (MC / 2 + TB - 1) / TB * TB;
-        rc = ensure_vbuf(h, MC);
-    }
+    int64_t MC = 0;                                          // test points per chunk
+    int rc = ensure_vchunk(h, std::min<int64_t>(32768, (M + TB - 1) / TB * TB), &MC);
     if (rc) return rc;
     h->cs = h->stream;
     std::vector<double> xt;
@@ -2905,17 +2952,12 @@ static int predict_local(gphip_handle h, const void* Xs, int64_t M, double* mean
         if (rc) return rc;
         DISPATCH(h, queue_cross, h, mc, mpad, 1);
         ensure_w64(h);
-        const bool dfp = df_forward_ok(h, mpad);
-        if (dfp) launch_dataflow_inverse<double, 64>(h, mpad);
+        if (df_forward_ok(h, mpad)) launch_dataflow_inverse<double, 64>(h, mpad);
         else DISPATCH(h, queue_forward_rows, h, mpad, 1);
         DISPATCH(h, queue_predict_reduce, h, mc, mpad, 1);
         HIPCHK(hipMemcpyAsync(mean + m0, h->dMean, (size_t)mc * 8, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipMemcpyAsync(var + m0, h->dVar, (size_t)mc * 8, hipMemcpyDeviceToHost, h->stream));
-        if (dfp) { rc = queue_abort_probe(h); if (rc) return rc; }
-        HIPCHK(hipStreamSynchronize(h->stream));
-        HIPCHK(hipGetLastError());
-        harvest(h);
-        if (dfp) { rc = abort_probe_verdict(h, "dataflow forward substitution timed out (set option predict_df=0 and report)"); if (rc) return rc; }
+        if ((rc = complete_call(h))) return rc;
     }
     return GPHIP_OK;
 }
@@ -2970,15 +3012,8 @@ static int predict_streamed(gphip_handle h, const void* Xs, int64_t M, double* m
         const int64_t Mi = lo[(size_t)i + 1] - lo[(size_t)i];
         if (Mi <= 0) continue;
         if (!SOFT(hipSetDevice(m->device))) break;
-        int64_t mc = (int64_t)((8.0 * (1 << 30)) / ((double)m->Npad * m->es)) / TB * TB;
-        mc = std::max<int64_t>(2048, std::min<int64_t>(mc, 32768));
-        if (Mi < mc) mc = (Mi + TB - 1) / TB * TB;
-        rc = ensure_vbuf(m, mc);
-        while (rc == GPHIP_ERR_HIP && mc > 2048) {
-            (void)hipGetLastError();
-            mc = (mc / 2 + TB - 1) / TB * TB;
-            rc = ensure_vbuf(m, mc);
-        }
+        int64_t mc = 0;
+        rc = ensure_vchunk(m, std::min<int64_t>(32768, (Mi + TB - 1) / TB * TB), &mc);
         if (rc) { local_fail(rc, m->err); break; }
         if (!m->dZ && !SOFT(hipMalloc(&m->dZ, (size_t)m->Npad * m->es))) break;
         MC[(size_t)i] = mc;
@@ -3188,26 +3223,21 @@ int gphip_predict_samples(gphip_handle h, const double* Thetas, int S, int p, co
             for (int64_t i = 0; i < mc; ++i)
                 for (int64_t j = 0; j < d; ++j) xt[(size_t)j * mpad + i] = X[(m0 + i) * d + j];
             note_test_range(h, xt, mc, mpad);
-        rc = DISPATCH(h, upload, h, h->dXsT, xt, h->stream);
+            rc = DISPATCH(h, upload, h, h->dXsT, xt, h->stream);
             if (rc) return rc;
             rc = upload_pw_test(h, s0, nb, m0, mc, mpad);
             if (rc) return rc;
             DISPATCH(h, queue_cross, h, mc, mpad, nb);
             // few test points per sample: the forward substitutions of ALL samples as ONE dataflow launch (slot = sample) instead
             // of two launches per tile column (samples_forward_df)
-            const bool dff = samples_forward_df(h, nb, mpad);
-            if (dff) launch_dataflow_inverse<double, 64>(h, mpad, false, nb, h->dW64s);
+            if (samples_forward_df(h, nb, mpad)) launch_dataflow_inverse<double, 64>(h, mpad, false, nb, h->dW64s);
             else DISPATCH(h, queue_forward_rows, h, mpad, nb);
-            if (dff) { rc = queue_abort_probe(h); if (rc) return rc; }
             DISPATCH(h, queue_predict_reduce, h, mc, mpad, nb);
             hm.resize((size_t)nb * mpad);
             hv.resize((size_t)nb * mpad);
             HIPCHK(hipMemcpyAsync(hm.data(), h->dMean, hm.size() * 8, hipMemcpyDeviceToHost, h->stream));
             HIPCHK(hipMemcpyAsync(hv.data(), h->dVar, hv.size() * 8, hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(hipStreamSynchronize(h->stream));
-            HIPCHK(hipGetLastError());
-            harvest(h);
-            if (dff) { rc = abort_probe_verdict(h, "dataflow forward substitution timed out (set option predict_df=0 and report)"); if (rc) return rc; }
+            if ((rc = complete_call(h))) return rc;
             for (int s = 0; s < nb; ++s)
                 for (int64_t t = 0; t < mc; ++t) {
                     mean[(size_t)(s0 + s) * M + m0 + t] = hm[(size_t)s * mpad + t];
@@ -3315,37 +3345,9 @@ int gphip_solve(gphip_handle h, const double* rhs, int64_t nrhs, double* out) {
             const int nr = (int)std::min<int64_t>(TRSV_MAXR, nrhs - m0);
             b.assign((size_t)nr * Npad, 0.0);
             for (int t = 0; t < nr; ++t) memcpy(&b[(size_t)t * Npad], rhs + (m0 + t) * N, (size_t)N * 8);
-            // (no synchronisation after the upload: `b` lives until the download below has synchronised the stream)
-            if (h->dtype == 64) {
-                HIPCHK(hipMemcpyAsync(h->dTrsvX, b.data(), b.size() * 8, hipMemcpyHostToDevice, h->stream));
-            } else {
-                b32.assign(b.begin(), b.end());
-                HIPCHK(hipMemcpyAsync(h->dTrsvX, b32.data(), b32.size() * 4, hipMemcpyHostToDevice, h->stream));
-            }
-            // forward: input -> pass 0; backward: pass 0 -> pass 1
-            int rc;
-            void* xres = nullptr;
-            if (h->dtype == 64) {
-                double *x0 = nullptr, *x1 = nullptr;
-                rc = queue_trsv_fill<double>(h, nr, 2);
-                if (!rc) rc = queue_trsv<double>(h, trsv_input<double>(h), 0, nr, false, &x0);
-                if (!rc) rc = queue_trsv<double>(h, x0, 1, nr, true, &x1);
-                xres = x1;
-            } else {
-                float *x0 = nullptr, *x1 = nullptr;
-                rc = queue_trsv_fill<float>(h, nr, 2);
-                if (!rc) rc = queue_trsv<float>(h, trsv_input<float>(h), 0, nr, false, &x0);
-                if (!rc) rc = queue_trsv<float>(h, x0, 1, nr, true, &x1);
-                xres = x1;
-            }
-            if (rc) return rc;
-            rc = queue_abort_probe(h);
-            if (rc) return rc;
-            rc = DISPATCH(h, download, h, b, xres, (size_t)nr * Npad, h->stream);
-            if (rc) return rc;
-            HIPCHK(hipGetLastError());
-            harvest(h);
-            rc = abort_probe_verdict(h, "single-vector substitution timed out (set option trsv=0 and report)");
+            void* x = nullptr;
+            int rc = DISPATCH(h, queue_trsv_solve, h, b, b32, nr, &x);
+            if (!rc) rc = complete_call(h, [&] { return DISPATCH(h, download, h, b, x, (size_t)nr * Npad, h->stream); });
             if (rc) return rc;
             for (int t = 0; t < nr; ++t) memcpy(out + (m0 + t) * N, &b[(size_t)t * Npad], (size_t)N * 8);
         }
@@ -3377,9 +3379,7 @@ int gphip_solve(gphip_handle h, const double* rhs, int64_t nrhs, double* out) {
             for (int64_t t = 0; t < mc; ++t) memcpy(&v[(size_t)t * Npad], rhs + (m0 + t) * N, (size_t)N * 8);
             rc = DISPATCH(h, upload, h, dRows, v, h->stream);
             if (rc) return rc;
-            const unsigned gx = (unsigned)((Npad + 255) / 256);
-            if (h->dtype == 64) hipLaunchKernelGGL(rows_to_vblock_kernel<double>, dim3(gx), dim3(256), 0, h->stream, (const double*)dRows, (int)mc, (long)Npad, (double*)h->dV, (long)mpad);
-            else hipLaunchKernelGGL(rows_to_vblock_kernel<float>, dim3(gx), dim3(256), 0, h->stream, (const float*)dRows, (int)mc, (long)Npad, (float*)h->dV, (long)mpad);
+            DISPATCH(h, queue_rows_vblock, h, dRows, mc, mpad, true);
         } else {
             v.assign((size_t)mpad * Npad, 0.0);
             for (int64_t t = 0; t < mc; ++t)
@@ -3390,24 +3390,14 @@ int gphip_solve(gphip_handle h, const double* rhs, int64_t nrhs, double* out) {
         // after a single-launch fit both halves are ONE dataflow launch each (forward as in gphip_predict; backward over a copy of
         // the factor with its 64 x 64 blocks transposed, made on the first solve of a fit)
         ensure_w64(h);                         // (also after a look-ahead-schedule fit: 64-block inverses cut out of the 128-block ones)
-        const bool dfs = df_forward_ok(h, mpad);
-        if (dfs) launch_dataflow_inverse<double, 64>(h, mpad);
+        const bool df_fwd = df_forward_ok(h, mpad);
+        if (df_fwd) launch_dataflow_inverse<double, 64>(h, mpad);
         else DISPATCH(h, queue_forward_rows, h, mpad, 1);
-        if (dfs && df_backward_ready<double>(h)) launch_dataflow_inverse<double, 64>(h, mpad, true);
+        if (df_fwd && df_backward_ready<double>(h)) launch_dataflow_inverse<double, 64>(h, mpad, true);
         else DISPATCH(h, queue_backward_rows, h, mpad);
-        if (dfs) { rc = queue_abort_probe(h); if (rc) return rc; }
-        if (dRows) {
-            const unsigned gx = (unsigned)((Npad + 255) / 256);
-            if (h->dtype == 64) hipLaunchKernelGGL(vblock_to_rows_kernel<double>, dim3(gx), dim3(256), 0, h->stream, (const double*)h->dV, (long)mpad, (int)mc, (long)Npad, (double*)dRows);
-            else hipLaunchKernelGGL(vblock_to_rows_kernel<float>, dim3(gx), dim3(256), 0, h->stream, (const float*)h->dV, (long)mpad, (int)mc, (long)Npad, (float*)dRows);
-            rc = DISPATCH(h, download, h, v, dRows, (size_t)mc * Npad, h->stream);
-        } else {
-            rc = DISPATCH(h, download, h, v, h->dV, (size_t)mpad * Npad, h->stream);
-        }
+        if (dRows) DISPATCH(h, queue_rows_vblock, h, dRows, mc, mpad, false);
+        rc = complete_call(h, [&] { return DISPATCH(h, download, h, v, dRows ? dRows : h->dV, (size_t)(dRows ? mc : mpad) * Npad, h->stream); });
         if (rc) return rc;
-        HIPCHK(hipGetLastError());
-        harvest(h);
-        if (dfs) { rc = abort_probe_verdict(h, "dataflow substitution timed out (set option predict_df=0 and report)"); if (rc) return rc; }
         if (dRows) {
             for (int64_t t = 0; t < mc; ++t) memcpy(out + (m0 + t) * N, &v[(size_t)t * Npad], (size_t)N * 8);
         } else {
@@ -3652,7 +3642,7 @@ int gphip_dist_end(gphip_handle h, double* logdet_partial, double* quad, int* in
     HIPCHK(hipGetLastError());
     harvest(h);
     if (h->dist_df_active && h->hInfo[1] != 0) {
-        HIPCHK(hipMemsetAsync(h->dTicket + 1, 0, 8 + DF_PARK_SLOTS * 4, h->stream));
+        if (const int rc = clear_abort_word(h)) return rc;
         h->dist_world = 0; h->dist_rank = 0;
         return fail(h, GPHIP_ERR_HIP, "dataflow panel schedule timed out (set option dist_panel_df=0 and report)");
     }
@@ -3684,6 +3674,7 @@ int* option_slot(gphip_ctx* h, const char* name) {
         {"replicate_factor", &gphip_ctx::replicate_factor}, {"share_local_panels", &gphip_ctx::share_local_panels},
         {"bcast_chunks", &gphip_ctx::bcast_chunks}, {"bcast_two_hop", &gphip_ctx::bcast_two_hop}, {"dist_panel_df", &gphip_ctx::dist_panel_df}, {"dist_owner_yield", &gphip_ctx::dist_owner_yield},
         {"debug_fail_alloc", &gphip_ctx::debug_fail_alloc}, {"debug_fail_hip", &gphip_ctx::debug_fail_hip},
+        {"debug_abort_word", &gphip_ctx::debug_abort_word},
     };
     // fault injection ("debug_*") exists for the test-suite only: the names resolve in a process that was started with
     // GPHIP_TEST_HOOKS=1 and nowhere else (not through GPHIP_OPTIONS either: apply_env_options skips them)

@@ -639,14 +639,9 @@ int group_eval_run(gphip_ctx* h, const double* theta, int p, bool keep, double* 
                 HIPCHK(hipStreamSynchronize(m->stream));
                 HIPCHK(hipGetLastError());
             }
-            m->fitted = true;
-            stamp_fit(m);
+            record_fit(m, true, theta, p, logdet);
             m->fit_id = g->fit_id;
             m->dist_fit = g->replicate == 0;
-            m->theta_fit.assign(theta, theta + p);
-            m->logdet_fit = logdet;
-            m->mu_fit = m->hSlotp[2];
-            m->kappa_fit = m->hSlotp[SP_KXX] + m->hSlotp[1];
             m->fit_rank = g->ranks[i]; m->fit_world = W;
         }
         g->in_sharded_fit = false;

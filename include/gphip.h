@@ -341,7 +341,7 @@ int gphip_ns_crude_weights(const double* points, const double* loglik, int64_t m
  *   "last_issue_us" (read-only): host microseconds the last sharded evaluation spent issuing its schedule (all members of a
  *                  one-process group together).
  *   "trsv"         0 / 1 (default): gphip_solve of up to 4 right-hand sides (up to 16 from Nt >= 96, in batches of 4) and the
- *                  alpha = K^-1 (y - m) of gphip_fit run each triangle as ONE persistent launch that streams the factor once
+ *                  alpha = K^-1 (y - m) of gphip_loglik_grad run each triangle as ONE persistent launch that streams the factor once
  *                  (csrc/gp_trsv.h: tiles in registers, a band-2 chain of workgroup pairs, sentinel hand-offs); 0 = the
  *                  GEMM-shaped substitution for every count.  fp64 and fp32.
  *   "predict_df_max_nt" (default 256): gphip_predict / gphip_solve after a look-ahead fit (Nt above "dataflow_max_nt") still run
@@ -359,6 +359,10 @@ int gphip_ns_crude_weights(const double* points, const double* loglik, int64_t m
  *                  HIP call of the next collective sequence fails (fault injection of the multi-process tests).  The names exist
  *                  only in a process started with GPHIP_TEST_HOOKS=1 in its environment ("unknown option" otherwise) and are
  *                  never taken from GPHIP_OPTIONS.
+ *   "debug_abort_word" 1 / 2 / 3: tests only, gated like the two above -- sets the abort word of the persistent kernels in front
+ *                  of the next dataflow Cholesky (1) / dataflow substitution or inverse (2) / single-vector substitution (3)
+ *                  launch, as a dependency wait that hit its spin limit would, then resets itself to 0.  The call fails with
+ *                  GPHIP_ERR_HIP; where it substitutes with a factor, the fit is dropped.
  *   "panel", "shard_min_n", "replicate_factor", "bcast_chunks", "bcast_two_hop" must have the same value on every rank of a
  *   multi-process job (checked by one small all-reduce at the start of every sharded evaluation: a mismatch fails the call on ALL
  *   ranks). */
