@@ -91,6 +91,9 @@ _SIGNATURES = {
     "gphip_fit": (C.c_int, [_h, _dp, C.c_int, _ip]),
     "gphip_predict": (C.c_int, [_h, C.c_void_p, C.c_int64, _dp, _dp]),
     "gphip_predict_samples": (C.c_int, [_h, _dp, C.c_int, C.c_int, C.c_void_p, C.c_int64, _dp, _dp, _ip]),
+    "gphip_predict_cov": (C.c_int, [_h, C.c_void_p, C.c_int64, C.c_int, _dp, _dp]),
+    "gphip_predict_draws": (C.c_int, [_h, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_uint64, _dp, C.c_double, _dp, _ip]),
+    "gphip_predict_logpdf": (C.c_int, [_h, C.c_void_p, C.c_int64, _dp, _dp, _ip]),
     "gphip_loglik_batch_pw": (C.c_int, [_h, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _ip]),
     "gphip_fit_pw": (C.c_int, [_h, _dp, C.c_int, _dp, _dp, _ip]),
     "gphip_predict_pw": (C.c_int, [_h, C.c_void_p, C.c_int64, _dp, _dp, _dp, _dp]),
@@ -435,6 +438,55 @@ class Handle:
         self._check(self._lib.gphip_predict_samples(self._h, _d(Th), S, Th.shape[1], Xs.ctypes.data, M,
                                                     _d(mean), _d(var), info.ctypes.data_as(_ip)))
         return mean, var, info
+
+    def _test_points(self, Xs):
+        Xs = np.ascontiguousarray(np.atleast_2d(np.asarray(Xs, dtype=np.float64)))
+        if Xs.ndim != 2 or Xs.shape[1] != self.d:
+            raise GphipError(2, "test points have the wrong dimension")
+        if Xs.shape[0] < 1:
+            raise GphipError(2, "M < 1")
+        return Xs
+
+    def predict_cov(self, Xs, latent: bool = False):
+        """Joint predictive distribution at Xs[M, d]: (mean[M], cov[M, M]).  latent=False: covariance of noisy observations
+        (its diagonal is predict()'s var); latent=True: of the latent function."""
+        Xs = self._test_points(Xs)
+        M = Xs.shape[0]
+        mean, cov = np.zeros(M), np.zeros((M, M))
+        self._check(self._lib.gphip_predict_cov(self._h, Xs.ctypes.data, M, int(bool(latent)), _d(mean), _d(cov)))
+        return mean, cov
+
+    def predict_draws(self, Xs, S: int, seed: int = 0, z=None, latent: bool = True, jitter: float = -1.0):
+        """S draws from the joint predictive distribution: (out[S, M], info).  z: the caller's standard normals [S, M]
+        (None: generated on the device from (seed, s, j)); jitter < 0: the library's default, 0: none."""
+        Xs = self._test_points(Xs)
+        M, S = Xs.shape[0], int(S)
+        if S < 1:
+            raise GphipError(2, "S < 1")
+        zp = None
+        if z is not None:
+            z = np.ascontiguousarray(np.asarray(z, dtype=np.float64))
+            if z.shape != (S, M):
+                raise GphipError(2, f"z must have shape ({S}, {M})")
+            zp = _d(z)
+        if not np.isfinite(jitter):
+            raise GphipError(1, "non-finite jitter")
+        out = np.zeros((S, M))
+        info = C.c_int(0)
+        self._check(self._lib.gphip_predict_draws(self._h, Xs.ctypes.data, M, int(bool(latent)), S, int(seed) & (2**64 - 1), zp,
+                                                  float(jitter), _d(out), C.byref(info)))
+        return out, info.value
+
+    def predict_logpdf(self, Xs, ystar):
+        """log N(ystar | mean, cov) with the noisy-observation covariance at Xs: (value, info)."""
+        Xs = self._test_points(Xs)
+        M = Xs.shape[0]
+        ys = np.ascontiguousarray(np.asarray(ystar, dtype=np.float64).ravel())
+        if ys.shape != (M,):
+            raise GphipError(2, f"ystar must have length {M}")
+        out, info = C.c_double(0.0), C.c_int(0)
+        self._check(self._lib.gphip_predict_logpdf(self._h, Xs.ctypes.data, M, _d(ys), C.byref(out), C.byref(info)))
+        return out.value, info.value
 
     def covariance(self, theta):
         """theta[p] -> K[N, N]; Theta[B, p] -> K[B, N, N] (the Listable form, BGP:59)."""

@@ -253,6 +253,14 @@ struct gphip_ctx {
     double *dPwMeanT = nullptr, *dPwNugT = nullptr;   // [vcap] test-point values of the current prediction chunk
     std::vector<double> null_diag, null_mean_test;    // fitted null kernel with a point-dependent nugget: the diagonal
     std::vector<double> fit_pw_mean, fit_pw_nug;      // the point-dependent arrays a DISTRIBUTED fit was made with (local refit)
+    bool fit_pw = false;                              // the resident fit came from gphip_fit_pw with a non-null array
+    // joint prediction (gphip_joint.inc): the child context whose training points are the test points, and its scratch
+    gphip_ctx* joint = nullptr;
+    void* dJZ = nullptr; size_t jz_bytes = 0;         // typed [Npad][128]: row 0 = z = L^-1 r, the downdate's rhs-row operand
+    void* dJPart = nullptr; size_t jpart_bytes = 0;   // typed [strip][tile][128 x 128]: the downdate's strip partials
+    double* dJOut = nullptr; size_t jout_bytes = 0;   // dense covariance + mean / the draws' mean
+    int joint_split = 0;                              // option: strips of the downdate's contraction (0 = by the split rule)
+    int joint_nsplit = 0;                             // read-only: strips the last downdate used
 };
 
 namespace {
@@ -2231,6 +2239,7 @@ void stamp_fit(gphip_ctx* h) {
 // the resident factor (slot 0, whole on this device) is theta's; ok: it may serve the calls that substitute with it
 void record_fit(gphip_ctx* h, bool ok, const double* theta, int p, double logdet) {
     h->fitted = ok;
+    h->fit_pw = h->pw_mean_host || h->pw_nug_host;
     h->dist_fit = false;
     stamp_fit(h);
     h->theta_fit.assign(theta, theta + p);
@@ -2530,7 +2539,9 @@ int gphip_destroy(gphip_handle h) {
     if (h->pstream) (void)hipStreamSynchronize(h->pstream);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     group_destroy(h);                          // communicators + the other members of a multi-device handle
+    if (h->joint) gphip_destroy(h->joint);
     (void)hipSetDevice(h->device);
+    (void)hipFree(h->dJZ); (void)hipFree(h->dJPart); (void)hipFree(h->dJOut);
     for (void* pk : h->packed) (void)hipFree(pk);
     (void)hipFree(h->dOwn); (void)hipFree(h->dDistAdj); (void)hipFree(h->dZ);
     (void)hipFree(h->dScal8); (void)hipFree(h->drain_buf);
@@ -2747,6 +2758,7 @@ int gphip_fit(gphip_handle h, const double* theta, int p, int* info) {
             *info = !fin ? GPHIP_INFO_NAN : (pos && std::isfinite(ld) ? GPHIP_INFO_OK : GPHIP_INFO_NOT_SPD);
         }
         h->fitted = h->null_fit = (*info == 0);
+        h->fit_pw = h->pw_mean_host || h->pw_nug_host;
         h->dist_fit = false;
         stamp_fit(h);
         h->theta_fit.assign(theta, theta + p);
@@ -2765,6 +2777,7 @@ int gphip_fit(gphip_handle h, const double* theta, int p, int* info) {
         h->fit_pw_nug.assign(h->pw_nug_host ? h->pw_nug_host : nullptr, h->pw_nug_host ? h->pw_nug_host + h->N : nullptr);
     }
     if (!sharded_fit) record_fit(h, *info == 0, theta, p, parts[0]);
+    h->fit_pw = h->pw_mean_host || h->pw_nug_host;
     return GPHIP_OK;
 }
 
@@ -3674,7 +3687,7 @@ int* option_slot(gphip_ctx* h, const char* name) {
         {"replicate_factor", &gphip_ctx::replicate_factor}, {"share_local_panels", &gphip_ctx::share_local_panels},
         {"bcast_chunks", &gphip_ctx::bcast_chunks}, {"bcast_two_hop", &gphip_ctx::bcast_two_hop}, {"dist_panel_df", &gphip_ctx::dist_panel_df}, {"dist_owner_yield", &gphip_ctx::dist_owner_yield},
         {"debug_fail_alloc", &gphip_ctx::debug_fail_alloc}, {"debug_fail_hip", &gphip_ctx::debug_fail_hip},
-        {"debug_abort_word", &gphip_ctx::debug_abort_word},
+        {"debug_abort_word", &gphip_ctx::debug_abort_word}, {"joint_split", &gphip_ctx::joint_split}, {"last_joint_nsplit", &gphip_ctx::joint_nsplit},
     };
     // fault injection ("debug_*") exists for the test-suite only: the names resolve in a process that was started with
     // GPHIP_TEST_HOOKS=1 and nowhere else (not through GPHIP_OPTIONS either: apply_env_options skips them)
@@ -3780,3 +3793,4 @@ int gphip_sync(gphip_handle h) {
 
 #include "gphip_hostlogic.inc"
 #include "gphip_sampler.inc"
+#include "gphip_joint.inc"

@@ -1,0 +1,342 @@
+// gphip_joint.inc -- joint predictive distribution of the current fit (include/gphip.h: gphip_predict_cov, gphip_predict_draws,
+// gphip_predict_logpdf).  Included at the end of gphip.hip.
+//
+//   parent (the fitted handle)   V = L^-1 K(X, X*)    queue_cross + the forward substitution of gphip_predict, all M rows at once
+//                                Z = [z^T; 0]         z = L^-1 r gathered from the factor's rhs tile row
+//   child  (h->joint)            a context whose TRAINING points are X*, same kernel / theta / dtype, y = y* (or 0):
+//                                queue_build         C = K(X*, X*) + nugget (+ jitter), rhs row = y* - m(X*)
+//                                downdate_kernel     C -= [V; z^T] V^T   -> Sigma, rhs row = y* - mu
+//                                queue_factor        L_Sigma, log det Sigma, (y* - mu)^T Sigma^-1 (y* - mu)   (draws / logpdf)
+// The child is made on the first call and kept while M stays the same (its points and y are uploaded again per call); it dies
+// with the parent.  It never runs the fused single-launch evaluation (h->fused_eval: that one builds K inside the factorisation).
+#include "gp_joint.h"
+
+namespace {
+
+constexpr int64_t JOINT_MAX_M = GPHIP_JOINT_MAX_M;
+// default jitter, relative to the prior variance k(x*, x*) + sn^2: far above the rounding of Sigma, and above the factorisation's
+// pivot tolerance (64 eps, pivot_tol_rel) -- fp32: 7.6e-6, so 1e-6 would still leave a smooth latent Sigma "not SPD"
+double joint_jitter_rel(const gphip_ctx* h) { return h->dtype == 64 ? 1e-10 : 1e-4; }
+
+int joint_common_checks(gphip_ctx* h) {
+    if (!has_fit(h)) return fail(h, GPHIP_ERR_STATE, "joint prediction before a successful gphip_fit");
+    if (h->dist_fit) return fail(h, GPHIP_ERR_UNSUPPORTED, "joint prediction from a sharded factor (replicate_factor = 0)");
+    if (h->fit_pw) return fail(h, GPHIP_ERR_UNSUPPORTED, "joint prediction after gphip_fit_pw with a point-dependent nugget / mean");
+    return GPHIP_OK;
+}
+
+int joint_dim_check(gphip_ctx* h, int64_t M) {
+    if (M < 1) return fail(h, GPHIP_ERR_DIM, "M < 1");
+    if (M > JOINT_MAX_M) return fail(h, GPHIP_ERR_DIM, "M above GPHIP_JOINT_MAX_M (all rows of V must be resident at once)");
+    return GPHIP_OK;
+}
+
+int joint_alloc(gphip_ctx* h, void** p, size_t* cap, size_t bytes) {
+    if (bytes <= *cap) return GPHIP_OK;
+    (void)hipFree(*p);
+    *p = nullptr; *cap = 0;
+    HIPCHK(hipMalloc(p, bytes));
+    *cap = bytes;
+    return GPHIP_OK;
+}
+
+// the child context for M test points at Xs with outputs y (nullptr: zeros)
+int joint_child(gphip_ctx* h, const double* Xs, int64_t M, const double* y) {
+    std::vector<double> y0;
+    if (!y) { y0.assign((size_t)M, 0.0); y = y0.data(); }
+    gphip_ctx* c = h->joint;
+    if (c && c->N != M) {
+        gphip_destroy(c);
+        h->joint = c = nullptr;
+    }
+    if (!c) {
+        gphip_handle out = nullptr;
+        std::string why;
+        const int rc = create_ctx(Xs, y, M, h->d, h->custom ? (int)GPHIP_KERNEL_CUSTOM : h->kernel_id, h->mean_id, h->dtype, h->device,
+                                  &out, h->custom ? h->custom_body.c_str() : nullptr, h->ncp, &why);
+        (void)hipSetDevice(h->device);
+        if (rc) return fail(h, rc, ("joint prediction: creating the test-point context failed " + why).c_str());
+        c = h->joint = out;
+        c->kbuild_mfma = 0;                    // K(X*, X*) by the direct build: its diagonal is k(x, x) to the last bit
+    } else {
+        std::vector<double> xt((size_t)h->d * c->Npad, 0.0), yp((size_t)c->Npad, 0.0);
+        for (int64_t i = 0; i < M; ++i) {
+            for (int64_t j = 0; j < h->d; ++j) xt[(size_t)j * c->Npad + i] = Xs[i * h->d + j];
+            yp[(size_t)i] = y[i];
+        }
+        int rc = DISPATCH(c, upload, c, c->dXt, xt, c->stream);
+        if (!rc) rc = DISPATCH(c, upload, c, c->dY, yp, c->stream);
+        if (rc) return fail(h, rc, c->err.c_str());
+    }
+    const int rc = ensure_slots(c, 1);
+    if (rc) return fail(h, rc, c->err.c_str());
+    return GPHIP_OK;
+}
+
+// k(x*, x*) of a run-time compiled kernel averaged over the test points (the default jitter's scale)
+int joint_mean_kss(gphip_ctx* h, int64_t M, int64_t mpad, double* out) {
+    int rc = queue_custom_kss(h, M, mpad, 1);         // (the test points are in dXsT)
+    if (rc) return rc;
+    std::vector<double> k((size_t)M);
+    HIPCHK(hipMemcpyAsync(k.data(), h->dKss, (size_t)M * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    double s = 0.0;
+    for (double v : k) s += v;
+    *out = s / (double)M;
+    return GPHIP_OK;
+}
+
+// C -= [V; z^T] V^T on the child's workspace.  Split rule: while the output tiles (incl. the rhs row) are fewer than two per CU,
+// the contraction is cut into strips of whole 128-columns so that tiles x strips >= 2 per CU; strips are equal but the last.
+template <typename T>
+int queue_downdate(gphip_ctx* h, gphip_ctx* c, int64_t mpad) {
+    DowndateArgs<T> g{};
+    g.C = (T*)c->dA; g.R = (int)c->R;
+    g.V = (const T*)h->dV; g.ldv = (long)mpad; g.Z = (const T*)h->dJZ;
+    g.Mt = (int)(mpad / TB); g.ntri = g.Mt * (g.Mt + 1) / 2; g.ntiles = g.ntri + g.Mt;
+    g.K = (int)h->Npad;
+    const long target = 2l * std::max(h->ncu, 1);
+    const int kt = (int)h->Nt;
+    int nsplit = g.ntiles >= target ? 1 : (int)std::min<long>(kt, (target + g.ntiles - 1) / g.ntiles);
+    if (h->joint_split > 0) nsplit = std::min(h->joint_split, kt);
+    const int strip_tiles = (kt + nsplit - 1) / nsplit;
+    nsplit = (kt + strip_tiles - 1) / strip_tiles;
+    g.kstrip = strip_tiles * TB;
+    h->joint_nsplit = nsplit;
+    if (nsplit > 1) {
+        const int rc = joint_alloc(h, &h->dJPart, &h->jpart_bytes, (size_t)nsplit * g.ntiles * TS * sizeof(T));
+        if (rc) return rc;
+        g.P = (T*)h->dJPart;
+    }
+    c->cs = c->stream;
+    {
+        // algorithmic flops M (M + 1) N (the lower triangle and the rhs row of an M x M downdate of contraction length N)
+        ProfScope ps(c, 4, (double)mpad * (mpad + 1) * (double)h->N, (double)sizeof(T) * (mpad + TB) * (double)h->Npad);
+        hipLaunchKernelGGL(downdate_kernel<T>, dim3((unsigned)g.ntiles, (unsigned)nsplit), dim3(256), GEMM_LDS, c->stream, g);
+        if (nsplit > 1)
+            hipLaunchKernelGGL(downdate_reduce_kernel<T>, dim3((unsigned)g.ntiles, 16), dim3(256), 0, c->stream, (T*)c->dA, (int)c->R,
+                               g.ntri, g.Mt, g.ntiles, (const T*)g.P, nsplit);
+    }
+    return GPHIP_OK;
+}
+
+// Everything up to Sigma in the child's workspace: V and z on the parent, then build + downdate on the child.  The child's
+// diagonal carries k(x*, x*) + (noisy: sn^2) + (*jitter_io, which a negative value turns into the default first).
+int joint_sigma(gphip_ctx* h, const double* Xs, int64_t M, const double* ystar, bool noisy, double* jitter_io) {
+    HIPCHK(hipSetDevice(h->device));
+    const int64_t mpad = (M + TB - 1) / TB * TB, d = h->d;
+    int rc = ensure_vbuf(h, mpad);
+    if (rc) { (void)hipGetLastError(); return fail(h, GPHIP_ERR_HIP, "joint prediction: no device memory for all M rows of V"); }
+    rc = joint_alloc(h, &h->dJZ, &h->jz_bytes, (size_t)TB * h->Npad * h->es);
+    if (rc) return rc;
+    h->cs = h->stream;
+    HIPCHK(hipMemsetAsync(h->dJZ, 0, (size_t)TB * h->Npad * h->es, h->stream));
+    std::vector<double> xt((size_t)d * mpad, 0.0);
+    for (int64_t i = 0; i < M; ++i)
+        for (int64_t j = 0; j < d; ++j) xt[(size_t)j * mpad + i] = Xs[i * d + j];
+    note_test_range(h, xt, M, mpad);
+    rc = DISPATCH(h, upload, h, h->dXsT, xt, h->stream);
+    if (rc) return rc;
+    DISPATCH(h, queue_cross, h, M, mpad, 1);
+    ensure_w64(h);
+    if (df_forward_ok(h, mpad)) launch_dataflow_inverse<double, 64>(h, mpad);
+    else DISPATCH(h, queue_forward_rows, h, mpad, 1);
+    if (h->dtype == 64)
+        hipLaunchKernelGGL(gather_rhs_row_kernel<double>, dim3((unsigned)((h->Npad + 255) / 256)), dim3(256), 0, h->stream,
+                           (const double*)h->dA, (int)h->R, 0, (int)h->Npad, (double*)h->dJZ, (long)TB, 0);
+    else
+        hipLaunchKernelGGL(gather_rhs_row_kernel<float>, dim3((unsigned)((h->Npad + 255) / 256)), dim3(256), 0, h->stream,
+                           (const float*)h->dA, (int)h->R, 0, (int)h->Npad, (float*)h->dJZ, (long)TB, 0);
+    double kss_mean = 0.0;                            // (run-time compiled kernels: k(x*, x*) is a function of the point)
+    if (jitter_io && *jitter_io < 0.0 && h->custom && (rc = joint_mean_kss(h, M, mpad, &kss_mean))) return rc;
+    if ((rc = complete_call(h))) return rc;           // (the forward substitution's abort word)
+    if ((rc = joint_child(h, Xs, M, ystar))) return rc;
+    gphip_ctx* c = h->joint;
+    HIPCHK(hipSetDevice(c->device));
+    invalidate_fit(c);
+    if (!stage_theta(c, 0, h->theta_fit.data())) return fail(h, GPHIP_ERR_ARG, "the fitted theta does not stage");
+    const double sn2 = c->hSlotp[1];
+    if (jitter_io && *jitter_io < 0.0)                // default jitter: relative to the prior variance k(x*, x*) + sn^2
+        *jitter_io = joint_jitter_rel(h) * ((h->custom ? kss_mean : c->hSlotp[SP_KXX]) + sn2);
+    c->hSlotp[1] = (noisy ? sn2 : 0.0) + (jitter_io ? *jitter_io : 0.0);
+    c->hSlotp[SP_MFMA] = 0.0;
+    if ((rc = copy_theta(c, 1))) return fail(h, rc, c->err.c_str());
+    HIPCHK(hipMemsetAsync(c->dInfo, 0, 4, c->stream));
+    c->cs = c->stream;
+    c->theta_packed = false; c->fused_eval = false; c->want_w = false; c->want_u = false;
+    DISPATCH(c, queue_build, c, 1);
+    return DISPATCH(h, queue_downdate, h, c, mpad);
+}
+
+// the child's rhs row -> out[M] (y* = 0: the predictive mean)
+template <typename T>
+int queue_joint_rhs(gphip_ctx* c, int64_t M, double* out) {
+    hipLaunchKernelGGL(joint_rhs_kernel<T>, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, c->stream, (const T*)c->dA, (int)c->R, (int)M,
+                       (const double*)nullptr, out);
+    return GPHIP_OK;
+}
+
+// the child's factorisation; *info as gphip_loglik's
+int joint_factor(gphip_ctx* h, int* info) {
+    gphip_ctx* c = h->joint;
+    DISPATCH(c, queue_factor, c, 1);
+    c->abort_unread = "joint prediction: the factorisation of Sigma timed out (set option dataflow=0 and report)";
+    const int rc = complete_call(c);
+    if (rc) return fail(h, rc, c->err.c_str());
+    *info = c->hInfo[0];
+    return GPHIP_OK;
+}
+
+int joint_download(gphip_ctx* h, gphip_ctx* c, double* dst, const double* src, size_t n) {
+    HIPCHK(hipMemcpyAsync(dst, src, n * 8, hipMemcpyDeviceToHost, c->stream));
+    const int rc = complete_call(c);
+    return rc ? fail(h, rc, c->err.c_str()) : GPHIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gphip_predict_cov(gphip_handle h, const void* Xs, int64_t M, int latent, double* mean, double* cov) {
+    if (!h || !Xs || !mean || !cov) return fail(h, GPHIP_ERR_ARG, "null argument");
+    if (int rc = joint_dim_check(h, M)) return rc;
+    std::lock_guard<std::recursive_mutex> lk(h->mu);
+    if (int rc = joint_common_checks(h)) return rc;
+    if (h->null_fit) {                             // null kernel: k = 0, Sigma = diag(nugget) (latent: 0)
+        for (int64_t i = 0; i < M; ++i) {
+            mean[i] = h->mu_fit;
+            for (int64_t j = 0; j < M; ++j) cov[i * M + j] = (i == j && !latent) ? h->kappa_fit : 0.0;
+        }
+        return GPHIP_OK;
+    }
+    const double* X = static_cast<const double*>(Xs);
+    int rc = joint_sigma(h, X, M, nullptr, !latent, nullptr);
+    if (rc) return rc;
+    gphip_ctx* c = h->joint;
+    rc = joint_alloc(h, (void**)&h->dJOut, &h->jout_bytes, ((size_t)M * M + (size_t)M) * 8);
+    if (rc) return rc;
+    const long n = (long)M * M;
+    if (h->dtype == 64) {
+        hipLaunchKernelGGL(joint_unpack_kernel<double>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const double*)c->dA,
+                           (int)c->R, (int)M, h->dJOut);
+    } else {
+        hipLaunchKernelGGL(joint_unpack_kernel<float>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const float*)c->dA,
+                           (int)c->R, (int)M, h->dJOut);
+    }
+    DISPATCH(c, queue_joint_rhs, c, M, h->dJOut + n);
+    HIPCHK(hipMemcpyAsync(mean, h->dJOut + n, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream));
+    return joint_download(h, c, cov, h->dJOut, (size_t)n);
+}
+
+int gphip_predict_draws(gphip_handle h, const void* Xs, int64_t M, int latent, int S, uint64_t seed, const double* z, double jitter,
+                        double* out, int* info) {
+    if (!h || !Xs || !out || !info) return fail(h, GPHIP_ERR_ARG, "null argument");
+    if (!std::isfinite(jitter)) return fail(h, GPHIP_ERR_ARG, "non-finite jitter");
+    if (int rc = joint_dim_check(h, M)) return rc;
+    if (S < 1) return fail(h, GPHIP_ERR_DIM, "S < 1");
+    std::lock_guard<std::recursive_mutex> lk(h->mu);
+    if (int rc = joint_common_checks(h)) return rc;
+    *info = GPHIP_INFO_OK;
+    const size_t total = (size_t)S * (size_t)M;
+    if (h->null_fit) {                             // Sigma = diag(nugget) (latent: 0) + jitter: independent draws
+        const double jit = jitter < 0.0 ? joint_jitter_rel(h) * h->kappa_fit : jitter;
+        const double v = (latent ? 0.0 : h->kappa_fit) + jit;
+        if (!(v > 0.0)) {
+            *info = GPHIP_INFO_NOT_SPD;
+            for (size_t e = 0; e < total; ++e) out[e] = NAN;
+            return GPHIP_OK;
+        }
+        const double sd = std::sqrt(v);
+        for (int s = 0; s < S; ++s)
+            for (int64_t j = 0; j < M; ++j) {
+                const double zz = z ? z[(size_t)s * M + j] : philox_normal(seed, (uint32_t)s, (uint32_t)j);
+                out[(size_t)s * M + j] = h->mu_fit + sd * zz;
+            }
+        for (size_t e = 0; e < total; ++e)
+            if (!std::isfinite(out[e])) *info = GPHIP_INFO_NAN;
+        return GPHIP_OK;
+    }
+    const double* X = static_cast<const double*>(Xs);
+    double jit = jitter;
+    int rc = joint_sigma(h, X, M, nullptr, !latent, &jit);
+    if (rc) return rc;
+    gphip_ctx* c = h->joint;
+    const int64_t mpad = (M + TB - 1) / TB * TB;
+    // the mean (rhs row = -mu with y* = 0) before the factorisation overwrites that row
+    rc = joint_alloc(h, (void**)&h->dJOut, &h->jout_bytes, (size_t)mpad * 8);
+    if (rc) return rc;
+    DISPATCH(c, queue_joint_rhs, c, M, h->dJOut);
+    int inf = 0;
+    if ((rc = joint_factor(h, &inf))) return rc;
+    if (inf != 0) {
+        *info = inf;
+        for (size_t e = 0; e < total; ++e) out[e] = NAN;
+        return GPHIP_OK;
+    }
+    // draws in chunks of at most ~512 MiB of Z and of out each
+    const int sc = (int)std::max<int64_t>(1, std::min<int64_t>(S, ((int64_t)1 << 26) / mpad));
+    double* dZ = nullptr;
+    double* dOut = nullptr;
+    auto cleanup = [&]() { (void)hipFree(dZ); (void)hipFree(dOut); };
+    if (hipMalloc((void**)&dZ, (size_t)sc * mpad * 8) != hipSuccess || hipMalloc((void**)&dOut, (size_t)sc * M * 8) != hipSuccess) {
+        (void)hipGetLastError();
+        cleanup();
+        return fail(h, GPHIP_ERR_HIP, "joint prediction: no device memory for the draws");
+    }
+    std::vector<double> zh;
+    for (int s0 = 0; s0 < S && !rc; s0 += sc) {
+        const int ns = std::min(sc, S - s0);
+        if (z) {
+            zh.assign((size_t)ns * mpad, 0.0);
+            for (int s = 0; s < ns; ++s)
+                for (int64_t j = 0; j < M; ++j) zh[(size_t)s * mpad + j] = z[(size_t)(s0 + s) * M + j];
+            if (hipMemcpyAsync(dZ, zh.data(), zh.size() * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess) { rc = GPHIP_ERR_HIP; break; }
+        } else {
+            const long n = (long)ns * mpad;
+            hipLaunchKernelGGL(joint_normal_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, dZ, (long)mpad, ns, (int)M,
+                               s0, (uint64_t)seed);
+        }
+        const dim3 grid((unsigned)((M + JT_B - 1) / JT_B), (unsigned)((ns + JT_B - 1) / JT_B));
+        if (h->dtype == 64)
+            hipLaunchKernelGGL(joint_trmm_kernel<double>, grid, dim3(256), 0, c->stream, (const double*)c->dA, (int)c->R, (int)M,
+                               (const double*)dZ, (long)mpad, ns, (const double*)h->dJOut, dOut, (long)M);
+        else
+            hipLaunchKernelGGL(joint_trmm_kernel<float>, grid, dim3(256), 0, c->stream, (const float*)c->dA, (int)c->R, (int)M,
+                               (const double*)dZ, (long)mpad, ns, (const double*)h->dJOut, dOut, (long)M);
+        rc = joint_download(h, c, out + (size_t)s0 * M, dOut, (size_t)ns * M);
+    }
+    if (rc == GPHIP_ERR_HIP && h->err.empty()) h->err = "joint prediction: copying the normals failed";
+    cleanup();
+    if (rc) return rc;
+    for (size_t e = 0; e < total; ++e)
+        if (!std::isfinite(out[e])) { *info = GPHIP_INFO_NAN; break; }
+    return GPHIP_OK;
+}
+
+int gphip_predict_logpdf(gphip_handle h, const void* Xs, int64_t M, const double* ystar, double* out, int* info) {
+    if (!h || !Xs || !ystar || !out || !info) return fail(h, GPHIP_ERR_ARG, "null argument");
+    if (int rc = joint_dim_check(h, M)) return rc;
+    std::lock_guard<std::recursive_mutex> lk(h->mu);
+    if (int rc = joint_common_checks(h)) return rc;
+    for (int64_t j = 0; j < M; ++j)
+        if (!std::isfinite(ystar[j])) { *out = NAN; *info = GPHIP_INFO_NAN; return GPHIP_OK; }
+    if (h->null_fit) {                             // independent normals N(mu, nugget)
+        const double v = h->kappa_fit;
+        double q = 0.0;
+        for (int64_t j = 0; j < M; ++j) q += (ystar[j] - h->mu_fit) * (ystar[j] - h->mu_fit) / v;
+        *out = -0.5 * ((double)M * LOG_TWO_PI + (double)M * std::log(v) + q);
+        *info = v > 0.0 ? (std::isfinite(*out) ? GPHIP_INFO_OK : GPHIP_INFO_NAN) : GPHIP_INFO_NOT_SPD;
+        return GPHIP_OK;
+    }
+    int rc = joint_sigma(h, static_cast<const double*>(Xs), M, ystar, true, nullptr);
+    if (rc) return rc;
+    int inf = 0;
+    if ((rc = joint_factor(h, &inf))) return rc;
+    const gphip_ctx* c = h->joint;
+    const double logdet = c->hRes[0], quad = c->hRes[1];
+    *out = -0.5 * ((double)M * LOG_TWO_PI + logdet + quad);
+    *info = inf != 0 ? inf : (std::isfinite(*out) ? GPHIP_INFO_OK : GPHIP_INFO_NAN);
+    return GPHIP_OK;
+}
+
+}  // extern "C"

@@ -502,6 +502,95 @@ def _predict_samples(handle, points, weights, P, nugget_fn=None, mean_fn=None, X
     return {"Points": P, "Weights": weights, "Mean": mean, "StandardDeviation": sd}
 
 
+def _direct_handle(examples, kernel, theta, meanFunction):
+    """(handle fitted at theta, X) for the direct forms below; None when the data are not GP data or theta does not factor."""
+    norm = dataNormalForm(examples)
+    if norm is None or not isinstance(norm, tuple) or norm[1].shape[1] != 1:
+        return None
+    mean = "zero" if meanFunction in (None, 0, "Zero", "zero") else "const"
+    handle = _lib.Handle(norm[0], norm[1][:, 0], _resolve_kernel(kernel), mean)
+    if handle.fit(np.asarray(theta, dtype=np.float64).ravel()) != 0:
+        handle.close()
+        return None
+    return handle
+
+
+def predictJointFromGaussianProcess(examples, pts, kernel, theta, meanFunction=None):
+    """Joint form of the direct predictFromGaussianProcess((X, Y), pts, kernel, theta[, meanFunction]): duplicates in pts are
+    removed first (as BGP:380), then {"Points" [M,d], "Mean" [M], "Covariance" [M,M]} -- the MultinormalDistribution of noisy
+    observations at the points, whose diagonal is the per-point variance of predictFromGaussianProcess.  None on bad data or a
+    theta whose covariance matrix does not factor."""
+    P = dataNormalForm(pts)
+    if P is None or isinstance(P, tuple):
+        return None
+    _, first = np.unique(P, axis=0, return_index=True)
+    P = P[np.sort(first)]
+    handle = _direct_handle(examples, kernel, theta, meanFunction)
+    if handle is None:
+        return None
+    try:
+        mean, cov = handle.predict_cov(P, latent=False)
+    finally:
+        handle.close()
+    return {"Points": P, "Mean": mean, "Covariance": cov}
+
+
+def predictiveLogDensity(examples, heldout, kernel, theta, meanFunction=None):
+    """log N(ys | mean, Covariance) of held-out data heldout = (Xs, ys) under the GP of (X, Y) at theta: the joint predictive
+    log density (the correlations between the held-out points included).  None on bad data or a failed factorisation."""
+    P = dataNormalForm(heldout[0])
+    if P is None or isinstance(P, tuple):
+        return None
+    ys = np.asarray(heldout[1], dtype=np.float64).ravel()
+    if ys.shape != (len(P),):
+        return None
+    handle = _direct_handle(examples, kernel, theta, meanFunction)
+    if handle is None:
+        return None
+    try:
+        value, info = handle.predict_logpdf(P, ys)
+    finally:
+        handle.close()
+    return value if info == 0 else None
+
+
+def gaussianProcessFunctionSamples(obj, pts, n: int, seed: int = 0, latent: bool = True):
+    """n draws of the function values at pts from the posterior MIXTURE of a sampled GP object: each draw picks a theta from
+    "Samples" by CrudePosteriorWeight (numpy generator seeded by `seed`), then the values come from the joint predictive
+    distribution of that theta (one fit and one gphip_predict_draws per distinct theta).  latent = True: draws of f;
+    False: of noisy observations.  Returns {"Points" [M,d], "Sample" [n] (index into "Samples"), "Values" [n,M]}; rows of a
+    theta that does not factor are NaN.  None for an unsampled object and for objects with a point-dependent nugget or
+    mean function (not supported by the joint path).  pts may be an int > 1 as for predictFromGaussianProcess."""
+    if not isinstance(obj, inferenceObject) or obj.failed or "GaussianProcessData" not in obj or "Samples" not in obj:
+        return None
+    mf = obj["GaussianProcessData"]["ModelFunctions"]
+    if callable(mf["NuggetFunction"]) or callable(mf["MeanFunction"]):
+        return None
+    X = obj["Data"][0]
+    if isinstance(pts, (int, np.integer)):
+        if pts <= 1 or X.shape[1] != 1:
+            return None
+        pts = np.linspace(X.min(), X.max(), int(pts))
+    P = dataNormalForm(pts)
+    if P is None or isinstance(P, tuple) or int(n) < 1:
+        return None
+    handle = obj["GaussianProcessData"]["HIPHandle"]
+    samples = obj["Samples"]
+    points = np.array([s["Point"] for s in samples], dtype=np.float64)
+    w = np.array([s["CrudePosteriorWeight"] for s in samples], dtype=np.float64)
+    which = np.random.default_rng(seed).choice(len(samples), size=int(n), p=w / w.sum())
+    values = np.full((int(n), len(P)), np.nan)
+    for k in np.unique(which):
+        rows = np.flatnonzero(which == k)
+        if handle.fit(points[k]) != 0:
+            continue
+        key = int(np.random.SeedSequence([int(seed) & (2**63 - 1), int(k)]).generate_state(1, np.uint64)[0])
+        out, info = handle.predict_draws(P, len(rows), seed=key, latent=latent)
+        if info == 0:
+            values[rows] = out
+    return {"Points": P, "Sample": which, "Values": values}
+
+
 def mixture_moments(pred: Mapping):
     """Mean and variance of the per-point MixtureDistribution (what regressionPlot1D draws, BV:310-374)."""
     w = np.asarray(pred["Weights"], dtype=np.float64)

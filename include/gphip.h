@@ -11,6 +11,7 @@
  *   gphip_cross_covariance  compiledKandKappa[points1, kernel, nugget][X*]     BGP:63-124
  *   gphip_predict       predictFromGaussianProcessInternal                 BGP:396-422
  *   gphip_predict_samples  predictFromGaussianProcess over all samples     BGP:343-376
+ *   gphip_predict_cov / _draws / _logpdf  the joint N(mu, Sigma) of the test points (no reference counterpart)
  *   gphip_*_pw          the same with point-dependent nugget[x] / mean[x]  BGP:37, 113, 171, 300, 408
  *   gphip_covariance    "CovarianceFunction" = compiledCovarianceMatrix    BGP:45-61
  *   gphip_solve         "InverseCovarianceFunction"[theta]["Inverse"][b]   BGP:130-141
@@ -190,6 +191,33 @@ int gphip_predict(gphip_handle h, const void* Xs, int64_t M, double* mean, doubl
  * are factored and solved in one batched pass (one workspace slot per sample). */
 int gphip_predict_samples(gphip_handle h, const double* Thetas, int S, int p, const void* Xs, int64_t M,
                           double* mean, double* var, int* info);
+/* ---- Joint predictive distribution of the current fit (no reference counterpart: the reference stops at the marginals of
+ * gphip_predict).  Sigma = k(X*,X*) + [latent ? 0 : diag(sn^2)] - k*^T K^-1 k*, the full M x M covariance:
+ *   latent = 0: of noisy observations (diag(cov) == gphip_predict's var, up to the order of summation);
+ *   latent = 1: of the latent function f.
+ * On the device: V = L^-1 k* (the forward substitution of gphip_predict, all M rows at once), then C -= [V; z^T] V^T on a
+ * tile-major M x M workspace (z = L^-1 r: the same launch turns y* - m(X*) into y* - mu), then -- draws / log density -- the
+ * library's own Cholesky of Sigma.  Work on the fitted handle like gphip_predict and never invalidate its fit.
+ * Supported: every kernel of the library (named, composed, run-time compiled; the null kernel on the host: Sigma =
+ * diag(sn^2), or 0 when latent), fp64 and fp32 handles, and a multi-device handle whose first device holds the whole factor
+ * (it computes there).  GPHIP_ERR_STATE: no successful fit.  GPHIP_ERR_UNSUPPORTED: a sharded fit with replicate_factor = 0,
+ * and a fit made by gphip_fit_pw with a non-NULL array.  GPHIP_ERR_DIM: M < 1 or M > GPHIP_JOINT_MAX_M (every row of V,
+ * M x Npad elements, is resident at once).  Xs: row-major M x d fp64. */
+#define GPHIP_JOINT_MAX_M 16384
+/* mean[M] (= gphip_predict's mean); cov row-major M x M, both triangles, exactly symmetric. */
+int gphip_predict_cov(gphip_handle h, const void* Xs, int64_t M, int latent, double* mean, double* cov);
+/* S draws from N(mean, Sigma), row-major S x M: out[s] = mean + chol(Sigma + jitter I) z_s.
+ * z == NULL: z_s(j) standard normals made on the device by a counter-based generator (Philox4x32-10, Box-Muller) keyed by
+ *            (seed, s, j) only -- the first S rows of a call with S' > S are bit-identical to a call with S.
+ * z != NULL: the caller's normals, row-major S x M.
+ * jitter < 0: the default, 1e-10 (fp64) / 1e-4 (fp32) x (mean of k(x*,x*) over the test points + sn^2) -- above the
+ *            factorisation's pivot tolerance of 64 eps; 0 = none.
+ * *info = GPHIP_INFO_NOT_SPD if Sigma + jitter I does not factor (out = NaN), GPHIP_INFO_NAN on non-finite results. */
+int gphip_predict_draws(gphip_handle h, const void* Xs, int64_t M, int latent, int S, uint64_t seed, const double* z,
+                        double jitter, double* out, int* info);
+/* log N(ystar | mean, Sigma) with the noisy-observation Sigma (latent = 0): the joint predictive log density of held-out
+ * data.  *info as gphip_loglik's (*out undefined if *info != 0). */
+int gphip_predict_logpdf(gphip_handle h, const void* Xs, int64_t M, const double* ystar, double* out, int* info);
 /* ---- Point-dependent nugget and mean functions.  The reference evaluates nugget[points[[i]]] (BGP:37), meanFunction /@
  * inputData (BGP:171, 300), kernel[p, p] + nugget[p] at the test points (BGP:113) and meanFunction /@ inputs (BGP:408) for
  * ANY functions of the point (heteroscedastic noise, any m(x)).  Those functions live on the host (WL / Python); the host
