@@ -47,6 +47,37 @@ struct ProfRec {
     double flops, bytes;
 };
 
+// One device (or pinned host) allocation that knows its size and frees itself: every buffer a context owns is one of these.
+struct Buf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    bool pinned = false;                       // hipHostMalloc'd host memory
+    Buf() = default;
+    Buf(const Buf&) = delete;
+    Buf& operator=(const Buf&) = delete;
+    ~Buf() { release(); }
+    template <typename T> T* as() const { return static_cast<T*>(p); }
+    void release() {
+        if (p) (void)(pinned ? hipHostFree(p) : hipFree(p));
+        p = nullptr;
+        bytes = 0;
+    }
+    // at least `want` bytes, contents not kept: frees first, then allocates exactly `want`.  On failure the buffer is empty
+    // and the error is returned (HIP's last-error state is left to the caller).
+    hipError_t grow(size_t want, bool host = false) {
+        if (want <= bytes) return hipSuccess;
+        release();
+        pinned = host;
+        const hipError_t e = host ? hipHostMalloc(&p, want) : hipMalloc(&p, want);
+        if (e != hipSuccess) {
+            p = nullptr;
+            return e;
+        }
+        bytes = want;
+        return hipSuccess;
+    }
+};
+
 }  // namespace
 
 struct gphip_ctx {
@@ -73,11 +104,11 @@ struct gphip_ctx {
     int cgrad_state = 0;
     int custom_grad = 1;                         // option: 0 = always central differences of the likelihood
     int grad_analytic = 0;                       // read-only: the last gphip_loglik_grad used the one-factorisation route
-    double *dCustomP = nullptr, *hCustomP = nullptr;   // [slot][ncp]
-    double* dKss = nullptr; size_t kss_cap = 0;  // k(x*, x*) of the current test points, [slot][mpad]
+    Buf dCustomP, hCustomP;                      // double [slot][ncp]
+    Buf dKss;                                    // double: k(x*, x*) of the current test points, [slot][mpad]
     int panel_df = -1;                           // one-GPU look-ahead schedule, one theta, fp64: every outer panel as ONE fused dataflow launch
-    void* dW64s = nullptr; size_t w64s_bytes = 0;                  // gphip_predict_samples: 64-block inverses of every slot (samples_forward_df)
-    double* dGpart = nullptr; size_t gpart_bytes = 0, ngacc = 0;   // gradient reduction: per-workgroup accumulator rows (grad_rows)
+    Buf dW64s;                                                     // gphip_predict_samples: 64-block inverses of every slot (samples_forward_df)
+    Buf dGpart; size_t ngacc = 0;                                  // gradient reduction: per-workgroup accumulator rows, double (grad_rows)
     int dist_owner_yield = -1;                   // sharded schedule: the owner's trailing updates wait for its panel launch (-1 = from 4 ranks)
     int dist_panel_df = -1;                      // sharded evaluation, fp64: the owner factors its outer panel as ONE 64-tile dataflow launch
                                                  // (1), which also applies the look-ahead update (2), and hands its tile columns to the
@@ -91,7 +122,7 @@ struct gphip_ctx {
     // dist_panel_df = 3: a dataflow panel launch counts finished tiles per tile column (DfArgs::colsig); the owner's communication
     // stream waits for a column's count with hipStreamWaitValue32.  Counters are cumulative over the panels of one evaluation
     // (zeroed in gphip_dist_begin): the target of a wait = everything counted before + the column's own tiles.
-    unsigned int* dColSig = nullptr;                 // [64] counters (the first `panel` are used)
+    Buf dColSig;                                     // unsigned int [64] counters (the first `panel` are used)
     unsigned int colsig_target[64] = {0};
     std::vector<std::pair<unsigned int*, unsigned int>>* col_waits = nullptr;   // where gphip_dist_factor_panel reports (address, target) per tile column
     int fuse_potrf = 1;                          // option: panel-stream updates factor the diagonal tile they have just updated
@@ -110,13 +141,12 @@ struct gphip_ctx {
     KSpec ks{0, 0, 0, 0};
     int nl2 = 0;                       // length scales of term 2 (0: no second term)
     bool has_a1 = false, has_a2 = false;
-    void* dXs2 = nullptr;              // typed [slots][d][Npad]: inputs scaled by term 2's length scales
-    void* dXsS2 = nullptr;             // typed [vcap][d]: test points scaled by term 2's length scales
-    double *dInvEll2 = nullptr, *hInvEll2 = nullptr;
-    double *dNullMu = nullptr, *dNullOut = nullptr;          // null-kernel path: per-theta mu and the two sums
-    int null_cap = 0;
-    void *dXt = nullptr, *dY = nullptr;                     // typed: [d][Npad], [Npad]
-    double* dExp2 = nullptr;                                // [EXP_TAB] 2^(j/512): the kernel build's exp table
+    Buf dXs2;                          // typed [slots][d][Npad]: inputs scaled by term 2's length scales
+    Buf dXsS2;                         // typed [vcap][d]: test points scaled by term 2's length scales
+    Buf dInvEll2, hInvEll2;            // double
+    Buf dNullMu, dNullOut;                                  // double: null-kernel path: per-theta mu and the two sums
+    Buf dXt, dY;                                            // typed: [d][Npad], [Npad]
+    Buf dExp2;                                              // double [EXP_TAB] 2^(j/512): the kernel build's exp table
     // Kernel build with the distance cross term on the matrix pipe (kbuild_mfma_kernel): mid-range and half range of the
     // training inputs per dimension.  A theta's slot goes to that kernel while sum_k (half_k / l_k)^2 <= kbuild_mfma_bound
     // (fp32: / 8) -- the rounding error of its squared distances grows with that sum (gp_kernels.h); above it, and for every
@@ -130,23 +160,21 @@ struct gphip_ctx {
     // it the difference no longer shrinks with B -- table exponential, other summation order), so at the default 1e-9
     // a theta routed to the MFMA form stays within 1.5e-10 of the direct form.  The ill-conditioned theta (near-duplicate
     // points, small nugget) go to the direct form, whose error is eps r^2 k_ij.
-    double* dCentre = nullptr;                              // [d]
+    Buf dCentre;                                            // double [d]
     std::vector<double> x_centre, x_half;
     int kbuild_mfma = 1, kbuild_mfma_bound = 512, kbuild_mfma_digits = 9;
     double test_ratio = 0.0;                                // current test points: largest |x* - centre| / half range over the dimensions
     // batch workspace
     int slots = 0;
-    void *dA = nullptr, *dXs = nullptr, *dW = nullptr;      // typed
-    void* dDinv = nullptr;                                  // typed [slots][2 Nt][4][16 x 16]: DfArgs::D
-    void* dW64 = nullptr;                                   // typed [2 Nt][64 x 64]: the 64-block inverses of a single-launch factorisation
+    Buf dA, dXs, dW;                                        // typed
+    Buf dDinv;                                              // typed [slots][2 Nt][4][16 x 16]: DfArgs::D
+    Buf dW64;                                               // typed [2 Nt][64 x 64]: the 64-block inverses of a single-launch factorisation
                                                             // whose caller substitutes afterwards (fit, gradient); dW then takes the 128-blocks
     unsigned long w64_gen = ~0ul;                           // ws_gen of the factor dW64 belongs to
-    void *dLT = nullptr, *dW64T = nullptr;                  // typed: the factor / the 64-block inverses with every 64 x 64 block transposed in place
+    Buf dLT, dW64T;                                         // typed: the factor / the 64-block inverses with every 64 x 64 block transposed in place
     unsigned long lt_gen = ~0ul;                            // (gphip_solve's backward launch, DfArgs::LT); ws_gen of the factor they were made from
-    double *dInvEll = nullptr, *dSlotp = nullptr, *dPartial = nullptr, *dRes = nullptr;
-    int* dInfo = nullptr;
-    double *hInvEll = nullptr, *hSlotp = nullptr, *hRes = nullptr;
-    int* hInfo = nullptr;
+    Buf dInvEll, dSlotp, dPartial, dRes, dInfo;             // double, dInfo int
+    Buf hInvEll, hSlotp, hRes, hInfo;                       // pinned: double, hInfo int
     // options
     int panel = 4, profile = 0, swizzle = 1, max_slots = 256, lookahead = 1;
     int supertile = 2;                 // trailing SYRK tile order: 0 column-major chunks per XCD, 2 the tile LIST in 8x8 super-tile order,
@@ -176,8 +204,8 @@ struct gphip_ctx {
     bool want_w = false;                         // the caller substitutes with W_b afterwards (fit / predict / gradient)
     bool want_u = false, u_ready = false;        // gradient: a single-launch factorisation is followed by the inverse launch of the same
                                                  // kernel (U = L^-T into dV, see DfArgs::U); u_ready: it ran for the current factor
-    int* dFlags = nullptr;                       // [slots][(Nt+1)^2] ready flags (value = epoch)
-    unsigned long long* dTicket = nullptr;       // task ticket counter (+ abort flag in the next word)
+    Buf dFlags;                                  // int [slots][(Nt+1)^2] ready flags (value = epoch)
+    Buf dTicket;                                 // unsigned long long: task ticket counter (+ abort flag in the next word)
     const char* abort_unread = nullptr;          // a launch without a finalize behind it left the abort word to the call: its error text
     unsigned long long ticket_base = 0;
     int epoch = 0;
@@ -191,21 +219,20 @@ struct gphip_ctx {
     unsigned long ws_gen = 0, fit_gen = ~0ul, fit_id = 0;
     double logdet_fit = 0, mu_fit = 0, kappa_fit = 0;
     // prediction / solve scratch
-    void *dV = nullptr, *dXsT = nullptr, *dXsS = nullptr;   // typed
-    double *dMean = nullptr, *dVar = nullptr;
-    double* dPart = nullptr;                                 // strip partials of the prediction epilogue
-    size_t part_cap = 0;
+    Buf dV, dXsT, dXsS;                                      // typed
+    Buf dMean, dVar;                                         // double
+    Buf dPart;                                               // double: strip partials of the prediction epilogue
     int64_t vcap = 0;
-    void* dAlpha = nullptr;                                  // typed [Npad] (gradient)
+    Buf dAlpha;                                              // typed [Npad] (gradient)
     // single-vector substitutions (gp_trsv.h): input block + two passes of {solution, chain copy, row sums, ticket} (trsv_pass_elems)
-    void* dTrsvX = nullptr;
-    void* dRows = nullptr; size_t rows_cap = 0;              // gphip_solve, few vectors on the GEMM path: [mc][Npad] staging block (rows_to_vblock_kernel)
-    void* dTrsvP = nullptr;                                  // typed [2 directions][2 gaps][Nt][128 x 128]: the chain's products (trsv_prep_kernel)
+    Buf dTrsvX;
+    Buf dRows;                                               // gphip_solve, few vectors on the GEMM path: [mc][Npad] staging block (rows_to_vblock_kernel)
+    Buf dTrsvP;                                              // typed [2 directions][2 gaps][Nt][128 x 128]: the chain's products (trsv_prep_kernel)
     unsigned long trsvp_gen = ~0ul;                          // ws_gen of the factor they were made from
     int trsv = 1;                                            // option: gphip_solve with <= 4 right-hand sides and alpha through trsv_dataflow_kernel
     int ncu = 0;                                             // compute units of the device
-    void* dKinv = nullptr;                                   // typed [(Npad + GRAD_LD_PAD) x Npad] lower tiles of K^-1 (gradient, potri route)
-    double* dGacc = nullptr;                                 // [d + 2] gradient accumulators
+    Buf dKinv;                                               // typed [(Npad + GRAD_LD_PAD) x Npad] lower tiles of K^-1 (gradient, potri route)
+    Buf dGacc;                                               // double [d + 2] gradient accumulators
     // profiling
     std::vector<ProfRec> recs;
     std::vector<hipEvent_t> pool;
@@ -217,11 +244,9 @@ struct gphip_ctx {
     struct gphip_group* group = nullptr;
     int shard_min_n = 16384;                     // one factorisation is sharded over the group's devices from this N on
     hipStream_t cstream = nullptr;               // communication stream (panel broadcasts), group members only
-    void* packed[3] = {nullptr, nullptr, nullptr};   // rotating packed-panel buffers, group members only
-    size_t packed_bytes = 0;
-    double* dScal8 = nullptr;                    // 8 doubles for the scalar all-reduces (multi-process groups)
-    void* drain_buf = nullptr;                   // scratch a draining member broadcasts through (group_drain_buf)
-    size_t drain_bytes = 0;
+    Buf packed[3];                               // rotating packed-panel buffers, group members only
+    Buf dScal8;                                  // 8 doubles for the scalar all-reduces (multi-process groups)
+    Buf drain_buf;                               // scratch a draining member broadcasts through (group_drain_buf)
     int last_issue_us = 0;                       // read-only: host microseconds the last sharded evaluation spent issuing its schedule
     int debug_fail_hip = 0;                      // tests: make the n-th checked HIP call of the next collective sequence fail
     int fit_rank = 0, fit_world = 0;             // the layout a distributed fit was made in
@@ -231,15 +256,14 @@ struct gphip_ctx {
     // workspace; 1: the dense workspace dA (every received panel is received in place: all ranks end up with all of L).
     int replicate_factor = 0;
     int share_local_panels = 1;                  // virtual ranks on the owner's GPU read a factored panel where the owner keeps it
-    void* dOwn = nullptr;                        // typed compact own-panel storage
-    size_t own_bytes = 0;
+    Buf dOwn;                                    // typed compact own-panel storage
     void* dist_base = nullptr;                   // dOwn or dA: base of the storage the current sharded evaluation runs in
     std::vector<long> dist_adj;                  // [nouter + 1] tiles to add to a dense tile index of panel slot q (owned slots)
-    long* dDistAdj = nullptr;                    // device copy; null while every entry is 0 (dense)
+    Buf dDistAdj;                                // long: device copy; null while every entry is 0 (dense)
     int lay_rank = -1, lay_world = 0, lay_panel = 0, lay_full = -1;   // what dist_adj / dOwn were laid out for
     void* ws_override = nullptr;                 // tl<T>() / queue_panel address this base instead of dA (one owned panel)
     bool dist_fit = false;                       // the factor of theta_fit is spread over the ranks (owned panels only)
-    void* dZ = nullptr;                          // typed [Npad]: z = L^-1 r gathered while the panels stream by (sharded prediction)
+    Buf dZ;                                      // typed [Npad]: z = L^-1 r gathered while the panels stream by (sharded prediction)
     bool z_vector = false;                       // the prediction epilogue reads z from dZ (set only inside predict_streamed)
     bool null_fit = false;                       // fitted state of a null-kernel handle (no factor: K = diag(sn^2))
     // Point-dependent nugget / mean of the CURRENT call (gphip_*_pw, BGP:37, 113, 300, 408): host rows [B][N] (training
@@ -247,18 +271,17 @@ struct gphip_ctx {
     const double *pw_mean_host = nullptr, *pw_nug_host = nullptr;
     const double *pw_mean_test = nullptr, *pw_nug_test = nullptr;
     long pw_test_stride = 0;                     // elements between the samples' rows of pw_*_test
-    void *dPwMean = nullptr, *dPwNug = nullptr;  // typed [pw_cap][Npad]
-    int pw_cap = 0;
+    Buf dPwMean, dPwNug;                         // typed [max(slots, nb)][Npad] (upload_pw)
     bool pw_mean_on = false, pw_nug_on = false;  // queue_build reads the device copies
-    double *dPwMeanT = nullptr, *dPwNugT = nullptr;   // [vcap] test-point values of the current prediction chunk
+    Buf dPwMeanT, dPwNugT;                            // double [vcap] test-point values of the current prediction chunk
     std::vector<double> null_diag, null_mean_test;    // fitted null kernel with a point-dependent nugget: the diagonal
     std::vector<double> fit_pw_mean, fit_pw_nug;      // the point-dependent arrays a DISTRIBUTED fit was made with (local refit)
     bool fit_pw = false;                              // the resident fit came from gphip_fit_pw with a non-null array
     // joint prediction (gphip_joint.inc): the child context whose training points are the test points, and its scratch
     gphip_ctx* joint = nullptr;
-    void* dJZ = nullptr; size_t jz_bytes = 0;         // typed [Npad][128]: row 0 = z = L^-1 r, the downdate's rhs-row operand
-    void* dJPart = nullptr; size_t jpart_bytes = 0;   // typed [strip][tile][128 x 128]: the downdate's strip partials
-    double* dJOut = nullptr; size_t jout_bytes = 0;   // dense covariance + mean / the draws' mean
+    Buf dJZ;                                          // typed [Npad][128]: row 0 = z = L^-1 r, the downdate's rhs-row operand
+    Buf dJPart;                                       // typed [strip][tile][128 x 128]: the downdate's strip partials
+    Buf dJOut;                                        // double: dense covariance + mean / the draws' mean
     int joint_split = 0;                              // option: strips of the downdate's contraction (0 = by the split rule)
     int joint_nsplit = 0;                             // read-only: strips the last downdate used
 };
@@ -350,25 +373,13 @@ void harvest(gphip_ctx* h) {   // call after stream sync
 }
 
 void free_slots(gphip_ctx* h) {
-    (void)hipFree(h->dA); (void)hipFree(h->dXs); (void)hipFree(h->dInvEll); (void)hipFree(h->dSlotp);
-    (void)hipFree(h->dW); (void)hipFree(h->dPartial); (void)hipFree(h->dRes); (void)hipFree(h->dInfo);
-    (void)hipFree(h->dFlags); (void)hipFree(h->dTicket); (void)hipFree(h->dW64); (void)hipFree(h->dDinv); (void)hipFree(h->dLT); (void)hipFree(h->dW64T);
-    h->dW64 = h->dDinv = h->dLT = h->dW64T = nullptr; h->w64_gen = h->lt_gen = ~0ul;
-    (void)hipFree(h->dPwMean); (void)hipFree(h->dPwNug);
-    h->dPwMean = h->dPwNug = nullptr; h->pw_cap = 0;
-    (void)hipFree(h->dXs2); (void)hipFree(h->dInvEll2); (void)hipHostFree(h->hInvEll2);
-    h->dXs2 = nullptr; h->dInvEll2 = h->hInvEll2 = nullptr;
-    (void)hipFree(h->dCustomP); (void)hipHostFree(h->hCustomP);
-    h->dCustomP = h->hCustomP = nullptr;
-    h->dFlags = nullptr; h->dTicket = nullptr; h->ticket_base = 0;
-    (void)hipHostFree(h->hInvEll); (void)hipHostFree(h->hSlotp); (void)hipHostFree(h->hRes);
-    (void)hipHostFree(h->hInfo);
-    if (h->dist_base == h->dA) { h->dist_base = nullptr; if (h->lay_full == 1) { h->lay_rank = -1; h->lay_full = -1; } }
-    h->dA = h->dXs = h->dW = nullptr;
-    h->dInvEll = h->dSlotp = h->dPartial = h->dRes = nullptr;
-    h->dInfo = nullptr;
-    h->hInvEll = h->hSlotp = h->hRes = nullptr;
-    h->hInfo = nullptr;
+    if (h->dist_base == h->dA.p) { h->dist_base = nullptr; if (h->lay_full == 1) { h->lay_rank = -1; h->lay_full = -1; } }
+    for (Buf* b : {&h->dA, &h->dXs, &h->dW, &h->dDinv, &h->dInvEll, &h->dXs2, &h->dInvEll2, &h->dSlotp, &h->dPartial, &h->dRes,
+                   &h->dInfo, &h->dFlags, &h->dTicket, &h->dCustomP, &h->dPwMean, &h->dPwNug, &h->dW64, &h->dLT, &h->dW64T,
+                   &h->hInvEll, &h->hInvEll2, &h->hSlotp, &h->hCustomP, &h->hRes, &h->hInfo})
+        b->release();
+    h->w64_gen = h->lt_gen = ~0ul;
+    h->ticket_base = 0;
     h->slots = 0;
     invalidate_fit(h);                         // (a distributed fit keeps its block inverses / scalars in these buffers too)
 }
@@ -381,16 +392,16 @@ size_t slot_bytes(const gphip_ctx* h) {
 // workspace = false (sharded evaluations of a rank that keeps only its own panels): everything a slot needs EXCEPT the
 // workspace matrix itself (scaled inputs, block inverses, scalars, flags)
 int ensure_slots(gphip_ctx* h, int want, bool workspace = true) {
-    if (want <= h->slots && (h->dA || !workspace)) return GPHIP_OK;
+    if (want <= h->slots && (h->dA.p || !workspace)) return GPHIP_OK;
     size_t fr = 0, tot = 0;
     HIPCHK(hipMemGetInfo(&fr, &tot));
     const size_t per_slot = slot_bytes(h) - (workspace ? 0 : (size_t)h->slot_elems * h->es);
-    fr += (size_t)h->slots * (slot_bytes(h) - (h->dA ? 0 : (size_t)h->slot_elems * h->es));   // what we are about to give back
+    fr += (size_t)h->slots * (slot_bytes(h) - (h->dA.p ? 0 : (size_t)h->slot_elems * h->es));   // what we are about to give back
     int fit = (int)((double)fr * 0.85 / (double)per_slot);
     if (fit < 1) return fail(h, GPHIP_ERR_HIP, "not enough device memory for one workspace matrix");
     if (want > fit) want = fit;
     if (want > h->max_slots) want = h->max_slots;
-    if (want <= h->slots && (h->dA || !workspace)) return GPHIP_OK;
+    if (want <= h->slots && (h->dA.p || !workspace)) return GPHIP_OK;
     if (want < h->slots) want = h->slots;                 // (adding the workspace to existing small slots)
     free_slots(h);
     const size_t S = (size_t)want;
@@ -398,45 +409,45 @@ int ensure_slots(gphip_ctx* h, int want, bool workspace = true) {
     // usable and the next call simply allocates again (scripts/gpu_api_fuzz.py drives this to out-of-memory).
     hipError_t e = hipSuccess;
     const char* what = "";
-    auto dev = [&](void** p, size_t bytes, const char* name) {
+    auto dev = [&](Buf& b, size_t bytes, const char* name) {
         if (e != hipSuccess) return;
         if (h->debug_fail_alloc > 0 && --h->debug_fail_alloc == 0) { e = hipErrorOutOfMemory; what = name; return; }   // fault injection (tests)
-        if ((e = hipMalloc(p, bytes)) != hipSuccess) what = name;
+        if ((e = b.grow(bytes)) != hipSuccess) what = name;
     };
-    auto host = [&](void** p, size_t bytes, const char* name) {
-        if (e == hipSuccess && (e = hipHostMalloc(p, bytes)) != hipSuccess) what = name;
+    auto host = [&](Buf& b, size_t bytes, const char* name) {
+        if (e == hipSuccess && (e = b.grow(bytes, true)) != hipSuccess) what = name;
     };
     const size_t nflags = S * (size_t)(2 * h->Nt + 1) * (size_t)(2 * h->Nt + 1) * 4;
-    if (workspace) dev(&h->dA, S * (size_t)h->slot_elems * h->es, "workspace");
-    dev(&h->dXs, S * h->d * h->Npad * h->es, "scaled inputs");
-    dev(&h->dW, S * h->Nt * TB * TB * h->es, "block inverses");
-    dev(&h->dDinv, S * 2 * h->Nt * 1024 * h->es, "diagonal inverses of the 64-blocks");      // (64-tile dataflow chain, DfArgs::D)
-    dev((void**)&h->dInvEll, S * h->d * 8, "inverse length scales");
+    if (workspace) dev(h->dA, S * (size_t)h->slot_elems * h->es, "workspace");
+    dev(h->dXs, S * h->d * h->Npad * h->es, "scaled inputs");
+    dev(h->dW, S * h->Nt * TB * TB * h->es, "block inverses");
+    dev(h->dDinv, S * 2 * h->Nt * 1024 * h->es, "diagonal inverses of the 64-blocks");      // (64-tile dataflow chain, DfArgs::D)
+    dev(h->dInvEll, S * h->d * 8, "inverse length scales");
     if (h->nl2 > 0) {                          // second term of a sum / product kernel: its own scaled copy of the inputs
-        dev(&h->dXs2, S * h->d * h->Npad * h->es, "scaled inputs (term 2)");
-        dev((void**)&h->dInvEll2, S * h->d * 8, "inverse length scales (term 2)");
-        host((void**)&h->hInvEll2, S * h->d * 8, "pinned inverse length scales (term 2)");
+        dev(h->dXs2, S * h->d * h->Npad * h->es, "scaled inputs (term 2)");
+        dev(h->dInvEll2, S * h->d * 8, "inverse length scales (term 2)");
+        host(h->hInvEll2, S * h->d * 8, "pinned inverse length scales (term 2)");
     }
-    dev((void**)&h->dSlotp, S * SLOTP * 8, "slot scalars");
-    dev((void**)&h->dPartial, S * 2 * h->Nt * 8, "log-det partials");     // per 64-block in the fine dataflow schedule
-    dev((void**)&h->dRes, S * 2 * 8, "results");
-    dev((void**)&h->dInfo, S * 4, "info words");
-    dev((void**)&h->dFlags, nflags, "dependency flags");
-    dev((void**)&h->dTicket, DF_TICKET_BYTES, "ticket counter");        // + the per-CU "chain task here" counters
-    host((void**)&h->hInvEll, S * h->d * 8, "pinned inverse length scales");
-    host((void**)&h->hSlotp, S * SLOTP * 8, "pinned slot scalars");
+    dev(h->dSlotp, S * SLOTP * 8, "slot scalars");
+    dev(h->dPartial, S * 2 * h->Nt * 8, "log-det partials");     // per 64-block in the fine dataflow schedule
+    dev(h->dRes, S * 2 * 8, "results");
+    dev(h->dInfo, S * 4, "info words");
+    dev(h->dFlags, nflags, "dependency flags");
+    dev(h->dTicket, DF_TICKET_BYTES, "ticket counter");        // + the per-CU "chain task here" counters
+    host(h->hInvEll, S * h->d * 8, "pinned inverse length scales");
+    host(h->hSlotp, S * SLOTP * 8, "pinned slot scalars");
     if (h->custom) {
-        dev((void**)&h->dCustomP, S * (size_t)std::max(h->ncp, 1) * 8, "covariance-function parameters");
-        host((void**)&h->hCustomP, S * (size_t)std::max(h->ncp, 1) * 8, "pinned covariance-function parameters");
+        dev(h->dCustomP, S * (size_t)std::max(h->ncp, 1) * 8, "covariance-function parameters");
+        host(h->hCustomP, S * (size_t)std::max(h->ncp, 1) * 8, "pinned covariance-function parameters");
     }
-    host((void**)&h->hRes, S * 2 * 8, "pinned results");
-    host((void**)&h->hInfo, (S + 2) * 4, "pinned info words");            // + the dataflow abort flag (factorisations: [nb]; later launches: [S + 1])
+    host(h->hRes, S * 2 * 8, "pinned results");
+    host(h->hInfo, (S + 2) * 4, "pinned info words");            // + the dataflow abort flag (factorisations: [nb]; later launches: [S + 1])
     // ON THE HANDLE'S STREAM: the handle's streams are non-blocking, so a null-stream hipMemset is not ordered before
     // the kernels queued next -- a dataflow task could read a recycled allocation's stale flags (another handle's epoch
     // numbers) or tickets before the clear landed.  Found by scripts/gpu_api_fuzz.py (wrong likelihood / memory fault
     // right after a batch grew the slot count), present since round 1.
-    if (e == hipSuccess && (e = hipMemsetAsync(h->dFlags, 0, nflags, h->stream)) != hipSuccess) what = "flag clear";
-    if (e == hipSuccess && (e = hipMemsetAsync(h->dTicket, 0, DF_TICKET_BYTES, h->stream)) != hipSuccess) what = "ticket clear";
+    if (e == hipSuccess && (e = hipMemsetAsync(h->dFlags.p, 0, nflags, h->stream)) != hipSuccess) what = "flag clear";
+    if (e == hipSuccess && (e = hipMemsetAsync(h->dTicket.p, 0, DF_TICKET_BYTES, h->stream)) != hipSuccess) what = "ticket clear";
     if (e != hipSuccess) {
         (void)hipGetLastError();               // (clear the sticky out-of-memory status)
         free_slots(h);
@@ -503,10 +514,10 @@ void launch_kbuild(gphip_ctx* h, const KBuildArgs<T>& a0, dim3 grid, const T* xr
     const int mk = mfma_family(h);                 // family the matrix-pipe build serves this handle with (-1: none)
     if (!h->custom && mk >= 0 && xri && xrj) {
         int nm = 0;                                // slots of this launch the staged thetas hand to the matrix-pipe build
-        for (unsigned s2 = 0; s2 < grid.y; ++s2) nm += h->hSlotp[(size_t)s2 * SLOTP + SP_MFMA] != 0.0;
+        for (unsigned s2 = 0; s2 < grid.y; ++s2) nm += h->hSlotp.as<double>()[(size_t)s2 * SLOTP + SP_MFMA] != 0.0;
         if (nm > 0) {
             KBuildMArgs<T> m{};
-            m.b = a0; m.xri = xri; m.xrj = xrj; m.inv_ell = h->dInvEll; m.centre = h->dCentre;
+            m.b = a0; m.xri = xri; m.xrj = xrj; m.inv_ell = h->dInvEll.as<double>(); m.centre = h->dCentre.as<double>();
             if (mk == 0) launch_kbuild_mfma_kt<T, 0>(h, m, grid);
             else if (mk == 1) launch_kbuild_mfma_kt<T, 1>(h, m, grid);
             else if (mk == 2) launch_kbuild_mfma_kt<T, 2>(h, m, grid);
@@ -522,7 +533,7 @@ void launch_kbuild(gphip_ctx* h, const KBuildArgs<T>& a0, dim3 grid, const T* xr
     }
     if (h->custom) {                               // the run-time compiled instantiation kbuild_kernel<T, 0, 3>
         KBuildArgs<T> a = a0;
-        a.cp = h->dCustomP; a.ncp = std::max(h->ncp, 1);
+        a.cp = h->dCustomP.as<double>(); a.ncp = std::max(h->ncp, 1);
         void* params[] = {&a};
         const size_t lds = (a.d > KB_LDS_MAXD ? 0 : (size_t)2 * a.d * TB * sizeof(T)) + (size_t)a.ncp * sizeof(double);   // point tiles + hyper-parameters
         (void)hipModuleLaunchKernel(h->f_cbuild, grid.x, grid.y, grid.z, 256, 1, 1, (unsigned)lds, h->cs, params, nullptr);
@@ -562,40 +573,40 @@ int queue_build(gphip_ctx* h, int nslots) {
     if (gx > 1024) gx = 1024;
     if (h->theta_packed) {
         ThetaPack tp;
-        memcpy(tp.v, h->hInvEll, (size_t)nslots * h->d * 8);
-        memcpy(tp.v + (size_t)nslots * h->d, h->hSlotp, (size_t)nslots * SLOTP * 8);
-        hipLaunchKernelGGL(k_scale_theta<T>, dim3(gx, nslots), dim3(256), 0, h->cs, (const T*)h->dXt, (T*)h->dXs, tp,
-                           h->dInvEll, h->dSlotp, h->dInfo, (int)h->d, (int)h->Npad, nslots);
+        memcpy(tp.v, h->hInvEll.as<double>(), (size_t)nslots * h->d * 8);
+        memcpy(tp.v + (size_t)nslots * h->d, h->hSlotp.as<double>(), (size_t)nslots * SLOTP * 8);
+        hipLaunchKernelGGL(k_scale_theta<T>, dim3(gx, nslots), dim3(256), 0, h->cs, (const T*)h->dXt.p, (T*)h->dXs.p, tp,
+                           h->dInvEll.as<double>(), h->dSlotp.as<double>(), h->dInfo.as<int>(), (int)h->d, (int)h->Npad, nslots);
     } else {
-        hipLaunchKernelGGL(k_scale<T>, dim3(gx, nslots), dim3(256), 0, h->cs, (const T*)h->dXt, (T*)h->dXs,
-                           h->dInvEll, (int)h->d, (int)h->Npad);
+        hipLaunchKernelGGL(k_scale<T>, dim3(gx, nslots), dim3(256), 0, h->cs, (const T*)h->dXt.p, (T*)h->dXs.p,
+                           h->dInvEll.as<double>(), (int)h->d, (int)h->Npad);
     }
     if (h->nl2 > 0)
-        hipLaunchKernelGGL(k_scale<T>, dim3(gx, nslots), dim3(256), 0, h->cs, (const T*)h->dXt, (T*)h->dXs2, h->dInvEll2,
+        hipLaunchKernelGGL(k_scale<T>, dim3(gx, nslots), dim3(256), 0, h->cs, (const T*)h->dXt.p, (T*)h->dXs2.p, h->dInvEll2.as<double>(),
                            (int)h->d, (int)h->Npad);
     if (h->custom) {                               // prior variance scale -> pivot tolerance, per slot (device: only it can evaluate k)
-        const void* x = h->dXt;
+        const void* x = h->dXt.p;
         int npad = (int)h->Npad, n = (int)h->N, d = (int)h->d, ncp = std::max(h->ncp, 1);
-        const double* cp = h->dCustomP;
-        double* sp = h->dSlotp;
+        const double* cp = h->dCustomP.as<double>();
+        double* sp = h->dSlotp.as<double>();
         void* params[] = {&x, &npad, &n, &d, &cp, &ncp, &sp};
         (void)hipModuleLaunchKernel(h->f_cprep, (unsigned)nslots, 1, 1, 256, 1, 1, 0, h->cs, params, nullptr);
     }
     KBuildArgs<T> a{};
-    a.ks = h->ks; a.xi2 = a.xj2 = (const T*)h->dXs2;
-    a.out = (T*)h->dA; a.ld = TB; a.bstride = h->slot_elems;
-    a.xi = (const T*)h->dXs; a.xj = (const T*)h->dXs; a.xi_bstride = a.xj_bstride = tot;
+    a.ks = h->ks; a.xi2 = a.xj2 = (const T*)h->dXs2.p;
+    a.out = (T*)h->dA.p; a.ld = TB; a.bstride = h->slot_elems;
+    a.xi = (const T*)h->dXs.p; a.xj = (const T*)h->dXs.p; a.xi_bstride = a.xj_bstride = tot;
     a.npad_i = a.npad_j = (int)h->Npad; a.n_i = a.n_j = (int)h->N;
-    a.y = (const T*)h->dY; a.slotp = h->dSlotp; a.d = (int)h->d; a.mode = 0; a.exp2tab = h->dExp2;
+    a.y = (const T*)h->dY.p; a.slotp = h->dSlotp.as<double>(); a.d = (int)h->d; a.mode = 0; a.exp2tab = h->dExp2.as<double>();
     a.nt_i = (int)h->Nt + 1; a.nt_j = (int)h->Nt;
     a.own_panel = h->panel; a.own_world = h->dist_world; a.own_rank = h->dist_rank;
-    if (h->dist_world > 0) { a.out = (T*)h->dist_base; a.adj = h->dDistAdj; }     // sharded evaluation: this rank's own storage
-    a.pw_nug = h->pw_nug_on ? (const T*)h->dPwNug : nullptr;
-    a.pw_mean = h->pw_mean_on ? (const T*)h->dPwMean : nullptr;
+    if (h->dist_world > 0) { a.out = (T*)h->dist_base; a.adj = h->dDistAdj.as<long>(); }     // sharded evaluation: this rank's own storage
+    a.pw_nug = h->pw_nug_on ? (const T*)h->dPwNug.p : nullptr;
+    a.pw_mean = h->pw_mean_on ? (const T*)h->dPwMean.p : nullptr;
     a.pw_bstride = h->Npad;
     const long ntiles = (long)(h->Nt + 1) * (h->Nt + 2) / 2;
     ProfScope ps(h, 0, 0.0, (double)sizeof(T) * nslots * ((double)h->N * (h->N + 1) / 2 + (double)h->N * h->d));
-    launch_kbuild<T>(h, a, dim3((unsigned)ntiles, nslots), (const T*)h->dXt, (const T*)h->dXt);
+    launch_kbuild<T>(h, a, dim3((unsigned)ntiles, nslots), (const T*)h->dXt.p, (const T*)h->dXt.p);
     return 0;
 }
 
@@ -620,7 +631,7 @@ Opnd<T> wb(const T* W, int b, long lrs) {
 }
 template <typename T>
 Opnd<T> tl(const gphip_ctx* h, int k0 = 0, bool all_slots = true) {
-    return Opnd<T>{(const T*)(h->ws_override ? h->ws_override : h->dA), TB, all_slots ? (long)h->slot_elems : 0l, (int)h->R, k0};
+    return Opnd<T>{(const T*)(h->ws_override ? h->ws_override : h->dA.p), TB, all_slots ? (long)h->slot_elems : 0l, (int)h->R, k0};
 }
 
 template <typename T>
@@ -713,7 +724,7 @@ void launch_gemm(gphip_ctx* h, int cls, Opnd<T> Co, Opnd<T> Ao, Opnd<T> Bo, int 
     if (h->fuse_b >= 0 && cls == 3 && mode == 0 && !lat && !ktri && groups == 1 && tri && h->fuse_b >= c0 && h->fuse_b < c1 &&
         h->fuse_b >= r0) {
         g.fuse_b = h->fuse_b;
-        g.fuse_W = (T*)h->dW; g.fuse_partial = h->dPartial; g.fuse_info = h->dInfo; g.fuse_slotp = h->dSlotp; g.fuse_nt = (int)h->Nt;
+        g.fuse_W = (T*)h->dW.p; g.fuse_partial = h->dPartial.as<double>(); g.fuse_info = h->dInfo.as<int>(); g.fuse_slotp = h->dSlotp.as<double>(); g.fuse_nt = (int)h->Nt;
         lds2 = std::max(lds2, potrf_lds<T>());
         h->fuse_done = true;
     }
@@ -748,8 +759,8 @@ template <typename T>
 int queue_panel(gphip_ctx* h, int K0, int nin, int nslots, bool first_factored = false) {
     const int Nt = (int)h->Nt, R = Nt + 1;
     const long bs = h->slot_elems, lrs = (long)Nt * TB * TB;
-    T* A = (T*)(h->ws_override ? h->ws_override : h->dA);
-    T* W = (T*)h->dW;
+    T* A = (T*)(h->ws_override ? h->ws_override : h->dA.p);
+    T* W = (T*)h->dW.p;
     // In-panel updates: right-looking (after column b, K = 128 onto every remaining column of the panel: few,
     // wide launches -- shortest chain for one theta) or left-looking (before column b, ONE update of that
     // column with K = 128 (b - K0): each tile read and written once per panel, longer contractions --
@@ -773,7 +784,7 @@ int queue_panel(gphip_ctx* h, int K0, int nin, int nslots, bool first_factored =
         if (!factored) {
             ProfScope ps(h, 1, 2.0 * TB * TB * TB / 3.0 * nslots, 0.0);
             hipLaunchKernelGGL(potrf128_kernel<T>, dim3(nslots), dim3(256), potrf_lds<T>(), h->cs, A, bs, b, W,
-                               h->dPartial, Nt, h->dInfo, h->dSlotp);
+                               h->dPartial.as<double>(), Nt, h->dInfo.as<int>(), h->dSlotp.as<double>());
         }
         // panel solve X <- X W_b^T for every row tile below the diagonal block (incl. rhs rows)
         launch_gemm<T>(h, 2, tl<T>(h), tl<T>(h, b), wb<T>(W, b, lrs), TB, b + 1, R, b, b + 1, 0, nslots, 1, 0, Nt);
@@ -849,7 +860,7 @@ bool use_dataflow(const gphip_ctx* h, int nslots) {
 void abort_hook(gphip_ctx* h, int kind) {
     if (h->debug_abort_word != kind) return;
     h->debug_abort_word = 0;
-    (void)hipMemsetAsync(h->dTicket + 1, 1, 4, h->stream);
+    (void)hipMemsetAsync(h->dTicket.as<unsigned long long>() + 1, 1, 4, h->stream);
 }
 
 // c0 > 0 (128-tiles only): factor the trailing submatrix that starts at tile column c0 -- the tail of the
@@ -865,38 +876,38 @@ void launch_dataflow(gphip_ctx* h, int nslots, int c0 = 0, double* part = nullpt
     DfArgs<T> g{};
     g.nprev = nprev; g.task0 = task0; g.Aprev = (const T*)aprev;
     g.colsig = (TBX == 64 && ncols > 0 && ncols < R) ? colsig : nullptr;
-    g.A = (T*)(h->ws_override ? h->ws_override : h->dA); g.bstride = h->slot_elems; g.R128 = (int)h->R; g.c0 = c0;
+    g.A = (T*)(h->ws_override ? h->ws_override : h->dA.p); g.bstride = h->slot_elems; g.R128 = (int)h->R; g.c0 = c0;
     g.ncols = (ncols > 0 && ncols < R) ? ncols : 0;
-    g.W = (T*)h->dW + (long)c0 * TBX * TBX; g.w_bstride = (long)h->Nt * TB * TB;
+    g.W = (T*)h->dW.p + (long)c0 * TBX * TBX; g.w_bstride = (long)h->Nt * TB * TB;
     if constexpr (TBX == 64) {
         // the whole factor in one launch for a caller that substitutes afterwards: the 64-block inverses get a buffer of their
         // own (the 128-blocks rebuilt from L go to dW), so that the inverse / forward launches of this kernel find them later
         if (h->want_w && nslots == 1 && c0 == 0 && g.ncols == 0 && nprev == 0) {
-            if (!h->dW64 && hipMalloc(&h->dW64, (size_t)h->Nt * TB * TB * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); h->dW64 = nullptr; }
-            if (h->dW64) { g.W = (T*)h->dW64; h->w64_gen = h->ws_gen; }
+            if (h->dW64.grow((size_t)h->Nt * TB * TB * sizeof(T)) != hipSuccess) (void)hipGetLastError();
+            if (h->dW64.p) { g.W = (T*)h->dW64.p; h->w64_gen = h->ws_gen; }
         }
     }
     if constexpr (TBX == 64) {
-        g.D = (T*)h->dDinv + (long)c0 * 1024; g.d_bstride = (long)2 * h->Nt * 1024;      // chain hand-over by blocked substitution
+        g.D = (T*)h->dDinv.p + (long)c0 * 1024; g.d_bstride = (long)2 * h->Nt * 1024;      // chain hand-over by blocked substitution
     }
-    g.partial = h->dPartial + c0; g.p_bstride = h->Npad / TBX;
+    g.partial = h->dPartial.as<double>() + c0; g.p_bstride = h->Npad / TBX;
     if (part) { g.partial = part; g.p_bstride = pstride; }       // (a 64-tile tail keeps its own list of blocks)
-    g.info = h->dInfo; g.slotp = h->dSlotp;
-    g.flags = h->dFlags; g.f_bstride = (long)(2 * h->Nt + 1) * (2 * h->Nt + 1);
-    g.ticket = h->dTicket; g.ticket_base = h->ticket_base;
-    g.abort_flag = reinterpret_cast<int*>(h->dTicket + 1);
+    g.info = h->dInfo.as<int>(); g.slotp = h->dSlotp.as<double>();
+    g.flags = h->dFlags.as<int>(); g.f_bstride = (long)(2 * h->Nt + 1) * (2 * h->Nt + 1);
+    g.ticket = h->dTicket.as<unsigned long long>(); g.ticket_base = h->ticket_base;
+    g.abort_flag = reinterpret_cast<int*>(h->dTicket.as<unsigned long long>() + 1);
     g.nd = nd; g.nslots = nslots; g.epoch = ++h->epoch;
     h->ticket_base += (unsigned long long)tasks;
     // profile class 3 (panel work): class 4 stays the trailing SYRK alone, it is what the bench's roofline reads
     ProfScope ps(h, 3, ((double)nd * TBX) * ((double)nd * TBX) * ((double)nd * TBX) / 3.0 * nslots, 0.0);
     ThetaPack tp;
     if constexpr (BUILD) {
-        memcpy(tp.v, h->hInvEll, (size_t)nslots * h->d * 8);
-        memcpy(tp.v + (size_t)nslots * h->d, h->hSlotp, (size_t)nslots * SLOTP * 8);
-        g.xt = (const T*)h->dXt; g.yv = (const T*)h->dY;
+        memcpy(tp.v, h->hInvEll.as<double>(), (size_t)nslots * h->d * 8);
+        memcpy(tp.v + (size_t)nslots * h->d, h->hSlotp.as<double>(), (size_t)nslots * SLOTP * 8);
+        g.xt = (const T*)h->dXt.p; g.yv = (const T*)h->dY.p;
         g.n = (int)h->N; g.npad = (int)h->Npad; g.d = (int)h->d; g.kt = h->kt;
-        g.hres = h->hRes; g.hinfo = h->hInfo;
-        h->hInfo[nslots] = 0;                  // the abort word: only ever SET by the kernel
+        g.hres = h->hRes.as<double>(); g.hinfo = h->hInfo.as<int>();
+        h->hInfo.as<int>()[nslots] = 0;                  // the abort word: only ever SET by the kernel
     }
     size_t lds = df_lds_bytes<T, TBX, NST>();
     if (TBX == 64 && OCC <= 2 && lds < DF_XXF_LDS) lds = DF_XXF_LDS;      // (potrf image behind the stage area, see DF_XXF_POTRF_AT)
@@ -914,7 +925,7 @@ void launch_dataflow(gphip_ctx* h, int nslots, int c0 = 0, double* part = nullpt
         const int kib = h->dataflow_lds_kib < 0 ? (tasks <= one_wg_tasks ? 84 : 0) : h->dataflow_lds_kib;   // (round 4, after the fence changes: N=4096 1/CU 1.34 vs 1.36, N=5120 1.83 vs 1.72 two per CU)
         if ((size_t)kib * 1024 > lds) lds = (size_t)kib * 1024;
         // two workgroups per CU: the neighbour of a diagonal task steps aside while that task is on the chain
-        if (lds <= 80 * 1024 && h->dataflow_park) g.park = reinterpret_cast<int*>(h->dTicket + 2);
+        if (lds <= 80 * 1024 && h->dataflow_park) g.park = reinterpret_cast<int*>(h->dTicket.as<unsigned long long>() + 2);
     }
     abort_hook(h, 1);
     hipLaunchKernelGGL((chol_dataflow_kernel<T, TBX, OCC, NST, BUILD>), dim3((unsigned)tasks), dim3(256), lds, h->stream, g, tp);
@@ -936,20 +947,20 @@ void launch_dataflow_inverse(gphip_ctx* h, int64_t fwd_rows = 0, bool back = fal
     const int nd = (int)(h->Npad / TBX);
     const long tasks = (fwd_rows > 0 ? (long)(fwd_rows / TBX) * nd : (long)nd * (nd + 1) / 2) * nslots;
     if (fwd_rows == 0)
-        (void)hipMemsetAsync(h->dKinv, 0, (size_t)(h->Npad + GRAD_LD_PAD) * h->Npad * sizeof(T), h->stream);      // (dV stays free for the alpha solve)
+        (void)hipMemsetAsync(h->dKinv.p, 0, (size_t)(h->Npad + GRAD_LD_PAD) * h->Npad * sizeof(T), h->stream);      // (dV stays free for the alpha solve)
     DfArgs<T> g{};
-    g.A = (T*)h->dA; g.bstride = h->slot_elems; g.R128 = (int)h->R; g.c0 = 0;
-    g.W = (T*)((TBX == 64 && h->dW64 && h->w64_gen == h->ws_gen) ? h->dW64 : h->dW); g.w_bstride = (long)h->Nt * TB * TB;
-    g.partial = h->dPartial; g.p_bstride = h->Npad / TBX;
-    g.info = h->dInfo; g.slotp = h->dSlotp;
-    g.flags = h->dFlags; g.f_bstride = (long)(2 * h->Nt + 1) * (2 * h->Nt + 1);
-    g.ticket = h->dTicket; g.ticket_base = h->ticket_base;
-    g.abort_flag = reinterpret_cast<int*>(h->dTicket + 1);
+    g.A = (T*)h->dA.p; g.bstride = h->slot_elems; g.R128 = (int)h->R; g.c0 = 0;
+    g.W = (T*)((TBX == 64 && h->dW64.p && h->w64_gen == h->ws_gen) ? h->dW64.p : h->dW.p); g.w_bstride = (long)h->Nt * TB * TB;
+    g.partial = h->dPartial.as<double>(); g.p_bstride = h->Npad / TBX;
+    g.info = h->dInfo.as<int>(); g.slotp = h->dSlotp.as<double>();
+    g.flags = h->dFlags.as<int>(); g.f_bstride = (long)(2 * h->Nt + 1) * (2 * h->Nt + 1);
+    g.ticket = h->dTicket.as<unsigned long long>(); g.ticket_base = h->ticket_base;
+    g.abort_flag = reinterpret_cast<int*>(h->dTicket.as<unsigned long long>() + 1);
     g.nd = nd; g.nslots = nslots; g.epoch = ++h->epoch;
-    g.U = (T*)h->dKinv; g.ldu = (long)(h->Npad + GRAD_LD_PAD);
-    if (fwd_rows > 0) { g.U = (T*)h->dV; g.ldu = (long)fwd_rows; g.u_rows = (int)(fwd_rows / TBX); g.u_bstride = (long)fwd_rows * h->Npad; }
+    g.U = (T*)h->dKinv.p; g.ldu = (long)(h->Npad + GRAD_LD_PAD);
+    if (fwd_rows > 0) { g.U = (T*)h->dV.p; g.ldu = (long)fwd_rows; g.u_rows = (int)(fwd_rows / TBX); g.u_bstride = (long)fwd_rows * h->Npad; }
     if (w64s) g.W = (T*)w64s;
-    if (back) { g.u_back = 1; g.LT = (const T*)h->dLT; g.W = (T*)h->dW64T; }        // (the caller made them for this factor: df_backward_ready)
+    if (back) { g.u_back = 1; g.LT = (const T*)h->dLT.p; g.W = (T*)h->dW64T.p; }        // (the caller made them for this factor: df_backward_ready)
     h->ticket_base += (unsigned long long)tasks;
     ProfScope ps(h, 2, fwd_rows > 0 ? (double)fwd_rows * h->Npad * h->Npad : ((double)h->Npad * h->Npad * h->Npad) / 3.0, 0.0);
     size_t lds = df_lds_bytes<T, TBX, NST>();
@@ -972,12 +983,14 @@ void launch_dataflow_inverse(gphip_ctx* h, int64_t fwd_rows = 0, bool back = fal
 // 64-block inverses: made once per fit, on the first solve (one pass over the factor, N^2 / 2 elements).  false: no memory.
 template <typename T>
 bool df_backward_ready(gphip_ctx* h) {
-    if (h->dLT && h->dW64T && h->lt_gen == h->ws_gen) return true;
-    if (!h->dLT && hipMalloc(&h->dLT, (size_t)h->slot_elems * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); h->dLT = nullptr; return false; }
-    if (!h->dW64T && hipMalloc(&h->dW64T, (size_t)h->Nt * TB * TB * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); h->dW64T = nullptr; return false; }
+    if (h->dLT.p && h->dW64T.p && h->lt_gen == h->ws_gen) return true;
+    if (h->dLT.grow((size_t)h->slot_elems * sizeof(T)) != hipSuccess || h->dW64T.grow((size_t)h->Nt * TB * TB * sizeof(T)) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
     const long ntiles = (long)h->R * (h->R + 1) / 2;
-    hipLaunchKernelGGL(transpose_blocks64_kernel<T>, dim3((unsigned)ntiles), dim3(256), 0, h->stream, (const T*)h->dA, (T*)h->dLT, (long)TS, (int)TB, 4);
-    hipLaunchKernelGGL(transpose_blocks64_kernel<T>, dim3((unsigned)(2 * h->Nt)), dim3(256), 0, h->stream, (const T*)h->dW64, (T*)h->dW64T, 4096l, 64, 1);
+    hipLaunchKernelGGL(transpose_blocks64_kernel<T>, dim3((unsigned)ntiles), dim3(256), 0, h->stream, (const T*)h->dA.p, (T*)h->dLT.p, (long)TS, (int)TB, 4);
+    hipLaunchKernelGGL(transpose_blocks64_kernel<T>, dim3((unsigned)(2 * h->Nt)), dim3(256), 0, h->stream, (const T*)h->dW64.p, (T*)h->dW64T.p, 4096l, 64, 1);
     h->lt_gen = h->ws_gen;
     return true;
 }
@@ -986,16 +999,16 @@ bool df_backward_ready(gphip_ctx* h) {
 // dW): cut the 64-block inverses out of them, so that a prediction of few test points is ONE forward dataflow launch there too
 // instead of two launches per tile column (N = 16384, 100 test points: 256 launches, 9.1 ms per call).
 void ensure_w64(gphip_ctx* h) {
-    if (!h->dataflow || h->predict_df <= 0 || h->dtype != 64 || h->dist_world != 0 || h->dist_fit || !has_fit(h) || !h->dW) return;
-    if (h->dW64 && h->w64_gen == h->ws_gen) return;
+    if (!h->dataflow || h->predict_df <= 0 || h->dtype != 64 || h->dist_world != 0 || h->dist_fit || !has_fit(h) || !h->dW.p) return;
+    if (h->dW64.p && h->w64_gen == h->ws_gen) return;
     if (h->Nt > h->predict_df_max_nt) return;
-    if (!h->dW64 && hipMalloc(&h->dW64, (size_t)h->Nt * TB * TB * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); h->dW64 = nullptr; return; }
-    hipLaunchKernelGGL(w128_to_w64_kernel<double>, dim3((unsigned)(2 * h->Nt)), dim3(256), 0, h->stream, (const double*)h->dW, (double*)h->dW64);
+    if (h->dW64.grow((size_t)h->Nt * TB * TB * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); return; }
+    hipLaunchKernelGGL(w128_to_w64_kernel<double>, dim3((unsigned)(2 * h->Nt)), dim3(256), 0, h->stream, (const double*)h->dW.p, (double*)h->dW64.p);
     h->w64_gen = h->ws_gen;
 }
 
 bool df_forward_ok(const gphip_ctx* h, int64_t mpad) {
-    return h->dataflow && h->predict_df > 0 && h->dtype == 64 && h->dist_world == 0 && h->dW64 && h->w64_gen == h->ws_gen &&
+    return h->dataflow && h->predict_df > 0 && h->dtype == 64 && h->dist_world == 0 && h->dW64.p && h->w64_gen == h->ws_gen &&
            h->w64_gen == h->fit_gen && mpad <= (h->Npad <= 8192 ? 2 : 1) * (int64_t)h->predict_df && mpad / 64 <= h->Npad / 64;
 }
 
@@ -1005,18 +1018,12 @@ bool df_forward_ok(const gphip_ctx* h, int64_t mpad) {
 // rows per slot and 12 000 tasks in all -- beyond that the batched GEMM substitution, whose launches are shared by all slots.
 // 8 samples x 100 points: N = 1024 0.75 -> 0.51 ms, N = 2048 1.64 -> 1.11 ms, N = 4096 6.4 -> 5.1 ms per call; 32 x 100: -12 .. -22 %.)
 bool samples_forward_df(gphip_ctx* h, int nb, int64_t mpad) {
-    if (!h->dataflow || h->predict_df <= 0 || h->dtype != 64 || h->dist_world != 0 || !h->dW || h->Nt > h->dataflow_fine_nt) return false;
+    if (!h->dataflow || h->predict_df <= 0 || h->dtype != 64 || h->dist_world != 0 || !h->dW.p || h->Nt > h->dataflow_fine_nt) return false;
     const long nd = h->Npad / 64, tasks = (long)nb * (mpad / 64) * nd;
     if (mpad > h->predict_df || mpad / 64 > nd || tasks > 12000) return false;      // (measured: wins up to ~8 000 tasks, loses from ~16 000)
-    const size_t need = (size_t)nb * h->Nt * TB * TB * sizeof(double);
-    if (need > h->w64s_bytes) {
-        (void)hipFree(h->dW64s);
-        h->dW64s = nullptr; h->w64s_bytes = 0;
-        if (hipMalloc(&h->dW64s, need) != hipSuccess) { (void)hipGetLastError(); h->dW64s = nullptr; return false; }
-        h->w64s_bytes = need;
-    }
-    hipLaunchKernelGGL(w128_to_w64_kernel<double>, dim3((unsigned)(2 * h->Nt), (unsigned)nb), dim3(256), 0, h->stream, (const double*)h->dW,
-                       (double*)h->dW64s, (long)h->Nt * TB * TB);
+    if (h->dW64s.grow((size_t)nb * h->Nt * TB * TB * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); return false; }
+    hipLaunchKernelGGL(w128_to_w64_kernel<double>, dim3((unsigned)(2 * h->Nt), (unsigned)nb), dim3(256), 0, h->stream, (const double*)h->dW.p,
+                       (double*)h->dW64s.p, (long)h->Nt * TB * TB);
     return true;
 }
 
@@ -1024,7 +1031,7 @@ bool samples_forward_df(gphip_ctx* h, int nb, int64_t mpad) {
 // unread after this.
 int clear_abort_word(gphip_ctx* h) {
     h->abort_unread = nullptr;
-    HIPCHK(hipMemsetAsync(h->dTicket + 1, 0, 8 + DF_PARK_SLOTS * 4, h->stream));
+    HIPCHK(hipMemsetAsync(h->dTicket.as<unsigned long long>() + 1, 0, 8 + DF_PARK_SLOTS * 4, h->stream));
     return GPHIP_OK;
 }
 
@@ -1033,14 +1040,14 @@ int clear_abort_word(gphip_ctx* h) {
 // through: the results are void); they leave h->abort_unread set instead.  complete_call copies the word in front of the call's
 // synchronisation and turns it into the call's error.
 int queue_abort_probe(gphip_ctx* h) {
-    HIPCHK(hipMemcpyAsync(h->hInfo + h->slots + 1, reinterpret_cast<int*>(h->dTicket + 1), 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(h->hInfo.as<int>() + h->slots + 1, reinterpret_cast<int*>(h->dTicket.as<unsigned long long>() + 1), 4, hipMemcpyDeviceToHost, h->stream));
     return GPHIP_OK;
 }
 int abort_probe_verdict(gphip_ctx* h) {
     const char* what = h->abort_unread;
     h->abort_unread = nullptr;
-    if (h->hInfo[h->slots + 1] == 0) return GPHIP_OK;
-    h->hInfo[h->slots + 1] = 0;
+    if (h->hInfo.as<int>()[h->slots + 1] == 0) return GPHIP_OK;
+    h->hInfo.as<int>()[h->slots + 1] = 0;
     if (const int rc = clear_abort_word(h)) return rc;
     h->fitted = false;                         // the factor itself may be intact, but nothing derived from it in this call is
     h->u_ready = false;
@@ -1065,9 +1072,9 @@ int complete_call(gphip_ctx* h) {
 
 template <typename T>
 void launch_finalize(gphip_ctx* h, int nslots, int nparts, int pstride = 0, const double* part2 = nullptr, int n2 = 0) {
-    hipLaunchKernelGGL(finalize_kernel<T>, dim3(nslots), dim3(64), 0, h->stream, (const T*)h->dA, (long)h->slot_elems,
-                       (long)(h->slot_elems - TS), h->dPartial, nparts, h->dRes, (const int*)h->dInfo,
-                       (const int*)reinterpret_cast<int*>(h->dTicket + 1), h->hRes, h->hInfo, pstride, part2, n2);
+    hipLaunchKernelGGL(finalize_kernel<T>, dim3(nslots), dim3(64), 0, h->stream, (const T*)h->dA.p, (long)h->slot_elems,
+                       (long)(h->slot_elems - TS), h->dPartial.as<double>(), nparts, h->dRes.as<double>(), h->dInfo.as<int>(),
+                       (const int*)reinterpret_cast<int*>(h->dTicket.as<unsigned long long>() + 1), h->hRes.as<double>(), h->hInfo.as<int>(), pstride, part2, n2);
 }
 
 template <typename T>
@@ -1095,7 +1102,7 @@ int queue_factor_dataflow(gphip_ctx* h, int nslots) {
             }
             if (h->want_w)
                 hipLaunchKernelGGL(trtri128_kernel<T>, dim3((unsigned)h->Nt, nslots), dim3(256), potrf_lds<T>(), h->stream,
-                                   (const T*)h->dA, (long)h->slot_elems, (T*)h->dW, (int)h->Nt);
+                                   (const T*)h->dA.p, (long)h->slot_elems, (T*)h->dW.p, (int)h->Nt);
             return 0;
         }
     }
@@ -1145,7 +1152,7 @@ int queue_factor(gphip_ctx* h, int nslots) {
             hipStream_t keep = h->stream;
             h->stream = h->pstream;
             const int c0 = 2 * (kprev >= 0 ? k0(kprev) : k0(kp));
-            launch_dataflow<T, 64>(h, 1, c0, nullptr, 0, 2 * k0(kp + 1) - c0, kprev >= 0 ? 2 * (k0(kp) - k0(kprev)) : 0, h->dA);
+            launch_dataflow<T, 64>(h, 1, c0, nullptr, 0, 2 * k0(kp + 1) - c0, kprev >= 0 ? 2 * (k0(kp) - k0(kprev)) : 0, h->dA.p);
             h->stream = keep;
         }
     };
@@ -1185,7 +1192,7 @@ int queue_factor(gphip_ctx* h, int nslots) {
                 if (rem == 0) break;                               // (no tail: this was the last panel -- batches, or dataflow_tail off)
                 if constexpr (sizeof(T) == 8) {
                     if (2 * rem <= Nt || pdf) {                    // 64-tiles: the faster chain; its 2 rem block partials
-                        tail_part = h->dPartial + (long)h->slots * Nt;         // live behind the 128-block list
+                        tail_part = h->dPartial.as<double>() + (long)h->slots * Nt;         // live behind the 128-block list
                         tail_n = 2 * rem;
                         if (pdf) { tail_part = nullptr; tail_n = 0; }          // (panel_df: one list of 64-blocks for everything)
                         if (h->dataflow_occ3 > 0 || (h->dataflow_occ3 < 0 && (long)(2 * rem + 1) * (2 * rem + 2) / 2 * nslots >= 6000))
@@ -1225,12 +1232,12 @@ int queue_factor(gphip_ctx* h, int nslots) {
         launch_finalize<T>(h, nslots, 2 * Nt);
         if (h->want_w)                             // 64-block inverses everywhere: rebuild the 128-blocks
             hipLaunchKernelGGL(trtri128_kernel<T>, dim3((unsigned)Nt, nslots), dim3(256), potrf_lds<T>(), h->stream,
-                               (const T*)h->dA, (long)h->slot_elems, (T*)h->dW, Nt);
+                               (const T*)h->dA.p, (long)h->slot_elems, (T*)h->dW.p, Nt);
     } else if (tail_k0 >= 0) {
         launch_finalize<T>(h, nslots, tail_k0, Nt, tail_part, tail_n);
         if (h->want_w)                             // the tail left 64-block inverses over part of dW: rebuild the 128-blocks
             hipLaunchKernelGGL(trtri128_kernel<T>, dim3((unsigned)Nt, nslots), dim3(256), potrf_lds<T>(), h->stream,
-                               (const T*)h->dA, (long)h->slot_elems, (T*)h->dW, Nt);
+                               (const T*)h->dA.p, (long)h->slot_elems, (T*)h->dW.p, Nt);
     } else {
         launch_finalize<T>(h, nslots, Nt);
     }
@@ -1239,19 +1246,19 @@ int queue_factor(gphip_ctx* h, int nslots) {
 
 // the staged hyper-parameters of slots [0, nb) -> device (the launches that follow read them there)
 int copy_theta(gphip_ctx* h, int nb) {
-    HIPCHK(hipMemcpyAsync(h->dInvEll, h->hInvEll, (size_t)nb * h->d * 8, hipMemcpyHostToDevice, h->stream));
-    if (h->nl2 > 0) HIPCHK(hipMemcpyAsync(h->dInvEll2, h->hInvEll2, (size_t)nb * h->d * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->dSlotp, h->hSlotp, (size_t)nb * SLOTP * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->dInvEll.p, h->hInvEll.p, (size_t)nb * h->d * 8, hipMemcpyHostToDevice, h->stream));
+    if (h->nl2 > 0) HIPCHK(hipMemcpyAsync(h->dInvEll2.p, h->hInvEll2.p, (size_t)nb * h->d * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->dSlotp.p, h->hSlotp.p, (size_t)nb * SLOTP * 8, hipMemcpyHostToDevice, h->stream));
     if (h->custom && h->ncp > 0)
-        HIPCHK(hipMemcpyAsync(h->dCustomP, h->hCustomP, (size_t)nb * h->ncp * 8, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(h->dCustomP.p, h->hCustomP.p, (size_t)nb * h->ncp * 8, hipMemcpyHostToDevice, h->stream));
     return GPHIP_OK;
 }
 
 // stage theta of one slot into the pinned host buffers; returns false if theta is unusable
 bool stage_theta(gphip_ctx* h, int slot, const double* th, const double* nug_row = nullptr, const double* mean_row = nullptr) {
-    double* ie = h->hInvEll + (size_t)slot * h->d;
-    double* ie2 = h->nl2 > 0 ? h->hInvEll2 + (size_t)slot * h->d : nullptr;
-    double* sp = h->hSlotp + (size_t)slot * SLOTP;
+    double* ie = h->hInvEll.as<double>() + (size_t)slot * h->d;
+    double* ie2 = h->nl2 > 0 ? h->hInvEll2.as<double>() + (size_t)slot * h->d : nullptr;
+    double* sp = h->hSlotp.as<double>() + (size_t)slot * SLOTP;
     bool ok = true;
     for (int i = 0; i < h->p; ++i)
         if (!std::isfinite(th[i])) ok = false;
@@ -1260,7 +1267,7 @@ bool stage_theta(gphip_ctx* h, int slot, const double* th, const double* nug_row
         // NOT rescaled: inverse length scales of one); k(x, x), which scales the pivot tolerance, is evaluated on the
         // device (custom_prep_kernel) -- it finds the relative tolerance in sp[3] and the nugget's scale in sp[SP_SF2B]
         for (int j = 0; j < h->d; ++j) ie[j] = 1.0;
-        double* cp = h->hCustomP + (size_t)slot * std::max(h->ncp, 1);
+        double* cp = h->hCustomP.as<double>() + (size_t)slot * std::max(h->ncp, 1);
         for (int k = 0; k < h->ncp; ++k) cp[k] = ok ? th[k] : 1.0;
         double sn = ok ? th[h->ncp] : 1.0;
         const double mu = (ok && h->mean_id == GPHIP_MEAN_CONST) ? th[h->ncp + 1] : 0.0;
@@ -1330,7 +1337,7 @@ bool stage_theta(gphip_ctx* h, int slot, const double* th, const double* nug_row
     sp[4] = ok ? 0.0 : 1.0;
     // which kernel builds this slot's K (see gphip_ctx::kbuild_mfma)
     sp[SP_MFMA] = 0.0;
-    if (h->kbuild_mfma && mfma_family(h) >= 0 && h->d <= KB_LDS_MAXD && h->dCentre && ok) {
+    if (h->kbuild_mfma && mfma_family(h) >= 0 && h->d <= KB_LDS_MAXD && h->dCentre.p && ok) {
         double bound = 0.0;
         for (int j = 0; j < h->d; ++j) bound += (h->x_half[(size_t)j] * ie[j]) * (h->x_half[(size_t)j] * ie[j]);
         const double lim = h->dtype == 64 ? (double)h->kbuild_mfma_bound : (double)h->kbuild_mfma_bound / 8.0;
@@ -1346,8 +1353,8 @@ bool stage_theta(gphip_ctx* h, int slot, const double* th, const double* nug_row
 
 template <typename T>
 int queue_null_reduce(gphip_ctx* h, int B) {
-    hipLaunchKernelGGL(null_reduce_kernel<T>, dim3(B), dim3(1024), 0, h->stream, (const T*)h->dY, (int)h->N, h->dNullMu,
-                       h->dNullOut);
+    hipLaunchKernelGGL(null_reduce_kernel<T>, dim3(B), dim3(1024), 0, h->stream, (const T*)h->dY.p, (int)h->N, h->dNullMu.as<double>(),
+                       h->dNullOut.as<double>());
     return 0;
 }
 
@@ -1365,22 +1372,17 @@ int upload_rows(gphip_ctx* h, void* dst, const double* src, int nb, int64_t n, i
 int upload_pw(gphip_ctx* h, int s0, int nb) {
     h->pw_mean_on = h->pw_nug_on = false;
     if (!h->pw_mean_host && !h->pw_nug_host) return GPHIP_OK;
-    const int cap = std::max(h->slots, nb);
-    if (h->pw_cap < cap) {
-        (void)hipFree(h->dPwMean); (void)hipFree(h->dPwNug);
-        h->dPwMean = h->dPwNug = nullptr; h->pw_cap = 0;
-        HIPCHK(hipMalloc(&h->dPwMean, (size_t)cap * h->Npad * h->es));
-        HIPCHK(hipMalloc(&h->dPwNug, (size_t)cap * h->Npad * h->es));
-        h->pw_cap = cap;
-    }
+    const size_t bytes = (size_t)std::max(h->slots, nb) * h->Npad * h->es;
+    HIPCHK(h->dPwMean.grow(bytes));
+    HIPCHK(h->dPwNug.grow(bytes));
     int rc = GPHIP_OK;
     if (h->pw_mean_host) {
-        rc = DISPATCH(h, upload_rows, h, h->dPwMean, h->pw_mean_host + (size_t)s0 * h->N, nb, h->N, h->Npad);
+        rc = DISPATCH(h, upload_rows, h, h->dPwMean.p, h->pw_mean_host + (size_t)s0 * h->N, nb, h->N, h->Npad);
         if (rc) return rc;
         h->pw_mean_on = true;
     }
     if (h->pw_nug_host) {
-        rc = DISPATCH(h, upload_rows, h, h->dPwNug, h->pw_nug_host + (size_t)s0 * h->N, nb, h->N, h->Npad);
+        rc = DISPATCH(h, upload_rows, h, h->dPwNug.p, h->pw_nug_host + (size_t)s0 * h->N, nb, h->N, h->Npad);
         if (rc) return rc;
         h->pw_nug_on = true;
     }
@@ -1388,8 +1390,8 @@ int upload_pw(gphip_ctx* h, int s0, int nb) {
 }
 
 template <typename T>
-int queue_null_reduce_pw(gphip_ctx* h, int B, const double* c_nug, const double* nug, const double* mean, double* out) {
-    hipLaunchKernelGGL(null_reduce_pw_kernel<T>, dim3(B), dim3(1024), 0, h->stream, (const T*)h->dY, (int)h->N, h->dNullMu, c_nug,
+int queue_null_reduce_pw(gphip_ctx* h, int B, const double* mu, const double* c_nug, const double* nug, const double* mean, double* out) {
+    hipLaunchKernelGGL(null_reduce_pw_kernel<T>, dim3(B), dim3(1024), 0, h->stream, (const T*)h->dY.p, (int)h->N, mu, c_nug,
                        nug, mean, out);
     return 0;
 }
@@ -1397,8 +1399,7 @@ int queue_null_reduce_pw(gphip_ctx* h, int B, const double* c_nug, const double*
 // null kernel with a point-dependent nugget and / or mean: K = diag(nu_i) (BGP:25-27, 156-159 with nugget /@ points)
 int null_kernel_batch_pw(gphip_ctx* h, const double* Theta, int B, double* out, double* parts, int* info) {
     const int64_t N = h->N;
-    double *dNug = nullptr, *dMean = nullptr, *dC = nullptr, *dMu = nullptr, *dOut = nullptr;
-    auto cleanup = [&]() { (void)hipFree(dNug); (void)hipFree(dMean); (void)hipFree(dC); (void)hipFree(dMu); (void)hipFree(dOut); };
+    Buf dNug, dMean, dC, dMu, dOut;            // double
     std::vector<double> cn((size_t)B), mu((size_t)B), sums((size_t)3 * B);
     for (int s = 0; s < B; ++s) {
         const double sn = Theta[(size_t)s * h->p];
@@ -1408,25 +1409,21 @@ int null_kernel_batch_pw(gphip_ctx* h, const double* Theta, int B, double* out, 
     }
     int rc = GPHIP_OK;
     auto chk = [&](hipError_t e) { if (e != hipSuccess && rc == GPHIP_OK) { h->err = hipGetErrorString(e); rc = GPHIP_ERR_HIP; } };
-    chk(hipMalloc(&dC, (size_t)B * 8)); chk(hipMalloc(&dMu, (size_t)B * 8)); chk(hipMalloc(&dOut, (size_t)B * 24));
-    if (h->pw_nug_host) chk(hipMalloc(&dNug, (size_t)B * N * 8));
-    if (h->pw_mean_host) chk(hipMalloc(&dMean, (size_t)B * N * 8));
+    chk(dC.grow((size_t)B * 8)); chk(dMu.grow((size_t)B * 8)); chk(dOut.grow((size_t)B * 24));
+    if (h->pw_nug_host) chk(dNug.grow((size_t)B * N * 8));
+    if (h->pw_mean_host) chk(dMean.grow((size_t)B * N * 8));
     if (rc == GPHIP_OK) {
-        chk(hipMemcpyAsync(dC, cn.data(), (size_t)B * 8, hipMemcpyHostToDevice, h->stream));
-        chk(hipMemcpyAsync(dMu, mu.data(), (size_t)B * 8, hipMemcpyHostToDevice, h->stream));
-        if (dNug) chk(hipMemcpyAsync(dNug, h->pw_nug_host, (size_t)B * N * 8, hipMemcpyHostToDevice, h->stream));
-        if (dMean) chk(hipMemcpyAsync(dMean, h->pw_mean_host, (size_t)B * N * 8, hipMemcpyHostToDevice, h->stream));
+        chk(hipMemcpyAsync(dC.p, cn.data(), (size_t)B * 8, hipMemcpyHostToDevice, h->stream));
+        chk(hipMemcpyAsync(dMu.p, mu.data(), (size_t)B * 8, hipMemcpyHostToDevice, h->stream));
+        if (dNug.p) chk(hipMemcpyAsync(dNug.p, h->pw_nug_host, (size_t)B * N * 8, hipMemcpyHostToDevice, h->stream));
+        if (dMean.p) chk(hipMemcpyAsync(dMean.p, h->pw_mean_host, (size_t)B * N * 8, hipMemcpyHostToDevice, h->stream));
     }
     if (rc == GPHIP_OK) {
-        double* keep = h->dNullMu;
-        h->dNullMu = dMu;
-        DISPATCH(h, queue_null_reduce_pw, h, B, dC, dNug, dMean, dOut);
-        h->dNullMu = keep;
-        chk(hipMemcpyAsync(sums.data(), dOut, (size_t)B * 24, hipMemcpyDeviceToHost, h->stream));
+        DISPATCH(h, queue_null_reduce_pw, h, B, dMu.as<double>(), dC.as<double>(), dNug.as<double>(), dMean.as<double>(), dOut.as<double>());
+        chk(hipMemcpyAsync(sums.data(), dOut.p, (size_t)B * 24, hipMemcpyDeviceToHost, h->stream));
         chk(hipStreamSynchronize(h->stream));
         chk(hipGetLastError());
     }
-    cleanup();
     if (rc) return rc;
     for (int s = 0; s < B; ++s) {
         const double* th = Theta + (size_t)s * h->p;
@@ -1446,21 +1443,16 @@ int null_kernel_batch_pw(gphip_ctx* h, const double* Theta, int B, double* out, 
 // the ABI.  grad (optional, B x p): d/dsn = (quad - N)/sn, d/dmu = sum(y - mu)/sn^2.
 int null_kernel_batch(gphip_ctx* h, const double* Theta, int B, double* out, double* parts, int* info, double* grad) {
     if ((h->pw_mean_host || h->pw_nug_host) && !grad) return null_kernel_batch_pw(h, Theta, B, out, parts, info);
-    if (B > h->null_cap) {
-        (void)hipFree(h->dNullMu); (void)hipFree(h->dNullOut);
-        h->dNullMu = h->dNullOut = nullptr; h->null_cap = 0;
-        HIPCHK(hipMalloc(&h->dNullMu, (size_t)B * 8));
-        HIPCHK(hipMalloc(&h->dNullOut, (size_t)B * 16));
-        h->null_cap = B;
-    }
+    HIPCHK(h->dNullMu.grow((size_t)B * 8));
+    HIPCHK(h->dNullOut.grow((size_t)B * 16));
     std::vector<double> mu((size_t)B), sums((size_t)2 * B);
     for (int s = 0; s < B; ++s) {
         const double m = (h->mean_id == GPHIP_MEAN_CONST) ? Theta[(size_t)s * h->p + 1] : 0.0;
         mu[(size_t)s] = std::isfinite(m) ? m : 0.0;
     }
-    HIPCHK(hipMemcpyAsync(h->dNullMu, mu.data(), (size_t)B * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->dNullMu.p, mu.data(), (size_t)B * 8, hipMemcpyHostToDevice, h->stream));
     DISPATCH(h, queue_null_reduce, h, B);
-    HIPCHK(hipMemcpyAsync(sums.data(), h->dNullOut, (size_t)B * 16, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(sums.data(), h->dNullOut.p, (size_t)B * 16, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipGetLastError());
     for (int s = 0; s < B; ++s) {
@@ -1498,7 +1490,7 @@ int eval_chunk(gphip_ctx* h, const double* Theta, int nb, double* out, double* p
     if (!h->theta_packed) {
         const int rc = copy_theta(h, nb);
         if (rc) return rc;
-        HIPCHK(hipMemsetAsync(h->dInfo, 0, (size_t)nb * 4, h->stream));
+        HIPCHK(hipMemsetAsync(h->dInfo.p, 0, (size_t)nb * 4, h->stream));
     }
     // one theta (or a few), fp64, small enough for 64-tiles and nobody needs the scaled inputs / 128-block
     // inverses afterwards: the evaluation is ONE launch
@@ -1516,19 +1508,19 @@ int eval_chunk(gphip_ctx* h, const double* Theta, int nb, double* out, double* p
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipGetLastError());
     harvest(h);
-    if (h->hInfo[nb] != 0 && getenv("GPHIP_DEBUG")) {
-        fprintf(stderr, "gphip debug: nb=%d hInfo[nb]=%d slots=%d; hInfo[0..]:", nb, h->hInfo[nb], h->slots);
-        for (int i = 0; i <= nb && i < 80; ++i) fprintf(stderr, " %d", h->hInfo[i]);
+    if (h->hInfo.as<int>()[nb] != 0 && getenv("GPHIP_DEBUG")) {
+        fprintf(stderr, "gphip debug: nb=%d hInfo[nb]=%d slots=%d; hInfo[0..]:", nb, h->hInfo.as<int>()[nb], h->slots);
+        for (int i = 0; i <= nb && i < 80; ++i) fprintf(stderr, " %d", h->hInfo.as<int>()[i]);
         fprintf(stderr, "\n");
     }
-    if (h->hInfo[nb] != 0) {                   // a dataflow dependency wait hit its spin limit: results are void
+    if (h->hInfo.as<int>()[nb] != 0) {                   // a dataflow dependency wait hit its spin limit: results are void
         if (const int rc = clear_abort_word(h)) return rc;
         return fail(h, GPHIP_ERR_HIP, "dataflow Cholesky schedule timed out (set option dataflow=0 and report)");
     }
     for (int s = 0; s < nb; ++s) {
-        const double logdet = h->hRes[2 * s], quad = h->hRes[2 * s + 1];
+        const double logdet = h->hRes.as<double>()[2 * s], quad = h->hRes.as<double>()[2 * s + 1];
         const double ll = -0.5 * ((double)h->N * LOG_TWO_PI + logdet + quad);
-        int inf = h->hInfo[s];
+        int inf = h->hInfo.as<int>()[s];
         if (!okv[s]) inf = GPHIP_INFO_NAN;
         else if (inf == 0 && !std::isfinite(ll)) inf = GPHIP_INFO_NAN;
         info[s] = inf;
@@ -1631,20 +1623,16 @@ int download(gphip_ctx* h, std::vector<double>& dst, const void* src, size_t n, 
 
 int ensure_vbuf(gphip_ctx* h, int64_t cap) {
     if (cap <= h->vcap) return GPHIP_OK;
-    (void)hipFree(h->dV); (void)hipFree(h->dXsT); (void)hipFree(h->dXsS); (void)hipFree(h->dMean); (void)hipFree(h->dVar);
-    (void)hipFree(h->dPwMeanT); (void)hipFree(h->dPwNugT); (void)hipFree(h->dXsS2);
-    h->dXsS2 = nullptr;
-    h->dV = h->dXsT = h->dXsS = nullptr;
-    h->dMean = h->dVar = h->dPwMeanT = h->dPwNugT = nullptr;
+    for (Buf* b : {&h->dV, &h->dXsT, &h->dXsS, &h->dXsS2, &h->dMean, &h->dVar, &h->dPwMeanT, &h->dPwNugT}) b->release();
     h->vcap = 0;
-    HIPCHK(hipMalloc(&h->dV, (size_t)cap * h->Npad * h->es));
-    HIPCHK(hipMalloc(&h->dXsT, (size_t)cap * h->d * h->es));
-    HIPCHK(hipMalloc(&h->dXsS, (size_t)cap * h->d * h->es));
-    if (h->nl2 > 0) HIPCHK(hipMalloc(&h->dXsS2, (size_t)cap * h->d * h->es));
-    HIPCHK(hipMalloc(&h->dMean, (size_t)cap * 8));
-    HIPCHK(hipMalloc(&h->dVar, (size_t)cap * 8));
-    HIPCHK(hipMalloc(&h->dPwMeanT, (size_t)cap * 8));
-    HIPCHK(hipMalloc(&h->dPwNugT, (size_t)cap * 8));
+    HIPCHK(h->dV.grow((size_t)cap * h->Npad * h->es));
+    HIPCHK(h->dXsT.grow((size_t)cap * h->d * h->es));
+    HIPCHK(h->dXsS.grow((size_t)cap * h->d * h->es));
+    if (h->nl2 > 0) HIPCHK(h->dXsS2.grow((size_t)cap * h->d * h->es));
+    HIPCHK(h->dMean.grow((size_t)cap * 8));
+    HIPCHK(h->dVar.grow((size_t)cap * 8));
+    HIPCHK(h->dPwMeanT.grow((size_t)cap * 8));
+    HIPCHK(h->dPwNugT.grow((size_t)cap * 8));
     h->vcap = cap;
     return GPHIP_OK;
 }
@@ -1672,7 +1660,7 @@ template <typename T>
 int queue_forward_panel(gphip_ctx* h, int64_t mpad, int nslots, int k0, int k1, int b_start, bool identity_rows) {
     const int Nt = (int)h->Nt, Mt = (int)(mpad / TB);
     const long vs = (long)mpad * h->Npad, lrs = (long)Nt * TB * TB;
-    T *V = (T*)h->dV, *W = (T*)h->dW;
+    T *V = (T*)h->dV.p, *W = (T*)h->dW.p;
     auto rows_at = [&](int b) { return identity_rows ? std::min(Mt, b - b_start + 1) : Mt; };
     for (int b = k0; b < k1; ++b) {
         launch_gemm<T>(h, 2, cm<T>(V, mpad, vs), cm<T>(V + (long)b * TB * mpad, mpad, vs), wb<T>(W, b, lrs), TB, 0, rows_at(b), b,
@@ -1710,7 +1698,7 @@ int queue_forward_rows(gphip_ctx* h, int64_t mpad, int nslots, int b_start = 0, 
 template <typename T>
 int queue_backward_rows(gphip_ctx* h, int64_t mpad) {
     const int Nt = (int)h->Nt, Mt = (int)(mpad / TB), P = (Mt >= 8 && h->panel_wide) ? std::max(h->panel, 12) : h->panel;
-    T *V = (T*)h->dV, *W = (T*)h->dW;
+    T *V = (T*)h->dV.p, *W = (T*)h->dW.p;
     for (int k1 = Nt; k1 > 0; k1 -= P) {         // outer panel = tile columns [k0, k1)
         const int k0 = (k1 - P > 0) ? k1 - P : 0;
         for (int b = k1 - 1; b >= k0; --b) {
@@ -1733,10 +1721,10 @@ int queue_scale_train(gphip_ctx* h) {
     const long tot = (long)h->d * h->Npad;
     int gx = (int)((tot + 255) / 256);
     if (gx > 1024) gx = 1024;
-    hipLaunchKernelGGL(k_scale<T>, dim3(gx, 1), dim3(256), 0, h->cs, (const T*)h->dXt, (T*)h->dXs, h->dInvEll, (int)h->d,
+    hipLaunchKernelGGL(k_scale<T>, dim3(gx, 1), dim3(256), 0, h->cs, (const T*)h->dXt.p, (T*)h->dXs.p, h->dInvEll.as<double>(), (int)h->d,
                        (int)h->Npad);
     if (h->nl2 > 0)
-        hipLaunchKernelGGL(k_scale<T>, dim3(gx, 1), dim3(256), 0, h->cs, (const T*)h->dXt, (T*)h->dXs2, h->dInvEll2, (int)h->d,
+        hipLaunchKernelGGL(k_scale<T>, dim3(gx, 1), dim3(256), 0, h->cs, (const T*)h->dXt.p, (T*)h->dXs2.p, h->dInvEll2.as<double>(), (int)h->d,
                            (int)h->Npad);
     return 0;
 }
@@ -1744,7 +1732,7 @@ int queue_scale_train(gphip_ctx* h) {
 // the test points about to be uploaded ([d][mpad], mc of them): how far outside the training inputs' range do they lie?
 void note_test_range(gphip_ctx* h, const std::vector<double>& xt, int64_t mc, int64_t mpad) {
     double r = 0.0;
-    if (h->dCentre)
+    if (h->dCentre.p)
         for (int64_t j = 0; j < h->d; ++j) {
             const double c = h->x_centre[(size_t)j], half = h->x_half[(size_t)j];
             for (int64_t i = 0; i < mc; ++i) {
@@ -1761,20 +1749,20 @@ template <typename T>
 int queue_cross(gphip_ctx* h, int64_t mc, int64_t mpad, int nslots) {
     const long tot = (long)h->d * mpad;
     hipLaunchKernelGGL(k_scale<T>, dim3((unsigned)((tot + 255) / 256), nslots), dim3(256), 0, h->stream,
-                       (const T*)h->dXsT, (T*)h->dXsS, h->dInvEll, (int)h->d, (int)mpad);
+                       (const T*)h->dXsT.p, (T*)h->dXsS.p, h->dInvEll.as<double>(), (int)h->d, (int)mpad);
     if (h->nl2 > 0)
         hipLaunchKernelGGL(k_scale<T>, dim3((unsigned)((tot + 255) / 256), nslots), dim3(256), 0, h->stream,
-                           (const T*)h->dXsT, (T*)h->dXsS2, h->dInvEll2, (int)h->d, (int)mpad);
+                           (const T*)h->dXsT.p, (T*)h->dXsS2.p, h->dInvEll2.as<double>(), (int)h->d, (int)mpad);
     KBuildArgs<T> a{};
-    a.ks = h->ks; a.xi2 = (const T*)h->dXsS2; a.xj2 = (const T*)h->dXs2;
-    a.out = (T*)h->dV; a.ld = mpad; a.bstride = (long)mpad * h->Npad;
-    a.xi = (const T*)h->dXsS; a.xj = (const T*)h->dXs; a.xi_bstride = tot; a.xj_bstride = (long)h->d * h->Npad;
+    a.ks = h->ks; a.xi2 = (const T*)h->dXsS2.p; a.xj2 = (const T*)h->dXs2.p;
+    a.out = (T*)h->dV.p; a.ld = mpad; a.bstride = (long)mpad * h->Npad;
+    a.xi = (const T*)h->dXsS.p; a.xj = (const T*)h->dXs.p; a.xi_bstride = tot; a.xj_bstride = (long)h->d * h->Npad;
     a.npad_i = (int)mpad; a.npad_j = (int)h->Npad; a.n_i = (int)mc; a.n_j = (int)h->N;
-    a.y = nullptr; a.slotp = h->dSlotp; a.d = (int)h->d; a.mode = 1; a.nt_i = (int)(mpad / TB); a.nt_j = (int)h->Nt;
-    a.exp2tab = h->dExp2;
+    a.y = nullptr; a.slotp = h->dSlotp.as<double>(); a.d = (int)h->d; a.mode = 1; a.nt_i = (int)(mpad / TB); a.nt_j = (int)h->Nt;
+    a.exp2tab = h->dExp2.as<double>();
     // (test points far outside the training inputs' range would void the bound the slots' SP_MFMA verdicts rest on)
     const bool far = !(h->test_ratio <= 2.0);
-    launch_kbuild<T>(h, a, dim3((unsigned)((mpad / TB) * h->Nt), nslots), far ? nullptr : (const T*)h->dXsT, (const T*)h->dXt);
+    launch_kbuild<T>(h, a, dim3((unsigned)((mpad / TB) * h->Nt), nslots), far ? nullptr : (const T*)h->dXsT.p, (const T*)h->dXt.p);
     return 0;
 }
 
@@ -1787,7 +1775,7 @@ int upload_pw_test(gphip_ctx* h, int s0, int nb, int64_t m0, int64_t mc, int64_t
         std::vector<double> tmp((size_t)nb * mpad, 0.0);
         for (int s = 0; s < nb; ++s)
             for (int64_t t = 0; t < mc; ++t) tmp[(size_t)s * mpad + t] = src[(size_t)(s0 + s) * h->pw_test_stride + m0 + t];
-        HIPCHK(hipMemcpyAsync(which ? h->dPwNugT : h->dPwMeanT, tmp.data(), tmp.size() * 8, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(which ? h->dPwNugT.p : h->dPwMeanT.p, tmp.data(), tmp.size() * 8, hipMemcpyHostToDevice, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
     }
     return GPHIP_OK;
@@ -1795,18 +1783,12 @@ int upload_pw_test(gphip_ctx* h, int s0, int nb, int64_t m0, int64_t mc, int64_t
 
 // run-time compiled covariance function: k(x*_t, x*_t) of the test points in dXsT for every slot -> dKss[slot][mpad] (fp64)
 int queue_custom_kss(gphip_ctx* h, int64_t mc, int64_t mpad, int nslots) {
-    const size_t want = (size_t)nslots * mpad * 8;
-    if (want > h->kss_cap) {
-        (void)hipFree(h->dKss);
-        h->dKss = nullptr; h->kss_cap = 0;
-        HIPCHK(hipMalloc(&h->dKss, want));
-        h->kss_cap = want;
-    }
-    const void* x = h->dXsT;                       // the (unscaled) test points [d][mpad], shared by the slots
+    HIPCHK(h->dKss.grow((size_t)nslots * mpad * 8));
+    const void* x = h->dXsT.p;                       // the (unscaled) test points [d][mpad], shared by the slots
     long xbs = 0, ostride = (long)mpad;
     int npad = (int)mpad, n = (int)mc, d = (int)h->d, ncp = std::max(h->ncp, 1);
-    const double* cp = h->dCustomP;
-    double* out = h->dKss;
+    const double* cp = h->dCustomP.as<double>();
+    double* out = h->dKss.as<double>();
     void* params[] = {&x, &xbs, &npad, &n, &d, &cp, &ncp, &out, &ostride};
     HIPCHK(hipModuleLaunchKernel(h->f_cdiag, (unsigned)((mc + 255) / 256), (unsigned)nslots, 1, 256, 1, 1, 0, h->stream, params, nullptr));
     return GPHIP_OK;
@@ -1824,29 +1806,23 @@ int queue_predict_reduce(gphip_ctx* h, int64_t mc, int64_t mpad, int nslots) {
     int js = (Nt + nstrips - 1) / nstrips * TB;
     if (js > 4096) js = 4096;
     nstrips = (int)((h->Npad + js - 1) / js);
-    const size_t need = (size_t)nslots * nstrips * 2 * mpad * 8;
-    if (need > h->part_cap) {
-        (void)hipFree(h->dPart);
-        h->dPart = nullptr; h->part_cap = 0;
-        HIPCHK(hipMalloc(&h->dPart, need));
-        h->part_cap = need;
-    }
+    HIPCHK(h->dPart.grow((size_t)nslots * nstrips * 2 * mpad * 8));
     const double* kss = nullptr;
     if (h->custom) {                               // k(x*, x*) is a function of the test point for a general covariance function
         const int rc = queue_custom_kss(h, mc, mpad, nslots);
         if (rc) return rc;
-        kss = h->dKss;
+        kss = h->dKss.as<double>();
     }
     {
         ProfScope ps(h, 6, 4.0 * (double)mpad * h->Npad * nslots, (double)sizeof(T) * mpad * h->Npad * nslots);
         hipLaunchKernelGGL(predict_partial_kernel<T>, dim3((unsigned)Mt, (unsigned)nstrips, (unsigned)nslots), dim3(256),
-                           (size_t)js * 8 + 8 * TB * 8, h->stream, (const T*)h->dV, (long)mpad, (long)mpad * h->Npad, (int)h->N,
-                           h->z_vector ? (const T*)h->dZ : (const T*)h->dA, h->z_vector ? 0 : (int)h->R, (long)h->slot_elems, js,
-                           h->dPart, nstrips);
+                           (size_t)js * 8 + 8 * TB * 8, h->stream, (const T*)h->dV.p, (long)mpad, (long)mpad * h->Npad, (int)h->N,
+                           h->z_vector ? (const T*)h->dZ.p : (const T*)h->dA.p, h->z_vector ? 0 : (int)h->R, (long)h->slot_elems, js,
+                           h->dPart.as<double>(), nstrips);
         hipLaunchKernelGGL(predict_finish_kernel, dim3((unsigned)((mc + 255) / 256), (unsigned)nslots), dim3(256), 0, h->stream,
-                           (const double*)h->dPart, nstrips, (long)mpad, (const double*)h->dSlotp, (int)mc, (long)mpad,
-                           h->dMean, h->dVar, h->pw_mean_test ? (const double*)h->dPwMeanT : nullptr,
-                           h->pw_nug_test ? (const double*)h->dPwNugT : nullptr, kss);
+                           h->dPart.as<double>(), nstrips, (long)mpad, h->dSlotp.as<double>(), (int)mc, (long)mpad,
+                           h->dMean.as<double>(), h->dVar.as<double>(), h->pw_mean_test ? h->dPwMeanT.as<double>() : nullptr,
+                           h->pw_nug_test ? h->dPwNugT.as<double>() : nullptr, kss);
     }
     return 0;
 }
@@ -1859,7 +1835,7 @@ int queue_dist_update(gphip_ctx* h, const void* packed, long K0, long rows, long
     Opnd<T> pk{(const T*)packed - tile_index((int)K0, (int)K0, (int)h->R) * TS, TB, 0, (int)h->R, (int)K0};
     // C = this rank's own panels: the dense workspace, or its compact own-panel storage addressed through the adj table
     Opnd<T> co{(const T*)h->dist_base, TB, 0, (int)h->R, 0};
-    co.adj = h->dDistAdj; co.adj_panel = h->panel;
+    co.adj = h->dDistAdj.as<long>(); co.adj_panel = h->panel;
     launch_gemm<T>(h, cls, co, pk, pk, (int)cols, c_lo, (int)h->Nt + 1, c_lo, c_hi, 1, 1, 0, 0, (int)h->Nt, groups,
                    grp_stride, h->panel);
     return 0;
@@ -1870,8 +1846,8 @@ int queue_finalize(gphip_ctx* h) {         // sharded evaluation: the corner til
     const int nouter = (int)((h->Nt + h->panel - 1) / h->panel);
     const long corner = h->dist_rank == 0 ? (h->dist_adj[(size_t)nouter] + tile_index((int)h->Nt, (int)h->Nt, (int)h->R)) * TS : 0l;
     // (dataflow panels: log-det partials per 64-block, 2 Nt entries; un-owned entries stay zero either way)
-    hipLaunchKernelGGL(finalize_kernel<T>, dim3(1), dim3(64), 0, h->stream, (const T*)h->dist_base, 0l, corner, h->dPartial,
-                       (int)(h->dist_df_active ? 2 * h->Nt : h->Nt), h->dRes);
+    hipLaunchKernelGGL(finalize_kernel<T>, dim3(1), dim3(64), 0, h->stream, (const T*)h->dist_base, 0l, corner, h->dPartial.as<double>(),
+                       (int)(h->dist_df_active ? 2 * h->Nt : h->Nt), h->dRes.as<double>());
     return 0;
 }
 
@@ -1897,13 +1873,8 @@ size_t grad_rows(gphip_ctx* h, GradArgs<T>& a, dim3 grid, size_t lds) {
     const size_t np = h->ngacc, nwg = (size_t)grid.x * grid.y, need = nwg * np * 8;
     a.gpart = nullptr; a.np = (int)np; a.ws_off = (int)((lds + 7) / 8);
     if (np == 0 || 4 * np * 8 > 8192) return lds;
-    if (need > h->gpart_bytes) {
-        (void)hipFree(h->dGpart);
-        h->dGpart = nullptr; h->gpart_bytes = 0;
-        if (hipMalloc((void**)&h->dGpart, need) != hipSuccess) { (void)hipGetLastError(); h->dGpart = nullptr; return lds; }
-        h->gpart_bytes = need;
-    }
-    a.gpart = h->dGpart;
+    if (h->dGpart.grow(need) != hipSuccess) { (void)hipGetLastError(); return lds; }
+    a.gpart = h->dGpart.as<double>();
     return (size_t)a.ws_off * 8 + 4 * np * 8;
 }
 template <typename T>
@@ -1915,7 +1886,7 @@ void grad_rows_finish(gphip_ctx* h, const GradArgs<T>& a, dim3 grid) {
 template <typename T>
 void launch_grad(gphip_ctx* h, GradArgs<T>& a, dim3 grid) {
     if (h->custom) {                               // the run-time compiled custom_grad_kernel<T> (dual-number instantiation)
-        const double* cp = h->dCustomP;
+        const double* cp = h->dCustomP.as<double>();
         int ncp = h->ncp;
         const size_t lds = grad_rows<T>(h, a, grid, (size_t)((a.d > KB_LDS_MAXD ? 0 : a.d) + 1) * TB * sizeof(T));
         void* params[] = {&a, &cp, &ncp};
@@ -1926,7 +1897,7 @@ void launch_grad(gphip_ctx* h, GradArgs<T>& a, dim3 grid) {
     if (a.d > KB_LDS_MAXD) {
         // any form, more dimensions than the specialised kernels hold in LDS / registers: the general kernel reading the points
         // from global memory, one launch per window of 32 length-scale derivatives
-        a.ks = h->ks; a.xs2 = (const T*)h->dXs2;
+        a.ks = h->ks; a.xs2 = (const T*)h->dXs2.p;
         const size_t lds = grad_rows<T>(h, a, grid, (size_t)TB * sizeof(T));
         for (a.d0 = 0; a.d0 < a.d; a.d0 += 32) {
             hipLaunchKernelGGL(grad_reduce_general_kernel<T>, grid, dim3(256), lds, h->cs, a);
@@ -1940,7 +1911,7 @@ void launch_grad(gphip_ctx* h, GradArgs<T>& a, dim3 grid) {
         if (h->kt == 0) launch_grad_kt<T, 0>(h, a, grid, lds);
         else launch_grad_kt<T, 1>(h, a, grid, lds);
     } else {
-        a.ks = h->ks; a.xs2 = (const T*)h->dXs2;
+        a.ks = h->ks; a.xs2 = (const T*)h->dXs2.p;
         const size_t lds = grad_rows<T>(h, a, grid, (size_t)(4 * a.d + 1) * TB * sizeof(T));
         hipLaunchKernelGGL(grad_reduce_general_kernel<T>, grid, dim3(256), lds, h->cs, a);
     }
@@ -1960,12 +1931,14 @@ size_t trsv_pass_elems(const gphip_ctx* h, int nrhs) {
 bool trsv_ok(gphip_ctx* h, int nrhs) {
     if (!h->trsv || nrhs < 1 || nrhs > TRSV_MAXR || h->Nt > 512 || h->dist_world > 0 || h->ws_override) return false;
     const size_t bytes = ((size_t)TRSV_MAXR * h->Npad + 2 * trsv_pass_elems(h, TRSV_MAXR)) * h->es;
-    if (!h->dTrsvX && hipMalloc(&h->dTrsvX, bytes) != hipSuccess) { (void)hipGetLastError(); h->dTrsvX = nullptr; return false; }
-    if (!h->dTrsvP && hipMalloc(&h->dTrsvP, (size_t)4 * h->Nt * TS * h->es) != hipSuccess) { (void)hipGetLastError(); h->dTrsvP = nullptr; return false; }
+    if (h->dTrsvX.grow(bytes) != hipSuccess || h->dTrsvP.grow((size_t)4 * h->Nt * TS * h->es) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
     return true;
 }
-template <typename T> T* trsv_input(gphip_ctx* h) { return (T*)h->dTrsvX; }
-template <typename T> T* trsv_pass(gphip_ctx* h, int nrhs, int pass) { return (T*)h->dTrsvX + (size_t)TRSV_MAXR * h->Npad + (size_t)pass * trsv_pass_elems(h, nrhs); }
+template <typename T> T* trsv_input(gphip_ctx* h) { return (T*)h->dTrsvX.p; }
+template <typename T> T* trsv_pass(gphip_ctx* h, int nrhs, int pass) { return (T*)h->dTrsvX.p + (size_t)TRSV_MAXR * h->Npad + (size_t)pass * trsv_pass_elems(h, nrhs); }
 
 // the sentinel for `npasses` launches of a call with nrhs right-hand sides
 template <typename T>
@@ -1980,18 +1953,18 @@ int queue_trsv(gphip_ctx* h, const T* B, int pass, int nrhs, bool back, T** Xout
     const int nt = (int)h->Nt;
     if (h->trsvp_gen != h->ws_gen) {             // first substitution with this factor: the chain's products, both directions
         for (int dir = 0; dir < 2; ++dir)
-            hipLaunchKernelGGL(trsv_prep_kernel<T>, dim3((unsigned)nt, 2), dim3(256), 0, h->stream, (const T*)h->dA, (int)h->R, (const T*)h->dW,
-                               (T*)h->dTrsvP + (size_t)dir * 2 * nt * TS, nt, dir);
+            hipLaunchKernelGGL(trsv_prep_kernel<T>, dim3((unsigned)nt, 2), dim3(256), 0, h->stream, (const T*)h->dA.p, (int)h->R, (const T*)h->dW.p,
+                               (T*)h->dTrsvP.p + (size_t)dir * 2 * nt * TS, nt, dir);
         h->trsvp_gen = h->ws_gen;
     }
     T* base = trsv_pass<T>(h, nrhs, pass);
     TrsvArgs<T> g{};
-    g.A = (const T*)h->dA; g.R128 = (int)h->R; g.W = (const T*)h->dW; g.B = B; g.ldx = (long)h->Npad;
-    g.P = (const T*)h->dTrsvP + (size_t)(back ? 1 : 0) * 2 * nt * TS;
+    g.A = (const T*)h->dA.p; g.R128 = (int)h->R; g.W = (const T*)h->dW.p; g.B = B; g.ldx = (long)h->Npad;
+    g.P = (const T*)h->dTrsvP.p + (size_t)(back ? 1 : 0) * 2 * nt * TS;
     g.X = base; g.Xc = base + (size_t)nrhs * h->Npad; g.S = base + (size_t)2 * nrhs * h->Npad;
     g.ticket = reinterpret_cast<unsigned int*>(g.S + (size_t)nrhs * TB * (size_t)(nt * (nt - 1) / 2 + 1));
     g.nt = nt; g.nrhs = nrhs; g.back = back ? 1 : 0; g.dbg = 0;              // (dbg: developer timing bits, scripts/micro/trsv_trace.hip only)
-    g.abort_flag = reinterpret_cast<int*>(h->dTicket + 1);
+    g.abort_flag = reinterpret_cast<int*>(h->dTicket.as<unsigned long long>() + 1);
     const long ntasks = nt >= 5 ? (long)(nt - 4) * (nt - 3) / 2 : 0;                 // common ticket list: I >= K + 4
     const long grid = std::min<long>((long)h->ncu, 3 * TRSV_CHAIN + ntasks);         // chain pairs + feeders + tile role; one per CU: all resident
     ProfScope ps(h, 2, 0.0, (double)h->slot_elems * sizeof(T));
@@ -2010,7 +1983,7 @@ template <typename T>
 int queue_trsv_solve(gphip_ctx* h, const std::vector<double>& b, std::vector<float>& b32, int nr, void** x) {
     const void* src = b.data();
     if constexpr (sizeof(T) == 4) { b32.assign(b.begin(), b.end()); src = b32.data(); }
-    HIPCHK(hipMemcpyAsync(h->dTrsvX, src, b.size() * sizeof(T), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->dTrsvX.p, src, b.size() * sizeof(T), hipMemcpyHostToDevice, h->stream));
     T *x0 = nullptr, *x1 = nullptr;
     int rc = queue_trsv_fill<T>(h, nr, 2);
     if (!rc) rc = queue_trsv<T>(h, trsv_input<T>(h), 0, nr, false, &x0);
@@ -2023,8 +1996,8 @@ int queue_trsv_solve(gphip_ctx* h, const std::vector<double>& b, std::vector<flo
 template <typename T>
 void queue_rows_vblock(gphip_ctx* h, void* rows, int64_t mc, int64_t mpad, bool to_v) {
     const unsigned gx = (unsigned)((h->Npad + 255) / 256);
-    if (to_v) hipLaunchKernelGGL(rows_to_vblock_kernel<T>, dim3(gx), dim3(256), 0, h->stream, (const T*)rows, (int)mc, (long)h->Npad, (T*)h->dV, (long)mpad);
-    else hipLaunchKernelGGL(vblock_to_rows_kernel<T>, dim3(gx), dim3(256), 0, h->stream, (const T*)h->dV, (long)mpad, (int)mc, (long)h->Npad, (T*)rows);
+    if (to_v) hipLaunchKernelGGL(rows_to_vblock_kernel<T>, dim3(gx), dim3(256), 0, h->stream, (const T*)rows, (int)mc, (long)h->Npad, (T*)h->dV.p, (long)mpad);
+    else hipLaunchKernelGGL(vblock_to_rows_kernel<T>, dim3(gx), dim3(256), 0, h->stream, (const T*)h->dV.p, (long)mpad, (int)mc, (long)h->Npad, (T*)rows);
 }
 
 // alpha = K^-1 r from the fitted factor (z = L^-1 r sits in the rhs row): one backward pass on a
@@ -2034,19 +2007,19 @@ int queue_alpha(gphip_ctx* h) {
     const int64_t mpad = TB, Npad = h->Npad;
     if (trsv_ok(h, 1)) {                       // one backward launch that streams L once
         T *z = trsv_input<T>(h), *x = nullptr;
-        hipLaunchKernelGGL(gather_rhs_row_kernel<T>, dim3((unsigned)((Npad + 255) / 256)), dim3(256), 0, h->stream, (const T*)h->dA,
+        hipLaunchKernelGGL(gather_rhs_row_kernel<T>, dim3((unsigned)((Npad + 255) / 256)), dim3(256), 0, h->stream, (const T*)h->dA.p,
                            (int)h->R, 0, (int)Npad, z, 1l);
         int rc = queue_trsv_fill<T>(h, 1, 1);
         if (!rc) rc = queue_trsv<T>(h, z, 0, 1, true, &x);
         if (rc) return rc;
-        HIPCHK(hipMemcpyAsync(h->dAlpha, x, (size_t)Npad * sizeof(T), hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(h->dAlpha.p, x, (size_t)Npad * sizeof(T), hipMemcpyDeviceToDevice, h->stream));
         return GPHIP_OK;
     }
-    HIPCHK(hipMemsetAsync(h->dV, 0, (size_t)mpad * Npad * sizeof(T), h->stream));
-    hipLaunchKernelGGL(gather_rhs_row_kernel<T>, dim3((unsigned)((Npad + 255) / 256)), dim3(256), 0, h->stream, (const T*)h->dA,
-                       (int)h->R, 0, (int)Npad, (T*)h->dV, (long)mpad);
+    HIPCHK(hipMemsetAsync(h->dV.p, 0, (size_t)mpad * Npad * sizeof(T), h->stream));
+    hipLaunchKernelGGL(gather_rhs_row_kernel<T>, dim3((unsigned)((Npad + 255) / 256)), dim3(256), 0, h->stream, (const T*)h->dA.p,
+                       (int)h->R, 0, (int)Npad, (T*)h->dV.p, (long)mpad);
     queue_backward_rows<T>(h, mpad);
-    HIPCHK(hipMemcpy2DAsync(h->dAlpha, sizeof(T), h->dV, (size_t)mpad * sizeof(T), sizeof(T), (size_t)Npad,
+    HIPCHK(hipMemcpy2DAsync(h->dAlpha.p, sizeof(T), h->dV.p, (size_t)mpad * sizeof(T), sizeof(T), (size_t)Npad,
                             hipMemcpyDeviceToDevice, h->stream));
     return GPHIP_OK;
 }
@@ -2057,14 +2030,14 @@ int queue_grad_chunk(gphip_ctx* h, int64_t c0, int64_t mc, int64_t mpad) {
     const long tot = (long)mpad * h->Npad;
     int gx = (int)((tot + 255) / 256);
     if (gx > 4096) gx = 4096;
-    hipLaunchKernelGGL(identity_rows_kernel<T>, dim3(gx), dim3(256), 0, h->stream, (T*)h->dV, (long)mpad, (int)h->Npad,
+    hipLaunchKernelGGL(identity_rows_kernel<T>, dim3(gx), dim3(256), 0, h->stream, (T*)h->dV.p, (long)mpad, (int)h->Npad,
                        (int)c0, (int)mc);
     queue_forward_rows<T>(h, mpad, 1, (int)(c0 / TB), true);
     queue_backward_rows<T>(h, mpad);
     GradArgs<T> a{};
-    a.Kinv = (const T*)h->dV; a.ldv = mpad; a.alpha = (const T*)h->dAlpha; a.xs = (const T*)h->dXs;
+    a.Kinv = (const T*)h->dV.p; a.ldv = mpad; a.alpha = (const T*)h->dAlpha.p; a.xs = (const T*)h->dXs.p;
     a.npad = (int)h->Npad; a.n = (int)h->N; a.c0 = (int)c0; a.mc = (int)mc; a.d = (int)h->d;
-    a.slotp = h->dSlotp; a.gacc = h->dGacc;
+    a.slotp = h->dSlotp.as<double>(); a.gacc = h->dGacc.as<double>();
     const dim3 grid((unsigned)(mpad / TB), (unsigned)h->Nt);
     launch_grad<T>(h, a, grid);
     return GPHIP_OK;
@@ -2075,14 +2048,14 @@ int queue_grad_chunk(gphip_ctx* h, int64_t c0, int64_t mc, int64_t mpad) {
 template <typename T>
 int queue_alpha_from_u(gphip_ctx* h) {
     const int npad = (int)h->Npad, chunk = 128, nch = (npad + chunk - 1) / chunk;     // (128-column chunks: Nt x Nt / 2 workgroups with work)
-    T* z = (T*)h->dV;
-    double* part = reinterpret_cast<double*>(static_cast<char*>(h->dV) + (((size_t)npad * sizeof(T) + 255) / 256) * 256);
-    hipLaunchKernelGGL(gather_rhs_row_kernel<T>, dim3((unsigned)((npad + 255) / 256)), dim3(256), 0, h->stream, (const T*)h->dA,
+    T* z = (T*)h->dV.p;
+    double* part = reinterpret_cast<double*>(static_cast<char*>(h->dV.p) + (((size_t)npad * sizeof(T) + 255) / 256) * 256);
+    hipLaunchKernelGGL(gather_rhs_row_kernel<T>, dim3((unsigned)((npad + 255) / 256)), dim3(256), 0, h->stream, (const T*)h->dA.p,
                        (int)h->R, 0, npad, z, 1l);
     hipLaunchKernelGGL(utri_gemv_partial_kernel<T>, dim3((unsigned)(npad / TB), (unsigned)nch), dim3(TB), 0, h->stream,
-                       (const T*)h->dKinv, (long)(npad + GRAD_LD_PAD), (const T*)z, npad, chunk, part);
+                       (const T*)h->dKinv.p, (long)(npad + GRAD_LD_PAD), (const T*)z, npad, chunk, part);
     hipLaunchKernelGGL(utri_gemv_finish_kernel<T>, dim3((unsigned)((npad + 255) / 256)), dim3(256), 0, h->stream, (const double*)part, nch,
-                       npad, (T*)h->dAlpha);
+                       npad, (T*)h->dAlpha.p);
     return GPHIP_OK;
 }
 
@@ -2099,19 +2072,19 @@ int queue_grad_potri(gphip_ctx* h) {
     // a single-launch factorisation has left U = L^-T in dKinv already (launch_dataflow_inverse): K^-1 then goes to dV
     const bool pre = h->u_ready;
     h->u_ready = false;
-    const T* Ub = (const T*)(pre ? h->dKinv : h->dV);
-    const T* Kb = (const T*)(pre ? h->dV : h->dKinv);
+    const T* Ub = (const T*)(pre ? h->dKinv.p : h->dV.p);
+    const T* Kb = (const T*)(pre ? h->dV.p : h->dKinv.p);
     if (!pre) {
-        hipLaunchKernelGGL(identity_rows_kernel<T>, dim3(gx), dim3(256), 0, h->stream, (T*)h->dV, npad, (int)npad, 0, (int)h->N);
+        hipLaunchKernelGGL(identity_rows_kernel<T>, dim3(gx), dim3(256), 0, h->stream, (T*)h->dV.p, npad, (int)npad, 0, (int)h->N);
         queue_forward_rows<T>(h, npad, 1, 0, true);
     }
     const long ldk = pre ? npad + GRAD_LD_PAD : npad;
     launch_gemm<T>(h, 2, cm<T>(Kb, ldk, 0), cm<T>(Ub, ldk, 0), cm<T>(Ub, ldk, 0),
                    (int)npad, 0, (int)h->Nt, 0, (int)h->Nt, 1, 1, 1, 1);
     GradArgs<T> a{};
-    a.Kinv = Kb; a.ldv = ldk; a.alpha = (const T*)h->dAlpha; a.xs = (const T*)h->dXs;
+    a.Kinv = Kb; a.ldv = ldk; a.alpha = (const T*)h->dAlpha.p; a.xs = (const T*)h->dXs.p;
     a.npad = (int)npad; a.n = (int)h->N; a.c0 = 0; a.mc = (int)h->N; a.d = (int)h->d; a.tri = 1;
-    a.slotp = h->dSlotp; a.gacc = h->dGacc;
+    a.slotp = h->dSlotp.as<double>(); a.gacc = h->dGacc.as<double>();
     const dim3 grid((unsigned)h->Nt, (unsigned)h->Nt);
     launch_grad<T>(h, a, grid);
     return GPHIP_OK;
@@ -2131,8 +2104,8 @@ long dist_panel_first(const gphip_ctx* h, int k) { return tile_index(k * h->pane
 int dist_layout(gphip_ctx* h, int rank, int world, bool full) {
     const int nouter = (int)((h->Nt + h->panel - 1) / h->panel);
     if (h->lay_rank == rank && h->lay_world == world && h->lay_panel == h->panel && h->lay_full == (int)full &&
-        (full ? h->dA != nullptr : h->dOwn != nullptr)) {
-        h->dist_base = full ? h->dA : h->dOwn;
+        (full ? h->dA.p != nullptr : h->dOwn.p != nullptr)) {
+        h->dist_base = full ? h->dA.p : h->dOwn.p;
         return GPHIP_OK;
     }
     // any failure below leaves NO layout behind (a draining member must never address panel storage through a stale one)
@@ -2142,9 +2115,8 @@ int dist_layout(gphip_ctx* h, int rank, int world, bool full) {
     if (full) {
         int rc = ensure_slots(h, 1, true);
         if (rc) return rc;
-        (void)hipFree(h->dDistAdj);
-        h->dDistAdj = nullptr;
-        h->dist_base = h->dA;
+        h->dDistAdj.release();
+        h->dist_base = h->dA.p;
     } else {
         long off = 0;
         for (int q = 0; q < nouter; ++q)
@@ -2157,21 +2129,14 @@ int dist_layout(gphip_ctx* h, int rank, int world, bool full) {
             off += 1;
         }
         if (off < 1) off = 1;                               // (a rank that owns nothing still gets a valid pointer)
-        const size_t need = (size_t)off * TS * h->es;
-        if (need > h->own_bytes) {
-            (void)hipFree(h->dOwn);
-            h->dOwn = nullptr; h->own_bytes = 0;
-            HIPCHK(hipMalloc(&h->dOwn, need));
-            h->own_bytes = need;
+        HIPCHK(h->dOwn.grow((size_t)off * TS * h->es));
+        if (!h->dDistAdj.p || h->lay_panel != h->panel) {
+            h->dDistAdj.release();
+            HIPCHK(h->dDistAdj.grow(((size_t)nouter + 1) * sizeof(long)));
         }
-        if (!h->dDistAdj || h->lay_panel != h->panel) {
-            (void)hipFree(h->dDistAdj);
-            h->dDistAdj = nullptr;
-            HIPCHK(hipMalloc(&h->dDistAdj, ((size_t)nouter + 1) * sizeof(long)));
-        }
-        HIPCHK(hipMemcpyAsync(h->dDistAdj, h->dist_adj.data(), ((size_t)nouter + 1) * sizeof(long), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(h->dDistAdj.p, h->dist_adj.data(), ((size_t)nouter + 1) * sizeof(long), hipMemcpyHostToDevice, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
-        h->dist_base = h->dOwn;
+        h->dist_base = h->dOwn.p;
     }
     h->lay_rank = rank; h->lay_world = world; h->lay_panel = h->panel; h->lay_full = (int)full;
     return GPHIP_OK;
@@ -2244,8 +2209,8 @@ void record_fit(gphip_ctx* h, bool ok, const double* theta, int p, double logdet
     stamp_fit(h);
     h->theta_fit.assign(theta, theta + p);
     h->logdet_fit = logdet;
-    h->mu_fit = h->hSlotp[2];
-    h->kappa_fit = h->hSlotp[SP_KXX] + h->hSlotp[1];
+    h->mu_fit = h->hSlotp.as<double>()[2];
+    h->kappa_fit = h->hSlotp.as<double>()[SP_KXX] + h->hSlotp.as<double>()[1];
 }
 }  // namespace
 
@@ -2372,16 +2337,18 @@ static int create_ctx(const void* X, const void* y, int64_t N, int64_t d, int ke
         for (int64_t j = 0; j < d; ++j) xt[(size_t)j * h->Npad + i] = Xd[i * d + j];
         yp[i] = yd[i];
     }
-    if (hipMalloc(&h->dXt, xt.size() * h->es) != hipSuccess) return bail(GPHIP_ERR_HIP);
-    if (hipMalloc(&h->dY, yp.size() * h->es) != hipSuccess) return bail(GPHIP_ERR_HIP);
+    if (h->dXt.grow(xt.size() * h->es) != hipSuccess) return bail(GPHIP_ERR_HIP);
+    if (h->dY.grow(yp.size() * h->es) != hipSuccess) return bail(GPHIP_ERR_HIP);
     {
         std::vector<double> tab(EXP_TAB);
         for (int j = 0; j < EXP_TAB; ++j) tab[(size_t)j] = std::exp2((double)j / EXP_TAB);
-        if (hipMalloc(&h->dExp2, tab.size() * 8) != hipSuccess) return bail(GPHIP_ERR_HIP);
-        if (hipMemcpy(h->dExp2, tab.data(), tab.size() * 8, hipMemcpyHostToDevice) != hipSuccess) return bail(GPHIP_ERR_HIP);
+        if (h->dExp2.grow(tab.size() * 8) != hipSuccess) return bail(GPHIP_ERR_HIP);
+        if (hipMemcpyAsync(h->dExp2.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+            hipStreamSynchronize(h->stream) != hipSuccess)
+            return bail(GPHIP_ERR_HIP);
     }
-    if (DISPATCH(h, upload, h, h->dXt, xt, h->stream) != GPHIP_OK) return bail(GPHIP_ERR_HIP);
-    if (DISPATCH(h, upload, h, h->dY, yp, h->stream) != GPHIP_OK) return bail(GPHIP_ERR_HIP);
+    if (DISPATCH(h, upload, h, h->dXt.p, xt, h->stream) != GPHIP_OK) return bail(GPHIP_ERR_HIP);
+    if (DISPATCH(h, upload, h, h->dY.p, yp, h->stream) != GPHIP_OK) return bail(GPHIP_ERR_HIP);
     if (kernel_id != GPHIP_KERNEL_NULL && !custom_body && mfma_family(h) >= 0) {
         // mid-range / half range of the inputs AS THE DEVICE HOLDS THEM (fp32 handles: rounded to float)
         h->x_centre.assign((size_t)d, 0.0); h->x_half.assign((size_t)d, 0.0);
@@ -2400,8 +2367,10 @@ static int create_ctx(const void* X, const void* y, int64_t N, int64_t d, int ke
             h->x_half[(size_t)j] = std::max(hi - c, c - lo);
         }
         if (finite) {
-            if (hipMalloc(&h->dCentre, (size_t)d * 8) != hipSuccess) return bail(GPHIP_ERR_HIP);
-            if (hipMemcpy(h->dCentre, h->x_centre.data(), (size_t)d * 8, hipMemcpyHostToDevice) != hipSuccess) return bail(GPHIP_ERR_HIP);
+            if (h->dCentre.grow((size_t)d * 8) != hipSuccess) return bail(GPHIP_ERR_HIP);
+            if (hipMemcpyAsync(h->dCentre.p, h->x_centre.data(), (size_t)d * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+                hipStreamSynchronize(h->stream) != hipSuccess)
+                return bail(GPHIP_ERR_HIP);
         }
     }
     if (DISPATCH(h, set_func_attrs, h) != GPHIP_OK) return bail(GPHIP_ERR_HIP);
@@ -2541,28 +2510,16 @@ int gphip_destroy(gphip_handle h) {
     group_destroy(h);                          // communicators + the other members of a multi-device handle
     if (h->joint) gphip_destroy(h->joint);
     (void)hipSetDevice(h->device);
-    (void)hipFree(h->dJZ); (void)hipFree(h->dJPart); (void)hipFree(h->dJOut);
-    for (void* pk : h->packed) (void)hipFree(pk);
-    (void)hipFree(h->dOwn); (void)hipFree(h->dDistAdj); (void)hipFree(h->dZ);
-    (void)hipFree(h->dScal8); (void)hipFree(h->drain_buf);
-    (void)hipFree(h->dKss);
     if (h->cmod) (void)hipModuleUnload(h->cmod);
-    if (h->cstream) (void)hipStreamDestroy(h->cstream);
-    free_slots(h);
-    (void)hipFree(h->dXt); (void)hipFree(h->dY); (void)hipFree(h->dExp2); (void)hipFree(h->dCentre);
     if (h->cgmod) (void)hipModuleUnload(h->cgmod);
-    (void)hipFree(h->dV); (void)hipFree(h->dXsT); (void)hipFree(h->dXsS); (void)hipFree(h->dMean);
-    (void)hipFree(h->dVar); (void)hipFree(h->dAlpha); (void)hipFree(h->dGacc); (void)hipFree(h->dKinv);
-    (void)hipFree(h->dTrsvX); (void)hipFree(h->dTrsvP); (void)hipFree(h->dRows); (void)hipFree(h->dColSig); (void)hipFree(h->dGpart); (void)hipFree(h->dW64s);
-    (void)hipFree(h->dXsS2); (void)hipFree(h->dPwMeanT); (void)hipFree(h->dPwNugT);
-    (void)hipFree(h->dNullMu); (void)hipFree(h->dNullOut); (void)hipFree(h->dPart);
+    if (h->cstream) (void)hipStreamDestroy(h->cstream);
     for (auto e : h->pool) (void)hipEventDestroy(e);
     for (auto e : h->sync_events) (void)hipEventDestroy(e);
     if (h->own_streams) {
         if (h->pstream) (void)hipStreamDestroy(h->pstream);
         if (h->stream) (void)hipStreamDestroy(h->stream);
     }
-    delete h;
+    delete h;                                  // (the buffers free themselves, on h->device)
     return GPHIP_OK;
 }
 
@@ -2647,17 +2604,16 @@ int gphip_loglik_grad(gphip_handle h, const double* theta, int p, double* out, d
     // potri route when U (Npad x Npad scratch) and the lower tiles of K^-1 both fit in a quarter of the HBM
     // that is free right now; otherwise K^-1 is streamed in row blocks through forward + backward substitution
     bool potri = h->grad_potri != 0;
-    if (potri && !(h->dKinv && h->vcap >= Npad + GRAD_LD_PAD)) {
+    if (potri && !(h->dKinv.p && h->vcap >= Npad + GRAD_LD_PAD)) {
         size_t fr = 0, tot = 0;
         HIPCHK(hipMemGetInfo(&fr, &tot));
-        const size_t need = (size_t)(h->dKinv ? 1 : 2) * (Npad + GRAD_LD_PAD) * Npad * h->es;
+        const size_t need = (size_t)(h->dKinv.p ? 1 : 2) * (Npad + GRAD_LD_PAD) * Npad * h->es;
         potri = need <= fr / 4;
     }
     if (potri) {
         rc = ensure_vbuf(h, Npad + GRAD_LD_PAD);
-        if (rc == GPHIP_OK && !h->dKinv && hipMalloc(&h->dKinv, (size_t)(Npad + GRAD_LD_PAD) * Npad * h->es) != hipSuccess) {
+        if (rc == GPHIP_OK && h->dKinv.grow((size_t)(Npad + GRAD_LD_PAD) * Npad * h->es) != hipSuccess) {
             (void)hipGetLastError();
-            h->dKinv = nullptr;
             potri = false;
         }
         if (rc != GPHIP_OK) { (void)hipGetLastError(); potri = false; }
@@ -2670,17 +2626,17 @@ int gphip_loglik_grad(gphip_handle h, const double* theta, int p, double* out, d
     if (rc) { h->u_ready = false; return rc; }
     for (int i = 0; i < p; ++i) grad[i] = std::nan("");
     if (*info != 0) { h->u_ready = false; return GPHIP_OK; }
-    if (!h->dAlpha) HIPCHK(hipMalloc(&h->dAlpha, (size_t)Npad * h->es));
+    HIPCHK(h->dAlpha.grow((size_t)Npad * h->es));
     // general form: both terms' length scales, sf, alpha, c, sn; run-time compiled function: its ncp parameters, sn
     const size_t ngacc = std::max((size_t)2 * d + 6, (size_t)h->ncp + 1);
-    if (!h->dGacc) HIPCHK(hipMalloc(&h->dGacc, ngacc * 8));
+    HIPCHK(h->dGacc.grow(ngacc * 8));
     h->ngacc = ngacc;
     int64_t MC = 0;                            // rows of K^-1 per pass (each pass a forward and a backward substitution)
     if (!potri && (rc = ensure_vchunk(h, Npad, &MC))) return rc;
     h->cs = h->stream;
     rc = (potri && h->u_ready) ? DISPATCH(h, queue_alpha_from_u, h) : DISPATCH(h, queue_alpha, h);
     if (rc) return rc;
-    HIPCHK(hipMemsetAsync(h->dGacc, 0, ngacc * 8, h->stream));
+    HIPCHK(hipMemsetAsync(h->dGacc.p, 0, ngacc * 8, h->stream));
     if (potri) {
         rc = DISPATCH(h, queue_grad_potri, h);
         if (rc) return rc;
@@ -2693,8 +2649,8 @@ int gphip_loglik_grad(gphip_handle h, const double* theta, int p, double* out, d
         }
     }
     std::vector<double> gacc(ngacc), alpha;
-    HIPCHK(hipMemcpyAsync(gacc.data(), h->dGacc, gacc.size() * 8, hipMemcpyDeviceToHost, h->stream));
-    rc = complete_call(h, [&] { return DISPATCH(h, download, h, alpha, h->dAlpha, (size_t)N, h->stream); });
+    HIPCHK(hipMemcpyAsync(gacc.data(), h->dGacc.p, gacc.size() * 8, hipMemcpyDeviceToHost, h->stream));
+    rc = complete_call(h, [&] { return DISPATCH(h, download, h, alpha, h->dAlpha.p, (size_t)N, h->stream); });
     if (rc) return rc;
     h->grad_analytic = 1;
     int o = 0;                                                // (theta index of the next derivative)
@@ -2809,7 +2765,7 @@ int gphip_covariance(gphip_handle h, const double* theta, int p, double* K) {
     DISPATCH(h, queue_build, h, 1);
     // the lower-triangle tiles of the packed workspace (tile (ti, tj) at tile_index(ti, tj, R), column-major inside)
     std::vector<double> tmp;
-    rc = DISPATCH(h, download, h, tmp, h->dA, (size_t)h->slot_elems, h->stream);
+    rc = DISPATCH(h, download, h, tmp, h->dA.p, (size_t)h->slot_elems, h->stream);
     if (rc) return rc;
     harvest(h);
     for (int64_t j = 0; j < N; ++j)
@@ -2855,10 +2811,10 @@ int gphip_cross_covariance(gphip_handle h, const double* theta, int p, const voi
         for (int64_t i = 0; i < mc; ++i)
             for (int64_t j = 0; j < d; ++j) xt[(size_t)j * mpad + i] = X[(m0 + i) * d + j];
         note_test_range(h, xt, mc, mpad);
-        rc = DISPATCH(h, upload, h, h->dXsT, xt, h->stream);
+        rc = DISPATCH(h, upload, h, h->dXsT.p, xt, h->stream);
         if (rc) return rc;
         DISPATCH(h, queue_cross, h, mc, mpad, 1);
-        rc = DISPATCH(h, download, h, v, h->dV, (size_t)mpad * (size_t)N, h->stream);   // V(t, j) at j*mpad + t
+        rc = DISPATCH(h, download, h, v, h->dV.p, (size_t)mpad * (size_t)N, h->stream);   // V(t, j) at j*mpad + t
         if (rc) return rc;
         HIPCHK(hipGetLastError());
         harvest(h);
@@ -2867,13 +2823,13 @@ int gphip_cross_covariance(gphip_handle h, const double* theta, int p, const voi
         if (h->custom) {                           // kappa_t = k(x*_t, x*_t) + nugget: a function of the point (device)
             rc = queue_custom_kss(h, mc, mpad, 1);
             if (rc) return rc;
-            HIPCHK(hipMemcpyAsync(kappa + m0, h->dKss, (size_t)mc * 8, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hipMemcpyAsync(kappa + m0, h->dKss.p, (size_t)mc * 8, hipMemcpyDeviceToHost, h->stream));
             HIPCHK(hipStreamSynchronize(h->stream));
-            for (int64_t t = 0; t < mc; ++t) kappa[m0 + t] += h->hSlotp[1];
+            for (int64_t t = 0; t < mc; ++t) kappa[m0 + t] += h->hSlotp.as<double>()[1];
         }
     }
     if (!h->custom)
-        for (int64_t t = 0; t < M; ++t) kappa[t] = h->hSlotp[SP_KXX] + h->hSlotp[1];
+        for (int64_t t = 0; t < M; ++t) kappa[t] = h->hSlotp.as<double>()[SP_KXX] + h->hSlotp.as<double>()[1];
     return GPHIP_OK;
 }
 
@@ -2959,7 +2915,7 @@ static int predict_local(gphip_handle h, const void* Xs, int64_t M, double* mean
         for (int64_t i = 0; i < mc; ++i)
             for (int64_t j = 0; j < d; ++j) xt[(size_t)j * mpad + i] = X[(m0 + i) * d + j];
         note_test_range(h, xt, mc, mpad);
-        rc = DISPATCH(h, upload, h, h->dXsT, xt, h->stream);
+        rc = DISPATCH(h, upload, h, h->dXsT.p, xt, h->stream);
         if (rc) return rc;
         rc = upload_pw_test(h, 0, 1, m0, mc, mpad);
         if (rc) return rc;
@@ -2968,8 +2924,8 @@ static int predict_local(gphip_handle h, const void* Xs, int64_t M, double* mean
         if (df_forward_ok(h, mpad)) launch_dataflow_inverse<double, 64>(h, mpad);
         else DISPATCH(h, queue_forward_rows, h, mpad, 1);
         DISPATCH(h, queue_predict_reduce, h, mc, mpad, 1);
-        HIPCHK(hipMemcpyAsync(mean + m0, h->dMean, (size_t)mc * 8, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipMemcpyAsync(var + m0, h->dVar, (size_t)mc * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(mean + m0, h->dMean.p, (size_t)mc * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(var + m0, h->dVar.p, (size_t)mc * 8, hipMemcpyDeviceToHost, h->stream));
         if ((rc = complete_call(h))) return rc;
     }
     return GPHIP_OK;
@@ -3028,7 +2984,7 @@ static int predict_streamed(gphip_handle h, const void* Xs, int64_t M, double* m
         int64_t mc = 0;
         rc = ensure_vchunk(m, std::min<int64_t>(32768, (Mi + TB - 1) / TB * TB), &mc);
         if (rc) { local_fail(rc, m->err); break; }
-        if (!m->dZ && !SOFT(hipMalloc(&m->dZ, (size_t)m->Npad * m->es))) break;
+        if (!SOFT(m->dZ.grow((size_t)m->Npad * m->es))) break;
         MC[(size_t)i] = mc;
         passes = std::max(passes, (double)((Mi + mc - 1) / mc));
     }
@@ -3041,17 +2997,17 @@ static int predict_streamed(gphip_handle h, const void* Xs, int64_t M, double* m
     if (nl < W) {                                  // ranks elsewhere: agree on the number of passes (max) AND on "everybody can"
         double v[2] = {passes, failed != GPHIP_OK ? 1.0 : 0.0};
         (void)hipSetDevice(h->device);
-        if (!h->dScal8) { g->broken = true; return fail(h, GPHIP_ERR_HIP, "scalar buffer of the multi-device handle is missing"); }
-        if (hipMemcpyAsync(h->dScal8, v, sizeof v, hipMemcpyHostToDevice, h->stream) != hipSuccess) {
+        if (!h->dScal8.p) { g->broken = true; return fail(h, GPHIP_ERR_HIP, "scalar buffer of the multi-device handle is missing"); }
+        if (hipMemcpyAsync(h->dScal8.p, v, sizeof v, hipMemcpyHostToDevice, h->stream) != hipSuccess) {
             (void)hipGetLastError();
             local_fail(GPHIP_ERR_HIP, "uploading the pass count of a streamed prediction failed");
-            (void)hipMemsetAsync(h->dScal8, 0x7f, sizeof v, h->stream);            // 1.4e306 in both entries: reads as "a rank cannot"
+            (void)hipMemsetAsync(h->dScal8.p, 0x7f, sizeof v, h->stream);            // 1.4e306 in both entries: reads as "a rank cannot"
         }
-        if (rccl().AllReduce(h->dScal8, h->dScal8, 2, NCCL_FLOAT64, NCCL_MAX, g->comms[0], h->stream) != 0) {
+        if (rccl().AllReduce(h->dScal8.as<double>(), h->dScal8.as<double>(), 2, NCCL_FLOAT64, NCCL_MAX, g->comms[0], h->stream) != 0) {
             g->broken = true;
             return fail(h, GPHIP_ERR_HIP, "ncclAllReduce (passes) failed");
         }
-        if (hipMemcpyAsync(v, h->dScal8, sizeof v, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+        if (hipMemcpyAsync(v, h->dScal8.p, sizeof v, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
             hipStreamSynchronize(h->stream) != hipSuccess) {
             (void)hipGetLastError();
             g->broken = true;                      // this rank cannot learn what its peers are about to do
@@ -3085,7 +3041,7 @@ static int predict_streamed(gphip_handle h, const void* Xs, int64_t M, double* m
             for (int64_t r = 0; r < mc; ++r)
                 for (int64_t j = 0; j < d; ++j) xt[(size_t)j * mpad + r] = X[(a + r) * d + j];
             note_test_range(m, xt, mc, mpad);
-            member_fail(m, DISPATCH(m, upload, m, m->dXsT, xt, m->stream));
+            member_fail(m, DISPATCH(m, upload, m, m->dXsT.p, xt, m->stream));
             m->pw_mean_test = pm0 ? pm0 + a : nullptr;
             m->pw_nug_test = pn0 ? pn0 + a : nullptr;
             if (failed == GPHIP_OK) member_fail(m, upload_pw_test(m, 0, 1, 0, mc, mpad));
@@ -3118,16 +3074,16 @@ static int predict_streamed(gphip_handle h, const void* Xs, int64_t M, double* m
                 m->cs = m->stream;
                 if (m->dtype == 64) {
                     if (!mine) hipLaunchKernelGGL(trtri128_kernel<double>, dim3((unsigned)(K1 - K0), 1), dim3(256), potrf_lds<double>(),
-                                                  m->stream, (const double*)base, 0l, (double*)m->dW, (int)m->Nt, K0);
+                                                  m->stream, (const double*)base, 0l, (double*)m->dW.p, (int)m->Nt, K0);
                     if (pass == 0)
                         hipLaunchKernelGGL(gather_rhs_row_kernel<double>, dim3((unsigned)(((K1 - K0) * TB + 255) / 256)), dim3(256), 0,
-                                           m->stream, (const double*)base, (int)m->R, 0, K1 * TB, (double*)m->dZ, 1l, K0 * TB);
+                                           m->stream, (const double*)base, (int)m->R, 0, K1 * TB, (double*)m->dZ.p, 1l, K0 * TB);
                 } else {
                     if (!mine) hipLaunchKernelGGL(trtri128_kernel<float>, dim3((unsigned)(K1 - K0), 1), dim3(256), potrf_lds<float>(),
-                                                  m->stream, (const float*)base, 0l, (float*)m->dW, (int)m->Nt, K0);
+                                                  m->stream, (const float*)base, 0l, (float*)m->dW.p, (int)m->Nt, K0);
                     if (pass == 0)
                         hipLaunchKernelGGL(gather_rhs_row_kernel<float>, dim3((unsigned)(((K1 - K0) * TB + 255) / 256)), dim3(256), 0,
-                                           m->stream, (const float*)base, (int)m->R, 0, K1 * TB, (float*)m->dZ, 1l, K0 * TB);
+                                           m->stream, (const float*)base, (int)m->R, 0, K1 * TB, (float*)m->dZ.p, 1l, K0 * TB);
                 }
                 m->ws_override = base;
                 DISPATCH(m, queue_forward_panel, m, mpadv[(size_t)i], 1, K0, K1, 0, false);
@@ -3144,8 +3100,8 @@ static int predict_streamed(gphip_handle h, const void* Xs, int64_t M, double* m
                 m->z_vector = true;
                 DISPATCH(m, queue_predict_reduce, m, mc, mpadv[(size_t)i], 1);
                 m->z_vector = false;
-                SOFT(hipMemcpyAsync(mean + a, m->dMean, (size_t)mc * 8, hipMemcpyDeviceToHost, m->stream));
-                SOFT(hipMemcpyAsync(var + a, m->dVar, (size_t)mc * 8, hipMemcpyDeviceToHost, m->stream));
+                SOFT(hipMemcpyAsync(mean + a, m->dMean.p, (size_t)mc * 8, hipMemcpyDeviceToHost, m->stream));
+                SOFT(hipMemcpyAsync(var + a, m->dVar.p, (size_t)mc * 8, hipMemcpyDeviceToHost, m->stream));
             }
             SOFT(hipStreamSynchronize(m->cstream));
             SOFT(hipStreamSynchronize(m->stream));
@@ -3236,20 +3192,20 @@ int gphip_predict_samples(gphip_handle h, const double* Thetas, int S, int p, co
             for (int64_t i = 0; i < mc; ++i)
                 for (int64_t j = 0; j < d; ++j) xt[(size_t)j * mpad + i] = X[(m0 + i) * d + j];
             note_test_range(h, xt, mc, mpad);
-            rc = DISPATCH(h, upload, h, h->dXsT, xt, h->stream);
+            rc = DISPATCH(h, upload, h, h->dXsT.p, xt, h->stream);
             if (rc) return rc;
             rc = upload_pw_test(h, s0, nb, m0, mc, mpad);
             if (rc) return rc;
             DISPATCH(h, queue_cross, h, mc, mpad, nb);
             // few test points per sample: the forward substitutions of ALL samples as ONE dataflow launch (slot = sample) instead
             // of two launches per tile column (samples_forward_df)
-            if (samples_forward_df(h, nb, mpad)) launch_dataflow_inverse<double, 64>(h, mpad, false, nb, h->dW64s);
+            if (samples_forward_df(h, nb, mpad)) launch_dataflow_inverse<double, 64>(h, mpad, false, nb, h->dW64s.p);
             else DISPATCH(h, queue_forward_rows, h, mpad, nb);
             DISPATCH(h, queue_predict_reduce, h, mc, mpad, nb);
             hm.resize((size_t)nb * mpad);
             hv.resize((size_t)nb * mpad);
-            HIPCHK(hipMemcpyAsync(hm.data(), h->dMean, hm.size() * 8, hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(hipMemcpyAsync(hv.data(), h->dVar, hv.size() * 8, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hipMemcpyAsync(hm.data(), h->dMean.p, hm.size() * 8, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hipMemcpyAsync(hv.data(), h->dVar.p, hv.size() * 8, hipMemcpyDeviceToHost, h->stream));
             if ((rc = complete_call(h))) return rc;
             for (int s = 0; s < nb; ++s)
                 for (int64_t t = 0; t < mc; ++t) {
@@ -3379,13 +3335,8 @@ int gphip_solve(gphip_handle h, const double* rhs, int64_t nrhs, double* out) {
         void* dRows = nullptr;
         if (compact) {
             const size_t need = (size_t)mc * Npad * h->es;
-            if (need > h->rows_cap) {
-                (void)hipFree(h->dRows);
-                h->dRows = nullptr; h->rows_cap = 0;
-                if (hipMalloc(&h->dRows, need) == hipSuccess) h->rows_cap = need;
-                else (void)hipGetLastError();
-            }
-            dRows = h->rows_cap >= need ? h->dRows : nullptr;
+            if (h->dRows.grow(need) != hipSuccess) (void)hipGetLastError();
+            dRows = h->dRows.p;
         }
         if (dRows) {
             v.assign((size_t)mc * Npad, 0.0);
@@ -3397,7 +3348,7 @@ int gphip_solve(gphip_handle h, const double* rhs, int64_t nrhs, double* out) {
             v.assign((size_t)mpad * Npad, 0.0);
             for (int64_t t = 0; t < mc; ++t)
                 for (int64_t j = 0; j < N; ++j) v[(size_t)j * mpad + t] = rhs[(m0 + t) * N + j];
-            rc = DISPATCH(h, upload, h, h->dV, v, h->stream);
+            rc = DISPATCH(h, upload, h, h->dV.p, v, h->stream);
             if (rc) return rc;
         }
         // after a single-launch fit both halves are ONE dataflow launch each (forward as in gphip_predict; backward over a copy of
@@ -3409,7 +3360,7 @@ int gphip_solve(gphip_handle h, const double* rhs, int64_t nrhs, double* out) {
         if (df_fwd && df_backward_ready<double>(h)) launch_dataflow_inverse<double, 64>(h, mpad, true);
         else DISPATCH(h, queue_backward_rows, h, mpad);
         if (dRows) DISPATCH(h, queue_rows_vblock, h, dRows, mc, mpad, false);
-        rc = complete_call(h, [&] { return DISPATCH(h, download, h, v, dRows ? dRows : h->dV, (size_t)(dRows ? mc : mpad) * Npad, h->stream); });
+        rc = complete_call(h, [&] { return DISPATCH(h, download, h, v, dRows ? dRows : h->dV.p, (size_t)(dRows ? mc : mpad) * Npad, h->stream); });
         if (rc) return rc;
         if (dRows) {
             for (int64_t t = 0; t < mc; ++t) memcpy(out + (m0 + t) * N, &v[(size_t)t * Npad], (size_t)N * 8);
@@ -3483,7 +3434,7 @@ int gphip_dist_begin(gphip_handle h, const double* theta, int p, int rank, int w
     if (rc) return rc;
     rc = copy_theta(h, 1);
     if (rc) return rc;
-    HIPCHK(hipMemsetAsync(h->dInfo, 0, 4, h->stream));
+    HIPCHK(hipMemsetAsync(h->dInfo.p, 0, 4, h->stream));
     // panel schedule of the owner (dist_panel_df; -1 = the library's choice).  Round 6, by scripts/scale_model.py on measured step
     // times: 3 (ONE dataflow launch per panel incl. the look-ahead update, every tile column handed to the broadcast stream by a
     // counter the launch bumps) from 2 ranks on; where the device has no stream-ordered wait on memory: 2 at two ranks, else 0.
@@ -3492,16 +3443,16 @@ int gphip_dist_begin(gphip_handle h, const double* theta, int p, int rank, int w
     if (h->dist_df_mode >= 3) {                // column signals: needs stream-ordered waits on device memory
         int can = 0;
         if (hipDeviceGetAttribute(&can, hipDeviceAttributeCanUseStreamWaitValue, h->device) != hipSuccess) { (void)hipGetLastError(); can = 0; }
-        if (can && !h->dColSig && hipMalloc((void**)&h->dColSig, 64 * sizeof(unsigned int)) != hipSuccess) { (void)hipGetLastError(); h->dColSig = nullptr; }
-        if (!can || !h->dColSig || h->panel > 64) h->dist_df_mode = (h->dist_panel_df < 0 && world != 2) ? 0 : 2;
+        if (can && h->dColSig.grow(64 * sizeof(unsigned int)) != hipSuccess) (void)hipGetLastError();
+        if (!can || !h->dColSig.p || h->panel > 64) h->dist_df_mode = (h->dist_panel_df < 0 && world != 2) ? 0 : 2;
         else {
-            HIPCHK(hipMemsetAsync(h->dColSig, 0, 64 * sizeof(unsigned int), h->pstream));
+            HIPCHK(hipMemsetAsync(h->dColSig.p, 0, 64 * sizeof(unsigned int), h->pstream));
             for (unsigned int& t : h->colsig_target) t = 0;
         }
     }
     h->dist_df_active = h->dist_df_mode != 0;
     h->df_prev_ptr = nullptr; h->df_prev_k = -2;
-    HIPCHK(hipMemsetAsync(h->dPartial, 0, (size_t)2 * h->Nt * 8, h->stream));
+    HIPCHK(hipMemsetAsync(h->dPartial.p, 0, (size_t)2 * h->Nt * 8, h->stream));
     h->cs = h->stream;
     DISPATCH(h, queue_build, h, 1);
     h->pw_mean_on = h->pw_nug_on = false;
@@ -3538,7 +3489,7 @@ int gphip_dist_factor_panel(gphip_handle h, int k, void* packed) {
             const int64_t Kp = K0 - h->panel;
             const char* pbase = static_cast<const char*>(h->df_prev_ptr) - dist_panel_first(h, k - 1) * TS * (long)h->es;
             // (three workgroups per CU once the launch is throughput bound: the early, tall panels)
-            unsigned int* sig = h->dist_df_mode >= 3 ? h->dColSig : nullptr;
+            unsigned int* sig = h->dist_df_mode >= 3 ? h->dColSig.as<unsigned int>() : nullptr;
             if (h->dataflow_occ3 > 0)
                 launch_dataflow<double, 64, 3>(h, 1, 2 * (int)Kp, nullptr, 0, 2 * (int)(K1 - Kp), 2 * (int)(K0 - Kp), pbase, sig);
             else
@@ -3549,17 +3500,17 @@ int gphip_dist_factor_panel(gphip_handle h, int k, void* packed) {
                 for (int c = 0; c < (int)(K1 - K0); ++c) {
                     const int j0 = nprev + 2 * c;
                     h->colsig_target[c] += (unsigned int)((R64 - j0) + (R64 - j0 - 1));
-                    if (h->col_waits) h->col_waits->push_back({h->dColSig + c, h->colsig_target[c]});
+                    if (h->col_waits) h->col_waits->push_back({h->dColSig.as<unsigned int>() + c, h->colsig_target[c]});
                 }
             }
         } else {
-            unsigned int* sig = h->dist_df_mode >= 3 ? h->dColSig : nullptr;
+            unsigned int* sig = h->dist_df_mode >= 3 ? h->dColSig.as<unsigned int>() : nullptr;
             launch_dataflow<double, 64>(h, 1, 2 * (int)K0, nullptr, 0, 2 * (int)(K1 - K0), 0, nullptr, sig);
             if (sig) {
                 const int R64 = 2 * (int)(h->Nt - K0) + 1;
                 for (int c = 0; c < (int)(K1 - K0); ++c) {
                     h->colsig_target[c] += (unsigned int)((R64 - 2 * c) + (R64 - 2 * c - 1));
-                    if (h->col_waits) h->col_waits->push_back({h->dColSig + c, h->colsig_target[c]});
+                    if (h->col_waits) h->col_waits->push_back({h->dColSig.as<unsigned int>() + c, h->colsig_target[c]});
                 }
             }
         }
@@ -3646,22 +3597,22 @@ int gphip_dist_end(gphip_handle h, double* logdet_partial, double* quad, int* in
     if (h->dist_world < 1) return fail(h, GPHIP_ERR_STATE, "gphip_dist_end without gphip_dist_begin");
     HIPCHK(hipSetDevice(h->device));
     DISPATCH(h, queue_finalize, h);
-    HIPCHK(hipMemcpyAsync(h->hRes, h->dRes, 16, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(h->hInfo, h->dInfo, 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(h->hRes.p, h->dRes.p, 16, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(h->hInfo.p, h->dInfo.p, 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->pstream));
     if (h->dist_df_active)                     // dataflow panels: did a dependency wait hit its spin limit?
-        HIPCHK(hipMemcpyAsync(h->hInfo + 1, reinterpret_cast<int*>(h->dTicket + 1), 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(h->hInfo.as<int>() + 1, reinterpret_cast<int*>(h->dTicket.as<unsigned long long>() + 1), 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipGetLastError());
     harvest(h);
-    if (h->dist_df_active && h->hInfo[1] != 0) {
+    if (h->dist_df_active && h->hInfo.as<int>()[1] != 0) {
         if (const int rc = clear_abort_word(h)) return rc;
         h->dist_world = 0; h->dist_rank = 0;
         return fail(h, GPHIP_ERR_HIP, "dataflow panel schedule timed out (set option dist_panel_df=0 and report)");
     }
-    *logdet_partial = h->hRes[0];
-    *quad = (h->dist_rank == 0) ? h->hRes[1] : 0.0;
-    *info = h->dist_theta_ok ? h->hInfo[0] : GPHIP_INFO_NAN;
+    *logdet_partial = h->hRes.as<double>()[0];
+    *quad = (h->dist_rank == 0) ? h->hRes.as<double>()[1] : 0.0;
+    *info = h->dist_theta_ok ? h->hInfo.as<int>()[0] : GPHIP_INFO_NAN;
     h->dist_world = 0; h->dist_rank = 0;
     return GPHIP_OK;
 }
@@ -3774,8 +3725,8 @@ int gphip_factor_bytes(gphip_handle h, int member, double* bytes) {
         if (member < 0 || member >= (int)h->group->members.size()) return fail(h, GPHIP_ERR_ARG, "no such local rank");
         m = h->group->members[(size_t)member];
     } else if (member != 0) return fail(h, GPHIP_ERR_ARG, "no such local rank");
-    double b = (m->dA ? (double)m->slots * (double)m->slot_elems * (double)m->es : 0.0) + (double)m->own_bytes;
-    for (void* pk : m->packed) b += pk ? (double)m->packed_bytes : 0.0;
+    double b = (double)m->dA.bytes + (double)m->dOwn.bytes;
+    for (const Buf& pk : m->packed) b += (double)pk.bytes;
     *bytes = b;
     return GPHIP_OK;
 }

@@ -31,15 +31,6 @@ int joint_dim_check(gphip_ctx* h, int64_t M) {
     return GPHIP_OK;
 }
 
-int joint_alloc(gphip_ctx* h, void** p, size_t* cap, size_t bytes) {
-    if (bytes <= *cap) return GPHIP_OK;
-    (void)hipFree(*p);
-    *p = nullptr; *cap = 0;
-    HIPCHK(hipMalloc(p, bytes));
-    *cap = bytes;
-    return GPHIP_OK;
-}
-
 // the child context for M test points at Xs with outputs y (nullptr: zeros)
 int joint_child(gphip_ctx* h, const double* Xs, int64_t M, const double* y) {
     std::vector<double> y0;
@@ -64,8 +55,8 @@ int joint_child(gphip_ctx* h, const double* Xs, int64_t M, const double* y) {
             for (int64_t j = 0; j < h->d; ++j) xt[(size_t)j * c->Npad + i] = Xs[i * h->d + j];
             yp[(size_t)i] = y[i];
         }
-        int rc = DISPATCH(c, upload, c, c->dXt, xt, c->stream);
-        if (!rc) rc = DISPATCH(c, upload, c, c->dY, yp, c->stream);
+        int rc = DISPATCH(c, upload, c, c->dXt.p, xt, c->stream);
+        if (!rc) rc = DISPATCH(c, upload, c, c->dY.p, yp, c->stream);
         if (rc) return fail(h, rc, c->err.c_str());
     }
     const int rc = ensure_slots(c, 1);
@@ -78,7 +69,7 @@ int joint_mean_kss(gphip_ctx* h, int64_t M, int64_t mpad, double* out) {
     int rc = queue_custom_kss(h, M, mpad, 1);         // (the test points are in dXsT)
     if (rc) return rc;
     std::vector<double> k((size_t)M);
-    HIPCHK(hipMemcpyAsync(k.data(), h->dKss, (size_t)M * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(k.data(), h->dKss.p, (size_t)M * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     double s = 0.0;
     for (double v : k) s += v;
@@ -91,8 +82,8 @@ int joint_mean_kss(gphip_ctx* h, int64_t M, int64_t mpad, double* out) {
 template <typename T>
 int queue_downdate(gphip_ctx* h, gphip_ctx* c, int64_t mpad) {
     DowndateArgs<T> g{};
-    g.C = (T*)c->dA; g.R = (int)c->R;
-    g.V = (const T*)h->dV; g.ldv = (long)mpad; g.Z = (const T*)h->dJZ;
+    g.C = (T*)c->dA.p; g.R = (int)c->R;
+    g.V = (const T*)h->dV.p; g.ldv = (long)mpad; g.Z = (const T*)h->dJZ.p;
     g.Mt = (int)(mpad / TB); g.ntri = g.Mt * (g.Mt + 1) / 2; g.ntiles = g.ntri + g.Mt;
     g.K = (int)h->Npad;
     const long target = 2l * std::max(h->ncu, 1);
@@ -104,9 +95,8 @@ int queue_downdate(gphip_ctx* h, gphip_ctx* c, int64_t mpad) {
     g.kstrip = strip_tiles * TB;
     h->joint_nsplit = nsplit;
     if (nsplit > 1) {
-        const int rc = joint_alloc(h, &h->dJPart, &h->jpart_bytes, (size_t)nsplit * g.ntiles * TS * sizeof(T));
-        if (rc) return rc;
-        g.P = (T*)h->dJPart;
+        HIPCHK(h->dJPart.grow((size_t)nsplit * g.ntiles * TS * sizeof(T)));
+        g.P = (T*)h->dJPart.p;
     }
     c->cs = c->stream;
     {
@@ -114,7 +104,7 @@ int queue_downdate(gphip_ctx* h, gphip_ctx* c, int64_t mpad) {
         ProfScope ps(c, 4, (double)mpad * (mpad + 1) * (double)h->N, (double)sizeof(T) * (mpad + TB) * (double)h->Npad);
         hipLaunchKernelGGL(downdate_kernel<T>, dim3((unsigned)g.ntiles, (unsigned)nsplit), dim3(256), GEMM_LDS, c->stream, g);
         if (nsplit > 1)
-            hipLaunchKernelGGL(downdate_reduce_kernel<T>, dim3((unsigned)g.ntiles, 16), dim3(256), 0, c->stream, (T*)c->dA, (int)c->R,
+            hipLaunchKernelGGL(downdate_reduce_kernel<T>, dim3((unsigned)g.ntiles, 16), dim3(256), 0, c->stream, (T*)c->dA.p, (int)c->R,
                                g.ntri, g.Mt, g.ntiles, (const T*)g.P, nsplit);
     }
     return GPHIP_OK;
@@ -127,15 +117,14 @@ int joint_sigma(gphip_ctx* h, const double* Xs, int64_t M, const double* ystar, 
     const int64_t mpad = (M + TB - 1) / TB * TB, d = h->d;
     int rc = ensure_vbuf(h, mpad);
     if (rc) { (void)hipGetLastError(); return fail(h, GPHIP_ERR_HIP, "joint prediction: no device memory for all M rows of V"); }
-    rc = joint_alloc(h, &h->dJZ, &h->jz_bytes, (size_t)TB * h->Npad * h->es);
-    if (rc) return rc;
+    HIPCHK(h->dJZ.grow((size_t)TB * h->Npad * h->es));
     h->cs = h->stream;
-    HIPCHK(hipMemsetAsync(h->dJZ, 0, (size_t)TB * h->Npad * h->es, h->stream));
+    HIPCHK(hipMemsetAsync(h->dJZ.p, 0, (size_t)TB * h->Npad * h->es, h->stream));
     std::vector<double> xt((size_t)d * mpad, 0.0);
     for (int64_t i = 0; i < M; ++i)
         for (int64_t j = 0; j < d; ++j) xt[(size_t)j * mpad + i] = Xs[i * d + j];
     note_test_range(h, xt, M, mpad);
-    rc = DISPATCH(h, upload, h, h->dXsT, xt, h->stream);
+    rc = DISPATCH(h, upload, h, h->dXsT.p, xt, h->stream);
     if (rc) return rc;
     DISPATCH(h, queue_cross, h, M, mpad, 1);
     ensure_w64(h);
@@ -143,10 +132,10 @@ int joint_sigma(gphip_ctx* h, const double* Xs, int64_t M, const double* ystar, 
     else DISPATCH(h, queue_forward_rows, h, mpad, 1);
     if (h->dtype == 64)
         hipLaunchKernelGGL(gather_rhs_row_kernel<double>, dim3((unsigned)((h->Npad + 255) / 256)), dim3(256), 0, h->stream,
-                           (const double*)h->dA, (int)h->R, 0, (int)h->Npad, (double*)h->dJZ, (long)TB, 0);
+                           (const double*)h->dA.p, (int)h->R, 0, (int)h->Npad, (double*)h->dJZ.p, (long)TB, 0);
     else
         hipLaunchKernelGGL(gather_rhs_row_kernel<float>, dim3((unsigned)((h->Npad + 255) / 256)), dim3(256), 0, h->stream,
-                           (const float*)h->dA, (int)h->R, 0, (int)h->Npad, (float*)h->dJZ, (long)TB, 0);
+                           (const float*)h->dA.p, (int)h->R, 0, (int)h->Npad, (float*)h->dJZ.p, (long)TB, 0);
     double kss_mean = 0.0;                            // (run-time compiled kernels: k(x*, x*) is a function of the point)
     if (jitter_io && *jitter_io < 0.0 && h->custom && (rc = joint_mean_kss(h, M, mpad, &kss_mean))) return rc;
     if ((rc = complete_call(h))) return rc;           // (the forward substitution's abort word)
@@ -155,13 +144,13 @@ int joint_sigma(gphip_ctx* h, const double* Xs, int64_t M, const double* ystar, 
     HIPCHK(hipSetDevice(c->device));
     invalidate_fit(c);
     if (!stage_theta(c, 0, h->theta_fit.data())) return fail(h, GPHIP_ERR_ARG, "the fitted theta does not stage");
-    const double sn2 = c->hSlotp[1];
+    const double sn2 = c->hSlotp.as<double>()[1];
     if (jitter_io && *jitter_io < 0.0)                // default jitter: relative to the prior variance k(x*, x*) + sn^2
-        *jitter_io = joint_jitter_rel(h) * ((h->custom ? kss_mean : c->hSlotp[SP_KXX]) + sn2);
-    c->hSlotp[1] = (noisy ? sn2 : 0.0) + (jitter_io ? *jitter_io : 0.0);
-    c->hSlotp[SP_MFMA] = 0.0;
+        *jitter_io = joint_jitter_rel(h) * ((h->custom ? kss_mean : c->hSlotp.as<double>()[SP_KXX]) + sn2);
+    c->hSlotp.as<double>()[1] = (noisy ? sn2 : 0.0) + (jitter_io ? *jitter_io : 0.0);
+    c->hSlotp.as<double>()[SP_MFMA] = 0.0;
     if ((rc = copy_theta(c, 1))) return fail(h, rc, c->err.c_str());
-    HIPCHK(hipMemsetAsync(c->dInfo, 0, 4, c->stream));
+    HIPCHK(hipMemsetAsync(c->dInfo.p, 0, 4, c->stream));
     c->cs = c->stream;
     c->theta_packed = false; c->fused_eval = false; c->want_w = false; c->want_u = false;
     DISPATCH(c, queue_build, c, 1);
@@ -171,7 +160,7 @@ int joint_sigma(gphip_ctx* h, const double* Xs, int64_t M, const double* ystar, 
 // the child's rhs row -> out[M] (y* = 0: the predictive mean)
 template <typename T>
 int queue_joint_rhs(gphip_ctx* c, int64_t M, double* out) {
-    hipLaunchKernelGGL(joint_rhs_kernel<T>, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, c->stream, (const T*)c->dA, (int)c->R, (int)M,
+    hipLaunchKernelGGL(joint_rhs_kernel<T>, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, c->stream, (const T*)c->dA.p, (int)c->R, (int)M,
                        (const double*)nullptr, out);
     return GPHIP_OK;
 }
@@ -183,7 +172,7 @@ int joint_factor(gphip_ctx* h, int* info) {
     c->abort_unread = "joint prediction: the factorisation of Sigma timed out (set option dataflow=0 and report)";
     const int rc = complete_call(c);
     if (rc) return fail(h, rc, c->err.c_str());
-    *info = c->hInfo[0];
+    *info = c->hInfo.as<int>()[0];
     return GPHIP_OK;
 }
 
@@ -213,19 +202,18 @@ int gphip_predict_cov(gphip_handle h, const void* Xs, int64_t M, int latent, dou
     int rc = joint_sigma(h, X, M, nullptr, !latent, nullptr);
     if (rc) return rc;
     gphip_ctx* c = h->joint;
-    rc = joint_alloc(h, (void**)&h->dJOut, &h->jout_bytes, ((size_t)M * M + (size_t)M) * 8);
-    if (rc) return rc;
+    HIPCHK(h->dJOut.grow(((size_t)M * M + (size_t)M) * 8));
     const long n = (long)M * M;
     if (h->dtype == 64) {
-        hipLaunchKernelGGL(joint_unpack_kernel<double>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const double*)c->dA,
-                           (int)c->R, (int)M, h->dJOut);
+        hipLaunchKernelGGL(joint_unpack_kernel<double>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const double*)c->dA.p,
+                           (int)c->R, (int)M, h->dJOut.as<double>());
     } else {
-        hipLaunchKernelGGL(joint_unpack_kernel<float>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const float*)c->dA,
-                           (int)c->R, (int)M, h->dJOut);
+        hipLaunchKernelGGL(joint_unpack_kernel<float>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const float*)c->dA.p,
+                           (int)c->R, (int)M, h->dJOut.as<double>());
     }
-    DISPATCH(c, queue_joint_rhs, c, M, h->dJOut + n);
-    HIPCHK(hipMemcpyAsync(mean, h->dJOut + n, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream));
-    return joint_download(h, c, cov, h->dJOut, (size_t)n);
+    DISPATCH(c, queue_joint_rhs, c, M, h->dJOut.as<double>() + n);
+    HIPCHK(hipMemcpyAsync(mean, h->dJOut.as<double>() + n, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream));
+    return joint_download(h, c, cov, h->dJOut.as<double>(), (size_t)n);
 }
 
 int gphip_predict_draws(gphip_handle h, const void* Xs, int64_t M, int latent, int S, uint64_t seed, const double* z, double jitter,
@@ -263,9 +251,8 @@ int gphip_predict_draws(gphip_handle h, const void* Xs, int64_t M, int latent, i
     gphip_ctx* c = h->joint;
     const int64_t mpad = (M + TB - 1) / TB * TB;
     // the mean (rhs row = -mu with y* = 0) before the factorisation overwrites that row
-    rc = joint_alloc(h, (void**)&h->dJOut, &h->jout_bytes, (size_t)mpad * 8);
-    if (rc) return rc;
-    DISPATCH(c, queue_joint_rhs, c, M, h->dJOut);
+    HIPCHK(h->dJOut.grow((size_t)mpad * 8));
+    DISPATCH(c, queue_joint_rhs, c, M, h->dJOut.as<double>());
     int inf = 0;
     if ((rc = joint_factor(h, &inf))) return rc;
     if (inf != 0) {
@@ -275,12 +262,9 @@ int gphip_predict_draws(gphip_handle h, const void* Xs, int64_t M, int latent, i
     }
     // draws in chunks of at most ~512 MiB of Z and of out each
     const int sc = (int)std::max<int64_t>(1, std::min<int64_t>(S, ((int64_t)1 << 26) / mpad));
-    double* dZ = nullptr;
-    double* dOut = nullptr;
-    auto cleanup = [&]() { (void)hipFree(dZ); (void)hipFree(dOut); };
-    if (hipMalloc((void**)&dZ, (size_t)sc * mpad * 8) != hipSuccess || hipMalloc((void**)&dOut, (size_t)sc * M * 8) != hipSuccess) {
+    Buf dZ, dOut;                              // double
+    if (dZ.grow((size_t)sc * mpad * 8) != hipSuccess || dOut.grow((size_t)sc * M * 8) != hipSuccess) {
         (void)hipGetLastError();
-        cleanup();
         return fail(h, GPHIP_ERR_HIP, "joint prediction: no device memory for the draws");
     }
     std::vector<double> zh;
@@ -290,23 +274,22 @@ int gphip_predict_draws(gphip_handle h, const void* Xs, int64_t M, int latent, i
             zh.assign((size_t)ns * mpad, 0.0);
             for (int s = 0; s < ns; ++s)
                 for (int64_t j = 0; j < M; ++j) zh[(size_t)s * mpad + j] = z[(size_t)(s0 + s) * M + j];
-            if (hipMemcpyAsync(dZ, zh.data(), zh.size() * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess) { rc = GPHIP_ERR_HIP; break; }
+            if (hipMemcpyAsync(dZ.p, zh.data(), zh.size() * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess) { rc = GPHIP_ERR_HIP; break; }
         } else {
             const long n = (long)ns * mpad;
-            hipLaunchKernelGGL(joint_normal_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, dZ, (long)mpad, ns, (int)M,
+            hipLaunchKernelGGL(joint_normal_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, dZ.as<double>(), (long)mpad, ns, (int)M,
                                s0, (uint64_t)seed);
         }
         const dim3 grid((unsigned)((M + JT_B - 1) / JT_B), (unsigned)((ns + JT_B - 1) / JT_B));
         if (h->dtype == 64)
-            hipLaunchKernelGGL(joint_trmm_kernel<double>, grid, dim3(256), 0, c->stream, (const double*)c->dA, (int)c->R, (int)M,
-                               (const double*)dZ, (long)mpad, ns, (const double*)h->dJOut, dOut, (long)M);
+            hipLaunchKernelGGL(joint_trmm_kernel<double>, grid, dim3(256), 0, c->stream, (const double*)c->dA.p, (int)c->R, (int)M,
+                               dZ.as<double>(), (long)mpad, ns, h->dJOut.as<double>(), dOut.as<double>(), (long)M);
         else
-            hipLaunchKernelGGL(joint_trmm_kernel<float>, grid, dim3(256), 0, c->stream, (const float*)c->dA, (int)c->R, (int)M,
-                               (const double*)dZ, (long)mpad, ns, (const double*)h->dJOut, dOut, (long)M);
-        rc = joint_download(h, c, out + (size_t)s0 * M, dOut, (size_t)ns * M);
+            hipLaunchKernelGGL(joint_trmm_kernel<float>, grid, dim3(256), 0, c->stream, (const float*)c->dA.p, (int)c->R, (int)M,
+                               dZ.as<double>(), (long)mpad, ns, h->dJOut.as<double>(), dOut.as<double>(), (long)M);
+        rc = joint_download(h, c, out + (size_t)s0 * M, dOut.as<double>(), (size_t)ns * M);
     }
     if (rc == GPHIP_ERR_HIP && h->err.empty()) h->err = "joint prediction: copying the normals failed";
-    cleanup();
     if (rc) return rc;
     for (size_t e = 0; e < total; ++e)
         if (!std::isfinite(out[e])) { *info = GPHIP_INFO_NAN; break; }
@@ -333,7 +316,7 @@ int gphip_predict_logpdf(gphip_handle h, const void* Xs, int64_t M, const double
     int inf = 0;
     if ((rc = joint_factor(h, &inf))) return rc;
     const gphip_ctx* c = h->joint;
-    const double logdet = c->hRes[0], quad = c->hRes[1];
+    const double logdet = c->hRes.as<double>()[0], quad = c->hRes.as<double>()[1];
     *out = -0.5 * ((double)M * LOG_TWO_PI + logdet + quad);
     *info = inf != 0 ? inf : (std::isfinite(*out) ? GPHIP_INFO_OK : GPHIP_INFO_NAN);
     return GPHIP_OK;

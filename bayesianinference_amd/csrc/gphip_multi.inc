@@ -85,7 +85,7 @@ int group_member_init(gphip_ctx* h, gphip_ctx* m) {
     else HIPCHK(hipStreamCreateWithFlags(&m->cstream, hipStreamNonBlocking));
     // the 8 doubles of the scalar all-reduces exist from the start: a rank must be able to JOIN a collective (with an error
     // flag) even when a later allocation fails -- returning before the all-reduce would leave its peers blocked in RCCL
-    if (!m->dScal8) HIPCHK(hipMalloc(&m->dScal8, 8 * sizeof(double)));
+    HIPCHK(m->dScal8.grow(8 * sizeof(double)));
     // (the three rotating RECEIVE buffers for panels of other ranks are allocated by group_resize_packed when the first
     //  sharded evaluation runs: a handle that only deals batches to its devices never needs them)
     return GPHIP_OK;
@@ -96,14 +96,11 @@ int group_resize_packed(gphip_ctx* h, gphip_group* g) {      // after "panel" ch
         bool shared = !g->use_rccl && m->share_local_panels;  // device copies and every rank on this GPU: panels are read in place
         for (gphip_ctx* o : g->members) shared = shared && o->device == m->device;
         const size_t need = (g->replicate != 0 || g->world == 1 || shared) ? 0 : group_panel_bytes(m);   // dense workspace: received in place
-        if (need <= m->packed_bytes) continue;
-        HIPCHK(hipSetDevice(m->device));
-        for (int i = 0; i < 3; ++i) {
-            (void)hipFree(m->packed[i]);
-            m->packed[i] = nullptr;
-            HIPCHK(hipMalloc(&m->packed[i], need));
+        for (Buf& pk : m->packed) {
+            if (need <= pk.bytes) continue;
+            HIPCHK(hipSetDevice(m->device));
+            HIPCHK(pk.grow(need));
         }
-        m->packed_bytes = need;
     }
     return GPHIP_OK;
 }
@@ -168,14 +165,14 @@ static int group_create(const void* X, const void* y, int64_t N, int64_t d, int 
         g->comms.push_back(c);
         g->use_rccl = true;
         g->comm_name = "rccl (ncclCommInitRank, " + rccl().origin + ")";
-        double* dflag = nullptr;
+        Buf dflag;
         double flag = rc != GPHIP_OK ? 1.0 : 0.0, total = -1.0;
-        const bool agreed = hipMalloc(&dflag, sizeof(double)) == hipSuccess &&
-                            hipMemcpy(dflag, &flag, sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
-                            rccl().AllReduce(dflag, dflag, 1, NCCL_FLOAT64, NCCL_SUM, c, nullptr) == 0 &&
+        const bool agreed = dflag.grow(sizeof(double)) == hipSuccess &&
+                            hipMemcpy(dflag.p, &flag, sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
+                            rccl().AllReduce(dflag.p, dflag.p, 1, NCCL_FLOAT64, NCCL_SUM, c, nullptr) == 0 &&
                             hipStreamSynchronize(nullptr) == hipSuccess &&
-                            hipMemcpy(&total, dflag, sizeof(double), hipMemcpyDeviceToHost) == hipSuccess;
-        (void)hipFree(dflag);
+                            hipMemcpy(&total, dflag.p, sizeof(double), hipMemcpyDeviceToHost) == hipSuccess;
+        dflag.release();
         if (rc != GPHIP_OK) return bail(rc);
         if (!agreed) return bail(GPHIP_ERR_HIP);
         if (total != 0.0) {
@@ -227,23 +224,19 @@ char* group_panel_ptr(gphip_group* g, int i, int k) {
         const int lo = local_index(g, o);
         if (lo >= 0 && g->members[(size_t)lo]->device == m->device) return dist_panel_range(g->members[(size_t)lo], k);
     }
-    return static_cast<char*>(m->packed[k % 3]);
+    return static_cast<char*>(m->packed[k % 3].p);
 }
 
 // Scratch a DRAINING member broadcasts from / into (see group_eval_run): never the panel storage -- a member whose
 // gphip_dist_begin failed has no layout (dist_base / dist_adj are void) and its receive buffers may not exist.  One
 // allocation of the largest panel's size, kept for the handle's life; null = not even that could be allocated.
 char* group_drain_buf(gphip_ctx* m, size_t bytes) {
-    if (m->drain_bytes >= bytes && m->drain_buf) return static_cast<char*>(m->drain_buf);
-    for (void* pk : m->packed)
-        if (pk && m->packed_bytes >= bytes) return static_cast<char*>(pk);
+    if (m->drain_buf.p && m->drain_buf.bytes >= bytes) return static_cast<char*>(m->drain_buf.p);
+    for (const Buf& pk : m->packed)
+        if (pk.p && pk.bytes >= bytes) return static_cast<char*>(pk.p);
     (void)hipSetDevice(m->device);
-    (void)hipFree(m->drain_buf);
-    m->drain_buf = nullptr; m->drain_bytes = 0;
-    const size_t want = std::max(bytes, group_panel_bytes(m));
-    if (hipMalloc(&m->drain_buf, want) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    m->drain_bytes = want;
-    return static_cast<char*>(m->drain_buf);
+    if (m->drain_buf.grow(std::max(bytes, group_panel_bytes(m))) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    return static_cast<char*>(m->drain_buf.p);
 }
 
 // broadcast panel k (bytes) from rank `root` to every rank, IN PLACE at the root (straight out of its own storage: the
@@ -337,20 +330,20 @@ int group_agree(gphip_ctx* h, gphip_group* g, const double* mine, int n, const c
     // Nothing rank-local may make this rank skip the all-reduces (its peers are about to enter them): a rank in trouble says so
     // in v[6] (or, if it cannot even upload, sends NaN), and EVERY rank then returns GPHIP_ERR_HIP from this call.
     bool sick = hipSetDevice(h->device) != hipSuccess;
-    if (!h->dScal8) return fail(h, GPHIP_ERR_HIP, "scalar buffer of the multi-device handle is missing");
+    if (!h->dScal8.p) return fail(h, GPHIP_ERR_HIP, "scalar buffer of the multi-device handle is missing");
     if (h->debug_fail_hip > 0 && --h->debug_fail_hip == 0) sick = true;                               // fault injection (tests)
     if (sick) v[6] = 1.0;
-    if (hipMemcpyAsync(h->dScal8, v, sizeof v, hipMemcpyHostToDevice, h->stream) != hipSuccess) {
+    if (hipMemcpyAsync(h->dScal8.p, v, sizeof v, hipMemcpyHostToDevice, h->stream) != hipSuccess) {
         (void)hipGetLastError();
         sick = true;
-        (void)hipMemsetAsync(h->dScal8, 0xff, sizeof v, h->stream);                                   // all-ones bytes = NaN
+        (void)hipMemsetAsync(h->dScal8.p, 0xff, sizeof v, h->stream);                                   // all-ones bytes = NaN
     }
-    if (rccl().AllReduce(h->dScal8, h->dScal8, 6, NCCL_FLOAT64, NCCL_MAX, g->comms[0], h->stream) != 0 ||
-        rccl().AllReduce(h->dScal8 + 6, h->dScal8 + 6, 2, NCCL_FLOAT64, NCCL_SUM, g->comms[0], h->stream) != 0) {
+    if (rccl().AllReduce(h->dScal8.p, h->dScal8.p, 6, NCCL_FLOAT64, NCCL_MAX, g->comms[0], h->stream) != 0 ||
+        rccl().AllReduce(h->dScal8.as<double>() + 6, h->dScal8.as<double>() + 6, 2, NCCL_FLOAT64, NCCL_SUM, g->comms[0], h->stream) != 0) {
         g->broken = true;
         return fail(h, GPHIP_ERR_HIP, "ncclAllReduce of the configuration check failed");
     }
-    if (hipMemcpyAsync(v, h->dScal8, sizeof v, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+    if (hipMemcpyAsync(v, h->dScal8.p, sizeof v, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
         hipStreamSynchronize(h->stream) != hipSuccess) {
         (void)hipGetLastError();
         g->broken = true;                                  // this rank cannot learn the verdict its peers act on
@@ -579,16 +572,16 @@ int group_eval_run(gphip_ctx* h, const double* theta, int p, bool keep, double* 
     vals[4] = failed != GPHIP_OK ? 1.0 : 0.0;
     if (nl < W || (g->use_rccl && W == 1)) {                           // ranks elsewhere: one tiny all-reduce
         (void)hipSetDevice(h->device);
-        if (!h->dScal8) return comm_fatal(fail(h, GPHIP_ERR_HIP, "scalar buffer of the multi-device handle is missing"));
-        if (hipMemcpyAsync(h->dScal8, vals, sizeof vals, hipMemcpyHostToDevice, h->stream) != hipSuccess) {
+        if (!h->dScal8.p) return comm_fatal(fail(h, GPHIP_ERR_HIP, "scalar buffer of the multi-device handle is missing"));
+        if (hipMemcpyAsync(h->dScal8.p, vals, sizeof vals, hipMemcpyHostToDevice, h->stream) != hipSuccess) {
             // cannot even upload the error count: send a poisoned vector (NaN in every entry reads as "somebody failed")
             (void)hipGetLastError();
             if (failed == GPHIP_OK) { failed = GPHIP_ERR_HIP; failed_why = "uploading the scalars of a sharded evaluation failed"; }
-            (void)hipMemsetAsync(h->dScal8, 0xff, sizeof vals, h->stream);
+            (void)hipMemsetAsync(h->dScal8.p, 0xff, sizeof vals, h->stream);
         }
-        if (rccl().AllReduce(h->dScal8, h->dScal8, 8, NCCL_FLOAT64, NCCL_SUM, g->comms[0], h->stream) != 0)
+        if (rccl().AllReduce(h->dScal8.p, h->dScal8.p, 8, NCCL_FLOAT64, NCCL_SUM, g->comms[0], h->stream) != 0)
             return comm_fatal(fail(h, GPHIP_ERR_HIP, "ncclAllReduce of the scalars failed"));
-        if (hipMemcpyAsync(vals, h->dScal8, sizeof vals, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+        if (hipMemcpyAsync(vals, h->dScal8.p, sizeof vals, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
             hipStreamSynchronize(h->stream) != hipSuccess) {
             (void)hipGetLastError();
             return comm_fatal(fail(h, GPHIP_ERR_HIP, "reading back the scalars of a sharded evaluation failed"));
@@ -619,10 +612,10 @@ int group_eval_run(gphip_ctx* h, const double* theta, int p, bool keep, double* 
             if (g->replicate != 0) {
                 if (m->dtype == 64)
                     hipLaunchKernelGGL(trtri128_kernel<double>, dim3((unsigned)m->Nt, 1), dim3(256), potrf_lds<double>(), m->stream,
-                                       (const double*)m->dA, (long)m->slot_elems, (double*)m->dW, (int)m->Nt, 0);
+                                       (const double*)m->dA.p, (long)m->slot_elems, (double*)m->dW.p, (int)m->Nt, 0);
                 else
                     hipLaunchKernelGGL(trtri128_kernel<float>, dim3((unsigned)m->Nt, 1), dim3(256), potrf_lds<float>(), m->stream,
-                                       (const float*)m->dA, (long)m->slot_elems, (float*)m->dW, (int)m->Nt, 0);
+                                       (const float*)m->dA.p, (long)m->slot_elems, (float*)m->dW.p, (int)m->Nt, 0);
                 HIPCHK(hipStreamSynchronize(m->stream));
                 HIPCHK(hipGetLastError());
             }
@@ -634,7 +627,7 @@ int group_eval_run(gphip_ctx* h, const double* theta, int p, bool keep, double* 
                 for (int k = g->ranks[i]; k < npan; k += W) {
                     const int K0 = k * m->panel, K1 = (int)std::min<int64_t>(K0 + m->panel, m->Nt);
                     hipLaunchKernelGGL(trtri128_kernel<double>, dim3((unsigned)(K1 - K0), 1), dim3(256), potrf_lds<double>(), m->stream,
-                                       (const double*)dist_panel_base(m, k), 0l, (double*)m->dW, (int)m->Nt, K0);
+                                       (const double*)dist_panel_base(m, k), 0l, (double*)m->dW.p, (int)m->Nt, K0);
                 }
                 HIPCHK(hipStreamSynchronize(m->stream));
                 HIPCHK(hipGetLastError());
