@@ -88,6 +88,8 @@ _SIGNATURES = {
     "gphip_loglik_batch": (C.c_int, [_h, _dp, C.c_int, C.c_int, _dp, _ip]),
     "gphip_loglik_parts": (C.c_int, [_h, _dp, C.c_int, _dp, _dp, _ip]),
     "gphip_loglik_grad": (C.c_int, [_h, _dp, C.c_int, _dp, _dp, _ip]),
+    "gphip_loo": (C.c_int, [_h, _dp, C.c_int, _dp, _dp, _dp, _dp, _ip]),
+    "gphip_loo_grad": (C.c_int, [_h, _dp, C.c_int, _dp, _dp, _ip]),
     "gphip_fit": (C.c_int, [_h, _dp, C.c_int, _ip]),
     "gphip_predict": (C.c_int, [_h, C.c_void_p, C.c_int64, _dp, _dp]),
     "gphip_predict_samples": (C.c_int, [_h, _dp, C.c_int, C.c_int, C.c_void_p, C.c_int64, _dp, _dp, _ip]),
@@ -409,6 +411,30 @@ class Handle:
         out, info = C.c_double(0.0), C.c_int(0)
         grad = np.zeros(th.size)
         self._check(self._lib.gphip_loglik_grad(self._h, _d(th), th.size, C.byref(out), _d(grad), C.byref(info)))
+        return out.value, grad, info.value
+
+    def _theta(self, theta):
+        th = np.ascontiguousarray(np.asarray(theta, dtype=np.float64).ravel())
+        if th.size != self.p:
+            raise GphipError(2, f"theta has {th.size} entries, the handle takes {self.p}")
+        return th
+
+    def loo(self, theta, mean: bool = True, var: bool = True, logp: bool = True) -> dict:
+        """Leave-one-out cross-validation at theta (gphip_loo): {"mean", "var", "logp"} (each [N], or None when not asked
+        for), "total" = the log pseudo-likelihood, "info".  Leaves the fit of theta resident."""
+        th = self._theta(theta)
+        out, info = C.c_double(0.0), C.c_int(0)
+        arrs = [np.zeros(self.N) if want else None for want in (mean, var, logp)]
+        ptrs = [_d(a) if a is not None else None for a in arrs]
+        self._check(self._lib.gphip_loo(self._h, _d(th), th.size, ptrs[0], ptrs[1], ptrs[2], C.byref(out), C.byref(info)))
+        return {"mean": arrs[0], "var": arrs[1], "logp": arrs[2], "total": out.value, "info": info.value}
+
+    def loo_grad(self, theta):
+        """(log pseudo-likelihood, grad[p], info) from gphip_loo_grad; grad has the layout of loglik_grad's."""
+        th = self._theta(theta)
+        out, info = C.c_double(0.0), C.c_int(0)
+        grad = np.zeros(th.size)
+        self._check(self._lib.gphip_loo_grad(self._h, _d(th), th.size, C.byref(out), _d(grad), C.byref(info)))
         return out.value, grad, info.value
 
     def fit(self, theta) -> int:

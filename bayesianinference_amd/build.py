@@ -15,7 +15,8 @@ SRC = os.path.join(PKG, "csrc", "gphip.hip")
 DEPS = [SRC, os.path.join(PKG, "csrc", "gp_kernels.h"), os.path.join(PKG, "csrc", "gp_trsv.h"), os.path.join(PKG, "csrc", "gphip_multi.inc"),
         os.path.join(PKG, "csrc", "gphip_sampler.inc"), os.path.join(PKG, "csrc", "rtc_dyn.h"), os.path.join(PKG, "csrc", "gp_dual.h"),
         os.path.join(PKG, "csrc", "gphip_hostlogic.inc"), os.path.join(PKG, "csrc", "gphip_joint.inc"), os.path.join(PKG, "csrc", "gp_joint.h"),
-        os.path.join(PKG, "csrc", "rccl_dyn.h"), os.path.join(os.path.dirname(PKG), "include", "gphip.h")]
+        os.path.join(PKG, "csrc", "rccl_dyn.h"), os.path.join(PKG, "csrc", "gphip_loo.inc"), os.path.join(PKG, "csrc", "gp_loo.h"),
+        os.path.join(os.path.dirname(PKG), "include", "gphip.h")]
 LIB = os.path.join(PKG, "lib", "libgphip.so")
 
 

@@ -39,7 +39,7 @@ namespace gphip {
 
 // Bumped whenever a struct or constant the run-time compiled copy of this region shares with the offline library changes
 // (KBuildArgs, SLOTP, the tile layout): rtc_dyn.h refuses a source tree whose value differs from the library's own.
-#define GP_RTC_ABI 5
+#define GP_RTC_ABI 6
 // A run-time compiled program is built for ONE handle, whose input dimension is known: the generated source defines GP_D and the
 // dimension loops of the caller's function unroll (their per-dimension reciprocals then leave the column loop).  Offline: the argument.
 #ifdef GP_D
@@ -710,7 +710,16 @@ struct GradArgs {
                                     // derivatives of dimensions [d0, d0 + 32) only (and the scalar ones when d0 == 0)
     double* gpart;                  // [workgroups][np] per-workgroup sums (grad_finish_kernel adds them into gacc), or null: atomics on gacc
     int np, ws_off;                 // accumulator slots per workgroup; where the [4 waves][np] staging area starts in LDS (doubles)
+    const T* beta;                  // [npad] or null.  Null: w = alpha_g alpha_j - Kinv_gj (the log-likelihood).  Set: the leave-one-out
+                                    // pseudo-likelihood, w = alpha_g beta_j + beta_g alpha_j - Kinv_gj with Kinv holding M (gp_loo.h)
 };
+
+// the weight of entry (g, j) in a gradient reduction: see GradArgs::beta (bg / beta[j] are read only when beta is set)
+template <typename T>
+__device__ __forceinline__ double grad_weight(const GradArgs<T>& a, double wt, T ag, T aj, double bg, int j, double kinv) {
+    if (a.beta) return wt * ((double)ag * (double)a.beta[j] + bg * (double)aj - kinv);
+    return wt * ((double)ag * (double)aj - kinv);
+}
 
 // How gradient accumulators leave a workgroup (round 6).  Every wave used to add its wave-reduced sums to gacc with atomics:
 // thousands of waves queued on a dozen addresses (N = 8192: 1 ms of a 12.5 ms gradient call) and the sums were not bit-repeatable.
@@ -763,6 +772,7 @@ __global__ __launch_bounds__(256) void custom_grad_kernel(GradArgs<T> a, const d
     for (int m = 0; m < GP_NCP; ++m) acc[m] = 0.0;
     double acc_dg = 0.0;
     const T ag = (t < a.mc) ? a.alpha[g] : (T)0;
+    const double bg = (a.beta && t < a.mc) ? (double)a.beta[g] : 0.0;
     __syncthreads();
     if (t < a.mc && g < a.n) {
         const PointRef<T> Xg{a.xs + g, (long)a.npad};
@@ -771,7 +781,7 @@ __global__ __launch_bounds__(256) void custom_grad_kernel(GradArgs<T> a, const d
             if (j >= a.n) break;
             const PointRef<T> Yj{glb ? a.xs + j : xjs + jj, glb ? (long)a.npad : (long)TB};
             const dual_t k = gphip_custom_k<dual_t, T>(Xg, Yj, cp, d);
-            const double w = wt * ((double)ag * (double)aj[jj] - (double)a.Kinv[(long)j * a.ldv + t]);
+            const double w = grad_weight(a, wt, ag, aj[jj], bg, j, (double)a.Kinv[(long)j * a.ldv + t]);
 #pragma unroll
             for (int m = 0; m < GP_NCP; ++m) acc[m] = __builtin_fma(w, (double)k.g[m], acc[m]);
             if (j == g) acc_dg += w;
@@ -3314,6 +3324,7 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(GradArgs<T> a) {
     }
     double acc_sf = 0.0, acc_dg = 0.0;
     const T ag = (t < a.mc) ? a.alpha[g] : (T)0;
+    const double bg = (a.beta && t < a.mc) ? (double)a.beta[g] : 0.0;
     const T sf2 = (T)a.slotp[0];
     __syncthreads();
     if (t < a.mc && g < a.n) {
@@ -3340,7 +3351,7 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(GradArgs<T> a) {
                 kpart = sf2 * ((T)1.0 + s5 + (T)(5.0 / 3.0) * r2) * e;
                 fac = sf2 * (T)(5.0 / 3.0) * ((T)1.0 + s5) * e;
             }
-            const double w = wt * ((double)ag * (double)aj[jj] - (double)a.Kinv[(long)j * a.ldv + t]);
+            const double w = grad_weight(a, wt, ag, aj[jj], bg, j, (double)a.Kinv[(long)j * a.ldv + t]);
             const double wf = w * (double)fac;
 #pragma unroll
             for (int dd = 0; dd < DM; ++dd)
@@ -3409,6 +3420,7 @@ __global__ __launch_bounds__(256) void grad_reduce_general_kernel(GradArgs<T> a)
     for (int dd = 0; dd < 32; ++dd) acc1[dd] = acc2[dd] = 0.0;
     double acc_sf1 = 0.0, acc_sf2 = 0.0, acc_dg = 0.0, acc_a1 = 0.0, acc_a2 = 0.0, acc_c = 0.0;
     const T ag = (t < a.mc) ? a.alpha[g] : (T)0;
+    const double bg = (a.beta && t < a.mc) ? (double)a.beta[g] : 0.0;
     const double* sp = a.slotp;
     const T sf2a = (T)sp[0], sf2b = (T)sp[SP_SF2B];
     __syncthreads();
@@ -3431,7 +3443,7 @@ __global__ __launch_bounds__(256) void grad_reduce_general_kernel(GradArgs<T> a)
             if (two) kfamily<T>(a.ks.fam2, r2b, (T)sp[SP_ALPHA2], g2, m2, da2);
             const double k1 = (double)sf2a * (double)g1, k2 = (double)sf2b * (double)g2;
             const double dk1 = (a.ks.op == 2) ? k2 : 1.0, dk2 = (a.ks.op == 2) ? k1 : 1.0;       // dk/dk1, dk/dk2
-            const double w = wt * ((double)ag * (double)aj[jj] - (double)a.Kinv[(long)j * a.ldv + t]);
+            const double w = grad_weight(a, wt, ag, aj[jj], bg, j, (double)a.Kinv[(long)j * a.ldv + t]);
             const double f1 = w * dk1 * (double)sf2a * (double)m1, f2 = w * dk2 * (double)sf2b * (double)m2;
 #pragma unroll
             for (int q = 0; q < 32; ++q)               // (static indices: the accumulators stay in registers)

@@ -233,6 +233,7 @@ struct gphip_ctx {
     int ncu = 0;                                             // compute units of the device
     Buf dKinv;                                               // typed [(Npad + GRAD_LD_PAD) x Npad] lower tiles of K^-1 (gradient, potri route)
     Buf dGacc;                                               // double [d + 2] gradient accumulators
+    Buf dLoo;                                                // leave-one-out scratch: vectors + per-chunk partial sums (gphip_loo.inc)
     // profiling
     std::vector<ProfRec> recs;
     std::vector<hipEvent_t> pool;
@@ -2541,6 +2542,60 @@ int gphip_loglik_batch(gphip_handle h, const double* Theta, int B, int p, double
     return eval_batch(h, Theta, B, p, out, nullptr, info);
 }
 
+// A run-time compiled covariance function's gradient program, compiled on first use: the function's text instantiated with
+// forward-mode dual numbers inside the gradient reduction (custom_grad_kernel), so that a gradient costs ONE factorisation.  A
+// body that does not compile that way (a math function gp_dual.h does not differentiate, intermediates of a fixed scalar type, ..)
+// leaves cgrad_state = -1: the callers keep their difference route.
+static int ensure_custom_grad(gphip_ctx* h) {
+    constexpr int CGRAD_MAX_NCP = 64;
+    if (h->cgrad_state == 0 && h->custom_grad && h->ncp >= 1 && h->ncp <= CGRAD_MAX_NCP) {
+        std::string msg;
+        const std::shared_ptr<const RtcResult> r = rtc_compile_custom(h->custom_body, h->dtype, h->arch.c_str(), msg, nullptr, h->ncp, h->d);
+        h->cgrad_state = -1;
+        HIPCHK(hipSetDevice(h->device));
+        if (r && hipModuleLoadData(&h->cgmod, r->code.data()) == hipSuccess &&
+            hipModuleGetFunction(&h->f_cgrad, h->cgmod, r->grad.c_str()) == hipSuccess)
+            h->cgrad_state = 1;
+        else
+            (void)hipGetLastError();
+    }
+    return GPHIP_OK;
+}
+
+// The chain rule from the accumulators of a gradient reduction (grad_reduce_*, custom_grad_kernel) onto the theta layout
+// [term 1: l.., (alpha), sf] [term 2] [c] sn [mu]  (run-time compiled function: [p_0 .. p_{ncp-1}] sn [mu]).  Returns the index
+// of the next derivative: the constant mean's, which the caller fills.
+static int grad_chain_rule(const gphip_ctx* h, const double* theta, const std::vector<double>& gacc, double* grad) {
+    const int64_t d = h->d;
+    int o = 0;                                                // (theta index of the next derivative)
+    if (h->custom) {
+        for (int m = 0; m < h->ncp; ++m) grad[m] = 0.5 * gacc[(size_t)m];
+        grad[h->ncp] = gacc[(size_t)h->ncp] * theta[h->ncp];
+        return h->ncp + 1;
+    }
+    auto lengths = [&](int nl, size_t base) {
+        if (nl == 1) {
+            double sum = 0.0;
+            for (int64_t j = 0; j < d; ++j) sum += gacc[base + (size_t)j];
+            grad[o] = 0.5 * sum / theta[o];                   // even in l: d/dl of f(l^2)
+        } else {
+            for (int64_t j = 0; j < d; ++j) grad[o + j] = 0.5 * gacc[base + (size_t)j] / theta[o + j];
+        }
+        o += nl;
+    };
+    lengths(h->nl, 0);
+    if (h->has_a1) grad[o++] = 0.5 * gacc[(size_t)2 * d + 3];
+    grad[o] = gacc[(size_t)d] / theta[o]; ++o;                // sf1: 1/2 * sum w (dk/dk1) k1 * 2/sf
+    if (h->nl2 > 0) {
+        lengths(h->nl2, (size_t)d + 2);
+        if (h->has_a2) grad[o++] = 0.5 * gacc[(size_t)2 * d + 4];
+        grad[o] = gacc[(size_t)2 * d + 2] / theta[o]; ++o;
+    }
+    if (h->ks.offset) grad[o++] = 0.5 * gacc[(size_t)2 * d + 5];
+    grad[o] = gacc[(size_t)d + 1] * theta[o]; ++o;            // sn: 1/2 * tr(W) * 2 sn
+    return o;
+}
+
 // log-likelihood and its gradient with respect to theta (same layout as theta).  One factorisation,
 // then K^-1 is streamed through the scratch block up to 8 GiB of rows at a time (forward + backward
 // substitution of identity rows) and contracted against dK/dtheta on the fly.
@@ -2555,21 +2610,7 @@ int gphip_loglik_grad(gphip_handle h, const double* theta, int p, double* out, d
     std::lock_guard<std::recursive_mutex> lk(h->mu);
     if (h->custom) {
         if (p != h->p) return fail(h, GPHIP_ERR_DIM, "theta has the wrong length");
-        // One factorisation: the function's text instantiated with forward-mode dual numbers inside the gradient reduction
-        // (custom_grad_kernel), compiled on first use.  A body that does not compile that way (a math function gp_dual.h
-        // does not differentiate, intermediates of a fixed scalar type, ..) keeps the difference route below.
-        constexpr int CGRAD_MAX_NCP = 64;
-        if (h->cgrad_state == 0 && h->custom_grad && h->ncp >= 1 && h->ncp <= CGRAD_MAX_NCP) {
-            std::string msg;
-            const std::shared_ptr<const RtcResult> r = rtc_compile_custom(h->custom_body, h->dtype, h->arch.c_str(), msg, nullptr, h->ncp, h->d);
-            h->cgrad_state = -1;
-            HIPCHK(hipSetDevice(h->device));
-            if (r && hipModuleLoadData(&h->cgmod, r->code.data()) == hipSuccess &&
-                hipModuleGetFunction(&h->f_cgrad, h->cgmod, r->grad.c_str()) == hipSuccess)
-                h->cgrad_state = 1;
-            else
-                (void)hipGetLastError();
-        }
+        if (const int rc = ensure_custom_grad(h)) return rc;
     }
     h->grad_analytic = 0;
     if (h->custom && !(h->custom_grad && h->cgrad_state == 1)) {
@@ -2653,35 +2694,7 @@ int gphip_loglik_grad(gphip_handle h, const double* theta, int p, double* out, d
     rc = complete_call(h, [&] { return DISPATCH(h, download, h, alpha, h->dAlpha.p, (size_t)N, h->stream); });
     if (rc) return rc;
     h->grad_analytic = 1;
-    int o = 0;                                                // (theta index of the next derivative)
-    if (h->custom) {
-        // theta = [p_0 .. p_{ncp-1}] sn [mu]  (accumulators: custom_grad_kernel)
-        for (int m = 0; m < h->ncp; ++m) grad[m] = 0.5 * gacc[(size_t)m];
-        grad[h->ncp] = gacc[(size_t)h->ncp] * theta[h->ncp];
-        o = h->ncp + 1;
-    } else {
-        // chain rule onto the theta layout [term 1: l.., (alpha), sf] [term 2] [c] sn [mu]  (accumulators: grad_reduce_*)
-        auto lengths = [&](int nl, size_t base) {
-            if (nl == 1) {
-                double sum = 0.0;
-                for (int64_t j = 0; j < d; ++j) sum += gacc[base + (size_t)j];
-                grad[o] = 0.5 * sum / theta[o];                   // even in l: d/dl of f(l^2)
-            } else {
-                for (int64_t j = 0; j < d; ++j) grad[o + j] = 0.5 * gacc[base + (size_t)j] / theta[o + j];
-            }
-            o += nl;
-        };
-        lengths(h->nl, 0);
-        if (h->has_a1) grad[o++] = 0.5 * gacc[(size_t)2 * d + 3];
-        grad[o] = gacc[(size_t)d] / theta[o]; ++o;                // sf1: 1/2 * sum w (dk/dk1) k1 * 2/sf
-        if (h->nl2 > 0) {
-            lengths(h->nl2, (size_t)d + 2);
-            if (h->has_a2) grad[o++] = 0.5 * gacc[(size_t)2 * d + 4];
-            grad[o] = gacc[(size_t)2 * d + 2] / theta[o]; ++o;
-        }
-        if (h->ks.offset) grad[o++] = 0.5 * gacc[(size_t)2 * d + 5];
-        grad[o] = gacc[(size_t)d + 1] * theta[o]; ++o;            // sn: 1/2 * tr(W) * 2 sn
-    }
+    const int o = grad_chain_rule(h, theta, gacc, grad);
     if (h->mean_id == GPHIP_MEAN_CONST) {
         double sum = 0.0;
         for (double v : alpha) sum += v;
@@ -3745,3 +3758,4 @@ int gphip_sync(gphip_handle h) {
 #include "gphip_hostlogic.inc"
 #include "gphip_sampler.inc"
 #include "gphip_joint.inc"
+#include "gphip_loo.inc"

@@ -349,6 +349,23 @@ def defineGaussianProcess(data, kernel, nugget="Constant", meanFunction=None, va
         ll, grad, info = handle.loglik_grad(theta)
         return (ll, grad) if info == 0 else (MACHINE_LOG_ZERO, np.full(len(params), np.nan))
 
+    def log_pseudo_likelihood(theta):
+        """The leave-one-out log pseudo-likelihood L_LOO(theta) (R&W GPML 5.4.2; gphip_loo): the alternative to the marginal
+        likelihood for choosing hyper-parameters.  Sentinel on numerical failure, like the likelihood closure."""
+        if pointwise:
+            return MACHINE_LOG_ZERO                               # (the library has no point-dependent form of it)
+        res = handle.loo(theta, mean=False, var=False, logp=False)
+        if res["info"] != 0 or not math.isfinite(res["total"]):
+            return MACHINE_LOG_ZERO
+        return min(max(res["total"], MACHINE_LOG_ZERO), -MACHINE_LOG_ZERO)
+
+    def log_pseudo_likelihood_gradient(theta):
+        """(L_LOO, gradient) from ONE factorisation (gphip_loo_grad); sentinel and NaN gradient on numerical failure."""
+        if pointwise:
+            return MACHINE_LOG_ZERO, np.full(len(params), np.nan)
+        total, grad, info = handle.loo_grad(theta)
+        return (total, grad) if info == 0 and math.isfinite(total) else (MACHINE_LOG_ZERO, np.full(len(params), np.nan))
+
     def covariance_function(theta):                               # "CovarianceFunction", BGP:264-271
         K = handle.covariance(theta)                              # Listable: B x p -> B matrices (BGP:59)
         if nugget_fn is not None:                                 # nugget[points[[i]]] on the diagonal instead of sn^2
@@ -391,6 +408,8 @@ def defineGaussianProcess(data, kernel, nugget="Constant", meanFunction=None, va
         },
         **rules,
         "LogLikelihoodGradientFunction": log_likelihood_gradient,
+        "LogPseudoLikelihoodFunction": log_pseudo_likelihood,
+        "LogPseudoLikelihoodGradientFunction": log_pseudo_likelihood_gradient,
         "LogLikelihoodFunction": loglik,
     })
 
@@ -589,6 +608,71 @@ def gaussianProcessFunctionSamples(obj, pts, n: int, seed: int = 0, latent: bool
         if info == 0:
             values[rows] = out
     return {"Points": P, "Sample": which, "Values": values}
+
+
+def _output_scale(obj):
+    """(inverse, scale) of the "Output" pre-processor of an object defined on normalizeData(..) data: y = inverse(z), and the
+    factor by which it stretches a standard deviation; (None, 1.0) for an object on raw data."""
+    pre = obj.get("DataPreProcessors") if hasattr(obj, "get") else None
+    if not pre or "Output" not in pre:
+        return None, 1.0
+    inv = pre["Output"]["InverseFunction"]
+    return inv, float(np.ravel(inv(np.array([1.0])))[0] - np.ravel(inv(np.array([0.0])))[0])
+
+
+def leaveOneOutFromGaussianProcess(obj, theta=None):
+    """Leave-one-out cross-validation of the training data of a HIP-backed GP object (R&W GPML 5.4.2; one factorisation per
+    theta, gphip_loo): how well the model predicts each point from all the others.  Returns, in the units of the data
+    ("DataPreProcessors" undone):
+        "Mean" [N], "StandardDeviation" [N]   of the leave-one-out predictive distribution of each training output
+        "LogDensity" [N]                      log p(y_i | X, y_-i)
+        "LogPseudoLikelihood"                 their sum
+        "StandardizedResiduals" [N]           (y_i - Mean_i) / StandardDeviation_i
+    theta given: that hyper-parameter vector.  theta=None on a sampled object: the posterior mixture over its "Samples" -- per
+    point, LogDensity = log of the CrudePosteriorWeight-weighted mean of exp(log p_i) over the samples, Mean / StandardDeviation
+    the moments of the mixture of the per-sample normals (one gphip_loo per distinct theta; samples that do not factor carry no
+    weight).  None for a failed object, an object with point-dependent nugget / mean functions, a theta that does not factor,
+    or theta=None without "Samples"."""
+    if not isinstance(obj, inferenceObject) or obj.failed or "GaussianProcessData" not in obj:
+        return None
+    mf = obj["GaussianProcessData"]["ModelFunctions"]
+    if callable(mf["NuggetFunction"]) or callable(mf["MeanFunction"]):
+        return None
+    handle = obj["GaussianProcessData"]["HIPHandle"]
+    y = np.asarray(obj["Data"][1], dtype=np.float64)[:, 0]
+    if theta is not None:
+        res = handle.loo(np.asarray(theta, dtype=np.float64).ravel())
+        if res["info"] != 0:
+            return None
+        mean, var, logp = res["mean"], res["var"], res["logp"]
+    else:
+        if "Samples" not in obj:
+            return None
+        samples = obj["Samples"]
+        points = np.array([s["Point"] for s in samples], dtype=np.float64)
+        w = np.array([s["CrudePosteriorWeight"] for s in samples], dtype=np.float64)
+        uniq, which = np.unique(points, axis=0, return_inverse=True)
+        which = np.ravel(which)
+        wu = np.array([w[which == k].sum() for k in range(len(uniq))])
+        rows = [handle.loo(t) for t in uniq]
+        ok = np.array([r["info"] == 0 for r in rows])
+        if not ok.any() or wu[ok].sum() <= 0:
+            return None
+        wu = wu[ok] / wu[ok].sum()
+        mus = np.array([r["mean"] for r, good in zip(rows, ok) if good])
+        vs = np.array([r["var"] for r, good in zip(rows, ok) if good])
+        lps = np.array([r["logp"] for r, good in zip(rows, ok) if good])
+        top = lps.max(axis=0)
+        logp = top + np.log((wu[:, None] * np.exp(lps - top)).sum(axis=0))
+        mean = (wu[:, None] * mus).sum(axis=0)
+        var = (wu[:, None] * (vs + mus * mus)).sum(axis=0) - mean * mean
+    sd = np.sqrt(var)
+    resid = (y - mean) / sd
+    inv, scale = _output_scale(obj)
+    if inv is not None:
+        mean, sd, logp = np.ravel(inv(mean)), sd * abs(scale), logp - math.log(abs(scale))
+    return {"Mean": mean, "StandardDeviation": sd, "LogDensity": logp, "LogPseudoLikelihood": float(np.sum(logp)),
+            "StandardizedResiduals": resid}
 
 
 def mixture_moments(pred: Mapping):

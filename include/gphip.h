@@ -12,6 +12,7 @@
  *   gphip_predict       predictFromGaussianProcessInternal                 BGP:396-422
  *   gphip_predict_samples  predictFromGaussianProcess over all samples     BGP:343-376
  *   gphip_predict_cov / _draws / _logpdf  the joint N(mu, Sigma) of the test points (no reference counterpart)
+ *   gphip_loo / gphip_loo_grad  leave-one-out cross-validation of the training set (no reference counterpart)
  *   gphip_*_pw          the same with point-dependent nugget[x] / mean[x]  BGP:37, 113, 171, 300, 408
  *   gphip_covariance    "CovarianceFunction" = compiledCovarianceMatrix    BGP:45-61
  *   gphip_solve         "InverseCovarianceFunction"[theta]["Inverse"][b]   BGP:130-141
@@ -218,6 +219,33 @@ int gphip_predict_draws(gphip_handle h, const void* Xs, int64_t M, int latent, i
 /* log N(ystar | mean, Sigma) with the noisy-observation Sigma (latent = 0): the joint predictive log density of held-out
  * data.  *info as gphip_loglik's (*out undefined if *info != 0). */
 int gphip_predict_logpdf(gphip_handle h, const void* Xs, int64_t M, const double* ystar, double* out, int* info);
+/* ---- Leave-one-out cross-validation (Rasmussen & Williams, GPML section 5.4.2; no reference counterpart): how well the model
+ * at theta predicts every training point from the other N - 1, from ONE factorisation.  With alpha = K^-1 (y - m) and
+ * k_i = [K^-1]_ii:
+ *     mean[i] = y_i - alpha_i / k_i        var[i] = 1 / k_i   (variance of a noisy observation: includes sn^2, as gphip_predict's)
+ *     logp[i] = 1/2 log k_i - 1/2 alpha_i^2 / k_i - 1/2 log 2 pi  = log p(y_i | X, y_-i, theta)
+ *     *out    = L_LOO = sum_i logp[i], the log pseudo-likelihood
+ * mean, var, logp: length N, each may be NULL (it is then not downloaded).  *out is summed on the device in a fixed order:
+ * partial sum t (t = 0 .. 1023) adds logp[t], logp[t + 1024], .. in that order, then p[t] += p[t + off] for off = 512, 256, .. 1;
+ * *out = p[0].  Two calls give the same bytes.
+ * On the device: the factorisation of gphip_loglik_grad, U = L^-T (upper triangular), then ONE pass over U gives alpha = U z
+ * (z = L^-1 (y - m)) and the squared row norms k_i = sum_{j >= i} U_ij^2 -- K^-1 itself is not formed.  Cost: a factorisation
+ * plus N^3 / 3 for U; one N x N scratch buffer.
+ * gphip_loo_grad: L_LOO and its gradient (grad: length p, layout and chain rule of gphip_loglik_grad).  With g = alpha / k,
+ * beta = K^-1 g, c_i = 1 / k_i + g_i^2 and M = K^-1 diag(c) K^-1:
+ *     dL_LOO/dtheta_j = 1/2 sum_ab (alpha_a beta_b + beta_a alpha_b - M_ab) dK_ab/dtheta_j,      dL_LOO/dmu = sum_i beta_i
+ * the contraction of gphip_loglik_grad with other weights.  K^-1 = U U^T as there, then M = B B^T with B = K^-1 diag(sqrt c)
+ * on the matrix pipe (N^3 flop, written over U): about twice the cost of gphip_loglik_grad; two N x N scratch buffers.
+ * Both calls evaluate at theta and leave that fit resident, like gphip_loglik_grad: gphip_predict / gphip_solve /
+ * gphip_predict_cov work afterwards without a gphip_fit.  *info as gphip_loglik's; outputs are NaN when *info != 0.
+ * Supported: every kernel (the null kernel on the host: mean = m, var = sn^2), fp64 and fp32 handles.  A run-time compiled
+ * function whose dual-number gradient program does not compile (see GPHIP_KERNEL_CUSTOM) gets central differences of gphip_loo
+ * (2 p + 1 factorisations, the step of gphip_loglik_grad).  A multi-device handle factors on its first device.
+ * GPHIP_ERR_UNSUPPORTED: a handle with a point-dependent nugget / mean array set, and scratch buffers that do not fit in a
+ * quarter of the free device memory (there is no row-block route).  GPHIP_ERR_ARG: NULL h, theta, out, (grad,) info;
+ * GPHIP_ERR_DIM: wrong p -- both before any device work. */
+int gphip_loo(gphip_handle h, const double* theta, int p, double* mean, double* var, double* logp, double* out, int* info);
+int gphip_loo_grad(gphip_handle h, const double* theta, int p, double* out, double* grad, int* info);
 /* ---- Point-dependent nugget and mean functions.  The reference evaluates nugget[points[[i]]] (BGP:37), meanFunction /@
  * inputData (BGP:171, 300), kernel[p, p] + nugget[p] at the test points (BGP:113) and meanFunction /@ inputs (BGP:408) for
  * ANY functions of the point (heteroscedastic noise, any m(x)).  Those functions live on the host (WL / Python); the host
