@@ -201,9 +201,9 @@ struct gphip_ctx {
     int dataflow_tail = 64;                      // large N: the last <= dataflow_tail tile columns go to the dataflow kernel (0 = off)
     bool fused_eval = false;                     // eval_chunk: the whole evaluation is ONE dataflow launch (build + factor + results)
     bool theta_packed = false;                   // eval_chunk: hyper-parameters travel as kernel arguments (k_scale_theta)
-    bool want_w = false;                         // the caller substitutes with W_b afterwards (fit / predict / gradient)
-    bool want_u = false, u_ready = false;        // gradient: a single-launch factorisation is followed by the inverse launch of the same
-                                                 // kernel (U = L^-T into dV, see DfArgs::U); u_ready: it ran for the current factor
+    bool want_w = false;                         // the caller substitutes with W_b afterwards (fit / predict / gradient); set by FactorMode only
+    bool want_u = false;                         // gradient / LOO: a single-launch factorisation is followed by the inverse launch of the same
+    unsigned long u_gen = ~0ul;                  // kernel (U = L^-T into dKinv, see DfArgs::U); u_gen: ws_gen of the factor it ran for
     Buf dFlags;                                  // int [slots][(Nt+1)^2] ready flags (value = epoch)
     Buf dTicket;                                 // unsigned long long: task ticket counter (+ abort flag in the next word)
     const char* abort_unread = nullptr;          // a launch without a finalize behind it left the abort word to the call: its error text
@@ -319,6 +319,15 @@ void invalidate_fit(gphip_ctx* h) {
 void stamp_fit(gphip_ctx* h);
 void record_fit(gphip_ctx* h, bool ok, const double* theta, int p, double logdet);
 bool has_fit(const gphip_ctx* h) { return h->fitted && h->fit_gen == h->ws_gen; }
+
+struct FactorMode {                            // what the next factorisation leaves for its caller: set here, restored on every exit path
+    gphip_ctx* h;
+    const bool w, u;
+    FactorMode(gphip_ctx* h_, bool want_w, bool want_u = false) : h(h_), w(h_->want_w), u(h_->want_u) { h->want_w = want_w; h->want_u = want_u; }
+    ~FactorMode() { h->want_w = w; h->want_u = u; }
+    FactorMode(const FactorMode&) = delete;
+    FactorMode& operator=(const FactorMode&) = delete;
+};
 
 double pivot_tol_rel(const gphip_ctx* h) {
     return 64.0 * (h->dtype == 64 ? 2.220446049250313e-16 : 1.1920929e-07);
@@ -933,7 +942,7 @@ void launch_dataflow(gphip_ctx* h, int nslots, int c0 = 0, double* part = nullpt
 }
 
 // U = L^-T of the factor a single dataflow launch has just queued (one slot), by a second launch of the same kernel whose
-// tasks are the tiles of U (DfArgs::U): column-major Npad x Npad in dKinv (queue_grad_potri then contracts K^-1 = U U^T into dV).
+// tasks are the tiles of U (DfArgs::U): column-major Npad x Npad in dKinv (queue_u hands it on; queue_kinv then contracts K^-1 = U U^T into dV).
 // The multi-kernel route to the same U (queue_forward_rows over the identity) is a chain of ~3 launches per tile column.
 // Column-major U / K^-1 of the inverse-launch route use a leading dimension that is NOT a multiple of a large power of two
 // (Npad + 16 elements): with ld = Npad = 8192 doubles every k-column of an operand tile starts 64 KiB after the previous one
@@ -969,7 +978,7 @@ void launch_dataflow_inverse(gphip_ctx* h, int64_t fwd_rows = 0, bool back = fal
     ThetaPack tp;
     abort_hook(h, 2);
     hipLaunchKernelGGL((chol_dataflow_kernel<T, TBX, OCC, NST, false>), dim3((unsigned)tasks), dim3(256), lds, h->stream, g, tp);
-    if (fwd_rows == 0) h->u_ready = true;
+    if (fwd_rows == 0) h->u_gen = h->ws_gen;
     if (!h->abort_unread)
         h->abort_unread = fwd_rows == 0 ? "dataflow inverse launch timed out (set option grad_potri=2 and report)"
                           : back        ? "dataflow backward substitution timed out (set option predict_df=0 and report)"
@@ -1051,7 +1060,6 @@ int abort_probe_verdict(gphip_ctx* h) {
     h->hInfo.as<int>()[h->slots + 1] = 0;
     if (const int rc = clear_abort_word(h)) return rc;
     h->fitted = false;                         // the factor itself may be intact, but nothing derived from it in this call is
-    h->u_ready = false;
     return fail(h, GPHIP_ERR_HIP, what);
 }
 
@@ -1475,6 +1483,14 @@ int null_kernel_batch(gphip_ctx* h, const double* Theta, int B, double* out, dou
     return GPHIP_OK;
 }
 
+// null kernel, theta = sn [mu]: the verdict on them as gphip_loglik's info (the calls that answer on the host: fit, leave-one-out)
+int null_theta_info(const gphip_ctx* h, const double* theta, double* mu) {
+    const double sn = theta[0], v = sn * sn;
+    *mu = (h->mean_id == GPHIP_MEAN_CONST) ? theta[1] : 0.0;
+    if (!(std::isfinite(sn) && std::isfinite(*mu))) return GPHIP_INFO_NAN;
+    return v > 0.0 && std::isfinite(std::log(v)) ? GPHIP_INFO_OK : GPHIP_INFO_NOT_SPD;
+}
+
 // s0: index of the chunk's first theta within the call (rows of the call's point-dependent nugget / mean arrays)
 int eval_chunk(gphip_ctx* h, const double* Theta, int nb, double* out, double* parts, int* info, int s0 = 0) {
     std::vector<char> okv(nb);
@@ -1692,6 +1708,16 @@ int queue_forward_rows(gphip_ctx* h, int64_t mpad, int nslots, int b_start = 0, 
     for (int k0 = b_start; k0 < Nt; k0 += P)     // b_start > 0: the rows are known to be zero left of tile column b_start
         queue_forward_panel<T>(h, mpad, nslots, k0, std::min(k0 + P, Nt), b_start, identity_rows);
     return 0;
+}
+
+// the forward substitution of the mpad rows in dV with the fitted factor (prediction, solve, joint prediction): ONE dataflow
+// launch where the 64-block inverses allow it (true), else the multi-kernel pass above
+bool queue_forward_fit(gphip_ctx* h, int64_t mpad) {
+    ensure_w64(h);
+    const bool df = df_forward_ok(h, mpad);
+    if (df) launch_dataflow_inverse<double, 64>(h, mpad);
+    else DISPATCH(h, queue_forward_rows, h, mpad, 1);
+    return df;
 }
 
 // V <- V L^-1 (backward substitution, block columns from last to first), "NN" GEMM role:
@@ -2025,6 +2051,16 @@ int queue_alpha(gphip_ctx* h) {
     return GPHIP_OK;
 }
 
+// the arguments of a gradient reduction over rows [c0, c0 + mc) of K^-1, held with leading dimension ld
+template <typename T>
+GradArgs<T> grad_args(gphip_ctx* h, const void* Kinv, long ld, int64_t c0, int64_t mc) {
+    GradArgs<T> a{};
+    a.Kinv = (const T*)Kinv; a.ldv = ld; a.alpha = (const T*)h->dAlpha.p; a.xs = (const T*)h->dXs.p;
+    a.npad = (int)h->Npad; a.n = (int)h->N; a.c0 = (int)c0; a.mc = (int)mc; a.d = (int)h->d;
+    a.slotp = h->dSlotp.as<double>(); a.gacc = h->dGacc.as<double>();
+    return a;
+}
+
 // rows [c0, c0+mc) of K^-1 into dV (identity rows -> forward -> backward), then the reduction
 template <typename T>
 int queue_grad_chunk(gphip_ctx* h, int64_t c0, int64_t mc, int64_t mpad) {
@@ -2035,59 +2071,84 @@ int queue_grad_chunk(gphip_ctx* h, int64_t c0, int64_t mc, int64_t mpad) {
                        (int)c0, (int)mc);
     queue_forward_rows<T>(h, mpad, 1, (int)(c0 / TB), true);
     queue_backward_rows<T>(h, mpad);
-    GradArgs<T> a{};
-    a.Kinv = (const T*)h->dV.p; a.ldv = mpad; a.alpha = (const T*)h->dAlpha.p; a.xs = (const T*)h->dXs.p;
-    a.npad = (int)h->Npad; a.n = (int)h->N; a.c0 = (int)c0; a.mc = (int)mc; a.d = (int)h->d;
-    a.slotp = h->dSlotp.as<double>(); a.gacc = h->dGacc.as<double>();
-    const dim3 grid((unsigned)(mpad / TB), (unsigned)h->Nt);
-    launch_grad<T>(h, a, grid);
+    GradArgs<T> a = grad_args<T>(h, h->dV.p, mpad, c0, mc);
+    launch_grad<T>(h, a, dim3((unsigned)(mpad / TB), (unsigned)h->Nt));
     return GPHIP_OK;
 }
 
-// alpha = L^-T z with the explicit U = L^-T that launch_dataflow_inverse left in dKinv (z = the factored right-hand-side row);
-// scratch: the head of dV (z, then the per-chunk partial sums), free until K^-1 is contracted into it
+// ---- The whole of K^-1 at once, LAPACK potri style (2/3 N^3 instead of the 4/3 N^3 of forward + backward substitution), for
+// the gradient's potri route and leave-one-out (gphip_loo.inc): two N x N buffers, dKinv and dV, both column-major ----
+// Claims those of the two a call needs, if what is still missing of them fits in a quarter of the device memory that is free
+// now.  false (HIP's last-error state cleaned): the caller decides what that means.
+bool claim_inverse_scratch(gphip_ctx* h, bool need_kinv, bool need_v) {
+    const int64_t cap = h->Npad + GRAD_LD_PAD;
+    const size_t nn = (size_t)cap * h->Npad * h->es;
+    const size_t missing = (size_t)(need_kinv && h->dKinv.bytes < nn) + (size_t)(need_v && h->vcap < cap);
+    size_t fr = 0, tot = 0;
+    const bool ok = (!missing || (hipMemGetInfo(&fr, &tot) == hipSuccess && missing * nn <= fr / 4)) &&
+                    (!need_v || ensure_vbuf(h, cap) == GPHIP_OK) && (!need_kinv || h->dKinv.grow(nn) == hipSuccess);
+    if (!ok) (void)hipGetLastError();
+    return ok;
+}
+
+// Where U = L^-T of the current factor is, and the other of the two buffers (scratch until K^-1 is contracted into it)
+struct InvBufs {
+    void *U, *other;
+    long ld;
+};
+bool inverse_launch_ran(const gphip_ctx* h) { return h->u_gen == h->ws_gen; }
+
+// U of a factor made under FactorMode's want_u: a single-launch factorisation has left it in dKinv already
+// (launch_dataflow_inverse); otherwise it is queued here into dV, a forward pass over all identity rows (upper triangular,
+// zero tiles skipped).  The one place that knows which buffer and which leading dimension.
 template <typename T>
-int queue_alpha_from_u(gphip_ctx* h) {
+InvBufs queue_u(gphip_ctx* h) {
+    const long npad = h->Npad;
+    if (inverse_launch_ran(h)) return {h->dKinv.p, h->dV.p, npad + GRAD_LD_PAD};
+    int gx = (int)((npad * npad + 255) / 256);
+    if (gx > 4096) gx = 4096;
+    hipLaunchKernelGGL(identity_rows_kernel<T>, dim3(gx), dim3(256), 0, h->stream, (T*)h->dV.p, npad, (int)npad, 0, (int)h->N);
+    queue_forward_rows<T>(h, npad, 1, 0, true);
+    return {h->dV.p, h->dKinv.p, npad};
+}
+
+// alpha = L^-T z = U z (z = the factored right-hand-side row); scratch: the head of b.other (z, then the per-chunk partial sums)
+template <typename T>
+int queue_alpha_from_u(gphip_ctx* h, const InvBufs& b) {
     const int npad = (int)h->Npad, chunk = 128, nch = (npad + chunk - 1) / chunk;     // (128-column chunks: Nt x Nt / 2 workgroups with work)
-    T* z = (T*)h->dV.p;
-    double* part = reinterpret_cast<double*>(static_cast<char*>(h->dV.p) + (((size_t)npad * sizeof(T) + 255) / 256) * 256);
+    T* z = (T*)b.other;
+    double* part = reinterpret_cast<double*>(static_cast<char*>(b.other) + (((size_t)npad * sizeof(T) + 255) / 256) * 256);
     hipLaunchKernelGGL(gather_rhs_row_kernel<T>, dim3((unsigned)((npad + 255) / 256)), dim3(256), 0, h->stream, (const T*)h->dA.p,
                        (int)h->R, 0, npad, z, 1l);
     hipLaunchKernelGGL(utri_gemv_partial_kernel<T>, dim3((unsigned)(npad / TB), (unsigned)nch), dim3(TB), 0, h->stream,
-                       (const T*)h->dKinv.p, (long)(npad + GRAD_LD_PAD), (const T*)z, npad, chunk, part);
+                       (const T*)b.U, b.ld, (const T*)z, npad, chunk, part);
     hipLaunchKernelGGL(utri_gemv_finish_kernel<T>, dim3((unsigned)((npad + 255) / 256)), dim3(256), 0, h->stream, (const double*)part, nch,
                        npad, (T*)h->dAlpha.p);
     return GPHIP_OK;
 }
 
-// The whole of K^-1 at once, LAPACK potri style (2/3 N^3 instead of the 4/3 N^3 of forward + backward
-// substitution): U = L^-T from a forward pass over all identity rows (upper triangular, zero tiles
-// skipped), then the lower tiles of K^-1 = U U^T as ONE triangular launch whose tile (i,j) contracts
-// k >= 128 i only, then the reduction over the lower triangle (strictly lower tiles counted twice).
+// the lower tiles of K^-1 = U U^T into b.other: ONE triangular launch whose tile (i,j) contracts k >= 128 i only
 template <typename T>
-int queue_grad_potri(gphip_ctx* h) {
-    const long npad = h->Npad;
-    const long tot = npad * npad;
-    int gx = (int)((tot + 255) / 256);
-    if (gx > 4096) gx = 4096;
-    // a single-launch factorisation has left U = L^-T in dKinv already (launch_dataflow_inverse): K^-1 then goes to dV
-    const bool pre = h->u_ready;
-    h->u_ready = false;
-    const T* Ub = (const T*)(pre ? h->dKinv.p : h->dV.p);
-    const T* Kb = (const T*)(pre ? h->dV.p : h->dKinv.p);
-    if (!pre) {
-        hipLaunchKernelGGL(identity_rows_kernel<T>, dim3(gx), dim3(256), 0, h->stream, (T*)h->dV.p, npad, (int)npad, 0, (int)h->N);
-        queue_forward_rows<T>(h, npad, 1, 0, true);
-    }
-    const long ldk = pre ? npad + GRAD_LD_PAD : npad;
-    launch_gemm<T>(h, 2, cm<T>(Kb, ldk, 0), cm<T>(Ub, ldk, 0), cm<T>(Ub, ldk, 0),
-                   (int)npad, 0, (int)h->Nt, 0, (int)h->Nt, 1, 1, 1, 1);
-    GradArgs<T> a{};
-    a.Kinv = Kb; a.ldv = ldk; a.alpha = (const T*)h->dAlpha.p; a.xs = (const T*)h->dXs.p;
-    a.npad = (int)npad; a.n = (int)h->N; a.c0 = 0; a.mc = (int)h->N; a.d = (int)h->d; a.tri = 1;
-    a.slotp = h->dSlotp.as<double>(); a.gacc = h->dGacc.as<double>();
-    const dim3 grid((unsigned)h->Nt, (unsigned)h->Nt);
-    launch_grad<T>(h, a, grid);
+void queue_kinv(gphip_ctx* h, const InvBufs& b) {
+    const T* Ub = (const T*)b.U;
+    launch_gemm<T>(h, 2, cm<T>((const T*)b.other, b.ld, 0), cm<T>(Ub, b.ld, 0), cm<T>(Ub, b.ld, 0), (int)h->Npad, 0, (int)h->Nt, 0, (int)h->Nt,
+                   1, 1, 1, 1);
+}
+
+// the reduction over the lower triangle of a lower-stored matrix (strictly lower tiles counted twice); beta: GradArgs::beta
+template <typename T>
+void queue_grad_full(gphip_ctx* h, const void* Kinv, long ld, const void* beta) {
+    GradArgs<T> a = grad_args<T>(h, Kinv, ld, 0, h->N);
+    a.tri = 1; a.beta = (const T*)beta;
+    launch_grad<T>(h, a, dim3((unsigned)h->Nt, (unsigned)h->Nt));
+}
+
+// the accumulators of a gradient reduction (h->ngacc of them) -- general form: both terms' length scales, sf, alpha, c, sn;
+// run-time compiled function: its ncp parameters, sn
+int ensure_gacc(gphip_ctx* h) {
+    const size_t n = std::max((size_t)2 * h->d + 6, (size_t)h->ncp + 1);
+    HIPCHK(h->dGacc.grow(n * 8));
+    h->ngacc = n;
     return GPHIP_OK;
 }
 
@@ -2596,6 +2657,24 @@ static int grad_chain_rule(const gphip_ctx* h, const double* theta, const std::v
     return o;
 }
 
+// the tail of an analytic gradient call: the chain rule, then d/dmu = the sum of dmu (alpha; leave-one-out: beta)
+static void grad_from_acc(gphip_ctx* h, const double* theta, const std::vector<double>& gacc, const std::vector<double>& dmu, double* grad) {
+    h->grad_analytic = 1;
+    const int o = grad_chain_rule(h, theta, gacc, grad);
+    if (h->mean_id == GPHIP_MEAN_CONST) {
+        double sum = 0.0;
+        for (double v : dmu) sum += v;
+        grad[o] = sum;
+    }
+}
+
+// Central differences where a custom body has no dual-number program: the step in theta_k, eps^(1/3) max(|theta_k|, 1e-2) in
+// the handle's arithmetic (fp64 6e-6, fp32 5e-3): the truncation error (h^2 / 6 times the third derivative) and the rounding
+// error eps_ll |ll| / h balance there; expect ~1e-6 relative in fp64 at moderate N, ~1e-2 in fp32.
+static double fd_step(const gphip_ctx* h, double theta_k) {
+    return (h->dtype == 64 ? 6.0e-6 : 5.0e-3) * std::max(std::fabs(theta_k), 1e-2);
+}
+
 // log-likelihood and its gradient with respect to theta (same layout as theta).  One factorisation,
 // then K^-1 is streamed through the scratch block up to 8 GiB of rows at a time (forward + backward
 // substitution of identity rows) and contracted against dK/dtheta on the fly.
@@ -2614,16 +2693,13 @@ int gphip_loglik_grad(gphip_handle h, const double* theta, int p, double* out, d
     }
     h->grad_analytic = 0;
     if (h->custom && !(h->custom_grad && h->cgrad_state == 1)) {
-        // central differences of the likelihood, all 2 p + 1 points as ONE batched evaluation.  Step eps^(1/3) max(|theta_k|,
-        // 1e-2) in the handle's arithmetic (fp64 6e-6, fp32 5e-3): the truncation error (h^2 / 6 times the third derivative)
-        // and the rounding error eps_ll |ll| / h balance there; expect ~1e-6 relative in fp64 at moderate N, ~1e-2 in fp32.
+        // central differences of the likelihood (fd_step), all 2 p + 1 points as ONE batched evaluation
         const int B = 2 * p + 1;
         std::vector<double> Th((size_t)B * p), ll((size_t)B, 0.0), step((size_t)p);
         std::vector<int> inf((size_t)B, 0);
         for (int r = 0; r < B; ++r) memcpy(&Th[(size_t)r * p], theta, (size_t)p * 8);
-        const double rel = h->dtype == 64 ? 6.0e-6 : 5.0e-3;
         for (int k = 0; k < p; ++k) {
-            step[(size_t)k] = rel * std::max(std::fabs(theta[k]), 1e-2);
+            step[(size_t)k] = fd_step(h, theta[k]);
             Th[(size_t)(1 + 2 * k) * p + k] += step[(size_t)k];
             Th[(size_t)(2 + 2 * k) * p + k] -= step[(size_t)k];
         }
@@ -2640,47 +2716,35 @@ int gphip_loglik_grad(gphip_handle h, const double* theta, int p, double* out, d
     //  launch_grad reads the points from global memory in windows of 32 length-scale derivatives)
     double parts[2] = {0, 0};
     HIPCHK(hipSetDevice(h->device));
-    const int64_t N = h->N, Npad = h->Npad, d = h->d;
+    const int64_t N = h->N, Npad = h->Npad;
     int rc = GPHIP_OK;
-    // potri route when U (Npad x Npad scratch) and the lower tiles of K^-1 both fit in a quarter of the HBM
-    // that is free right now; otherwise K^-1 is streamed in row blocks through forward + backward substitution
-    bool potri = h->grad_potri != 0;
-    if (potri && !(h->dKinv.p && h->vcap >= Npad + GRAD_LD_PAD)) {
-        size_t fr = 0, tot = 0;
-        HIPCHK(hipMemGetInfo(&fr, &tot));
-        const size_t need = (size_t)(h->dKinv.p ? 1 : 2) * (Npad + GRAD_LD_PAD) * Npad * h->es;
-        potri = need <= fr / 4;
+    // potri route when U and the lower tiles of K^-1 (two Npad x Npad buffers) can be claimed; otherwise K^-1 is streamed in
+    // row blocks through forward + backward substitution
+    const bool potri = h->grad_potri != 0 && claim_inverse_scratch(h, true, true);
+    {
+        // (a multi-device handle factors on its first device: the K^-1 contraction needs the whole factor)
+        // want_u: a single-launch factorisation goes on to U = L^-T in dKinv (launch_dataflow_inverse)
+        FactorMode mode(h, true, potri && h->grad_potri == 1);
+        rc = eval_batch_local(h, theta, 1, p, out, parts, info);
     }
-    if (potri) {
-        rc = ensure_vbuf(h, Npad + GRAD_LD_PAD);
-        if (rc == GPHIP_OK && h->dKinv.grow((size_t)(Npad + GRAD_LD_PAD) * Npad * h->es) != hipSuccess) {
-            (void)hipGetLastError();
-            potri = false;
-        }
-        if (rc != GPHIP_OK) { (void)hipGetLastError(); potri = false; }
-    }
-    h->want_w = true;                          // (a multi-device handle factors on its first device: the K^-1 contraction needs the whole factor)
-    h->want_u = potri && h->grad_potri == 1;   // a single-launch factorisation goes on to U = L^-T in dV (launch_dataflow_inverse)
-    h->u_ready = false;
-    rc = eval_batch_local(h, theta, 1, p, out, parts, info);
-    h->want_w = h->want_u = false;
-    if (rc) { h->u_ready = false; return rc; }
+    if (rc) return rc;
     for (int i = 0; i < p; ++i) grad[i] = std::nan("");
-    if (*info != 0) { h->u_ready = false; return GPHIP_OK; }
+    if (*info != 0) return GPHIP_OK;
     HIPCHK(h->dAlpha.grow((size_t)Npad * h->es));
-    // general form: both terms' length scales, sf, alpha, c, sn; run-time compiled function: its ncp parameters, sn
-    const size_t ngacc = std::max((size_t)2 * d + 6, (size_t)h->ncp + 1);
-    HIPCHK(h->dGacc.grow(ngacc * 8));
-    h->ngacc = ngacc;
-    int64_t MC = 0;                            // rows of K^-1 per pass (each pass a forward and a backward substitution)
+    if ((rc = ensure_gacc(h))) return rc;
+    int64_t MC = 0;                           // rows of K^-1 per pass (each pass a forward and a backward substitution)
     if (!potri && (rc = ensure_vchunk(h, Npad, &MC))) return rc;
     h->cs = h->stream;
-    rc = (potri && h->u_ready) ? DISPATCH(h, queue_alpha_from_u, h) : DISPATCH(h, queue_alpha, h);
+    const bool from_u = potri && inverse_launch_ran(h);       // alpha from the explicit U; else by a backward pass, whose scratch is dV:
+    InvBufs ib{};                                             // U goes there only afterwards
+    if (from_u) ib = DISPATCH(h, queue_u, h);
+    rc = from_u ? DISPATCH(h, queue_alpha_from_u, h, ib) : DISPATCH(h, queue_alpha, h);
     if (rc) return rc;
-    HIPCHK(hipMemsetAsync(h->dGacc.p, 0, ngacc * 8, h->stream));
+    HIPCHK(hipMemsetAsync(h->dGacc.p, 0, h->ngacc * 8, h->stream));
     if (potri) {
-        rc = DISPATCH(h, queue_grad_potri, h);
-        if (rc) return rc;
+        if (!from_u) ib = DISPATCH(h, queue_u, h);
+        DISPATCH(h, queue_kinv, h, ib);
+        DISPATCH(h, queue_grad_full, h, ib.other, ib.ld, nullptr);
     } else {
         for (int64_t c0 = 0; c0 < N; c0 += MC) {
             const int64_t mc = (N - c0 < MC) ? (N - c0) : MC;
@@ -2689,17 +2753,11 @@ int gphip_loglik_grad(gphip_handle h, const double* theta, int p, double* out, d
             if (rc) return rc;
         }
     }
-    std::vector<double> gacc(ngacc), alpha;
+    std::vector<double> gacc(h->ngacc), alpha;
     HIPCHK(hipMemcpyAsync(gacc.data(), h->dGacc.p, gacc.size() * 8, hipMemcpyDeviceToHost, h->stream));
     rc = complete_call(h, [&] { return DISPATCH(h, download, h, alpha, h->dAlpha.p, (size_t)N, h->stream); });
     if (rc) return rc;
-    h->grad_analytic = 1;
-    const int o = grad_chain_rule(h, theta, gacc, grad);
-    if (h->mean_id == GPHIP_MEAN_CONST) {
-        double sum = 0.0;
-        for (double v : alpha) sum += v;
-        grad[o] = sum;
-    }
+    grad_from_acc(h, theta, gacc, alpha, grad);
     record_fit(h, true, theta, p, parts[0]);                  // the factor of theta is still resident (whole, on this device)
     return GPHIP_OK;
 }
@@ -2713,9 +2771,10 @@ int gphip_fit(gphip_handle h, const double* theta, int p, int* info) {
         // division by the diagonal, LogDet = N log sn^2, and prediction has k = 0 (empty sparse array, BGP:72-74)
         // and kappa = nugget only (BGP:75-80): mu* = m(x*), var* = sn^2.
         if (p != h->p) return fail(h, GPHIP_ERR_DIM, "theta has the wrong length for this kernel/mean");
-        const double sn = theta[0], mu = (h->mean_id == GPHIP_MEAN_CONST) ? theta[1] : 0.0;
-        const bool finite = std::isfinite(sn) && std::isfinite(mu);
-        *info = !finite ? GPHIP_INFO_NAN : (sn * sn > 0.0 && std::isfinite(std::log(sn * sn)) ? GPHIP_INFO_OK : GPHIP_INFO_NOT_SPD);
+        double mu = 0.0;
+        *info = null_theta_info(h, theta, &mu);
+        const double sn = theta[0];
+        const bool finite = *info != GPHIP_INFO_NAN;
         h->logdet_fit = (double)h->N * std::log(sn * sn);
         h->null_diag.clear();
         if (h->pw_nug_host) {                  // nugget /@ points (BGP:27): the diagonal itself
@@ -2735,10 +2794,12 @@ int gphip_fit(gphip_handle h, const double* theta, int p, int* info) {
         h->kappa_fit = sn * sn;
         return GPHIP_OK;
     }
-    h->want_w = true;                          // the substitutions that follow a fit use the 128-block inverses
     const unsigned long id_before = h->group ? h->group->fit_id : 0;
-    int rc = eval_batch(h, theta, 1, p, &out, parts, info);
-    h->want_w = false;
+    int rc;
+    {
+        FactorMode mode(h, true);              // the substitutions that follow a fit use the 128-block inverses
+        rc = eval_batch(h, theta, 1, p, &out, parts, info);
+    }
     if (rc) return rc;
     const bool sharded_fit = h->group && h->group->fit_id != id_before;     // group_eval_run recorded every member itself
     if (h->dist_fit) {                         // (a later gphip_solve factors locally again: it needs the same K)
@@ -2933,9 +2994,7 @@ static int predict_local(gphip_handle h, const void* Xs, int64_t M, double* mean
         rc = upload_pw_test(h, 0, 1, m0, mc, mpad);
         if (rc) return rc;
         DISPATCH(h, queue_cross, h, mc, mpad, 1);
-        ensure_w64(h);
-        if (df_forward_ok(h, mpad)) launch_dataflow_inverse<double, 64>(h, mpad);
-        else DISPATCH(h, queue_forward_rows, h, mpad, 1);
+        queue_forward_fit(h, mpad);
         DISPATCH(h, queue_predict_reduce, h, mc, mpad, 1);
         HIPCHK(hipMemcpyAsync(mean + m0, h->dMean.p, (size_t)mc * 8, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipMemcpyAsync(var + m0, h->dVar.p, (size_t)mc * 8, hipMemcpyDeviceToHost, h->stream));
@@ -3186,9 +3245,10 @@ int gphip_predict_samples(gphip_handle h, const double* Thetas, int S, int p, co
     for (int s0 = 0; s0 < S; s0 += h->slots) {
         const int nb = (S - s0 < h->slots) ? (S - s0) : h->slots;
         std::vector<double> ll(nb);
-        h->want_w = true;
-        rc = eval_chunk(h, Thetas + (size_t)s0 * p, nb, ll.data(), nullptr, info + s0, s0);   // build + factor, kept
-        h->want_w = false;
+        {
+            FactorMode mode(h, true);          // the substitutions below use the 128-block inverses
+            rc = eval_chunk(h, Thetas + (size_t)s0 * p, nb, ll.data(), nullptr, info + s0, s0);   // build + factor, kept
+        }
         if (rc) return rc;
         // test-point chunk so that the nb V blocks stay within ~8 GiB
         int64_t mcap = (int64_t)((8.0 * (1 << 30)) / ((double)nb * h->Npad * h->es)) / TB * TB;
@@ -3292,13 +3352,12 @@ int gphip_solve(gphip_handle h, const double* rhs, int64_t nrhs, double* out) {
         const std::vector<double> th = h->theta_fit;
         double ll, parts[2];
         int info = 0;
-        h->want_w = true;
+        FactorMode mode(h, true);
         const double *pm = h->pw_mean_host, *pn = h->pw_nug_host;
         h->pw_mean_host = h->fit_pw_mean.empty() ? nullptr : h->fit_pw_mean.data();
         h->pw_nug_host = h->fit_pw_nug.empty() ? nullptr : h->fit_pw_nug.data();
         int rc = eval_batch_local(h, th.data(), 1, (int)th.size(), &ll, parts, &info);
         h->pw_mean_host = pm; h->pw_nug_host = pn;
-        h->want_w = false;
         if (rc) return rc;
         if (info != 0) return fail(h, GPHIP_ERR_STATE, "the fitted theta no longer factors");
         h->fitted = true;                      // now a LOCAL fit of the same theta (logdet_fit / mu_fit / kappa_fit unchanged)
@@ -3366,10 +3425,7 @@ int gphip_solve(gphip_handle h, const double* rhs, int64_t nrhs, double* out) {
         }
         // after a single-launch fit both halves are ONE dataflow launch each (forward as in gphip_predict; backward over a copy of
         // the factor with its 64 x 64 blocks transposed, made on the first solve of a fit)
-        ensure_w64(h);                         // (also after a look-ahead-schedule fit: 64-block inverses cut out of the 128-block ones)
-        const bool df_fwd = df_forward_ok(h, mpad);
-        if (df_fwd) launch_dataflow_inverse<double, 64>(h, mpad);
-        else DISPATCH(h, queue_forward_rows, h, mpad, 1);
+        const bool df_fwd = queue_forward_fit(h, mpad);   // (also after a look-ahead-schedule fit: 64-block inverses cut out of the 128-block ones)
         if (df_fwd && df_backward_ready<double>(h)) launch_dataflow_inverse<double, 64>(h, mpad, true);
         else DISPATCH(h, queue_backward_rows, h, mpad);
         if (dRows) DISPATCH(h, queue_rows_vblock, h, dRows, mc, mpad, false);

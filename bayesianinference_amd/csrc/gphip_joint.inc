@@ -127,9 +127,7 @@ int joint_sigma(gphip_ctx* h, const double* Xs, int64_t M, const double* ystar, 
     rc = DISPATCH(h, upload, h, h->dXsT.p, xt, h->stream);
     if (rc) return rc;
     DISPATCH(h, queue_cross, h, M, mpad, 1);
-    ensure_w64(h);
-    if (df_forward_ok(h, mpad)) launch_dataflow_inverse<double, 64>(h, mpad);
-    else DISPATCH(h, queue_forward_rows, h, mpad, 1);
+    queue_forward_fit(h, mpad);
     if (h->dtype == 64)
         hipLaunchKernelGGL(gather_rhs_row_kernel<double>, dim3((unsigned)((h->Npad + 255) / 256)), dim3(256), 0, h->stream,
                            (const double*)h->dA.p, (int)h->R, 0, (int)h->Npad, (double*)h->dJZ.p, (long)TB, 0);
@@ -152,7 +150,7 @@ int joint_sigma(gphip_ctx* h, const double* Xs, int64_t M, const double* ystar, 
     if ((rc = copy_theta(c, 1))) return fail(h, rc, c->err.c_str());
     HIPCHK(hipMemsetAsync(c->dInfo.p, 0, 4, c->stream));
     c->cs = c->stream;
-    c->theta_packed = false; c->fused_eval = false; c->want_w = false; c->want_u = false;
+    c->theta_packed = false; c->fused_eval = false;      // (want_w / want_u: no FactorMode is ever open on the child)
     DISPATCH(c, queue_build, c, 1);
     return DISPATCH(h, queue_downdate, h, c, mpad);
 }

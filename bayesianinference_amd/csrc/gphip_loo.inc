@@ -1,14 +1,13 @@
 // gphip_loo.inc -- leave-one-out cross-validation from one factorisation (include/gphip.h: gphip_loo, gphip_loo_grad; kernels
 // and formulas: gp_loo.h).  Included at the end of gphip.hip.
 //
-//   both calls   factor as gphip_loglik_grad does on its potri route; U = L^-T in dKinv (single-launch factorisations: the inverse
-//                launch, leading dimension Npad + GRAD_LD_PAD) or in dV (identity rows + forward substitution, leading dimension Npad)
+//   both calls   factor under FactorMode as gphip_loglik_grad does on its potri route; queue_u says where U = L^-T is (InvBufs)
 //                loo_rownorm_partial_kernel    alpha = U z and k = squared row norms of U, one pass over U
 //                loo_moments_kernel            mean, var, logp, g, sqrt(c) per point;   loo_total_kernel   L_LOO
-//   gradient     launch_gemm (ktri)            K^-1 = U U^T, lower tiles, into the OTHER buffer
+//   gradient     queue_kinv                    K^-1 = U U^T, lower tiles, into the OTHER buffer
 //                loo_mirror_scale_kernel       B = K^-1 diag(sqrt c) in place (full matrix) + the partial sums of beta = K^-1 g
 //                launch_gemm                   M = B B^T, lower tiles, into the buffer U occupied (U is dead by then)
-//                launch_grad                   the gradient reductions with GradArgs::beta set, Kinv = M
+//                queue_grad_full               the gradient reductions with GradArgs::beta set, Kinv = M
 // The value path touches ONE N x N buffer, the gradient two; there is no third.
 #include "gp_loo.h"
 
@@ -43,59 +42,44 @@ void loo_nan(gphip_ctx* h, double* mean, double* var, double* logp, double* out)
     if (out) *out = q;
 }
 
-// behind the factorisation, U = L^-T on the device (U, ldu): z, alpha and k in one pass, the per-point quantities in s.out6, L_LOO
+// behind the factorisation, U = L^-T on the device (b.U): z, alpha and k in one pass, the per-point quantities in s.out6, L_LOO
 template <typename T>
-int loo_queue_values(gphip_ctx* h, const LooScratch& s, const T* U, long ldu) {
+int loo_queue_values(gphip_ctx* h, const LooScratch& s, const InvBufs& b) {
     const int npad = (int)h->Npad, n = (int)h->N, chunk = TB;
     double* part_a = s.part;
     double* part_k = s.part + (size_t)s.nch * npad;
     hipLaunchKernelGGL(gather_rhs_row_kernel<T>, dim3((unsigned)((npad + 255) / 256)), dim3(256), 0, h->stream, (const T*)h->dA.p,
                        (int)h->R, 0, npad, (T*)s.z, 1l);
-    hipLaunchKernelGGL(loo_rownorm_partial_kernel<T>, dim3((unsigned)(npad / TB), (unsigned)s.nch), dim3(TB), 0, h->stream, U, ldu,
-                       (const T*)s.z, npad, chunk, part_a, part_k);
+    hipLaunchKernelGGL(loo_rownorm_partial_kernel<T>, dim3((unsigned)(npad / TB), (unsigned)s.nch), dim3(TB), 0, h->stream, (const T*)b.U,
+                       b.ld, (const T*)s.z, npad, chunk, part_a, part_k);
     hipLaunchKernelGGL(loo_moments_kernel<T>, dim3((unsigned)((npad + 255) / 256)), dim3(256), 0, h->stream, (const double*)part_a,
                        (const double*)part_k, s.nch, npad, n, (const T*)h->dY.p, (T*)h->dAlpha.p, s.out6);
     hipLaunchKernelGGL(loo_total_kernel, dim3(1), dim3(LOO_RED), 0, h->stream, (const double*)(s.out6 + 2 * (size_t)npad), n, s.total);
     return GPHIP_OK;
 }
 
-// the rest of the gradient: K^-1, beta, B, M, the reductions.  u_in_kinv: U sits in dKinv (inverse launch), else in dV.
+// the rest of the gradient: K^-1, beta, B, M, the reductions
 template <typename T>
-int loo_queue_grad(gphip_ctx* h, const LooScratch& s, bool u_in_kinv) {
-    const long npad = h->Npad, ld = u_in_kinv ? npad + GRAD_LD_PAD : npad;
-    T* Ub = (T*)(u_in_kinv ? h->dKinv.p : h->dV.p);
-    T* Kb = (T*)(u_in_kinv ? h->dV.p : h->dKinv.p);
-    launch_gemm<T>(h, 2, cm<T>(Kb, ld, 0), cm<T>(Ub, ld, 0), cm<T>(Ub, ld, 0), (int)npad, 0, (int)h->Nt, 0, (int)h->Nt, 1, 1, 1, 1);
+int loo_queue_grad(gphip_ctx* h, const LooScratch& s, const InvBufs& b) {
+    const long npad = h->Npad;
+    T *Ub = (T*)b.U, *Kb = (T*)b.other;
+    queue_kinv<T>(h, b);
     const unsigned nb = (unsigned)(npad / LOO_BLK);
-    hipLaunchKernelGGL(loo_mirror_scale_kernel<T>, dim3(nb, nb), dim3(256), 0, h->stream, Kb, ld, (int)npad,
+    hipLaunchKernelGGL(loo_mirror_scale_kernel<T>, dim3(nb, nb), dim3(256), 0, h->stream, Kb, b.ld, (int)npad,
                        (const double*)(s.out6 + 4 * (size_t)npad), (const double*)(s.out6 + 3 * (size_t)npad), s.part);
     hipLaunchKernelGGL(utri_gemv_finish_kernel<T>, dim3((unsigned)((npad + 255) / 256)), dim3(256), 0, h->stream, (const double*)s.part,
                        (int)nb, (int)npad, (T*)s.beta);
     // M = B B^T over the full contraction length (B is not triangular), lower tiles, over the dead U
-    launch_gemm<T>(h, 2, cm<T>(Ub, ld, 0), cm<T>(Kb, ld, 0), cm<T>(Kb, ld, 0), (int)npad, 0, (int)h->Nt, 0, (int)h->Nt, 1, 1, 1, 0);
-    GradArgs<T> a{};
-    a.Kinv = Ub; a.ldv = ld; a.alpha = (const T*)h->dAlpha.p; a.beta = (const T*)s.beta; a.xs = (const T*)h->dXs.p;
-    a.npad = (int)npad; a.n = (int)h->N; a.c0 = 0; a.mc = (int)h->N; a.d = (int)h->d; a.tri = 1;
-    a.slotp = h->dSlotp.as<double>(); a.gacc = h->dGacc.as<double>();
-    const dim3 grid((unsigned)h->Nt, (unsigned)h->Nt);
-    launch_grad<T>(h, a, grid);
+    launch_gemm<T>(h, 2, cm<T>(Ub, b.ld, 0), cm<T>(Kb, b.ld, 0), cm<T>(Kb, b.ld, 0), (int)npad, 0, (int)h->Nt, 0, (int)h->Nt, 1, 1, 1, 0);
+    queue_grad_full<T>(h, Ub, b.ld, s.beta);
     return GPHIP_OK;
-}
-
-template <typename T>
-void loo_queue_u_rows(gphip_ctx* h) {          // U by the multi-kernel route: identity rows, forward substitution (zero tiles skipped)
-    const long npad = h->Npad;
-    int gx = (int)((npad * npad + 255) / 256);
-    if (gx > 4096) gx = 4096;
-    hipLaunchKernelGGL(identity_rows_kernel<T>, dim3(gx), dim3(256), 0, h->stream, (T*)h->dV.p, npad, (int)npad, 0, (int)h->N);
-    queue_forward_rows<T>(h, npad, 1, 0, true);
 }
 
 // Null kernel: K = sn^2 I, so leaving a point out changes nothing: mu_-i = m, var_-i = sn^2 (host; y comes back from the device once)
 int loo_null(gphip_ctx* h, const double* theta, double* mean, double* var, double* logp, double* out, double* grad, int* info) {
-    const double sn = theta[0], v = sn * sn, mu = h->mean_id == GPHIP_MEAN_CONST ? theta[1] : 0.0;
-    const bool finite = std::isfinite(sn) && std::isfinite(mu);
-    *info = !finite ? GPHIP_INFO_NAN : (v > 0.0 && std::isfinite(std::log(v)) ? GPHIP_INFO_OK : GPHIP_INFO_NOT_SPD);
+    double mu = 0.0;
+    *info = null_theta_info(h, theta, &mu);
+    const double sn = theta[0], v = sn * sn;
     if (grad) for (int i = 0; i < h->p; ++i) grad[i] = std::nan("");
     if (*info != 0) { loo_nan(h, mean, var, logp, out); return GPHIP_OK; }
     HIPCHK(hipSetDevice(h->device));
@@ -131,60 +115,41 @@ int loo_call(gphip_ctx* h, const double* theta, int p, double* mean, double* var
     if (h->kernel_id == GPHIP_KERNEL_NULL) return loo_null(h, theta, mean, var, logp, out, grad, info);
     HIPCHK(hipSetDevice(h->device));
     const int64_t N = h->N, Npad = h->Npad;
-    // Where U will be: a single-launch factorisation goes on to the inverse launch (U in dKinv), every other schedule leaves U to
-    // the forward substitution of the identity (U in dV).  The value call claims that one buffer, the gradient both -- by the
-    // rule gphip_loglik_grad applies before it leaves its potri route: what is still to be allocated fits in a quarter of the
-    // memory that is free now.  There is no row-block route here.
-    h->want_w = true;
-    h->want_u = h->grad_potri == 1;
-    const bool inverse_launch = h->want_u && use_dataflow(h, 1);
-    h->want_u = inverse_launch;
-    const bool need_kinv = grad || inverse_launch, need_v = grad || !inverse_launch;
-    const size_t nn = (size_t)(Npad + GRAD_LD_PAD) * Npad * h->es;
-    const bool have_kinv = h->dKinv.bytes >= nn, have_v = h->vcap >= Npad + GRAD_LD_PAD;
-    const size_t missing = (size_t)((need_kinv && !have_kinv) ? 1 : 0) + (size_t)((need_v && !have_v) ? 1 : 0);
     auto unsupported = [&]() {
-        h->want_w = h->want_u = false;
         return fail(h, GPHIP_ERR_UNSUPPORTED, grad ? "gphip_loo_grad: two N x N scratch buffers do not fit in a quarter of the free device memory"
                                                    : "gphip_loo: one N x N scratch buffer does not fit in a quarter of the free device memory");
     };
-    if (missing) {
-        size_t fr = 0, tot = 0;
-        HIPCHK(hipMemGetInfo(&fr, &tot));
-        if (missing * nn > fr / 4) return unsupported();
-    }
-    if (need_v && ensure_vbuf(h, Npad + GRAD_LD_PAD) != GPHIP_OK) { (void)hipGetLastError(); return unsupported(); }
-    if (need_kinv && h->dKinv.grow(nn) != hipSuccess) { (void)hipGetLastError(); return unsupported(); }
-    h->u_ready = false;
     double parts[2] = {0, 0};
-    int rc = eval_batch_local(h, theta, 1, p, out, parts, info);      // (a multi-device handle factors on its first device, as the gradient does)
-    h->want_w = h->want_u = false;
-    const bool u_in_kinv = h->u_ready;
-    h->u_ready = false;
+    int rc = GPHIP_OK;
+    {
+        // Where U will be: a single-launch factorisation goes on to the inverse launch, every other schedule leaves U to the
+        // forward substitution of the identity (queue_u).  The value call claims that one buffer, the gradient both
+        // (claim_inverse_scratch).  There is no row-block route here.
+        FactorMode mode(h, true, h->grad_potri == 1);
+        const bool inverse_launch = h->want_u && use_dataflow(h, 1);
+        FactorMode predicted(h, true, inverse_launch);         // (the inverse launch runs only where its buffer was claimed)
+        if (!claim_inverse_scratch(h, grad || inverse_launch, grad || !inverse_launch)) return unsupported();
+        rc = eval_batch_local(h, theta, 1, p, out, parts, info);      // (a multi-device handle factors on its first device, as the gradient does)
+    }
     if (rc) return rc;
     if (grad) for (int i = 0; i < p; ++i) grad[i] = std::nan("");
     if (*info != 0) { loo_nan(h, mean, var, logp, out); return GPHIP_OK; }
-    if (!u_in_kinv && (rc = ensure_vbuf(h, Npad + GRAD_LD_PAD))) return rc;   // (no-op unless the schedule chose otherwise than predicted)
+    if (!inverse_launch_ran(h) && (rc = ensure_vbuf(h, Npad + GRAD_LD_PAD))) return rc;   // (no-op unless the schedule chose otherwise than predicted)
     LooScratch s{};
     if ((rc = loo_scratch(h, &s))) return rc;
     HIPCHK(h->dAlpha.grow((size_t)Npad * h->es));
-    const size_t ngacc = std::max((size_t)2 * h->d + 6, (size_t)h->ncp + 1);
-    if (grad) {
-        HIPCHK(h->dGacc.grow(ngacc * 8));
-        h->ngacc = ngacc;
-    }
+    if (grad && (rc = ensure_gacc(h))) return rc;
     h->cs = h->stream;
-    if (!u_in_kinv) DISPATCH(h, loo_queue_u_rows, h);
-    if (h->dtype == 64) rc = loo_queue_values<double>(h, s, (const double*)(u_in_kinv ? h->dKinv.p : h->dV.p), (long)(u_in_kinv ? Npad + GRAD_LD_PAD : Npad));
-    else rc = loo_queue_values<float>(h, s, (const float*)(u_in_kinv ? h->dKinv.p : h->dV.p), (long)(u_in_kinv ? Npad + GRAD_LD_PAD : Npad));
+    const InvBufs ib = DISPATCH(h, queue_u, h);
+    rc = DISPATCH(h, loo_queue_values, h, s, ib);
     if (rc) return rc;
     double total = 0.0;
-    std::vector<double> gacc(grad ? ngacc : 0), beta;
+    std::vector<double> gacc(grad ? h->ngacc : 0), beta;
     if (grad) {
-        HIPCHK(hipMemsetAsync(h->dGacc.p, 0, ngacc * 8, h->stream));
-        rc = DISPATCH(h, loo_queue_grad, h, s, u_in_kinv);
+        HIPCHK(hipMemsetAsync(h->dGacc.p, 0, gacc.size() * 8, h->stream));
+        rc = DISPATCH(h, loo_queue_grad, h, s, ib);
         if (rc) return rc;
-        HIPCHK(hipMemcpyAsync(gacc.data(), h->dGacc.p, ngacc * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(gacc.data(), h->dGacc.p, gacc.size() * 8, hipMemcpyDeviceToHost, h->stream));
     }
     // only what the caller asked for comes back
     double* want[3] = {mean, var, logp};
@@ -204,15 +169,7 @@ int loo_call(gphip_ctx* h, const double* theta, int p, double* mean, double* var
         record_fit(h, true, theta, p, parts[0]);
         return GPHIP_OK;
     }
-    if (grad) {
-        h->grad_analytic = 1;
-        const int o = grad_chain_rule(h, theta, gacc, grad);
-        if (h->mean_id == GPHIP_MEAN_CONST) {
-            double sum = 0.0;
-            for (double v : beta) sum += v;
-            grad[o] = sum;
-        }
-    }
+    if (grad) grad_from_acc(h, theta, gacc, beta, grad);
     record_fit(h, true, theta, p, parts[0]);   // the factor of theta is still resident (whole, on this device)
     return GPHIP_OK;
 }
@@ -235,12 +192,11 @@ int gphip_loo_grad(gphip_handle h, const double* theta, int p, double* out, doub
     }
     h->grad_analytic = 0;
     if (h->custom && !(h->custom_grad && h->cgrad_state == 1)) {
-        // central differences of gphip_loo with the step rule of gphip_loglik_grad (eps^(1/3) max(|theta_k|, 1e-2)); the value at
-        // theta itself is evaluated last, so the fit the call leaves resident is theta's
-        const double rel = h->dtype == 64 ? 6.0e-6 : 5.0e-3;
+        // central differences of gphip_loo with the step rule of gphip_loglik_grad (fd_step); the value at theta itself is
+        // evaluated last, so the fit the call leaves resident is theta's
         std::vector<double> th(theta, theta + p);
         for (int k = 0; k < p; ++k) {
-            const double step = rel * std::max(std::fabs(theta[k]), 1e-2);
+            const double step = fd_step(h, theta[k]);
             double lp = 0.0, lm = 0.0;
             int ip = 0, im = 0;
             th[(size_t)k] = theta[k] + step;

@@ -45,6 +45,24 @@ def test_device_and_pinned_memory_only_through_the_owning_buffer_type():
     assert not bad, bad
 
 
+def test_factorisation_mode_flags_only_through_the_scope_type():
+    # want_w / want_u tell the next factorisation what to leave behind; a caller that set them by hand had to clear them on
+    # every exit path, and one that returned early left every later evaluation on the handle in the wrong mode.  `struct
+    # FactorMode` (gphip.hip) sets them and restores them in its destructor; nothing else assigns them.
+    assign = re.compile(r"\bwant_[wu]\s*[|&^]?=(?!=)")
+    gphip = _code(os.path.join(CSRC, "gphip.hip"))
+    scope = re.search(r"\nstruct FactorMode \{.*?\n\};", gphip, flags=re.S)
+    assert scope and assign.search(scope.group(0)), "the scope type (struct FactorMode) is missing from gphip.hip"
+    sources = {"gphip.hip": gphip[:scope.start()] + gphip[scope.end():]}
+    for name in sorted(os.listdir(CSRC)):
+        if name.endswith(".inc"):
+            sources[name] = _code(os.path.join(CSRC, name))
+    # (the context's own member initialisers `bool want_w = false;` are declarations, not assignments by a caller)
+    bad = [(name, line.strip()) for name, code in sources.items() for line in code.splitlines()
+           if assign.search(line) and not re.match(r"\s*bool want_[wu] = false;", line)]
+    assert not bad, bad
+
+
 def test_gfx950_only_no_compat_layers():
     for name in os.listdir(CSRC):
         code = _code(os.path.join(CSRC, name))
