@@ -122,6 +122,19 @@ _SIGNATURES = {
     "gphip_dist_factor_panel": (C.c_int, [_h, C.c_int, C.c_void_p]),
     "gphip_dist_update": (C.c_int, [_h, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "gphip_dist_end": (C.c_int, [_h, _dp, _dp, _ip]),
+    "gphip_sparse_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int,
+                                      C.c_int, C.POINTER(_h)]),
+    "gphip_sparse_create_custom": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_char_p, C.c_int,
+                                             C.c_int, C.c_int, C.c_int, C.POINTER(_h)]),
+    "gphip_sparse_destroy": (C.c_int, [_h]),
+    "gphip_sparse_set_inducing": (C.c_int, [_h, C.c_void_p, C.c_int64]),
+    "gphip_sparse_num_params": (C.c_int, [_h, _ip]),
+    "gphip_sparse_bound": (C.c_int, [_h, _dp, C.c_int, C.c_double, _dp, _dp, _ip]),
+    "gphip_sparse_fit": (C.c_int, [_h, _dp, C.c_int, C.c_double, _ip]),
+    "gphip_sparse_predict": (C.c_int, [_h, C.c_void_p, C.c_int64, C.c_int, _dp, _dp]),
+    "gphip_sparse_set_option": (C.c_int, [_h, C.c_char_p, C.c_double]),
+    "gphip_sparse_get_option": (C.c_int, [_h, C.c_char_p, C.POINTER(C.c_double)]),
+    "gphip_sparse_last_error": (C.c_char_p, [_h]),
     "gphip_last_error": (C.c_char_p, [_h]),
     "gphip_version": (C.c_char_p, []),
     "gphip_device_count": (C.c_int, [_ip]),
@@ -637,3 +650,108 @@ class Handle:
         ld, qd, info = C.c_double(0.0), C.c_double(0.0), C.c_int(0)
         self._check(self._lib.gphip_dist_end(self._h, C.byref(ld), C.byref(qd), C.byref(info)))
         return ld.value, qd.value, info.value
+
+
+SPARSE_MAX_M = 16384
+SPARSE_PARTS = ("logdet_B", "ctc", "rtr", "tr_VVt", "sum_kxx")
+SPARSE_PHASES = ("ms_kuu_factor", "ms_cross", "ms_forward", "ms_accumulate", "ms_b_factor")
+
+
+class SparseHandle:
+    """Owns one gphip_sparse_handle: a sparse inducing-point GP (the collapsed bound of Titsias 2009, include/gphip.h
+    gphip_sparse_*).  The data X, y stay resident on the device; Z [m, d] are the inducing points.  theta has the layout of the
+    same kernel of `Handle`; jitter < 0 = the library's default (get_option("last_jitter") returns the value used)."""
+
+    def __init__(self, X, y, Z, kernel="se_ard", mean: str = "zero", dtype: int = 64, device=None):
+        lib = load()
+        X = np.ascontiguousarray(np.atleast_2d(np.asarray(X, dtype=np.float64)))
+        y = np.ascontiguousarray(np.asarray(y, dtype=np.float64).ravel())
+        Z = np.ascontiguousarray(np.atleast_2d(np.asarray(Z, dtype=np.float64)))
+        if X.shape[0] != y.shape[0]:
+            raise GphipError(2, "Input and output data are not of same length")
+        if Z.shape[1] != X.shape[1]:
+            raise GphipError(2, "inducing points and data differ in dimension")
+        if mean not in MEAN_IDS:
+            raise GphipError(1, f"unknown mean {mean!r}")
+        self.N, self.d = X.shape
+        self.m = Z.shape[0]
+        self.kernel, self.mean, self.dtype = kernel, mean, int(dtype)
+        self._lib = lib
+        self._h = _h()
+        dev = -1 if device is None else int(device)
+        if isinstance(kernel, CustomKernel):
+            rc = lib.gphip_sparse_create_custom(X.ctypes.data, y.ctypes.data, self.N, self.d, Z.ctypes.data, self.m, kernel.body.encode(),
+                                                int(kernel.nparams), MEAN_IDS[mean], int(dtype), dev, C.byref(self._h))
+        else:
+            rc = lib.gphip_sparse_create(X.ctypes.data, y.ctypes.data, self.N, self.d, Z.ctypes.data, self.m, kernel_id(kernel),
+                                         MEAN_IDS[mean], int(dtype), dev, C.byref(self._h))
+        if rc != OK:
+            self._h = None
+            why = {5: "no gfx950 GPU visible, or a device ordinal that does not exist", 6: "unsupported (the null kernel, dtype other than 64 / 32)",
+                   1: "bad argument (unknown kernel / mean id) " + (lib.gphip_create_error() or b"").decode(),
+                   2: f"bad shape (N < 1, d < 1, m < 1 or m > {SPARSE_MAX_M})"}.get(rc, "is a gfx950 GPU visible?")
+            raise GphipError(rc, "gphip_sparse_create failed: " + why)
+        p = C.c_int(0)
+        lib.gphip_sparse_num_params(self._h, C.byref(p))
+        self.p = p.value
+
+    def _check(self, rc: int):
+        if rc != OK:
+            raise GphipError(rc, (self._lib.gphip_sparse_last_error(self._h) or b"").decode())
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.gphip_sparse_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_option(self, name: str, value: float):
+        self._check(self._lib.gphip_sparse_set_option(self._h, name.encode(), float(value)))
+
+    def get_option(self, name: str) -> float:
+        v = C.c_double()
+        self._check(self._lib.gphip_sparse_get_option(self._h, name.encode(), C.byref(v)))
+        return v.value
+
+    def set_inducing(self, Z):
+        """Replace the inducing points (any m); the resident fit is dropped."""
+        Z = np.ascontiguousarray(np.atleast_2d(np.asarray(Z, dtype=np.float64)))
+        if Z.shape[1] != self.d:
+            raise GphipError(2, "inducing points and data differ in dimension")
+        self._check(self._lib.gphip_sparse_set_inducing(self._h, Z.ctypes.data, Z.shape[0]))
+        self.m = Z.shape[0]
+
+    def bound_parts(self, theta, jitter: float = -1.0):
+        """(F, parts[5] = (log det B, c'c, r'r, tr(V V'), sum_i k(x_i, x_i)), info); the fit stays resident."""
+        th = np.ascontiguousarray(np.asarray(theta, dtype=np.float64).ravel())
+        out, info, parts = C.c_double(0.0), C.c_int(0), np.zeros(5)
+        self._check(self._lib.gphip_sparse_bound(self._h, _d(th), th.size, float(jitter), C.byref(out), _d(parts), C.byref(info)))
+        return out.value, parts, info.value
+
+    def bound(self, theta, jitter: float = -1.0):
+        """(F(theta), info): the collapsed lower bound on the log marginal likelihood; the fit stays resident."""
+        th = np.ascontiguousarray(np.asarray(theta, dtype=np.float64).ravel())
+        out, info = C.c_double(0.0), C.c_int(0)
+        self._check(self._lib.gphip_sparse_bound(self._h, _d(th), th.size, float(jitter), C.byref(out), None, C.byref(info)))
+        return out.value, info.value
+
+    def fit(self, theta, jitter: float = -1.0) -> int:
+        th = np.ascontiguousarray(np.asarray(theta, dtype=np.float64).ravel())
+        info = C.c_int(0)
+        self._check(self._lib.gphip_sparse_fit(self._h, _d(th), th.size, float(jitter), C.byref(info)))
+        return info.value
+
+    def predict(self, Xs, latent: bool = False):
+        """(mean[M], var[M]) at Xs from the resident fit; latent: the variance of f(x*) without the noise sn^2."""
+        Xs = np.ascontiguousarray(np.atleast_2d(np.asarray(Xs, dtype=np.float64)))
+        if Xs.shape[1] != self.d:
+            raise GphipError(2, "test points and data differ in dimension")
+        M = Xs.shape[0]
+        mean, var = np.zeros(M), np.zeros(M)
+        self._check(self._lib.gphip_sparse_predict(self._h, Xs.ctypes.data, M, 1 if latent else 0, _d(mean), _d(var)))
+        return mean, var

@@ -3815,3 +3815,4 @@ int gphip_sync(gphip_handle h) {
 #include "gphip_sampler.inc"
 #include "gphip_joint.inc"
 #include "gphip_loo.inc"
+#include "gphip_sparse.inc"

@@ -1,0 +1,517 @@
+// gphip_sparse.inc -- sparse inducing-point GP: the collapsed variational bound of Titsias (2009), its fit and prediction
+// (include/gphip.h: gphip_sparse_*; kernels: gp_sparse.h).  Included at the end of gphip.hip.
+//
+//   u (a context whose TRAINING points are Z, y = 0; its nugget slot scalar carries the jitter j)
+//        queue_build + queue_factor        L_u L_u^T = k(Z, Z) + j I, direct-difference kernel build
+//        per chunk of data points, treated as test points of u:
+//        queue_cross + queue_forward_fit   the chunk of V = L_u^-1 k(Z, X) in u->dV, V(t, k) at V[t + k ld]
+//        sparse_resid_kernel               r = y - mu of the chunk (row 0 of the rhs operand), partial sums of r^2
+//        sparse_accumulate_kernel          b's workspace: lower tiles += V^T V, rhs tile row += r^T V  (chunks in order)
+//   b (a context of m points whose workspace is filled by hand)
+//        sparse_diag_kernel                tr(V V^T), then B = sn^2 I + V V^T
+//        queue_factor                      L_B, log det B, c = L_B^-1 V r in the rhs row, c^T c in the corner
+// Prediction: v1 = L_u^-1 k(Z, x*) by u's forward substitution, v2 = L_B^-1 v1 by b's, predict_partial_kernel on both and one
+// finishing kernel.  Everything of one evaluation up to B runs on u's stream; b's stream takes over after a host synchronisation.
+#include "gp_sparse.h"
+
+struct gphip_sparse_ctx {
+    std::recursive_mutex mu;
+    gphip_ctx *u = nullptr, *b = nullptr;
+    int device = 0, dtype = 64;
+    size_t es = 8;
+    int64_t N = 0, d = 0, Npad = 0, m = 0;
+    int kernel_id = 0, mean_id = 0;
+    bool custom = false;
+    std::string body;
+    int ncp = 0;
+    std::vector<std::pair<std::string, double>> forwarded;    // options handed on to u and b (replayed after gphip_sparse_set_inducing)
+    Buf dXt, dY;                               // typed [d][Npad], [Npad]: the data, resident
+    Buf dRz; int64_t rcap = 0;                 // typed [16][rcap]: row 0 = r of the current chunk, the other rows zero
+    Buf dAccP;                                 // typed [strip][tile][128 x 128]: strip partials of the accumulation
+    Buf dSum; std::vector<double> hSum;        // double: [0] tr(V V^T), then the per-block partial sums of r^2 and of k(x_i, x_i)
+    // options
+    int chunk = 0, split = 0, profile = 0;
+    // read-only results of the last call
+    int last_nsplit = 0;
+    int64_t last_chunk = 0;
+    double last_jitter = 0.0;
+    double ms[5] = {0, 0, 0, 0, 0};            // K_uu factor, cross build, forward substitution, accumulation, B factor
+    // the resident fit
+    bool fitted = false;
+    double sn2_fit = 0, mu_fit = 0, kxx_fit = 0;
+    std::string err;
+};
+
+namespace {
+
+constexpr int64_t SPARSE_MAX_M = GPHIP_SPARSE_MAX_M;
+
+int sfail(gphip_sparse_ctx* h, int code, const std::string& msg) {
+    if (h) h->err = msg;
+    return code;
+}
+
+struct SparsePhase { int phase; hipEvent_t e0, e1; };
+
+// HIP-event pair around a phase of the evaluation while option "profile" is on (the events come from u's pool)
+struct SparseScope {
+    gphip_sparse_ctx* h; std::vector<SparsePhase>* recs; SparsePhase r; hipStream_t st; bool on;
+    SparseScope(gphip_sparse_ctx* h_, std::vector<SparsePhase>* recs_, int phase, hipStream_t st_) : h(h_), recs(recs_), st(st_), on(h_->profile > 0) {
+        if (!on) return;
+        r.phase = phase; r.e0 = get_event(h->u); r.e1 = get_event(h->u);
+        (void)hipEventRecord(r.e0, st);
+    }
+    ~SparseScope() {
+        if (!on) return;
+        (void)hipEventRecord(r.e1, st);
+        recs->push_back(r);
+    }
+};
+void sparse_harvest(gphip_sparse_ctx* h, std::vector<SparsePhase>& recs) {      // after the streams' synchronisation
+    for (const SparsePhase& r : recs) {
+        float ms = 0.f;
+        (void)hipEventSynchronize(r.e1);       // (a scope's closing event may have been recorded after the call's last synchronisation)
+        if (hipEventElapsedTime(&ms, r.e0, r.e1) == hipSuccess) h->ms[r.phase] += ms;
+        else (void)hipGetLastError();
+        h->u->pool.push_back(r.e0);
+        h->u->pool.push_back(r.e1);
+    }
+    recs.clear();
+}
+
+template <typename T>
+int sparse_func_attrs(gphip_sparse_ctx* h) {
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(sparse_accumulate_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)SPA_LDS));
+    return GPHIP_OK;
+}
+
+// the two contexts for the inducing points Z [m][d]
+int sparse_make_children(gphip_sparse_ctx* h, const double* Z, int64_t m) {
+    std::vector<double> y0((size_t)m, 0.0);
+    gphip_handle u = nullptr, b = nullptr;
+    std::string why;
+    int rc = create_ctx(Z, y0.data(), m, h->d, h->custom ? (int)GPHIP_KERNEL_CUSTOM : h->kernel_id, h->mean_id, h->dtype, h->device, &u,
+                        h->custom ? h->body.c_str() : nullptr, h->ncp, &why);
+    if (rc) return sfail(h, rc, "creating the inducing-point context failed " + why);
+    rc = create_ctx(Z, y0.data(), m, h->d, GPHIP_KERNEL_SE, GPHIP_MEAN_ZERO, h->dtype, u->device, &b);
+    if (rc) { gphip_destroy(u); return sfail(h, rc, "creating the context of B failed"); }
+    u->kbuild_mfma = 0;                        // K_uu and k(Z, X) from the same, direct-difference form of the kernel build
+    if (h->u) gphip_destroy(h->u);
+    if (h->b) gphip_destroy(h->b);
+    h->u = u; h->b = b; h->m = m; h->device = u->device;
+    h->fitted = false;
+    for (const auto& o : h->forwarded) {
+        (void)gphip_set_option(u, o.first.c_str(), o.second);
+        (void)gphip_set_option(b, o.first.c_str(), o.second);
+    }
+    u->kbuild_mfma = 0;
+    return GPHIP_OK;
+}
+
+// data points [c0, c0 + mpad) of a resident [d][ld] block -> u's test-point block [d][mpad]
+int sparse_load_points(gphip_sparse_ctx* h, const void* xt, int64_t ld, int64_t c0, int64_t mpad) {
+    gphip_ctx* u = h->u;
+    HIPCHK(hipMemcpy2DAsync(u->dXsT.p, (size_t)mpad * h->es, static_cast<const char*>(xt) + (size_t)c0 * h->es, (size_t)ld * h->es,
+                            (size_t)mpad * h->es, (size_t)h->d, hipMemcpyDeviceToDevice, u->stream));
+    u->test_ratio = HUGE_VAL;                  // (no verdict of the MFMA kernel build applies: u builds with the direct form)
+    return GPHIP_OK;
+}
+
+// C += V^T V, rhs row += r^T V for the chunk of mpad rows in u->dV.  Split rule (queue_downdate's): while the output tiles are
+// fewer than two per CU the chunk is cut into strips of whole 128-rows so that tiles x strips >= 2 per CU.
+template <typename T>
+int sparse_queue_accumulate(gphip_sparse_ctx* h, int64_t mpad) {
+    gphip_ctx *u = h->u, *b = h->b;
+    SparseAccArgs<T> g{};
+    g.C = (T*)b->dA.p; g.R = (int)b->R;
+    g.V = (const T*)u->dV.p; g.ldv = (long)mpad;
+    g.Rz = (const T*)h->dRz.p; g.ldr = (long)h->rcap;
+    g.Mt = (int)u->Nt; g.ntri = g.Mt * (g.Mt + 1) / 2; g.ntiles = g.ntri + g.Mt;
+    g.K = (int)mpad;
+    const long target = 2l * std::max(u->ncu, 1);
+    const int kt = (int)(mpad / TB);
+    int nsplit = g.ntiles >= target ? 1 : (int)std::min<long>(kt, (target + g.ntiles - 1) / g.ntiles);
+    if (h->split > 0) nsplit = std::min(h->split, kt);
+    const int strip_tiles = (kt + nsplit - 1) / nsplit;
+    nsplit = (kt + strip_tiles - 1) / strip_tiles;
+    g.kstrip = strip_tiles * TB;
+    h->last_nsplit = nsplit;
+    if (nsplit > 1) {
+        HIPCHK(h->dAccP.grow((size_t)nsplit * g.ntiles * TS * sizeof(T)));
+        g.P = (T*)h->dAccP.p;
+    }
+    hipLaunchKernelGGL(sparse_accumulate_kernel<T>, dim3((unsigned)g.ntiles, (unsigned)nsplit), dim3(256), SPA_LDS, u->stream, g);
+    if (nsplit > 1)
+        hipLaunchKernelGGL(sparse_reduce_kernel<T>, dim3((unsigned)g.ntiles, 16), dim3(256), 0, u->stream, (T*)b->dA.p, (int)b->R, g.ntri,
+                           g.Mt, g.ntiles, (const T*)g.P, nsplit);
+    return GPHIP_OK;
+}
+
+template <typename T>
+int sparse_queue_resid(gphip_sparse_ctx* h, int64_t c0, int64_t mc, int64_t mpad, double mu, double* part) {
+    hipLaunchKernelGGL(sparse_resid_kernel<T>, dim3((unsigned)((mpad + 255) / 256)), dim3(256), 0, h->u->stream, (const T*)h->dY.p + c0, (int)mc,
+                       (int)mpad, mu, (T*)h->dRz.p, part);
+    return GPHIP_OK;
+}
+
+template <typename T>
+int sparse_queue_diag(gphip_sparse_ctx* h, double sn2, double* out) {
+    gphip_ctx* b = h->b;
+    hipLaunchKernelGGL(sparse_diag_kernel<T>, dim3(1), dim3(256), 0, h->u->stream, (T*)b->dA.p, (int)b->R, (int)b->N, (int)b->Npad, sn2, out);
+    return GPHIP_OK;
+}
+
+// queue_factor on a context whose workspace is ready, leaving what the substitutions need; *info as gphip_loglik's
+int sparse_factor(gphip_sparse_ctx* h, gphip_ctx* c, bool build, const char* what, int* info) {
+    {
+        FactorMode mode(c, true);              // the forward substitutions that follow use the block inverses
+        c->cs = c->stream;
+        c->theta_packed = false; c->fused_eval = false;
+        if (build) DISPATCH(c, queue_build, c, 1);
+        DISPATCH(c, queue_factor, c, 1);
+    }
+    c->abort_unread = what;
+    const int rc = complete_call(c);
+    if (rc) return sfail(h, rc, c->err);
+    *info = c->hInfo.as<int>()[0];
+    return GPHIP_OK;
+}
+
+// strip partials of predict_partial_kernel for the mpad rows in c->dV against c's rhs row (queue_predict_reduce's first stage)
+template <typename T>
+int sparse_queue_partial(gphip_ctx* h, int64_t mpad, int* nstrips_out) {
+    const int Mt = (int)(mpad / TB), Nt = (int)h->Nt;
+    int nstrips = (2048 + Mt - 1) / Mt;
+    if (nstrips > Nt) nstrips = Nt;
+    if (nstrips > 64) nstrips = 64;
+    if (nstrips < 1) nstrips = 1;
+    int js = (Nt + nstrips - 1) / nstrips * TB;
+    if (js > 4096) js = 4096;
+    nstrips = (int)((h->Npad + js - 1) / js);
+    HIPCHK(h->dPart.grow((size_t)nstrips * 2 * mpad * 8));
+    hipLaunchKernelGGL(predict_partial_kernel<T>, dim3((unsigned)Mt, (unsigned)nstrips, 1u), dim3(256), (size_t)js * 8 + 8 * TB * 8, h->stream,
+                       (const T*)h->dV.p, (long)mpad, (long)mpad * h->Npad, (int)h->N, (const T*)h->dA.p, (int)h->R, (long)h->slot_elems, js,
+                       h->dPart.as<double>(), nstrips);
+    *nstrips_out = nstrips;
+    return GPHIP_OK;
+}
+
+// mean of k(z, z) over the inducing points of a run-time compiled kernel (the default jitter's scale); theta is on the device
+int sparse_mean_kzz(gphip_sparse_ctx* h, int64_t rows, double* out) {
+    gphip_ctx* u = h->u;
+    std::vector<double> k;
+    double s = 0.0;
+    for (int64_t c0 = 0; c0 < u->N; c0 += rows) {
+        const int64_t mc = std::min(rows, u->N - c0), mpad = (mc + TB - 1) / TB * TB;
+        int rc = sparse_load_points(h, u->dXt.p, u->Npad, c0, mpad);
+        if (!rc) rc = queue_custom_kss(u, mc, mpad, 1);
+        if (rc) return rc == GPHIP_ERR_HIP && !u->err.empty() ? sfail(h, rc, u->err) : rc;
+        k.resize((size_t)mc);
+        HIPCHK(hipMemcpyAsync(k.data(), u->dKss.p, (size_t)mc * 8, hipMemcpyDeviceToHost, u->stream));
+        HIPCHK(hipStreamSynchronize(u->stream));
+        for (double v : k) s += v;
+    }
+    *out = s / (double)u->N;
+    return GPHIP_OK;
+}
+
+// One evaluation: the bound (out, parts: null = not wanted) and the resident fit.
+int sparse_eval(gphip_sparse_ctx* h, const double* theta, int p, double jitter, double* out, double* parts, int* info) {
+    gphip_ctx *u = h->u, *b = h->b;
+    if (p != u->p) return sfail(h, GPHIP_ERR_DIM, "theta has the wrong length for this kernel/mean");
+    if (std::isnan(jitter) || std::isinf(jitter)) return sfail(h, GPHIP_ERR_ARG, "non-finite jitter");
+    const double qnan = std::nan("");
+    auto give_up = [&](int inf) {
+        *info = inf;
+        if (out) *out = qnan;
+        if (parts) for (int k = 0; k < 5; ++k) parts[k] = qnan;
+        return GPHIP_OK;
+    };
+    h->fitted = false;
+    for (int k = 0; k < 5; ++k) h->ms[k] = 0.0;
+    for (int k = 0; k < p; ++k)
+        if (!std::isfinite(theta[k])) return give_up(GPHIP_INFO_NAN);
+    HIPCHK(hipSetDevice(h->device));
+    int rc = ensure_slots(u, 1);
+    if (rc) return sfail(h, rc, u->err);
+    if ((rc = ensure_slots(b, 1))) return sfail(h, rc, b->err);
+    invalidate_fit(u);
+    invalidate_fit(b);
+    if (!stage_theta(u, 0, theta)) return give_up(GPHIP_INFO_NAN);
+    double* sp = u->hSlotp.as<double>();
+    const double sn2 = sp[1], mu = sp[2], kxx = sp[SP_KXX];
+    // rows of V per pass: ensure_vchunk's rule (V within ~8 GiB, at least 2048 rows, halved while it does not fit) and the option
+    int64_t rows = 0;
+    const int64_t cap = h->chunk > 0 ? std::min<int64_t>(((int64_t)h->chunk + TB - 1) / TB * TB, h->Npad) : h->Npad;
+    if ((rc = ensure_vchunk(u, cap, &rows))) { (void)hipGetLastError(); return sfail(h, rc, "no device memory for a chunk of V: " + u->err); }
+    h->last_chunk = rows;
+    if (rows > h->rcap) {
+        HIPCHK(h->dRz.grow((size_t)16 * rows * h->es));
+        HIPCHK(hipMemsetAsync(h->dRz.p, 0, (size_t)16 * rows * h->es, u->stream));
+        h->rcap = rows;
+    }
+    double jit = jitter;
+    if (jit < 0.0) {                           // default: joint_jitter_rel x k(x, x) (run-time compiled kernels: the mean of k(z, z))
+        double scale = kxx;
+        if (h->custom) {
+            if ((rc = copy_theta(u, 1))) return sfail(h, rc, u->err);
+            if ((rc = sparse_mean_kzz(h, rows, &scale))) return rc;
+        }
+        jit = joint_jitter_rel(u) * scale;
+    }
+    if (!std::isfinite(jit) || jit < 0.0) return give_up(GPHIP_INFO_NAN);
+    h->last_jitter = jit;
+    // u: the nugget slot carries the jitter; the pivot tolerance follows it
+    sp[1] = jit;
+    sp[SP_MFMA] = 0.0;
+    if (h->custom) sp[SP_SF2B] = jit;
+    else sp[3] = pivot_tol_rel(u) * (std::fabs(kxx) + jit);
+    if ((rc = copy_theta(u, 1))) return sfail(h, rc, u->err);
+    HIPCHK(hipMemsetAsync(u->dInfo.p, 0, 4, u->stream));
+    std::vector<SparsePhase> recs;
+    int inf = 0;
+    {
+        SparseScope ps(h, &recs, 0, u->stream);
+        rc = sparse_factor(h, u, true, "sparse GP: the factorisation of K_uu timed out (set option dataflow=0 and report)", &inf);
+    }
+    if (rc) return rc;
+    if (inf != 0) { sparse_harvest(h, recs); return give_up(inf); }
+    record_fit(u, true, theta, p, u->hRes.as<double>()[0]);
+    // b: an empty bordered workspace; its nugget scalar is sn^2, its pivot tolerance relative to sn^2 (B >= sn^2 I)
+    const double thb[3] = {1.0, 1.0, std::sqrt(sn2)};
+    (void)stage_theta(b, 0, thb);
+    double* spb = b->hSlotp.as<double>();
+    spb[1] = sn2; spb[3] = pivot_tol_rel(b) * sn2; spb[4] = 0.0; spb[SP_MFMA] = 0.0;
+    if ((rc = copy_theta(b, 1))) return sfail(h, rc, b->err);
+    HIPCHK(hipMemsetAsync(b->dInfo.p, 0, 4, b->stream));
+    HIPCHK(hipMemsetAsync(b->dA.p, 0, (size_t)b->slot_elems * h->es, u->stream));
+    // partial sums: [0] the trace, then one per 256 data points of every chunk for r^2, then the same for k(x_i, x_i)
+    const int64_t nchunks = (h->N + rows - 1) / rows;
+    const size_t nblk = (size_t)(h->Npad / 256 + nchunks + 1);
+    HIPCHK(h->dSum.grow((1 + 2 * nblk) * 8));
+    double* d_tr = h->dSum.as<double>();
+    double* d_r2 = d_tr + 1;
+    double* d_kk = d_r2 + nblk;
+    size_t used = 0;
+    for (int64_t c0 = 0; c0 < h->N; c0 += rows) {
+        const int64_t mc = std::min(rows, h->N - c0), mpad = (mc + TB - 1) / TB * TB;
+        {
+            SparseScope ps(h, &recs, 1, u->stream);
+            if ((rc = sparse_load_points(h, h->dXt.p, h->Npad, c0, mpad))) return rc;
+            DISPATCH(u, queue_cross, u, mc, mpad, 1);
+        }
+        {
+            SparseScope ps(h, &recs, 2, u->stream);
+            queue_forward_fit(u, mpad);
+        }
+        DISPATCH(h, sparse_queue_resid, h, c0, mc, mpad, mu, d_r2 + used);
+        if (h->custom) {                       // k(x_i, x_i) per point for a run-time compiled kernel (u->dXsT still holds the chunk)
+            if ((rc = queue_custom_kss(u, mc, mpad, 1))) return sfail(h, rc, u->err);
+            hipLaunchKernelGGL(sparse_blocksum_kernel, dim3((unsigned)((mpad + 255) / 256)), dim3(256), 0, u->stream, u->dKss.as<double>(), (int)mc,
+                               d_kk + used);
+        }
+        used += (size_t)((mpad + 255) / 256);
+        {
+            SparseScope ps(h, &recs, 3, u->stream);
+            if ((rc = DISPATCH(h, sparse_queue_accumulate, h, mpad))) return rc;
+        }
+    }
+    DISPATCH(h, sparse_queue_diag, h, sn2, d_tr);
+    h->hSum.assign(1 + 2 * nblk, 0.0);
+    HIPCHK(hipMemcpyAsync(h->hSum.data(), h->dSum.p, (1 + (h->custom ? 2 * nblk : nblk)) * 8, hipMemcpyDeviceToHost, u->stream));
+    if ((rc = complete_call(u))) { sparse_harvest(h, recs); return sfail(h, rc, u->err); }      // (the forward substitutions' abort word)
+    {
+        SparseScope ps(h, &recs, 4, b->stream);
+        rc = sparse_factor(h, b, false, "sparse GP: the factorisation of B timed out (set option dataflow=0 and report)", &inf);
+    }
+    sparse_harvest(h, recs);
+    if (rc) return rc;
+    const double logdet = b->hRes.as<double>()[0], ctc = b->hRes.as<double>()[1];
+    double rtr = 0.0, skk = 0.0;
+    for (size_t k = 0; k < used; ++k) rtr += h->hSum[1 + k];
+    if (h->custom) for (size_t k = 0; k < used; ++k) skk += h->hSum[1 + nblk + k];
+    else skk = (double)h->N * kxx;
+    const double trvv = h->hSum[0];
+    const double F = -0.5 * ((double)h->N * LOG_TWO_PI + (double)(h->N - h->m) * std::log(sn2) + logdet + (rtr - ctc) / sn2) -
+                     (skk - trvv) / (2.0 * sn2);
+    if (parts) { parts[0] = logdet; parts[1] = ctc; parts[2] = rtr; parts[3] = trvv; parts[4] = skk; }
+    if (out) *out = F;
+    *info = inf != 0 ? inf : (std::isfinite(F) ? GPHIP_INFO_OK : GPHIP_INFO_NAN);
+    record_fit(b, *info == 0, thb, 3, logdet);
+    h->fitted = *info == 0;
+    h->sn2_fit = sn2; h->mu_fit = mu; h->kxx_fit = kxx;
+    return GPHIP_OK;
+}
+
+int sparse_create(const void* X, const void* y, int64_t N, int64_t d, const void* Z, int64_t m, int kernel_id, const char* body, int ncp,
+                  int mean_id, int dtype, int device, gphip_sparse_handle* out) {
+    if (!out) return GPHIP_ERR_ARG;
+    *out = nullptr;
+    if (!X || !y || !Z) return GPHIP_ERR_ARG;
+    if (N < 1 || d < 1 || m < 1 || m > SPARSE_MAX_M) return GPHIP_ERR_DIM;
+    if (!body && kernel_id == GPHIP_KERNEL_NULL) return GPHIP_ERR_UNSUPPORTED;
+    if (!body && kernel_id == GPHIP_KERNEL_CUSTOM) return GPHIP_ERR_ARG;
+    gphip_sparse_ctx* h = new gphip_sparse_ctx;
+    h->dtype = dtype; h->es = dtype == 64 ? 8 : 4;
+    h->N = N; h->d = d; h->Npad = (N + TB - 1) / TB * TB;
+    h->kernel_id = kernel_id; h->mean_id = mean_id; h->device = device;
+    if (body) { h->custom = true; h->body = body; h->ncp = ncp; }
+    auto bail = [&](int code) { gphip_sparse_destroy(h); return code; };
+    int rc = sparse_make_children(h, static_cast<const double*>(Z), m);
+    if (rc) {
+        if (body) g_create_error = h->err;
+        return bail(rc);
+    }
+    const double* Xd = static_cast<const double*>(X);
+    const double* yd = static_cast<const double*>(y);
+    std::vector<double> xt((size_t)d * h->Npad, 0.0), yp((size_t)h->Npad, 0.0);
+    for (int64_t i = 0; i < N; ++i) {
+        for (int64_t j = 0; j < d; ++j) xt[(size_t)j * h->Npad + i] = Xd[i * d + j];
+        yp[(size_t)i] = yd[i];
+    }
+    if (hipSetDevice(h->device) != hipSuccess) return bail(GPHIP_ERR_HIP);
+    if (h->dXt.grow(xt.size() * h->es) != hipSuccess || h->dY.grow(yp.size() * h->es) != hipSuccess) { (void)hipGetLastError(); return bail(GPHIP_ERR_HIP); }
+    if (DISPATCH(h->u, upload, h->u, h->dXt.p, xt, h->u->stream) != GPHIP_OK) return bail(GPHIP_ERR_HIP);
+    if (DISPATCH(h->u, upload, h->u, h->dY.p, yp, h->u->stream) != GPHIP_OK) return bail(GPHIP_ERR_HIP);
+    if (DISPATCH(h, sparse_func_attrs, h) != GPHIP_OK) return bail(GPHIP_ERR_HIP);
+    *out = h;
+    return GPHIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gphip_sparse_create(const void* X, const void* y, int64_t N, int64_t d, const void* Z, int64_t m, int kernel_id, int mean_id, int dtype,
+                        int device, gphip_sparse_handle* out) {
+    return sparse_create(X, y, N, d, Z, m, kernel_id, nullptr, 0, mean_id, dtype, device, out);
+}
+
+int gphip_sparse_create_custom(const void* X, const void* y, int64_t N, int64_t d, const void* Z, int64_t m, const char* body, int nparams,
+                               int mean_id, int dtype, int device, gphip_sparse_handle* out) {
+    g_create_error.clear();
+    if (!out) return GPHIP_ERR_ARG;
+    *out = nullptr;
+    if (!body || !*body || nparams < 0 || nparams > 4096) { g_create_error = "null / empty function body or bad parameter count"; return GPHIP_ERR_ARG; }
+    return sparse_create(X, y, N, d, Z, m, GPHIP_KERNEL_CUSTOM, body, nparams, mean_id, dtype, device, out);
+}
+
+int gphip_sparse_destroy(gphip_sparse_handle h) {
+    if (!h) return GPHIP_OK;
+    if (h->u) {
+        (void)hipSetDevice(h->u->device);
+        (void)hipStreamSynchronize(h->u->stream);
+    }
+    if (h->b) (void)hipStreamSynchronize(h->b->stream);
+    if (h->u) gphip_destroy(h->u);
+    if (h->b) gphip_destroy(h->b);
+    (void)hipSetDevice(h->device);
+    delete h;                                  // (the buffers free themselves)
+    return GPHIP_OK;
+}
+
+int gphip_sparse_set_inducing(gphip_sparse_handle h, const void* Z, int64_t m) {
+    if (!h || !Z) return sfail(h, GPHIP_ERR_ARG, "null argument");
+    if (m < 1 || m > SPARSE_MAX_M) return sfail(h, GPHIP_ERR_DIM, "m < 1 or above GPHIP_SPARSE_MAX_M");
+    std::lock_guard<std::recursive_mutex> lk(h->mu);
+    return sparse_make_children(h, static_cast<const double*>(Z), m);
+}
+
+int gphip_sparse_num_params(gphip_sparse_handle h, int* p) {
+    if (!h || !p) return GPHIP_ERR_ARG;
+    *p = h->u->p;
+    return GPHIP_OK;
+}
+
+int gphip_sparse_bound(gphip_sparse_handle h, const double* theta, int p, double jitter, double* out, double* parts, int* info) {
+    if (!h || !theta || !out || !info) return sfail(h, GPHIP_ERR_ARG, "null argument");
+    std::lock_guard<std::recursive_mutex> lk(h->mu);
+    return sparse_eval(h, theta, p, jitter, out, parts, info);
+}
+
+int gphip_sparse_fit(gphip_sparse_handle h, const double* theta, int p, double jitter, int* info) {
+    if (!h || !theta || !info) return sfail(h, GPHIP_ERR_ARG, "null argument");
+    std::lock_guard<std::recursive_mutex> lk(h->mu);
+    return sparse_eval(h, theta, p, jitter, nullptr, nullptr, info);
+}
+
+int gphip_sparse_predict(gphip_sparse_handle h, const void* Xs, int64_t M, int latent, double* mean, double* var) {
+    if (!h || !Xs || !mean || !var) return sfail(h, GPHIP_ERR_ARG, "null argument");
+    if (M < 1) return sfail(h, GPHIP_ERR_DIM, "M < 1");
+    std::lock_guard<std::recursive_mutex> lk(h->mu);
+    gphip_ctx *u = h->u, *b = h->b;
+    if (!h->fitted || !has_fit(u) || !has_fit(b)) return sfail(h, GPHIP_ERR_STATE, "gphip_sparse_predict before a successful gphip_sparse_fit");
+    HIPCHK(hipSetDevice(h->device));
+    const double* X = static_cast<const double*>(Xs);
+    const int64_t d = h->d;
+    int64_t MC = 0;
+    int rc = ensure_vchunk(u, std::min<int64_t>(32768, (M + TB - 1) / TB * TB), &MC);
+    if (rc) { (void)hipGetLastError(); return sfail(h, rc, "no device memory for the test points' V: " + u->err); }
+    if ((rc = ensure_vbuf(b, MC))) { (void)hipGetLastError(); return sfail(h, rc, "no device memory for the test points' V: " + b->err); }
+    std::vector<double> xt;
+    for (int64_t m0 = 0; m0 < M; m0 += MC) {
+        const int64_t mc = std::min(MC, M - m0), mpad = (mc + TB - 1) / TB * TB;
+        xt.assign((size_t)d * mpad, 0.0);
+        for (int64_t i = 0; i < mc; ++i)
+            for (int64_t j = 0; j < d; ++j) xt[(size_t)j * mpad + i] = X[(m0 + i) * d + j];
+        if ((rc = DISPATCH(u, upload, u, u->dXsT.p, xt, u->stream))) return sfail(h, rc, u->err);
+        u->test_ratio = HUGE_VAL;
+        u->cs = u->stream;
+        DISPATCH(u, queue_cross, u, mc, mpad, 1);
+        queue_forward_fit(u, mpad);
+        int ns1 = 0, ns2 = 0;
+        if ((rc = DISPATCH(u, sparse_queue_partial, u, mpad, &ns1))) return sfail(h, rc, u->err);
+        if (h->custom && (rc = queue_custom_kss(u, mc, mpad, 1))) return sfail(h, rc, u->err);
+        if ((rc = complete_call(u))) return sfail(h, rc, u->err);
+        // v2 = L_B^-1 v1: the same rows through b's factor
+        b->cs = b->stream;
+        HIPCHK(hipMemcpyAsync(b->dV.p, u->dV.p, (size_t)mpad * u->Npad * h->es, hipMemcpyDeviceToDevice, b->stream));
+        queue_forward_fit(b, mpad);
+        if ((rc = DISPATCH(b, sparse_queue_partial, b, mpad, &ns2))) return sfail(h, rc, b->err);
+        hipLaunchKernelGGL(sparse_predict_finish_kernel, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, b->stream, u->dPart.as<double>(), ns1,
+                           b->dPart.as<double>(), ns2, (long)mpad, (int)mc, h->mu_fit, h->kxx_fit, h->custom ? u->dKss.as<double>() : nullptr,
+                           h->sn2_fit, latent ? 1 : 0, b->dMean.as<double>(), b->dVar.as<double>());
+        HIPCHK(hipMemcpyAsync(mean + m0, b->dMean.p, (size_t)mc * 8, hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(hipMemcpyAsync(var + m0, b->dVar.p, (size_t)mc * 8, hipMemcpyDeviceToHost, b->stream));
+        if ((rc = complete_call(b))) return sfail(h, rc, b->err);
+    }
+    return GPHIP_OK;
+}
+
+int gphip_sparse_set_option(gphip_sparse_handle h, const char* name, double value) {
+    if (!h || !name) return GPHIP_ERR_ARG;
+    std::lock_guard<std::recursive_mutex> lk(h->mu);
+    const int v = (int)value;
+    if (!strcmp(name, "sparse_chunk")) { if (v < 0) return sfail(h, GPHIP_ERR_ARG, "sparse_chunk < 0"); h->chunk = v; return GPHIP_OK; }
+    if (!strcmp(name, "sparse_split")) { if (v < 0) return sfail(h, GPHIP_ERR_ARG, "sparse_split < 0"); h->split = v; return GPHIP_OK; }
+    if (!strcmp(name, "profile")) { h->profile = v; return GPHIP_OK; }
+    int rc = gphip_set_option(h->u, name, value);
+    if (!rc) rc = gphip_set_option(h->b, name, value);
+    if (rc) return sfail(h, rc, "unknown option");
+    h->u->kbuild_mfma = 0;
+    for (auto& o : h->forwarded)
+        if (o.first == name) { o.second = value; return GPHIP_OK; }
+    h->forwarded.emplace_back(name, value);
+    return GPHIP_OK;
+}
+
+int gphip_sparse_get_option(gphip_sparse_handle h, const char* name, double* value) {
+    if (!h || !name || !value) return GPHIP_ERR_ARG;
+    std::lock_guard<std::recursive_mutex> lk(h->mu);
+    static const char* const phases[5] = {"ms_kuu_factor", "ms_cross", "ms_forward", "ms_accumulate", "ms_b_factor"};
+    for (int k = 0; k < 5; ++k)
+        if (!strcmp(name, phases[k])) { *value = h->ms[k]; return GPHIP_OK; }
+    if (!strcmp(name, "sparse_chunk")) { *value = h->chunk; return GPHIP_OK; }
+    if (!strcmp(name, "sparse_split")) { *value = h->split; return GPHIP_OK; }
+    if (!strcmp(name, "profile")) { *value = h->profile; return GPHIP_OK; }
+    if (!strcmp(name, "last_jitter")) { *value = h->last_jitter; return GPHIP_OK; }
+    if (!strcmp(name, "last_sparse_chunk")) { *value = (double)h->last_chunk; return GPHIP_OK; }
+    if (!strcmp(name, "last_sparse_nsplit")) { *value = h->last_nsplit; return GPHIP_OK; }
+    const int rc = gphip_get_option(h->u, name, value);
+    return rc ? sfail(h, rc, "unknown option") : GPHIP_OK;
+}
+
+const char* gphip_sparse_last_error(gphip_sparse_handle h) { return h ? h->err.c_str() : "null handle"; }
+
+}  // extern "C"

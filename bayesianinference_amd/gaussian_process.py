@@ -792,3 +792,166 @@ def load_gaussian_process(path: str, variablePrior="Uniform", trust_kernel_sourc
     if theta is not None:
         obj["GaussianProcessData"]["HIPHandle"].fit(theta)
     return (obj.append(extra) if extra else obj), theta
+
+
+# ---------------------------------------------------------------------------------------------
+# Sparse inducing-point GP (Titsias 2009; include/gphip.h gphip_sparse_*): for data sizes the exact path cannot hold
+# ---------------------------------------------------------------------------------------------
+def selectInducingPoints(X, m: int, seed: int = 0):
+    """m distinct rows of X, chosen by the counter-based generator of synthetic.py: a partial Fisher-Yates shuffle of the row
+    indices whose k-th swap partner comes from uniform k of stream STREAM_X at `seed`.  Deterministic; nothing cleverer
+    (optimising the inducing locations needs gradients of the bound, which the library does not have)."""
+    from . import synthetic
+    X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+    n, m = len(X), int(m)
+    if m < 1 or m > n:
+        raise ValueError(f"m must be in 1 .. N = {n}")
+    idx = np.arange(n)
+    u = synthetic.uniform(synthetic.STREAM_X, 0, m, synthetic.SEED + 1000003 * (int(seed) + 1))
+    for k in range(m):
+        j = k + min(int(u[k] * (n - k)), n - k - 1)
+        idx[k], idx[j] = idx[j], idx[k]
+    return X[idx[:m]].copy()
+
+
+def make_sparse_log_likelihood(handle: "_lib.SparseHandle", jitter: float = -1.0):
+    """The closure for "LogLikelihoodFunction" of a sparse object: theta -> F(theta), the collapsed lower bound on the log
+    marginal likelihood; $MachineLogZero on numerical failure (info != 0), B x p -> B for a batch, like make_log_likelihood."""
+    def one(theta):
+        val, info = handle.bound(theta, jitter)
+        if info != 0 or not math.isfinite(val):
+            return MACHINE_LOG_ZERO
+        return min(max(val, MACHINE_LOG_ZERO), -MACHINE_LOG_ZERO)
+
+    def log_likelihood(theta):
+        theta = np.asarray(theta, dtype=np.float64)
+        if theta.ndim == 2:
+            return np.array([one(t) for t in theta], dtype=np.float64)
+        return one(theta)
+    return log_likelihood
+
+
+def defineSparseGaussianProcess(data, kernel, inducing, nugget="Constant", meanFunction=None, variables=(),
+                                variablePrior="Uniform", **rules) -> inferenceObject:
+    """defineGaussianProcess for a sparse inducing-point GP: `inducing` = an int m (-> selectInducingPoints(X, m)) or an array
+    [m, d]; the other arguments, parameter specs, priors and pre-processors are defineGaussianProcess's (constant nugget, zero or
+    constant mean).  Extra rules: Jitter (default -1: the library's), Device, Precision, Seed (of the inducing-point choice).
+    "LogLikelihoodFunction" of the returned object is the collapsed bound F(theta) <= log p(y | X, theta), so nestedSampling,
+    laplace.selectHyperparameters(Criterion="MarginalLikelihood") and approximateEvidence run on it unchanged.
+    "LogLikelihoodGradientFunction" is a DIFFERENCE QUOTIENT: central differences of F with the step eps^(1/3) max(|theta_k|,
+    1e-2), 2p + 1 evaluations of the bound (the library has no analytic gradient of F).  Also carries "InducingPoints" and
+    "Jitter"; no leave-one-out keys."""
+    if normalizedDataQ(data) and isinstance(data, Mapping) and "Input" in data:
+        rules.setdefault("DataPreProcessors", {k: {"Function": v["Function"], "InverseFunction": v["InverseFunction"]}
+                                               for k, v in data.items()})
+        data = (data["Input"]["NormalizedData"], data["Output"]["NormalizedData"])
+    norm = dataNormalForm(data)
+    if norm is None or not isinstance(norm, tuple):
+        return inferenceObject(None)
+    X, Y = norm
+    if Y.shape[1] != 1 or len(X) != len(Y):
+        return inferenceObject(None)
+    if not (isinstance(nugget, str) and nugget.lower() == "constant"):
+        raise ValueError('a sparse GP takes the constant nugget only (nugget="Constant")')
+    if callable(meanFunction):
+        raise ValueError("a sparse GP takes the zero or the constant mean only")
+    kname = _resolve_kernel(kernel)
+    if isinstance(kname, str) and kname == "null":
+        raise ValueError("a sparse GP needs a covariance function (the null kernel has nothing to approximate)")
+    mean = "zero" if meanFunction in (None, 0, "Zero", "zero") else "const"
+    if mean == "const" and str(meanFunction).lower() not in ("constant", "const"):
+        raise ValueError("meanFunction must be None/0 or 'Constant'")
+    params = [tuple(v) for v in variables]
+    if not params or any(len(v) != 3 for v in params):
+        return inferenceObject(None)
+    device = rules.pop("Device", None)
+    precision = str(rules.pop("Precision", "Double")).lower()
+    if precision not in ("double", "single"):
+        raise ValueError('Precision must be "Double" or "Single"')
+    jitter = float(rules.pop("Jitter", -1.0))
+    seed = int(rules.pop("Seed", 0))
+    if isinstance(inducing, (int, np.integer)):
+        Z = selectInducingPoints(X, int(inducing), seed)
+    else:
+        Z = np.atleast_2d(np.asarray(inducing, dtype=np.float64))
+        if Z.ndim != 2 or Z.shape[1] != X.shape[1] or len(Z) < 1:
+            return inferenceObject(None)
+    handle = _lib.SparseHandle(X, Y[:, 0], Z, kname, mean, dtype=64 if precision == "double" else 32,
+                               device=device)                     # raises loudly without the library / GPU
+    if handle.p != len(params):
+        handle.close()
+        raise ValueError(f"kernel {kname!r} with mean {mean!r} on d={X.shape[1]} needs {handle.p} "
+                         f"hyper-parameters (l.., sigma_f, sigma_n[, mu]); got {len(params)}")
+    loglik = make_sparse_log_likelihood(handle, jitter)
+
+    def log_likelihood_gradient(theta):
+        """(F, dF/dtheta) by central differences of the bound: a difference quotient, 2p + 1 bound evaluations, step
+        eps^(1/3) max(|theta_k|, 1e-2).  Sentinel and NaN gradient on numerical failure."""
+        theta = np.asarray(theta, dtype=np.float64).ravel()
+        val = loglik(theta)
+        grad = np.full(len(theta), np.nan)
+        if val <= MACHINE_LOG_ZERO:
+            return MACHINE_LOG_ZERO, grad
+        for k in range(len(theta)):
+            step = np.finfo(np.float64).eps ** (1.0 / 3.0) * max(abs(theta[k]), 1e-2)
+            tp, tm = theta.copy(), theta.copy()
+            tp[k] += step
+            tm[k] -= step
+            fp, fm = loglik(tp), loglik(tm)
+            if fp <= MACHINE_LOG_ZERO or fm <= MACHINE_LOG_ZERO:
+                return MACHINE_LOG_ZERO, np.full(len(theta), np.nan)
+            grad[k] = (fp - fm) / (tp[k] - tm[k])
+        return val, grad
+
+    return defineInferenceProblem({
+        "Data": (X, Y),
+        "PriorDistribution": variablePrior,
+        "Parameters": params,
+        "KernelName": kname, "MeanName": mean, "LikelihoodBranch": "SparseBound",
+        "InducingPoints": Z, "Jitter": jitter,
+        "SparseGaussianProcessData": {
+            "ModelFunctions": {
+                "KernelFunction": ((kname.name, kname.body) if isinstance(kname, _lib.CustomKernel)
+                                   else (kname, wl_kernel_expression(kname))),
+                "NuggetFunction": WL_NUGGET_EXPRESSION,
+                "MeanFunction": mean,
+            },
+            "HIPHandle": handle,
+        },
+        **rules,
+        "LogLikelihoodGradientFunction": log_likelihood_gradient,
+        "LogLikelihoodFunction": loglik,
+    })
+
+
+def predictFromSparseGaussianProcess(obj, pts, theta=None):
+    """Prediction from a sparse object: for one theta, or (theta=None) the posterior mixture of a sampled object -- one Normal
+    per posterior sample, mixed with the CrudePosteriorWeights.  Returns the dict of predictFromGaussianProcess: "Points" [M,d],
+    "Weights" [S], "Mean" [S,M], "StandardDeviation" [S,M] (S = 1 for one theta); the variance includes the noise sn^2.  Samples
+    whose fit fails give NaN rows.  None where the object is not a sparse GP object (or unsampled without a theta)."""
+    if not isinstance(obj, inferenceObject) or obj.failed or "SparseGaussianProcessData" not in obj:
+        return None
+    X = obj["Data"][0]
+    if isinstance(pts, (int, np.integer)):
+        if pts <= 1 or X.shape[1] != 1:
+            return None
+        pts = np.linspace(X.min(), X.max(), int(pts))
+    P = dataNormalForm(pts)
+    if P is None or isinstance(P, tuple):
+        return None
+    handle = obj["SparseGaussianProcessData"]["HIPHandle"]
+    if theta is not None:
+        points, weights = np.atleast_2d(np.asarray(theta, dtype=np.float64)), np.ones(1)
+    elif "Samples" in obj:
+        points = np.array([s["Point"] for s in obj["Samples"]], dtype=np.float64)
+        weights = np.array([s["CrudePosteriorWeight"] for s in obj["Samples"]], dtype=np.float64)
+    else:
+        return None
+    mean = np.full((len(points), len(P)), np.nan)
+    var = np.full((len(points), len(P)), np.nan)
+    for s, th in enumerate(points):
+        if handle.fit(th, obj["Jitter"]) == 0:
+            mean[s], var[s] = handle.predict(P)
+    with np.errstate(invalid="ignore"):
+        sd = np.sqrt(var)
+    return {"Points": P, "Weights": weights, "Mean": mean, "StandardDeviation": sd}

@@ -455,6 +455,60 @@ int gphip_dist_end(gphip_handle h, double* logdet_partial, double* quad, int* in
  * compact own-panel storage + receive buffers (diagnostics: a sharded evaluation keeps ~1 / world of the workspace). */
 int gphip_factor_bytes(gphip_handle h, int member, double* bytes);
 
+/* ---- Sparse inducing-point GP: the collapsed variational bound of Titsias (2009), "SGPR"; no reference equivalent.
+ * For data sizes the exact path cannot hold: m << N inducing points Z, a lower bound F(theta) <= log p(y | X, theta) that costs
+ * O(N m^2), predictions from two m x m factors.  theta has the layout of the same kernel in gphip_create (.., sf, sn [, mu]);
+ * r = y - m(X); j = jitter >= 0 is PART OF THE MODEL: K_uu always means k(Z, Z) + j I.
+ *
+ *     L_u L_u^T = K_uu                         (m x m)
+ *     V   = L_u^-1 k(Z, X)                     (m x N, never resident as a whole: streamed in chunks of data points)
+ *     B   = sn^2 I + V V^T                     (m x m)           L_B L_B^T = B
+ *     c   = L_B^-1 (V r)
+ *     F   = -1/2 [ N log 2 pi + (N - m) log sn^2 + log det B + (r^T r - c^T c) / sn^2 ] - (sum_i k(x_i, x_i) - tr(V V^T)) / (2 sn^2)
+ *
+ * prediction at x* with v1 = L_u^-1 k(Z, x*), v2 = L_B^-1 v1:
+ *     mean = m(x*) + v2^T c            var = k(x*, x*) [+ sn^2 unless latent] - |v1|^2 + sn^2 |v2|^2
+ *
+ * A separate opaque type: no other entry point of this header takes a sparse object.  Every named and composed kernel and the
+ * run-time compiled ones (gphip_sparse_create_custom: arguments as gphip_create_custom), zero and constant mean, fp64 and fp32;
+ * one device.  m > N is allowed.  Statuses, all decided before any device work: NULL arguments GPHIP_ERR_ARG; N < 1, d < 1,
+ * m < 1, m > GPHIP_SPARSE_MAX_M, wrong p GPHIP_ERR_DIM; the null kernel GPHIP_ERR_UNSUPPORTED, unknown ids GPHIP_ERR_ARG;
+ * gphip_sparse_predict before a successful fit GPHIP_ERR_STATE; non-finite jitter GPHIP_ERR_ARG.  Non-finite theta is
+ * *info = GPHIP_INFO_NAN and a failed factorisation of K_uu or of B *info = GPHIP_INFO_NOT_SPD, not error statuses.
+ *
+ * gphip_sparse_bound: *out = F; parts (NULL or 5 doubles) = {log det B, c^T c, r^T r, tr(V V^T), sum_i k(x_i, x_i)}.  It leaves
+ * the fit resident; gphip_sparse_fit is the same work without the scalar.  gphip_sparse_set_inducing replaces Z (any m) and
+ * drops the fit.
+ * jitter < 0: the default, 1e-10 (fp64) / 1e-4 (fp32) x k(x, x) (run-time compiled kernels: x the mean of k(z, z) over Z);
+ * option "last_jitter" returns the absolute value the last call used -- a reference has to use the same one.  The error of F
+ * grows with cond(K_uu) ~ k(x, x) / j; fp64 held 1e-8 against the reference in every measured case up to cond(K_uu) = 4.8e12
+ * (DESIGN.md section 8c).
+ * Two calls with the same options return the same bytes (fixed-order reductions, no atomics).
+ *
+ * Options (gphip_sparse_set_option / gphip_sparse_get_option):
+ *   "sparse_chunk"  data points per pass over V (rounded up to 128); 0 (default) = as many as keep the chunk of V within ~8 GiB,
+ *                   at least 2048, halved while it does not fit.  "last_sparse_chunk" (read-only): what the last call used.
+ *   "sparse_split"  strips the accumulation kernel cuts a chunk into; 0 (default) = by the split rule (output tiles x strips
+ *                   >= two per CU).  "last_sparse_nsplit" (read-only): strips of the last chunk of the last call.
+ *   "profile"       0 / 1: time the phases of gphip_sparse_bound / _fit with HIP events; read-only milliseconds of the last call:
+ *                   "ms_kuu_factor", "ms_cross", "ms_forward", "ms_accumulate", "ms_b_factor".
+ *   every other name is handed on to the two contexts that factor K_uu and B (see gphip_set_option; e.g. "dataflow"). ---- */
+#define GPHIP_SPARSE_MAX_M 16384
+typedef struct gphip_sparse_ctx* gphip_sparse_handle;
+int gphip_sparse_create(const void* X, const void* y, int64_t N, int64_t d, const void* Z, int64_t m, int kernel_id, int mean_id,
+                        int dtype, int device, gphip_sparse_handle* out);
+int gphip_sparse_create_custom(const void* X, const void* y, int64_t N, int64_t d, const void* Z, int64_t m, const char* body,
+                               int nparams, int mean_id, int dtype, int device, gphip_sparse_handle* out);
+int gphip_sparse_destroy(gphip_sparse_handle h);
+int gphip_sparse_set_inducing(gphip_sparse_handle h, const void* Z, int64_t m);
+int gphip_sparse_num_params(gphip_sparse_handle h, int* p);
+int gphip_sparse_bound(gphip_sparse_handle h, const double* theta, int p, double jitter, double* out, double* parts, int* info);
+int gphip_sparse_fit(gphip_sparse_handle h, const double* theta, int p, double jitter, int* info);
+int gphip_sparse_predict(gphip_sparse_handle h, const void* Xs, int64_t M, int latent, double* mean, double* var);
+int gphip_sparse_set_option(gphip_sparse_handle h, const char* name, double value);
+int gphip_sparse_get_option(gphip_sparse_handle h, const char* name, double* value);
+const char* gphip_sparse_last_error(gphip_sparse_handle h);   /* owned by the library */
+
 /* Block until all work queued on the handle's stream is complete. */
 int gphip_sync(gphip_handle h);
 
