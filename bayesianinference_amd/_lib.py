@@ -130,6 +130,7 @@ _SIGNATURES = {
     "gphip_sparse_set_inducing": (C.c_int, [_h, C.c_void_p, C.c_int64]),
     "gphip_sparse_num_params": (C.c_int, [_h, _ip]),
     "gphip_sparse_bound": (C.c_int, [_h, _dp, C.c_int, C.c_double, _dp, _dp, _ip]),
+    "gphip_sparse_bound_grad": (C.c_int, [_h, _dp, C.c_int, C.c_double, _dp, _dp, _dp, _ip]),
     "gphip_sparse_fit": (C.c_int, [_h, _dp, C.c_int, C.c_double, _ip]),
     "gphip_sparse_predict": (C.c_int, [_h, C.c_void_p, C.c_int64, C.c_int, _dp, _dp]),
     "gphip_sparse_set_option": (C.c_int, [_h, C.c_char_p, C.c_double]),
@@ -655,6 +656,7 @@ class Handle:
 SPARSE_MAX_M = 16384
 SPARSE_PARTS = ("logdet_B", "ctc", "rtr", "tr_VVt", "sum_kxx")
 SPARSE_PHASES = ("ms_kuu_factor", "ms_cross", "ms_forward", "ms_accumulate", "ms_b_factor")
+SPARSE_GRAD_PHASES = ("ms_grad_small", "ms_grad_weights", "ms_grad_backward", "ms_grad_reduce")
 
 
 class SparseHandle:
@@ -739,6 +741,15 @@ class SparseHandle:
         out, info = C.c_double(0.0), C.c_int(0)
         self._check(self._lib.gphip_sparse_bound(self._h, _d(th), th.size, float(jitter), C.byref(out), None, C.byref(info)))
         return out.value, info.value
+
+    def bound_grad(self, theta, jitter: float = -1.0):
+        """(F(theta), dF/dtheta, info): the bound -- the same bytes as `bound` -- and its gradient in theta's layout, the jitter
+        held fixed; the gradient is NaN when info != 0.  get_option("grad_analytic") tells whether the analytic route ran.  The
+        fit stays resident."""
+        th = np.ascontiguousarray(np.asarray(theta, dtype=np.float64).ravel())
+        out, info, grad = C.c_double(0.0), C.c_int(0), np.zeros(th.size)
+        self._check(self._lib.gphip_sparse_bound_grad(self._h, _d(th), th.size, float(jitter), C.byref(out), _d(grad), None, C.byref(info)))
+        return out.value, grad, info.value
 
     def fit(self, theta, jitter: float = -1.0) -> int:
         th = np.ascontiguousarray(np.asarray(theta, dtype=np.float64).ravel())

@@ -39,7 +39,7 @@ namespace gphip {
 
 // Bumped whenever a struct or constant the run-time compiled copy of this region shares with the offline library changes
 // (KBuildArgs, SLOTP, the tile layout): rtc_dyn.h refuses a source tree whose value differs from the library's own.
-#define GP_RTC_ABI 6
+#define GP_RTC_ABI 7
 // A run-time compiled program is built for ONE handle, whose input dimension is known: the generated source defines GP_D and the
 // dimension loops of the caller's function unroll (their per-dimension reciprocals then leave the column loop).  Offline: the argument.
 #ifdef GP_D
@@ -712,7 +712,16 @@ struct GradArgs {
     int np, ws_off;                 // accumulator slots per workgroup; where the [4 waves][np] staging area starts in LDS (doubles)
     const T* beta;                  // [npad] or null.  Null: w = alpha_g alpha_j - Kinv_gj (the log-likelihood).  Set: the leave-one-out
                                     // pseudo-likelihood, w = alpha_g beta_j + beta_g alpha_j - Kinv_gj with Kinv holding M (gp_loo.h)
+    const T* xr; const T* xr2;      // null: the rows are training points as the columns are (square).  Set: a RECTANGLE -- the rows are
+    int npad_r;                     // the mc points [d][npad_r] of xr (xr2: scaled by term 2), the columns the training points; the weight
+                                    // is w = -Kinv(t, j) alone (no alpha term), no entry counts as a diagonal one and tri does not apply
+    int diag; double wdiag;         // run-time compiled function only: 1 = no matrix at all, sum_t wdiag dk(x_t, x_t)/dp over the rows
 };
+
+// the row points of a gradient reduction and their leading dimension (GradArgs::xr)
+template <typename T> __device__ __forceinline__ const T* grad_row_points(const GradArgs<T>& a) { return a.xr ? a.xr : a.xs; }
+template <typename T> __device__ __forceinline__ const T* grad_row_points2(const GradArgs<T>& a) { return a.xr ? a.xr2 : a.xs2; }
+template <typename T> __device__ __forceinline__ int grad_row_ld(const GradArgs<T>& a) { return a.xr ? a.npad_r : a.npad; }
 
 // the weight of entry (g, j) in a gradient reduction: see GradArgs::beta (bg / beta[j] are read only when beta is set)
 template <typename T>
@@ -771,12 +780,18 @@ __global__ __launch_bounds__(256) void custom_grad_kernel(GradArgs<T> a, const d
 #pragma unroll
     for (int m = 0; m < GP_NCP; ++m) acc[m] = 0.0;
     double acc_dg = 0.0;
-    const T ag = (t < a.mc) ? a.alpha[g] : (T)0;
+    const bool rect = a.xr != nullptr;
+    const T ag = (t < a.mc && !rect) ? a.alpha[g] : (T)0;
     const double bg = (a.beta && t < a.mc) ? (double)a.beta[g] : 0.0;
     __syncthreads();
-    if (t < a.mc && g < a.n) {
-        const PointRef<T> Xg{a.xs + g, (long)a.npad};
-        for (int jj = half * 64; jj < half * 64 + 64; ++jj) {
+    if (t < a.mc && (rect || g < a.n)) {
+        const PointRef<T> Xg{grad_row_points(a) + g, (long)grad_row_ld(a)};
+        if (a.diag && half == 0) {                 // the rows' own k(x_t, x_t) only: one thread of the two that share a row
+            const dual_t k = gphip_custom_k<dual_t, T>(Xg, Xg, cp, d);
+#pragma unroll
+            for (int m = 0; m < GP_NCP; ++m) acc[m] = a.wdiag * (double)k.g[m];
+        }
+        for (int jj = half * 64; jj < (a.diag ? 0 : half * 64 + 64); ++jj) {
             const int j = tj * TB + jj;
             if (j >= a.n) break;
             const PointRef<T> Yj{glb ? a.xs + j : xjs + jj, glb ? (long)a.npad : (long)TB};
@@ -784,7 +799,7 @@ __global__ __launch_bounds__(256) void custom_grad_kernel(GradArgs<T> a, const d
             const double w = grad_weight(a, wt, ag, aj[jj], bg, j, (double)a.Kinv[(long)j * a.ldv + t]);
 #pragma unroll
             for (int m = 0; m < GP_NCP; ++m) acc[m] = __builtin_fma(w, (double)k.g[m], acc[m]);
-            if (j == g) acc_dg += w;
+            if (j == g && !rect) acc_dg += w;
         }
     }
 #pragma unroll
@@ -3315,19 +3330,22 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(GradArgs<T> a) {
     for (int idx = tid; idx < d * TB; idx += 256) xjs[idx] = a.xs[(long)(idx >> 7) * a.npad + tj * TB + (idx & 127)];
     if (tid < TB) aj[tid] = a.alpha[tj * TB + tid];
     constexpr int DM = (D > 0) ? D : 32;
+    const bool rect = a.xr != nullptr;
+    const T* xrow = grad_row_points(a);
+    const int ldr = grad_row_ld(a);
     T xg[DM];
     double acc[DM];
 #pragma unroll
     for (int dd = 0; dd < DM; ++dd) {
         acc[dd] = 0.0;
-        xg[dd] = (dd < d && t < a.mc) ? a.xs[(long)dd * a.npad + g] : (T)0;
+        xg[dd] = (dd < d && t < a.mc) ? xrow[(long)dd * ldr + g] : (T)0;
     }
     double acc_sf = 0.0, acc_dg = 0.0;
-    const T ag = (t < a.mc) ? a.alpha[g] : (T)0;
+    const T ag = (t < a.mc && !rect) ? a.alpha[g] : (T)0;
     const double bg = (a.beta && t < a.mc) ? (double)a.beta[g] : 0.0;
     const T sf2 = (T)a.slotp[0];
     __syncthreads();
-    if (t < a.mc && g < a.n) {
+    if (t < a.mc && (rect || g < a.n)) {
         for (int jj = half * 64; jj < half * 64 + 64; ++jj) {
             const int j = tj * TB + jj;
             if (j >= a.n) break;
@@ -3357,7 +3375,7 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(GradArgs<T> a) {
             for (int dd = 0; dd < DM; ++dd)
                 if (dd < d) acc[dd] = __builtin_fma(wf, (double)u2[dd], acc[dd]);
             acc_sf = __builtin_fma(w, (double)kpart, acc_sf);
-            if (j == g) acc_dg += w;
+            if (j == g && !rect) acc_dg += w;
         }
     }
     // out of the workgroup: wave sums -> LDS -> one row of per-workgroup sums (GradEmit)
@@ -3400,31 +3418,35 @@ __global__ __launch_bounds__(256) void grad_reduce_general_kernel(GradArgs<T> a)
     const double wt = (a.tri && tj < ti) ? 2.0 : 1.0;
     const int t = ti * TB + row, g = a.c0 + t;
     const int g0 = a.c0 + ti * TB;               // first row point of this tile
+    const bool rect = a.xr != nullptr;
+    const T* xrow = grad_row_points(a);
+    const T* xrow2 = grad_row_points2(a);
+    const int ldr = grad_row_ld(a);
     for (int idx = tid; idx < (glb ? 0 : d * TB); idx += 256) {
         const int dd = idx >> 7, c = idx & 127;
         xjs[idx] = a.xs[(long)dd * a.npad + tj * TB + c];
-        xis[idx] = (g0 + c < a.npad) ? a.xs[(long)dd * a.npad + g0 + c] : (T)0;
+        xis[idx] = (g0 + c < ldr) ? xrow[(long)dd * ldr + g0 + c] : (T)0;
         if (two) {
             xjs2[idx] = a.xs2[(long)dd * a.npad + tj * TB + c];
-            xis2[idx] = (g0 + c < a.npad) ? a.xs2[(long)dd * a.npad + g0 + c] : (T)0;
+            xis2[idx] = (g0 + c < ldr) ? xrow2[(long)dd * ldr + g0 + c] : (T)0;
         }
     }
     if (tid < TB) aj[tid] = a.alpha[tj * TB + tid];
     // coordinate dd of this thread's row point / of column point jj, term 1 and term 2
-    auto xi1 = [&](int dd) -> T { return glb ? a.xs[(long)dd * a.npad + g] : xis[dd * TB + row]; };
+    auto xi1 = [&](int dd) -> T { return glb ? xrow[(long)dd * ldr + g] : xis[dd * TB + row]; };
     auto xj1 = [&](int dd, int jj) -> T { return glb ? a.xs[(long)dd * a.npad + tj * TB + jj] : xjs[dd * TB + jj]; };
-    auto xi2 = [&](int dd) -> T { return glb ? a.xs2[(long)dd * a.npad + g] : xis2[dd * TB + row]; };
+    auto xi2 = [&](int dd) -> T { return glb ? xrow2[(long)dd * ldr + g] : xis2[dd * TB + row]; };
     auto xj2 = [&](int dd, int jj) -> T { return glb ? a.xs2[(long)dd * a.npad + tj * TB + jj] : xjs2[dd * TB + jj]; };
     double acc1[32], acc2[32];
 #pragma unroll
     for (int dd = 0; dd < 32; ++dd) acc1[dd] = acc2[dd] = 0.0;
     double acc_sf1 = 0.0, acc_sf2 = 0.0, acc_dg = 0.0, acc_a1 = 0.0, acc_a2 = 0.0, acc_c = 0.0;
-    const T ag = (t < a.mc) ? a.alpha[g] : (T)0;
+    const T ag = (t < a.mc && !rect) ? a.alpha[g] : (T)0;
     const double bg = (a.beta && t < a.mc) ? (double)a.beta[g] : 0.0;
     const double* sp = a.slotp;
     const T sf2a = (T)sp[0], sf2b = (T)sp[SP_SF2B];
     __syncthreads();
-    if (t < a.mc && g < a.n) {
+    if (t < a.mc && (rect || g < a.n)) {
         for (int jj = half * 64; jj < half * 64 + 64; ++jj) {
             const int j = tj * TB + jj;
             if (j >= a.n) break;
@@ -3464,7 +3486,7 @@ __global__ __launch_bounds__(256) void grad_reduce_general_kernel(GradArgs<T> a)
             acc_a1 = __builtin_fma(w * dk1, (double)sf2a * (double)da1, acc_a1);
             acc_a2 = __builtin_fma(w * dk2, (double)sf2b * (double)da2, acc_a2);
             acc_c += w;
-            if (j == g) acc_dg += w;
+            if (j == g && !rect) acc_dg += w;
         }
     }
 #pragma unroll

@@ -6,6 +6,7 @@
 //   sparse_blocksum_kernel       per-block partial sums of a double vector (k(x_i, x_i) of a run-time compiled kernel)
 //   sparse_diag_kernel           tr(V V^T) from C's diagonal, then + sn^2 on it (identity on the pad)
 //   sparse_predict_finish_kernel mean and variance of a chunk of test points from the strip partials of v1 and v2
+//   sparse_small / _trace / _vta / _w / _weight / _transpose_kernel   the gradient of the bound, see the second half of this file
 #pragma once
 #include "gp_kernels.h"
 
@@ -279,6 +280,207 @@ __global__ void sparse_predict_finish_kernel(const double* __restrict__ part1, i
     }
     mean[t] = mu + dot;
     var[t] = (kss ? kss[t] : kxx) + (latent ? 0.0 : sn2) - n1 + sn2 * n2;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The gradient of the bound (gphip_sparse_bound_grad).  With a = L_B^-T c, w = (r - V^T a) / sn^2 and
+// D = I / sn^2 - B^-1 the weights of d k(Z, X) are G = L_u^-T (D V + a w^T), those of d k(Z, Z) are
+// H = L_u^-T [I - sn^2 B^-1 / 2 - a a^T / 2 - B / (2 sn^2)] L_u^-1; both reach the gradient reductions of gp_kernels.h as the
+// "K^-1" operand scaled by -2 (their weight is -Kinv and the chain rule halves the sums).
+//
+//   sparse_small_kernel          S = D and Hm = -2 [..] (dense, symmetric, zero on the pad) from B^-1, a and the saved B
+//   sparse_trace_kernel          tr B^-1 and a^T a over the m inducing points
+//   sparse_vta_kernel            strip partials of V^T a for a chunk
+//   sparse_w_kernel              w of a chunk (fp64) + per-block partial sums of w
+//   sparse_weight_kernel         T = scale (V S + w a^T) on the matrix pipe (the hot path)
+//   sparse_transpose_kernel      out = in^T of a square column-major matrix
+// ---------------------------------------------------------------------------------------------
+
+// Binv: B^-1, column-major with leading dimension ld (= mpad; its lower triangle is read); a [mpad]; Bt: the tile-major lower tiles
+// of B = sn^2 I + V V^T as they were before the factorisation (R tile rows).  S and Hm: column-major, leading dimension mpad.
+template <typename T>
+__global__ __launch_bounds__(256) void sparse_small_kernel(const T* __restrict__ Binv, long ld, const T* __restrict__ a, const T* __restrict__ Bt,
+                                                           int R, int m, int mpad, double sn2, T* __restrict__ S, T* __restrict__ Hm) {
+    const long total = (long)mpad * mpad;
+    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+        const int i = (int)(idx % mpad), j = (int)(idx / mpad);
+        double s = 0.0, hm = 0.0;
+        if (i < m && j < m) {
+            const int lo = i < j ? i : j, hi = i < j ? j : i;              // element (hi, lo) of the lower triangle
+            const double binv = (double)Binv[(long)lo * ld + hi];
+            const double b = (double)Bt[tile_index(hi >> 7, lo >> 7, R) * TS + (long)(lo & 127) * TB + (hi & 127)];
+            const double eye = i == j ? 1.0 : 0.0;
+            s = eye / sn2 - binv;
+            hm = -2.0 * (eye - 0.5 * sn2 * binv - 0.5 * (double)a[i] * (double)a[j] - b / (2.0 * sn2));
+        }
+        S[idx] = (T)s;
+        Hm[idx] = (T)hm;
+    }
+}
+
+// out[0] = tr B^-1, out[1] = a^T a, both over k < m in a fixed order.  One workgroup.
+template <typename T>
+__global__ __launch_bounds__(256) void sparse_trace_kernel(const T* __restrict__ Binv, long ld, const T* __restrict__ a, int m,
+                                                           double* __restrict__ out) {
+    __shared__ double red[256];
+    double s = 0.0, q = 0.0;
+    for (int k = threadIdx.x; k < m; k += 256) {
+        s += (double)Binv[(long)k * ld + k];
+        q += (double)a[k] * (double)a[k];
+    }
+    s = sparse_block_sum(s, red);
+    __syncthreads();
+    q = sparse_block_sum(q, red);
+    if (threadIdx.x == 0) { out[0] = s; out[1] = q; }
+}
+
+// part[strip][t] = sum over the strip's 128 inducing indices of V(t, k) a_k.  grid = (npad_t / 256, Mt).
+template <typename T>
+__global__ __launch_bounds__(256) void sparse_vta_kernel(const T* __restrict__ V, long ldv, const T* __restrict__ a, int npad_t,
+                                                         double* __restrict__ part) {
+    __shared__ double as[TB];
+    const int t = blockIdx.x * 256 + threadIdx.x, k0 = blockIdx.y * TB;
+    if (threadIdx.x < TB) as[threadIdx.x] = (double)a[k0 + threadIdx.x];
+    __syncthreads();
+    if (t >= npad_t) return;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    const T* v = V + (long)k0 * ldv + t;
+#pragma unroll 2
+    for (int k = 0; k < TB; k += 4) {
+        s0 = __builtin_fma((double)v[(long)k * ldv], as[k], s0);
+        s1 = __builtin_fma((double)v[(long)(k + 1) * ldv], as[k + 1], s1);
+        s2 = __builtin_fma((double)v[(long)(k + 2) * ldv], as[k + 2], s2);
+        s3 = __builtin_fma((double)v[(long)(k + 3) * ldv], as[k + 3], s3);
+    }
+    part[(long)blockIdx.y * npad_t + t] = (s0 + s1) + (s2 + s3);
+}
+
+// w[t] = (r_t - sum_strips part[strip][t]) / sn2 for t < n, 0 on the pad; wsum[block] = the block's sum of w.  grid = npad_t / 256.
+template <typename T>
+__global__ __launch_bounds__(256) void sparse_w_kernel(const T* __restrict__ rz, const double* __restrict__ part, int nstrips, int n,
+                                                       int npad_t, double sn2, double* __restrict__ w, double* __restrict__ wsum) {
+    __shared__ double red[256];
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    double v = 0.0;
+    if (t < n) {
+        double s = 0.0;
+        for (int q = 0; q < nstrips; ++q) s += part[(long)q * npad_t + t];
+        v = ((double)rz[t] - s) / sn2;
+    }
+    if (t < npad_t) w[t] = v;
+    const double tot = sparse_block_sum(v, red);
+    if (threadIdx.x == 0) wsum[blockIdx.x] = tot;
+}
+
+// ---------------------------------------------------------------------------------------------
+// T(t, k) = scale (sum_k' V(t, k') S(k', k) + w_t a_k) for a chunk: V(t, k') at V[t + k' ldv] as the forward substitution leaves it,
+// S the symmetric m x m matrix of sparse_small_kernel (column-major, leading dimension lds_), out(t, k) at out[t + k ldo] -- the
+// layout queue_backward_rows and the gradient reductions read.  The contraction runs over the INDUCING index k', the strided one
+// of V (downdate_kernel's orientation, not sparse_accumulate_kernel's): for one k' both operands are contiguous in their output
+// index (V in t; S, being symmetric, in k), so a stage is KC rows of 128 contiguous elements per operand.
+// One workgroup = one 128 (t) x 128 (k) output tile, 2 x 2 waves of 64 x 64, 4 x 4 accumulators of v_mfma_*_16x16x4 per wave
+// (the accumulator layout of sparse_accumulate_kernel: i = t contiguous in the output, j = k).  Staging goes through registers
+// into two LDS stages of KC = 8 rows per operand: global loads of stage s + 1 are issued before the MFMAs of stage s and stored
+// after them, one barrier per stage.  An MFMA operand is one element per lane, row l & 15 at contraction index l >> 4: the 16
+// lanes of one l >> 4 read 16 consecutive elements of one LDS row, and the row stride of 144 elements (= 16 mod 32 doubles,
+// = 16 mod 64 floats) puts the rows of the lane groups that are served together on different banks: with 64 banks of 4 bytes the
+// four groups of an fp32 read start at banks 0 / 16 / 32 / 48; an fp64 read is served half a wave at a time, and the two groups of
+// a half start at banks 0 / 32 (groups 0 and 2 share banks, but not a half).  This follows from the layout; no bank-conflict
+// counter has been read for it.  The kernel runs at 0.85 of the fp64 matrix-pipe figure at m = 8192.
+// Pad rows of V (t beyond the chunk) and pad rows / columns of S are zeros, w_t is zero on the pad and a_k is zero for k >= m, so
+// the pad of T comes out as exact zeros.  grid = (npad_t / 128, mpad / 128).
+// ---------------------------------------------------------------------------------------------
+template <typename T>
+struct SparseWeightArgs {
+    const T* V; long ldv;        // V(t, k') at V[t + k' ldv]
+    const T* S; long lds;        // S(k', k) at S[k + k' lds] (symmetric)
+    const double* w;             // [npad_t]
+    const T* a;                  // [mpad]
+    T* out; long ldo;            // out(t, k) at out[t + k ldo]
+    int mpad;                    // padded inducing points: the contraction length (multiple of 128)
+    double scale;
+};
+
+constexpr int SPW_KC = 8;                      // contraction indices per stage
+constexpr int SPW_STR = 144;                   // elements between consecutive rows of a stage image
+
+template <typename T>
+__global__ __launch_bounds__(256, 2) void sparse_weight_kernel(SparseWeightArgs<T> g) {
+    constexpr int FI = 4, FJ = 4;
+    typedef typename Num<T>::acc_t acc_t;
+    typedef T v4 __attribute__((ext_vector_type(4)));
+    __shared__ __attribute__((aligned(32))) T img[2][2][SPW_KC * SPW_STR];      // [stage][V, S][row k'][128 (+ pad)]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wi = wave & 1, wj = wave >> 1;
+    const int l15 = lane & 15, l4 = lane >> 4;
+    const long t0 = (long)blockIdx.x * TB, k0 = (long)blockIdx.y * TB;
+    // staging: thread -> row tid >> 5 of the stage, elements 4 (tid & 31) .. + 3 of it
+    const int sr = tid >> 5, sc = (tid & 31) * 4;
+    const T* vg = g.V + t0 + sc + (long)sr * g.ldv;
+    const T* sg = g.S + k0 + sc + (long)sr * g.lds;
+    const int so = sr * SPW_STR + sc;
+    acc_t acc[FJ][FI];
+#pragma unroll
+    for (int x = 0; x < FJ; ++x)
+#pragma unroll
+        for (int y = 0; y < FI; ++y) acc[x][y] = (acc_t){0, 0, 0, 0};
+    const int nk = g.mpad / SPW_KC;
+    v4 rv = *reinterpret_cast<const v4*>(vg), rs = *reinterpret_cast<const v4*>(sg);
+    *reinterpret_cast<v4*>(&img[0][0][so]) = rv;
+    *reinterpret_cast<v4*>(&img[0][1][so]) = rs;
+    __syncthreads();
+    for (int kb = 0; kb < nk; ++kb) {
+        const int cur = kb & 1;
+        if (kb + 1 < nk) {
+            rv = *reinterpret_cast<const v4*>(vg + (long)(kb + 1) * SPW_KC * g.ldv);
+            rs = *reinterpret_cast<const v4*>(sg + (long)(kb + 1) * SPW_KC * g.lds);
+        }
+        const T* Vs = img[cur][0];
+        const T* Ss = img[cur][1];
+#pragma unroll
+        for (int kk = 0; kk < SPW_KC / 4; ++kk) {
+            T fi[FI], fj[FJ];
+            const int row = (kk * 4 + l4) * SPW_STR;
+#pragma unroll
+            for (int f = 0; f < FI; ++f) fi[f] = Vs[row + wi * 64 + f * 16 + l15];
+#pragma unroll
+            for (int f = 0; f < FJ; ++f) fj[f] = Ss[row + wj * 64 + f * 16 + l15];
+#pragma unroll
+            for (int x = 0; x < FJ; ++x)
+#pragma unroll
+                for (int y = 0; y < FI; ++y) acc[x][y] = Num<T>::mfma(fj[x], fi[y], acc[x][y]);
+        }
+        if (kb + 1 < nk) {
+            *reinterpret_cast<v4*>(&img[cur ^ 1][0][so]) = rv;
+            *reinterpret_cast<v4*>(&img[cur ^ 1][1][so]) = rs;
+        }
+        __syncthreads();
+    }
+    // lane holds t = t0 + wi*64 + y*16 + (lane & 15), k = k0 + wj*64 + x*16 + drow(lane >> 4, r)
+    double wt[FI];
+#pragma unroll
+    for (int y = 0; y < FI; ++y) wt[y] = g.w[t0 + wi * 64 + y * 16 + l15];
+#pragma unroll
+    for (int x = 0; x < FJ; ++x)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const long k = k0 + wj * 64 + x * 16 + Num<T>::drow(l4, r);
+            const double ak = (double)g.a[k];
+            T* cp = g.out + k * g.ldo + t0 + wi * 64 + l15;
+#pragma unroll
+            for (int y = 0; y < FI; ++y) cp[y * 16] = (T)(g.scale * ((double)acc[x][y][r] + wt[y] * ak));
+        }
+}
+
+// out(j, i) = in(i, j) for a square column-major matrix of n = 32 x gridDim.x rows (in: leading dimension ldi, out: ldo).
+// grid = (n / 32, n / 32), 256 threads.
+template <typename T>
+__global__ __launch_bounds__(256) void sparse_transpose_kernel(const T* __restrict__ in, long ldi, T* __restrict__ out, long ldo) {
+    __shared__ T t[32][33];
+    const int bi = blockIdx.x * 32, bj = blockIdx.y * 32, x = threadIdx.x & 31, y0 = threadIdx.x >> 5;
+    for (int y = y0; y < 32; y += 8) t[y][x] = in[(long)(bj + y) * ldi + bi + x];          // t[col][row]
+    __syncthreads();
+    for (int y = y0; y < 32; y += 8) out[(long)(bi + y) * ldo + bj + x] = t[x][y];          // element (bj + x, bi + y) <- (bi + y, bj + x)
 }
 
 }  // namespace gphip

@@ -1721,11 +1721,11 @@ bool queue_forward_fit(gphip_ctx* h, int64_t mpad) {
 }
 
 // V <- V L^-1 (backward substitution, block columns from last to first), "NN" GEMM role:
-//   X_b = Y_b W_b ;  Y_c -= X_b L(b,c) for c < b.   Two-level as above.
+//   X_b = Y_b W_b ;  Y_c -= X_b L(b,c) for c < b.   Two-level as above.  rows: the mpad x Npad block to work on (null: dV).
 template <typename T>
-int queue_backward_rows(gphip_ctx* h, int64_t mpad) {
+int queue_backward_rows(gphip_ctx* h, int64_t mpad, void* rows = nullptr) {
     const int Nt = (int)h->Nt, Mt = (int)(mpad / TB), P = (Mt >= 8 && h->panel_wide) ? std::max(h->panel, 12) : h->panel;
-    T *V = (T*)h->dV.p, *W = (T*)h->dW.p;
+    T *V = rows ? (T*)rows : (T*)h->dV.p, *W = (T*)h->dW.p;
     for (int k1 = Nt; k1 > 0; k1 -= P) {         // outer panel = tile columns [k0, k1)
         const int k0 = (k1 - P > 0) ? k1 - P : 0;
         for (int b = k1 - 1; b >= k0; --b) {

@@ -10,6 +10,12 @@
 //   b (a context of m points whose workspace is filled by hand)
 //        sparse_diag_kernel                tr(V V^T), then B = sn^2 I + V V^T
 //        queue_factor                      L_B, log det B, c = L_B^-1 V r in the rhs row, c^T c in the corner
+// Gradient (gphip_sparse_bound_grad, DESIGN.md section 8d): after that evaluation
+//   b    a = L_B^-T c, B^-1 by substitutions of identity rows, sparse_small_kernel: S = I / sn^2 - B^-1 and the inner matrix of H
+//   u    H by two backward substitutions around a transposition, queue_grad_full with Kinv := -2 H (the K_uu term)
+//        per chunk, as before: V (kept from the evaluation when the call has one chunk), w = (r - V^T a) / sn^2,
+//        sparse_weight_kernel T = -2 (V S + w a^T) into b's dV, queue_backward_rows on it (G = L_u^-T T), the rectangular
+//        gradient reduction (rows = the chunk's points, columns = Z) into the same accumulators, chunks in order
 // Prediction: v1 = L_u^-1 k(Z, x*) by u's forward substitution, v2 = L_B^-1 v1 by b's, predict_partial_kernel on both and one
 // finishing kernel.  Everything of one evaluation up to B runs on u's stream; b's stream takes over after a host synchronisation.
 #include "gp_sparse.h"
@@ -29,13 +35,17 @@ struct gphip_sparse_ctx {
     Buf dRz; int64_t rcap = 0;                 // typed [16][rcap]: row 0 = r of the current chunk, the other rows zero
     Buf dAccP;                                 // typed [strip][tile][128 x 128]: strip partials of the accumulation
     Buf dSum; std::vector<double> hSum;        // double: [0] tr(V V^T), then the per-block partial sums of r^2 and of k(x_i, x_i)
+    Buf dBc, dS, dH;                           // gradient, typed: B's tiles before its factorisation; S; the inner matrix of H (mpad x mpad)
+    Buf dGw;                                   // gradient, double: [0] tr B^-1, [1] a^T a, per-block sums of w, w of a chunk, strip partials of V^T a
     // options
     int chunk = 0, split = 0, profile = 0;
     // read-only results of the last call
     int last_nsplit = 0;
     int64_t last_chunk = 0;
     double last_jitter = 0.0;
-    double ms[5] = {0, 0, 0, 0, 0};            // K_uu factor, cross build, forward substitution, accumulation, B factor
+    int grad_analytic = 0;                     // the last gphip_sparse_bound_grad: 1 = the analytic route, 0 = central differences
+    double ms[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};        // K_uu factor, cross build, forward substitution, accumulation, B factor;
+                                               // gradient: small m x m work, weights, backward substitution, reductions
     // the resident fit
     bool fitted = false;
     double sn2_fit = 0, mu_fit = 0, kxx_fit = 0;
@@ -216,8 +226,147 @@ int sparse_mean_kzz(gphip_sparse_ctx* h, int64_t rows, double* out) {
     return GPHIP_OK;
 }
 
-// One evaluation: the bound (out, parts: null = not wanted) and the resident fit.
-int sparse_eval(gphip_sparse_ctx* h, const double* theta, int p, double jitter, double* out, double* parts, int* info) {
+// what the evaluation hands on to the gradient phase
+struct SparseGradIn {
+    const double* theta;
+    double sn2, mu, rtr, ctc, trvv, skk;
+    int64_t rows, nchunks;
+};
+
+// The gradient of the bound after a successful evaluation (u and b factored, both streams idle; the call's single chunk of V
+// still in u->dV when nchunks == 1).  grad: p derivatives in theta's layout.
+template <typename T>
+int sparse_grad_phase(gphip_sparse_ctx* h, const SparseGradIn& in, std::vector<SparsePhase>& recs, double* grad) {
+    gphip_ctx *u = h->u, *b = h->b;
+    const int64_t mpm = b->Npad;                // padded inducing points
+    const int Mt = (int)b->Nt;
+    const double sn2 = in.sn2;
+    int rc;
+    const size_t nblk = (size_t)(h->Npad / 256 + in.nchunks + 1);
+    HIPCHK(h->dS.grow((size_t)mpm * mpm * sizeof(T)));
+    HIPCHK(h->dH.grow((size_t)mpm * mpm * sizeof(T)));
+    HIPCHK(h->dGw.grow((2 + nblk + (size_t)in.rows * (1 + Mt)) * 8));
+    double* d_tr = h->dGw.as<double>();
+    double* d_ws = d_tr + 2;
+    double* d_w = d_ws + nblk;
+    double* d_vta = d_w + in.rows;
+    // ---- b: a, B^-1, S and the inner matrix of H
+    {
+        SparseScope ps(h, &recs, 5, b->stream);
+        b->cs = b->stream;
+        HIPCHK(b->dAlpha.grow((size_t)mpm * sizeof(T)));
+        if ((rc = queue_alpha<T>(b))) return sfail(h, rc, b->err);
+        int gx = (int)((mpm * mpm + 255) / 256);
+        if (gx > 4096) gx = 4096;
+        hipLaunchKernelGGL(identity_rows_kernel<T>, dim3(gx), dim3(256), 0, b->stream, (T*)b->dV.p, (long)mpm, (int)mpm, 0, (int)b->N);
+        queue_forward_rows<T>(b, mpm, 1, 0, true);
+        queue_backward_rows<T>(b, mpm);
+        hipLaunchKernelGGL(sparse_small_kernel<T>, dim3(gx), dim3(256), 0, b->stream, (const T*)b->dV.p, (long)mpm, (const T*)b->dAlpha.p,
+                           (const T*)h->dBc.p, (int)b->R, (int)b->N, (int)mpm, sn2, (T*)h->dS.p, (T*)h->dH.p);
+        hipLaunchKernelGGL(sparse_trace_kernel<T>, dim3(1), dim3(256), 0, b->stream, (const T*)b->dV.p, (long)mpm, (const T*)b->dAlpha.p,
+                           (int)b->N, d_tr);
+    }
+    if ((rc = complete_call(b))) return sfail(h, rc, b->err);
+    // ---- u: H = L_u^-T [..] L_u^-1 by two backward substitutions (the inner matrix is symmetric), then the K_uu term
+    u->cs = u->stream;
+    HIPCHK(u->dAlpha.grow((size_t)u->Npad * sizeof(T)));
+    HIPCHK(hipMemsetAsync(u->dAlpha.p, 0, (size_t)u->Npad * sizeof(T), u->stream));
+    if ((rc = ensure_gacc(u))) return sfail(h, rc, u->err);
+    HIPCHK(hipMemsetAsync(u->dGacc.p, 0, u->ngacc * 8, u->stream));
+    {
+        SparseScope ps(h, &recs, 5, u->stream);
+        queue_backward_rows<T>(u, mpm, h->dH.p);
+        hipLaunchKernelGGL(sparse_transpose_kernel<T>, dim3((unsigned)(mpm / 32), (unsigned)(mpm / 32)), dim3(256), 0, u->stream,
+                           (const T*)h->dH.p, (long)mpm, (T*)b->dV.p, (long)mpm);
+        queue_backward_rows<T>(u, mpm, b->dV.p);
+    }
+    {
+        SparseScope ps(h, &recs, 8, u->stream);
+        queue_grad_full<T>(u, b->dV.p, (long)mpm, nullptr);
+    }
+    // ---- the chunks of data points, in the evaluation's order
+    size_t used = 0;
+    for (int64_t c0 = 0; c0 < h->N; c0 += in.rows) {
+        const int64_t mc = std::min(in.rows, h->N - c0), mpad = (mc + TB - 1) / TB * TB;
+        const unsigned nb = (unsigned)((mpad + 255) / 256);
+        if (in.nchunks > 1) {
+            {
+                SparseScope ps(h, &recs, 1, u->stream);
+                if ((rc = sparse_load_points(h, h->dXt.p, h->Npad, c0, mpad))) return rc;
+                queue_cross<T>(u, mc, mpad, 1);
+            }
+            {
+                SparseScope ps(h, &recs, 2, u->stream);
+                queue_forward_fit(u, mpad);
+            }
+            sparse_queue_resid<T>(h, c0, mc, mpad, in.mu, h->dSum.as<double>() + 1);       // (its sums of r^2 are not read again)
+        }
+        {
+            SparseScope ps(h, &recs, 5, u->stream);
+            hipLaunchKernelGGL(sparse_vta_kernel<T>, dim3(nb, (unsigned)Mt), dim3(256), 0, u->stream, (const T*)u->dV.p, (long)mpad,
+                               (const T*)b->dAlpha.p, (int)mpad, d_vta);
+            hipLaunchKernelGGL(sparse_w_kernel<T>, dim3(nb), dim3(256), 0, u->stream, (const T*)h->dRz.p, (const double*)d_vta, Mt, (int)mc,
+                               (int)mpad, sn2, d_w, d_ws + used);
+        }
+        {
+            SparseScope ps(h, &recs, 6, u->stream);
+            SparseWeightArgs<T> g{};
+            g.V = (const T*)u->dV.p; g.ldv = (long)mpad;
+            g.S = (const T*)h->dS.p; g.lds = (long)mpm;
+            g.w = d_w; g.a = (const T*)b->dAlpha.p;
+            g.out = (T*)b->dV.p; g.ldo = (long)mpad;
+            g.mpad = (int)mpm; g.scale = -2.0;
+            hipLaunchKernelGGL(sparse_weight_kernel<T>, dim3((unsigned)(mpad / TB), (unsigned)Mt), dim3(256), 0, u->stream, g);
+        }
+        {
+            SparseScope ps(h, &recs, 7, u->stream);
+            queue_backward_rows<T>(u, mpad, b->dV.p);
+        }
+        {
+            SparseScope ps(h, &recs, 8, u->stream);
+            GradArgs<T> a = grad_args<T>(u, b->dV.p, (long)mpad, 0, mc);
+            a.xr = (const T*)u->dXsS.p; a.xr2 = (const T*)u->dXsS2.p; a.npad_r = (int)mpad;
+            launch_grad<T>(u, a, dim3((unsigned)(mpad / TB), (unsigned)u->Nt));
+            if (h->custom) {                   // - sum_i dk(x_i, x_i) / (2 sn^2): the dual-number program on the chunk's own points
+                GradArgs<T> dg = a;
+                dg.diag = 1; dg.wdiag = -1.0 / sn2;
+                launch_grad<T>(u, dg, dim3((unsigned)(mpad / TB), 1u));
+            }
+        }
+        used += nb;
+    }
+    std::vector<double> gacc(u->ngacc), hw(2 + used);
+    HIPCHK(hipMemcpyAsync(gacc.data(), u->dGacc.p, gacc.size() * 8, hipMemcpyDeviceToHost, u->stream));
+    HIPCHK(hipMemcpyAsync(hw.data(), h->dGw.p, hw.size() * 8, hipMemcpyDeviceToHost, u->stream));
+    if ((rc = complete_call(u))) return sfail(h, rc, u->err);
+    // ---- host: the diagonal term of a stationary family in closed form (weight -1 / sn^2 per point on the reductions' accumulators,
+    // every family is 1 at r = 0 and dg/dalpha is 0 there), the noise derivative, the chain rule, the mean
+    const int64_t d = h->d;
+    const double N = (double)h->N, m = (double)h->m;
+    if (!h->custom) {
+        const double* sp = u->hSlotp.as<double>();
+        const int op = u->ks.op;
+        const double wd = -N / sn2, k1 = sp[0], k2 = op != 0 ? sp[SP_SF2B] : 0.0;
+        gacc[(size_t)d] += wd * (op == 2 ? k2 : 1.0) * k1;
+        if (op != 0) gacc[(size_t)2 * d + 2] += wd * (op == 2 ? k1 : 1.0) * k2;
+        gacc[(size_t)2 * d + 5] += wd;
+    }
+    const double trbinv = hw[0], ata = hw[1];
+    const double dsn = -0.5 * (N - m + sn2 * trbinv) / sn2 + 0.5 * (in.rtr - in.ctc - sn2 * ata) / (sn2 * sn2) +
+                       (in.skk - in.trvv) / (2.0 * sn2 * sn2);
+    gacc[h->custom ? (size_t)u->ncp : (size_t)d + 1] = 2.0 * dsn;          // (the reductions' own diagonal slot was the jitter's derivative)
+    const int o = grad_chain_rule(u, in.theta, gacc, grad);
+    if (h->mean_id == GPHIP_MEAN_CONST) {
+        double sw = 0.0;
+        for (size_t k = 0; k < used; ++k) sw += hw[2 + k];
+        grad[o] = sw;
+    }
+    return GPHIP_OK;
+}
+
+// One evaluation: the bound (out, parts: null = not wanted) and the resident fit; grad (null = not wanted): the analytic gradient.
+int sparse_eval(gphip_sparse_ctx* h, const double* theta, int p, double jitter, double* out, double* parts, int* info,
+                double* grad = nullptr) {
     gphip_ctx *u = h->u, *b = h->b;
     if (p != u->p) return sfail(h, GPHIP_ERR_DIM, "theta has the wrong length for this kernel/mean");
     if (std::isnan(jitter) || std::isinf(jitter)) return sfail(h, GPHIP_ERR_ARG, "non-finite jitter");
@@ -228,8 +377,9 @@ int sparse_eval(gphip_sparse_ctx* h, const double* theta, int p, double jitter, 
         if (parts) for (int k = 0; k < 5; ++k) parts[k] = qnan;
         return GPHIP_OK;
     };
+    if (grad) for (int k = 0; k < p; ++k) grad[k] = qnan;
     h->fitted = false;
-    for (int k = 0; k < 5; ++k) h->ms[k] = 0.0;
+    for (double& v : h->ms) v = 0.0;
     for (int k = 0; k < p; ++k)
         if (!std::isfinite(theta[k])) return give_up(GPHIP_INFO_NAN);
     HIPCHK(hipSetDevice(h->device));
@@ -245,6 +395,17 @@ int sparse_eval(gphip_sparse_ctx* h, const double* theta, int p, double jitter, 
     int64_t rows = 0;
     const int64_t cap = h->chunk > 0 ? std::min<int64_t>(((int64_t)h->chunk + TB - 1) / TB * TB, h->Npad) : h->Npad;
     if ((rc = ensure_vchunk(u, cap, &rows))) { (void)hipGetLastError(); return sfail(h, rc, "no device memory for a chunk of V: " + u->err); }
+    if (grad) {
+        // the second m x rows buffer (the weights T; also the scratch of the m x m work) is b's dV: the rows are halved while both do not fit
+        rc = ensure_vbuf(b, std::max(rows, b->Npad));
+        while (rc == GPHIP_ERR_HIP && rows > 2048) {
+            (void)hipGetLastError();
+            rows = (rows / 2 + TB - 1) / TB * TB;
+            u->vcap = 0;                       // (u's V shrinks with it: ensure_vbuf frees and allocates again)
+            if (!(rc = ensure_vbuf(u, rows))) rc = ensure_vbuf(b, std::max(rows, b->Npad));
+        }
+        if (rc) { (void)hipGetLastError(); return sfail(h, rc, "no device memory for the gradient's weights: " + b->err); }
+    }
     h->last_chunk = rows;
     if (rows > h->rcap) {
         HIPCHK(h->dRz.grow((size_t)16 * rows * h->es));
@@ -318,6 +479,10 @@ int sparse_eval(gphip_sparse_ctx* h, const double* theta, int p, double jitter, 
         }
     }
     DISPATCH(h, sparse_queue_diag, h, sn2, d_tr);
+    if (grad) {                                // B itself, before its factorisation overwrites it (the B / (2 sn^2) term of H)
+        HIPCHK(h->dBc.grow((size_t)b->slot_elems * h->es));
+        HIPCHK(hipMemcpyAsync(h->dBc.p, b->dA.p, (size_t)b->slot_elems * h->es, hipMemcpyDeviceToDevice, u->stream));
+    }
     h->hSum.assign(1 + 2 * nblk, 0.0);
     HIPCHK(hipMemcpyAsync(h->hSum.data(), h->dSum.p, (1 + (h->custom ? 2 * nblk : nblk)) * 8, hipMemcpyDeviceToHost, u->stream));
     if ((rc = complete_call(u))) { sparse_harvest(h, recs); return sfail(h, rc, u->err); }      // (the forward substitutions' abort word)
@@ -325,8 +490,7 @@ int sparse_eval(gphip_sparse_ctx* h, const double* theta, int p, double jitter, 
         SparseScope ps(h, &recs, 4, b->stream);
         rc = sparse_factor(h, b, false, "sparse GP: the factorisation of B timed out (set option dataflow=0 and report)", &inf);
     }
-    sparse_harvest(h, recs);
-    if (rc) return rc;
+    if (rc) { sparse_harvest(h, recs); return rc; }
     const double logdet = b->hRes.as<double>()[0], ctc = b->hRes.as<double>()[1];
     double rtr = 0.0, skk = 0.0;
     for (size_t k = 0; k < used; ++k) rtr += h->hSum[1 + k];
@@ -341,7 +505,13 @@ int sparse_eval(gphip_sparse_ctx* h, const double* theta, int p, double jitter, 
     record_fit(b, *info == 0, thb, 3, logdet);
     h->fitted = *info == 0;
     h->sn2_fit = sn2; h->mu_fit = mu; h->kxx_fit = kxx;
-    return GPHIP_OK;
+    if (grad && *info == 0) {
+        const SparseGradIn in{theta, sn2, mu, rtr, ctc, trvv, skk, rows, nchunks};
+        rc = DISPATCH(h, sparse_grad_phase, h, in, recs, grad);
+        if (rc) for (int k = 0; k < p; ++k) grad[k] = qnan;
+    }
+    sparse_harvest(h, recs);
+    return rc;
 }
 
 int sparse_create(const void* X, const void* y, int64_t N, int64_t d, const void* Z, int64_t m, int kernel_id, const char* body, int ncp,
@@ -430,6 +600,51 @@ int gphip_sparse_bound(gphip_sparse_handle h, const double* theta, int p, double
     return sparse_eval(h, theta, p, jitter, out, parts, info);
 }
 
+int gphip_sparse_bound_grad(gphip_sparse_handle h, const double* theta, int p, double jitter, double* out, double* grad, double* parts,
+                            int* info) {
+    if (!h || !theta || !out || !grad || !info) return sfail(h, GPHIP_ERR_ARG, "null argument");
+    std::lock_guard<std::recursive_mutex> lk(h->mu);
+    gphip_ctx* u = h->u;
+    if (p != u->p) return sfail(h, GPHIP_ERR_DIM, "theta has the wrong length for this kernel/mean");
+    if (std::isnan(jitter) || std::isinf(jitter)) return sfail(h, GPHIP_ERR_ARG, "non-finite jitter");
+    h->grad_analytic = 0;
+    if (h->custom) {
+        if (const int rc = ensure_custom_grad(u)) return sfail(h, rc, u->err);
+    }
+    if (!h->custom || (u->custom_grad && u->cgrad_state == 1)) {
+        const int rc = sparse_eval(h, theta, p, jitter, out, parts, info, grad);
+        if (!rc && *info == 0) h->grad_analytic = 1;
+        return rc;
+    }
+    // No dual-number program (it does not compile, more than 64 parameters, option custom_grad = 0): central differences of the
+    // bound with gphip_loglik_grad's step, the jitter held at the unperturbed call's value.  The unperturbed evaluation comes last
+    // so that its fit stays resident; a default jitter (< 0) has to be found by an evaluation of its own first.
+    const double qnan = std::nan("");
+    for (int k = 0; k < p; ++k) grad[k] = qnan;
+    double jit = jitter;
+    int rc = GPHIP_OK;
+    if (jit < 0.0) {
+        if ((rc = sparse_eval(h, theta, p, jitter, out, nullptr, info))) return rc;
+        if (*info != 0) { if (parts) for (int k = 0; k < 5; ++k) parts[k] = qnan; return GPHIP_OK; }
+        jit = h->last_jitter;
+    }
+    std::vector<double> th(theta, theta + p), g((size_t)p, qnan);
+    for (int k = 0; k < p; ++k) {
+        const double step = fd_step(u, theta[k]);
+        double fp = 0.0, fm = 0.0;
+        int ip = 0, im = 0;
+        th[(size_t)k] = theta[k] + step;
+        if ((rc = sparse_eval(h, th.data(), p, jit, &fp, nullptr, &ip))) return rc;
+        th[(size_t)k] = theta[k] - step;
+        if ((rc = sparse_eval(h, th.data(), p, jit, &fm, nullptr, &im))) return rc;
+        th[(size_t)k] = theta[k];
+        if (ip == 0 && im == 0) g[(size_t)k] = (fp - fm) / (2.0 * step);
+    }
+    if ((rc = sparse_eval(h, theta, p, jitter, out, parts, info))) return rc;
+    if (*info == 0) for (int k = 0; k < p; ++k) grad[k] = g[(size_t)k];
+    return GPHIP_OK;
+}
+
 int gphip_sparse_fit(gphip_sparse_handle h, const double* theta, int p, double jitter, int* info) {
     if (!h || !theta || !info) return sfail(h, GPHIP_ERR_ARG, "null argument");
     std::lock_guard<std::recursive_mutex> lk(h->mu);
@@ -499,13 +714,15 @@ int gphip_sparse_set_option(gphip_sparse_handle h, const char* name, double valu
 int gphip_sparse_get_option(gphip_sparse_handle h, const char* name, double* value) {
     if (!h || !name || !value) return GPHIP_ERR_ARG;
     std::lock_guard<std::recursive_mutex> lk(h->mu);
-    static const char* const phases[5] = {"ms_kuu_factor", "ms_cross", "ms_forward", "ms_accumulate", "ms_b_factor"};
-    for (int k = 0; k < 5; ++k)
+    static const char* const phases[9] = {"ms_kuu_factor", "ms_cross", "ms_forward", "ms_accumulate", "ms_b_factor",
+                                          "ms_grad_small", "ms_grad_weights", "ms_grad_backward", "ms_grad_reduce"};
+    for (int k = 0; k < 9; ++k)
         if (!strcmp(name, phases[k])) { *value = h->ms[k]; return GPHIP_OK; }
     if (!strcmp(name, "sparse_chunk")) { *value = h->chunk; return GPHIP_OK; }
     if (!strcmp(name, "sparse_split")) { *value = h->split; return GPHIP_OK; }
     if (!strcmp(name, "profile")) { *value = h->profile; return GPHIP_OK; }
     if (!strcmp(name, "last_jitter")) { *value = h->last_jitter; return GPHIP_OK; }
+    if (!strcmp(name, "grad_analytic")) { *value = h->grad_analytic; return GPHIP_OK; }
     if (!strcmp(name, "last_sparse_chunk")) { *value = (double)h->last_chunk; return GPHIP_OK; }
     if (!strcmp(name, "last_sparse_nsplit")) { *value = h->last_nsplit; return GPHIP_OK; }
     const int rc = gphip_get_option(h->u, name, value);

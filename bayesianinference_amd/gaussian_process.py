@@ -838,9 +838,10 @@ def defineSparseGaussianProcess(data, kernel, inducing, nugget="Constant", meanF
     constant mean).  Extra rules: Jitter (default -1: the library's), Device, Precision, Seed (of the inducing-point choice).
     "LogLikelihoodFunction" of the returned object is the collapsed bound F(theta) <= log p(y | X, theta), so nestedSampling,
     laplace.selectHyperparameters(Criterion="MarginalLikelihood") and approximateEvidence run on it unchanged.
-    "LogLikelihoodGradientFunction" is a DIFFERENCE QUOTIENT: central differences of F with the step eps^(1/3) max(|theta_k|,
-    1e-2), 2p + 1 evaluations of the bound (the library has no analytic gradient of F).  Also carries "InducingPoints" and
-    "Jitter"; no leave-one-out keys."""
+    "LogLikelihoodGradientFunction" returns (F, dF/dtheta) from the device's analytic gradient (gphip_sparse_bound_grad: one
+    evaluation plus one more pass over the data, the jitter held fixed); rule Gradient="Differences" keeps the difference
+    quotient instead: central differences of F with the step eps^(1/3) max(|theta_k|, 1e-2), 2p + 1 evaluations of the bound.
+    Also carries "InducingPoints" and "Jitter"; no leave-one-out keys."""
     if normalizedDataQ(data) and isinstance(data, Mapping) and "Input" in data:
         rules.setdefault("DataPreProcessors", {k: {"Function": v["Function"], "InverseFunction": v["InverseFunction"]}
                                                for k, v in data.items()})
@@ -870,6 +871,9 @@ def defineSparseGaussianProcess(data, kernel, inducing, nugget="Constant", meanF
         raise ValueError('Precision must be "Double" or "Single"')
     jitter = float(rules.pop("Jitter", -1.0))
     seed = int(rules.pop("Seed", 0))
+    gradient = str(rules.pop("Gradient", "Analytic")).lower()
+    if gradient not in ("analytic", "differences"):
+        raise ValueError('Gradient must be "Analytic" or "Differences"')
     if isinstance(inducing, (int, np.integer)):
         Z = selectInducingPoints(X, int(inducing), seed)
     else:
@@ -885,6 +889,15 @@ def defineSparseGaussianProcess(data, kernel, inducing, nugget="Constant", meanF
     loglik = make_sparse_log_likelihood(handle, jitter)
 
     def log_likelihood_gradient(theta):
+        """(F, dF/dtheta) from the device (gphip_sparse_bound_grad; F is the value "LogLikelihoodFunction" returns); sentinel and
+        NaN gradient on numerical failure, like the exact object's."""
+        theta = np.asarray(theta, dtype=np.float64).ravel()
+        val, grad, info = handle.bound_grad(theta, jitter)
+        if info != 0 or not math.isfinite(val):
+            return MACHINE_LOG_ZERO, np.full(len(theta), np.nan)
+        return min(max(val, MACHINE_LOG_ZERO), -MACHINE_LOG_ZERO), grad
+
+    def log_likelihood_gradient_differences(theta):
         """(F, dF/dtheta) by central differences of the bound: a difference quotient, 2p + 1 bound evaluations, step
         eps^(1/3) max(|theta_k|, 1e-2).  Sentinel and NaN gradient on numerical failure."""
         theta = np.asarray(theta, dtype=np.float64).ravel()
@@ -919,7 +932,7 @@ def defineSparseGaussianProcess(data, kernel, inducing, nugget="Constant", meanF
             "HIPHandle": handle,
         },
         **rules,
-        "LogLikelihoodGradientFunction": log_likelihood_gradient,
+        "LogLikelihoodGradientFunction": log_likelihood_gradient if gradient == "analytic" else log_likelihood_gradient_differences,
         "LogLikelihoodFunction": loglik,
     })
 

@@ -41,28 +41,32 @@ def _prior_grad(logprior, theta, lo, hi, rel=1e-6):
     return g
 
 
-def _multi_start_minimum(fun, lo, hi, InitialGuess=None, Starts: int = 4, Seed: int = 0):
+def _multi_start_minimum(fun, lo, hi, InitialGuess=None, Starts: int = 4, Seed: int = 0, Tolerance=None):
     """The best L-BFGS-B minimum of fun (theta -> (value, gradient); 1e300 = the sentinel wall) over the box [lo, hi] from
-    InitialGuess, or from `Starts` random starts (log-uniform when the whole box is positive); None if no start ends finite."""
+    InitialGuess, or from `Starts` random starts (log-uniform when the whole box is positive); None if no start ends finite.
+    Tolerance: stop when the largest component of the projected gradient is at most this (and not on a small decrease of the
+    value); None keeps scipy's defaults."""
     from scipy.optimize import minimize
     rng = np.random.default_rng(Seed)
     starts = [np.asarray(InitialGuess, dtype=np.float64)] if InitialGuess is not None else \
         [np.exp(np.log(lo) + rng.random(len(lo)) * (np.log(hi) - np.log(lo))) if np.all(lo > 0)
          else lo + rng.random(len(lo)) * (hi - lo) for _ in range(max(1, Starts))]
     best = None
+    options = None if Tolerance is None else {"gtol": float(Tolerance), "ftol": 0.0}
     for x0 in starts:
-        res = minimize(fun, np.clip(x0, lo, hi), jac=True, method="L-BFGS-B", bounds=list(zip(lo, hi)))
+        res = minimize(fun, np.clip(x0, lo, hi), jac=True, method="L-BFGS-B", bounds=list(zip(lo, hi)), options=options)
         if math.isfinite(res.fun) and res.fun < 1e299 and (best is None or res.fun < best.fun):
             best = res
     return best
 
 
-def selectHyperparameters(obj, Criterion: str = "LeaveOneOut", InitialGuess=None, Starts: int = 4, Seed: int = 0):
+def selectHyperparameters(obj, Criterion: str = "LeaveOneOut", InitialGuess=None, Starts: int = 4, Seed: int = 0, Tolerance=None):
     """Point estimate of the hyper-parameters of a HIP-backed GP object over its parameter box, by multi-start L-BFGS-B with
     device gradients (one factorisation per step):
         Criterion="LeaveOneOut"          maximises the leave-one-out log pseudo-likelihood ("LogPseudoLikelihoodGradientFunction";
                                          R&W GPML 5.4.2: more robust than the evidence when the model is misspecified)
         Criterion="MarginalLikelihood"   maximises the log-likelihood ("LogLikelihoodGradientFunction"), no prior
+    Tolerance: L-BFGS-B stops when the largest component of the projected gradient is at most this (None: scipy's defaults).
     Returns {"Maximum": (value, theta), "Criterion": Criterion}; None for a failed object, an object without the closure, or
     when no start converges to a finite maximum."""
     key = {"leaveoneout": "LogPseudoLikelihoodGradientFunction", "marginallikelihood": "LogLikelihoodGradientFunction"}.get(
@@ -83,7 +87,7 @@ def selectHyperparameters(obj, Criterion: str = "LeaveOneOut", InitialGuess=None
             return 1e300, np.zeros_like(theta)               # the sentinel: a wall, never an exception
         return -v, -np.asarray(g, dtype=np.float64)
 
-    best = _multi_start_minimum(neg, lo, hi, InitialGuess, Starts, Seed)
+    best = _multi_start_minimum(neg, lo, hi, InitialGuess, Starts, Seed, Tolerance)
     if best is None:
         return None
     return {"Maximum": (-float(best.fun), np.clip(best.x, lo, hi)), "Criterion": Criterion}

@@ -485,13 +485,35 @@ int gphip_factor_bytes(gphip_handle h, int member, double* bytes);
  * (DESIGN.md section 8c).
  * Two calls with the same options return the same bytes (fixed-order reductions, no atomics).
  *
+ * gphip_sparse_bound_grad: the bound and its analytic gradient from one evaluation plus one more pass over the data.  grad has
+ * length p, theta's layout (the chain rule of gphip_loglik_grad); *out is the same bytes gphip_sparse_bound returns for the same
+ * arguments and options, parts as there (may be NULL), the fit stays resident, *info as there and grad is NaN when *info != 0;
+ * grad == NULL is GPHIP_ERR_ARG.  With a = L_B^-T c, w = (r - V^T a) / sn^2 and D = I / sn^2 - B^-1:
+ *
+ *     G = L_u^-T (D V + a w^T)                                            (m x N, streamed in the same chunks as V)
+ *     H = L_u^-T [ I - sn^2 B^-1 / 2 - a a^T / 2 - B / (2 sn^2) ] L_u^-1    (m x m)
+ *     dF/dtheta_q = sum_ki G_ki dk(z_k, x_i)/dtheta_q + sum_kl H_kl dk(z_k, z_l)/dtheta_q - sum_i dk(x_i, x_i)/dtheta_q / (2 sn^2)
+ *     dF/dsn = 2 sn [ -(N - m + sn^2 tr B^-1) / (2 sn^2) + (r^T r - c^T c - sn^2 a^T a) / (2 sn^4) + (sum_i k(x_i, x_i) - tr V V^T) / (2 sn^4) ]
+ *     dF/dmu = sum_i w_i
+ *
+ * THE JITTER IS HELD FIXED in the derivative: the gradient is that of F(theta; j) at the value the call used ("last_jitter"),
+ * also when j came from the default rule, which scales with k(x, x).  L_u^-1 and L_u^-T are applied as substitutions, never as
+ * products with an inverse of K_uu.  Two calls with the same options return the same bytes.  A run-time compiled kernel whose
+ * dual-number program does not compile, one with more than 64 parameters, and option "custom_grad" = 0 take central differences of
+ * the bound instead (2 p + 1 evaluations with gphip_loglik_grad's step, one more when the jitter is the default: it is found
+ * first and then held); *out is the unperturbed bound's bytes all the same.  Read-only option "grad_analytic": 1 / 0 = which route
+ * the last call took.  (When device memory is so short that the second m x chunk buffer forces a smaller chunk than
+ * gphip_sparse_bound would take, the two F differ by rounding.)
+ *
  * Options (gphip_sparse_set_option / gphip_sparse_get_option):
  *   "sparse_chunk"  data points per pass over V (rounded up to 128); 0 (default) = as many as keep the chunk of V within ~8 GiB,
  *                   at least 2048, halved while it does not fit.  "last_sparse_chunk" (read-only): what the last call used.
  *   "sparse_split"  strips the accumulation kernel cuts a chunk into; 0 (default) = by the split rule (output tiles x strips
  *                   >= two per CU).  "last_sparse_nsplit" (read-only): strips of the last chunk of the last call.
  *   "profile"       0 / 1: time the phases of gphip_sparse_bound / _fit with HIP events; read-only milliseconds of the last call:
- *                   "ms_kuu_factor", "ms_cross", "ms_forward", "ms_accumulate", "ms_b_factor".
+ *                   "ms_kuu_factor", "ms_cross", "ms_forward", "ms_accumulate", "ms_b_factor"; of gphip_sparse_bound_grad also
+ *                   "ms_grad_small" (the m x m work and the vector w), "ms_grad_weights" (sparse_weight_kernel alone),
+ *                   "ms_grad_backward", "ms_grad_reduce" (its second pass over the data adds to "ms_cross" and "ms_forward").
  *   every other name is handed on to the two contexts that factor K_uu and B (see gphip_set_option; e.g. "dataflow"). ---- */
 #define GPHIP_SPARSE_MAX_M 16384
 typedef struct gphip_sparse_ctx* gphip_sparse_handle;
@@ -503,6 +525,8 @@ int gphip_sparse_destroy(gphip_sparse_handle h);
 int gphip_sparse_set_inducing(gphip_sparse_handle h, const void* Z, int64_t m);
 int gphip_sparse_num_params(gphip_sparse_handle h, int* p);
 int gphip_sparse_bound(gphip_sparse_handle h, const double* theta, int p, double jitter, double* out, double* parts, int* info);
+int gphip_sparse_bound_grad(gphip_sparse_handle h, const double* theta, int p, double jitter, double* out, double* grad, double* parts,
+                            int* info);
 int gphip_sparse_fit(gphip_sparse_handle h, const double* theta, int p, double jitter, int* info);
 int gphip_sparse_predict(gphip_sparse_handle h, const void* Xs, int64_t M, int latent, double* mean, double* var);
 int gphip_sparse_set_option(gphip_sparse_handle h, const char* name, double value);
