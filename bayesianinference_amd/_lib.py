@@ -131,6 +131,7 @@ _SIGNATURES = {
     "gphip_sparse_num_params": (C.c_int, [_h, _ip]),
     "gphip_sparse_bound": (C.c_int, [_h, _dp, C.c_int, C.c_double, _dp, _dp, _ip]),
     "gphip_sparse_bound_grad": (C.c_int, [_h, _dp, C.c_int, C.c_double, _dp, _dp, _dp, _ip]),
+    "gphip_sparse_bound_grad_inducing": (C.c_int, [_h, _dp, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _ip]),
     "gphip_sparse_fit": (C.c_int, [_h, _dp, C.c_int, C.c_double, _ip]),
     "gphip_sparse_predict": (C.c_int, [_h, C.c_void_p, C.c_int64, C.c_int, _dp, _dp]),
     "gphip_sparse_set_option": (C.c_int, [_h, C.c_char_p, C.c_double]),
@@ -657,6 +658,7 @@ SPARSE_MAX_M = 16384
 SPARSE_PARTS = ("logdet_B", "ctc", "rtr", "tr_VVt", "sum_kxx")
 SPARSE_PHASES = ("ms_kuu_factor", "ms_cross", "ms_forward", "ms_accumulate", "ms_b_factor")
 SPARSE_GRAD_PHASES = ("ms_grad_small", "ms_grad_weights", "ms_grad_backward", "ms_grad_reduce")
+SPARSE_ZGRAD_PHASES = ("ms_grad_inducing",)
 
 
 class SparseHandle:
@@ -721,7 +723,8 @@ class SparseHandle:
         return v.value
 
     def set_inducing(self, Z):
-        """Replace the inducing points (any m); the resident fit is dropped."""
+        """Replace the inducing points (any m); the resident fit is dropped.  With an unchanged m the points are replaced in
+        place (no buffer, stream or compiled program is made again)."""
         Z = np.ascontiguousarray(np.atleast_2d(np.asarray(Z, dtype=np.float64)))
         if Z.shape[1] != self.d:
             raise GphipError(2, "inducing points and data differ in dimension")
@@ -750,6 +753,20 @@ class SparseHandle:
         out, info, grad = C.c_double(0.0), C.c_int(0), np.zeros(th.size)
         self._check(self._lib.gphip_sparse_bound_grad(self._h, _d(th), th.size, float(jitter), C.byref(out), _d(grad), None, C.byref(info)))
         return out.value, grad, info.value
+
+    def bound_grad_inducing(self, theta, jitter: float = -1.0, with_theta: bool = True):
+        """(F(theta), dF/dtheta or None, dF/dZ [m, d], info): the bound -- the same bytes as `bound` --, its gradient in theta
+        (the same bytes as `bound_grad`; None with with_theta=False, which skips those reductions) and its gradient in the
+        inducing locations, in the coordinates Z was given in, all from one pass; the jitter is held fixed.  The gradients are
+        NaN when info != 0.  Named and composed kernels only: a run-time compiled one raises GphipError (status 6).  The fit
+        stays resident."""
+        th = np.ascontiguousarray(np.asarray(theta, dtype=np.float64).ravel())
+        out, info = C.c_double(0.0), C.c_int(0)
+        grad = np.zeros(th.size) if with_theta else None
+        gz = np.zeros((self.m, self.d))
+        self._check(self._lib.gphip_sparse_bound_grad_inducing(self._h, _d(th), th.size, float(jitter), C.byref(out),
+                                                               _d(grad) if with_theta else None, _d(gz), None, C.byref(info)))
+        return out.value, grad, gz, info.value
 
     def fit(self, theta, jitter: float = -1.0) -> int:
         th = np.ascontiguousarray(np.asarray(theta, dtype=np.float64).ravel())

@@ -3313,6 +3313,23 @@ __global__ void identity_rows_kernel(T* __restrict__ V, long ldv, int npad, int 
     }
 }
 
+// The diagonal tiles L_bb of the factor in the tile-major workspace (R tile rows), one per workgroup, as [Nt][128 x 128]
+// column-major blocks with an explicit zero upper triangle -- the layout of the W_b; the workspace itself promises nothing
+// above a diagonal tile's diagonal.  (The refined diagonal solves of queue_backward_rows multiply by them.)
+template <typename T>
+__global__ __launch_bounds__(256) void diag_tiles_lower_kernel(const T* __restrict__ ws, int R, T* __restrict__ out) {
+    const int b = blockIdx.x;
+    const T* in = ws + tile_index(b, b, R) * TS;
+    T* o = out + (long)b * TS;
+    for (int e = threadIdx.x; e < (int)TS; e += 256) o[e] = ((e & (TB - 1)) >= (e >> 7)) ? in[e] : (T)0;     // row >= column
+}
+
+// x += r, elementwise over n elements
+template <typename T>
+__global__ void add_rows_kernel(T* __restrict__ x, const T* __restrict__ r, long n) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) x[i] += r[i];
+}
+
 
 // One 128 (rows of the block) x 128 (columns) tile per workgroup; thread = one row, 64 columns.
 template <typename T, int D, int KT>

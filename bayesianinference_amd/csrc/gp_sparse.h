@@ -7,6 +7,7 @@
 //   sparse_diag_kernel           tr(V V^T) from C's diagonal, then + sn^2 on it (identity on the pad)
 //   sparse_predict_finish_kernel mean and variance of a chunk of test points from the strip partials of v1 and v2
 //   sparse_small / _trace / _vta / _w / _weight / _transpose_kernel   the gradient of the bound, see the second half of this file
+//   sparse_zgrad_kernel / sparse_zgrad_finish_kernel   the gradient of the bound in the inducing LOCATIONS, see the end of this file
 #pragma once
 #include "gp_kernels.h"
 
@@ -481,6 +482,173 @@ __global__ __launch_bounds__(256) void sparse_transpose_kernel(const T* __restri
     for (int y = y0; y < 32; y += 8) t[y][x] = in[(long)(bj + y) * ldi + bi + x];          // t[col][row]
     __syncthreads();
     for (int y = y0; y < 32; y += 8) out[(long)(bi + y) * ldo + bj + x] = t[x][y];          // element (bj + x, bi + y) <- (bi + y, bj + x)
+}
+
+// ---------------------------------------------------------------------------------------------
+// The gradient of the bound in the inducing locations (gphip_sparse_bound_grad_inducing).  The weights are
+// the ones the theta reductions contract -- W = -2 G per chunk, W = -2 H once -- but the sums run per COLUMN (inducing point)
+// instead of over all entries:
+//     A_s(j, c) = sum_t (-W(t, j)) (dk/dk_s) sf_s^2 m2dg_s(r_s^2) u_sc,     u_sc = xs_s(t, c) - zs_s(j, c)   (scaled differences)
+// for term s of the covariance form, so that dF/dz_jc = scale sum_s A_s(j, c) / l_sc (scale = 1/2 for -2 G, 1 for -2 H: the sum
+// over the rows of -2 H is already the 2 sum_l H_kl term; the l = k entry contributes u = 0).  Contracting with the differences
+// and not with sum f x - z sum f keeps the cancellation out.
+//
+// One workgroup = one tile of 128 columns x one strip of rows, walked in slabs of 32 rows.  W is contiguous in t, the index the
+// threads do NOT own, so a slab of it goes through LDS: the staging reads 32 consecutive t (256 / 128 bytes) per column, lanes
+// along t, and stores the slab as [column][33]; thread (column jj, half) then reads its own row of the slab (stride 33 elements:
+// 32 lanes of an fp64 read, 64 lanes of an fp32 read fall on distinct banks) while the slab's points are LDS broadcasts (all lanes
+// read the same t) and the column points sit in LDS as [coordinate][128].  The two halves of the 256 threads take 16 rows of a
+// slab each and leave separate partials: no cross-lane reduction, no atomics, every sum in a fixed order.
+// DW = coordinates held per term (the tiles are zero-filled from d to DW: u = 0 there, no bounds test in the loops).  GLB: more than
+// KB_LDS_MAXD dimensions (two terms: more than 16) -- the points come from global memory as in grad_reduce_general_kernel and one launch covers the window
+// [d0, d0 + DW) of coordinates.  TWO: the covariance form has a second term (its accumulators exist only then).  Partials: part[(2 strip + half) nterm + s][mpad][d], fp64 whatever T is.
+// grid = (mpad / 128, strips).
+// ---------------------------------------------------------------------------------------------
+template <typename T>
+struct SparseZGradArgs {
+    const T* W; long ldw;              // W(t, j) at W[j ldw + t]
+    const T* xr; const T* xr2; int ldr;        // scaled row points [d][ldr] of term 1 / term 2
+    const T* zs; const T* zs2; int ldz;        // scaled column points (Z) [d][ldz]
+    int nrows, ncols, d, d0;
+    int strip_rows;                    // rows per strip (multiple of 32)
+    const double* slotp; KSpec ks;
+    double* part; int mpad;
+};
+
+constexpr int ZG_TR = 32;                      // rows per slab
+constexpr int ZG_PITCH = ZG_TR + 1;
+
+template <typename T, int DW, bool GLB> __host__ __device__ constexpr size_t sparse_zgrad_lds(int nterm) {
+    return ((size_t)TB * ZG_PITCH + (GLB ? 0 : (size_t)nterm * DW * (TB + ZG_TR))) * sizeof(T);
+}
+
+template <typename T, int DW, bool GLB, bool TWO>
+__global__ __launch_bounds__(256) void sparse_zgrad_kernel(SparseZGradArgs<T> a) {
+    extern __shared__ double lds_raw[];
+    constexpr bool two = TWO;                    // a second term (a.ks.op != 0)
+    constexpr int DW2 = TWO ? DW : 1;
+    const int d = a.d, d0 = GLB ? a.d0 : 0;
+    T* Ws = reinterpret_cast<T*>(lds_raw);       // [128][33] weight slab
+    T* zj1 = Ws + TB * ZG_PITCH;                 // [DW][128] column points, [DW][32] slab points; then the same for term 2
+    T* xt1 = zj1 + DW * TB;
+    T* zj2 = xt1 + DW * ZG_TR;
+    T* xt2 = zj2 + DW * TB;
+    const int tid = threadIdx.x, jj = tid & 127, half = tid >> 7;
+    const int j0 = blockIdx.x * TB, j = j0 + jj;
+    const long r0 = (long)blockIdx.y * a.strip_rows;
+    const long r1 = r0 + a.strip_rows < a.nrows ? r0 + a.strip_rows : a.nrows;
+    if (!GLB)
+        for (int idx = tid; idx < DW * TB; idx += 256) {
+            const int c = idx >> 7, q = idx & 127;
+            zj1[idx] = c < d ? a.zs[(long)c * a.ldz + j0 + q] : (T)0;
+            if (two) zj2[idx] = c < d ? a.zs2[(long)c * a.ldz + j0 + q] : (T)0;
+        }
+    const double* sp = a.slotp;
+    const double sf2a = sp[0], sf2b = two ? sp[SP_SF2B] : 0.0;
+    const T al1 = (T)sp[SP_ALPHA1], al2 = (T)sp[SP_ALPHA2];
+    double acc1[DW], acc2[DW2];
+#pragma unroll
+    for (int q = 0; q < DW; ++q) acc1[q] = 0.0;
+#pragma unroll
+    for (int q = 0; q < DW2; ++q) acc2[q] = 0.0;
+    const int st = tid & 31, sc = tid >> 5;      // staging: row st of the slab, columns sc, sc + 8, ..
+    for (long t0 = r0; t0 < r1; t0 += ZG_TR) {
+        __syncthreads();                         // (the previous slab has been read)
+        {
+            const bool in = t0 + st < a.nrows;
+            T v[16];
+#pragma unroll
+            for (int p = 0; p < 16; ++p) v[p] = in ? a.W[(long)(j0 + p * 8 + sc) * a.ldw + t0 + st] : (T)0;
+#pragma unroll
+            for (int p = 0; p < 16; ++p) Ws[(p * 8 + sc) * ZG_PITCH + st] = v[p];
+        }
+        if (!GLB)
+            for (int idx = tid; idx < DW * ZG_TR; idx += 256) {
+                const int c = idx >> 5, q = idx & 31;
+                const bool in = c < d && t0 + q < a.nrows;
+                xt1[idx] = in ? a.xr[(long)c * a.ldr + t0 + q] : (T)0;
+                if (two) xt2[idx] = in ? a.xr2[(long)c * a.ldr + t0 + q] : (T)0;
+            }
+        __syncthreads();
+        const int tl0 = half * (ZG_TR / 2);
+        const int left = (int)(r1 - t0);
+        const int tl1 = tl0 + ZG_TR / 2 < left ? tl0 + ZG_TR / 2 : left;
+        if (j >= a.ncols) continue;
+        for (int tl = tl0; tl < tl1; ++tl) {
+            T u1[DW], u2[DW2];
+            T r2a = (T)0, r2b = (T)0;
+            if (GLB) {
+                const long t = t0 + tl;
+                for (int c = 0; c < d; ++c) {
+                    const T u = a.xr[(long)c * a.ldr + t] - a.zs[(long)c * a.ldz + j];
+                    r2a += u * u;
+                }
+                if (two)
+                    for (int c = 0; c < d; ++c) {
+                        const T u = a.xr2[(long)c * a.ldr + t] - a.zs2[(long)c * a.ldz + j];
+                        r2b += u * u;
+                    }
+#pragma unroll
+                for (int q = 0; q < DW; ++q) {
+                    const bool in = d0 + q < d;
+                    u1[q] = in ? a.xr[(long)(d0 + q) * a.ldr + t] - a.zs[(long)(d0 + q) * a.ldz + j] : (T)0;
+                    if (two) u2[q] = in ? a.xr2[(long)(d0 + q) * a.ldr + t] - a.zs2[(long)(d0 + q) * a.ldz + j] : (T)0;
+                }
+            } else {
+#pragma unroll
+                for (int q = 0; q < DW; ++q) {
+                    u1[q] = xt1[q * ZG_TR + tl] - zj1[q * TB + jj];
+                    r2a += u1[q] * u1[q];
+                }
+                if (two) {
+#pragma unroll
+                    for (int q = 0; q < DW; ++q) {
+                        u2[q] = xt2[q * ZG_TR + tl] - zj2[q * TB + jj];
+                        r2b += u2[q] * u2[q];
+                    }
+                }
+            }
+            T g1, m1, da1, g2 = (T)0, m2 = (T)0, da2 = (T)0;
+            kfamily<T>(a.ks.fam1, r2a, al1, g1, m1, da1);
+            if (two) kfamily<T>(a.ks.fam2, r2b, al2, g2, m2, da2);
+            const double k1 = sf2a * (double)g1, k2 = sf2b * (double)g2;
+            const double dk1 = (a.ks.op == 2) ? k2 : 1.0, dk2 = (a.ks.op == 2) ? k1 : 1.0;       // dk/dk1, dk/dk2
+            const double w = -(double)Ws[jj * ZG_PITCH + tl];
+            const double f1 = w * dk1 * sf2a * (double)m1, f2 = w * dk2 * sf2b * (double)m2;
+#pragma unroll
+            for (int q = 0; q < DW; ++q) acc1[q] = __builtin_fma(f1, (double)u1[q], acc1[q]);
+            if (two) {
+#pragma unroll
+                for (int q = 0; q < DW; ++q) acc2[q] = __builtin_fma(f2, (double)u2[q], acc2[q]);
+            }
+        }
+    }
+    const int nterm = two ? 2 : 1;
+    const long md = (long)a.mpad * d;
+    double* p1 = a.part + (long)(2 * blockIdx.y + half) * nterm * md + (long)j * d + d0;
+#pragma unroll
+    for (int q = 0; q < DW; ++q)
+        if (d0 + q < d) {
+            p1[q] = acc1[q];
+            if (two) p1[md + q] = acc2[q];
+        }
+}
+
+// acc(j, c) += scale sum_s (sum over the nparts partials of A_s(j, c)) / l_sc, partials in order.  ie1 / ie2: 1 / l of the two terms [d].
+__global__ __launch_bounds__(256) void sparse_zgrad_finish_kernel(const double* __restrict__ part, int nparts, int nterm, long md, int d,
+                                                                  const double* __restrict__ ie1, const double* __restrict__ ie2, double scale,
+                                                                  double* __restrict__ acc) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= md) return;
+    const int c = (int)(idx % d);
+    double s1 = 0.0, s2 = 0.0;
+    for (int q = 0; q < nparts; ++q) {
+        s1 += part[(long)q * nterm * md + idx];
+        if (nterm == 2) s2 += part[((long)q * nterm + 1) * md + idx];
+    }
+    double v = s1 * ie1[c];
+    if (nterm == 2) v += s2 * ie2[c];
+    acc[idx] += scale * v;
 }
 
 }  // namespace gphip

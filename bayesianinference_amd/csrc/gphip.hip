@@ -1722,17 +1722,33 @@ bool queue_forward_fit(gphip_ctx* h, int64_t mpad) {
 
 // V <- V L^-1 (backward substitution, block columns from last to first), "NN" GEMM role:
 //   X_b = Y_b W_b ;  Y_c -= X_b L(b,c) for c < b.   Two-level as above.  rows: the mpad x Npad block to work on (null: dV).
+// Ld / res given: every diagonal solve is REFINED once in the working precision, X_b += (Y_b - X_b L_bb) W_b.  A product with
+// the explicit inverse W_b has a forward error of cond(L_bb) u but not the small residual of a substitution; one step restores
+// it (Skeel).  Ld: [Nt][128 x 128] scratch for the diagonal tiles with a zero upper triangle, res: mpad x 128 scratch.
 template <typename T>
-int queue_backward_rows(gphip_ctx* h, int64_t mpad, void* rows = nullptr) {
+int queue_backward_rows(gphip_ctx* h, int64_t mpad, void* rows = nullptr, void* Ld = nullptr, void* res = nullptr) {
     const int Nt = (int)h->Nt, Mt = (int)(mpad / TB), P = (Mt >= 8 && h->panel_wide) ? std::max(h->panel, 12) : h->panel;
-    T *V = rows ? (T*)rows : (T*)h->dV.p, *W = (T*)h->dW.p;
+    T *V = rows ? (T*)rows : (T*)h->dV.p, *W = (T*)h->dW.p, *L = (T*)Ld, *Rs = (T*)res;
+    const bool refine = L && Rs;
+    const long blk = (long)mpad * TB;            // elements of one block column of V
+    if (refine)
+        hipLaunchKernelGGL(diag_tiles_lower_kernel<T>, dim3((unsigned)Nt), dim3(256), 0, h->cs,
+                           (const T*)(h->ws_override ? h->ws_override : h->dA.p), (int)h->R, L);
     for (int k1 = Nt; k1 > 0; k1 -= P) {         // outer panel = tile columns [k0, k1)
         const int k0 = (k1 - P > 0) ? k1 - P : 0;
         for (int b = k1 - 1; b >= k0; --b) {
-            launch_gemm<T>(h, 6, cm<T>(V, mpad, 0), cm<T>(V + (long)b * TB * mpad, mpad, 0), cm<T>(W, TB, 0), TB, 0, Mt, b, b + 1, 0,
-                           1, 1);
+            T* Vb = V + (long)b * blk;
+            if (refine) HIPCHK(hipMemcpyAsync(Rs, Vb, (size_t)blk * sizeof(T), hipMemcpyDeviceToDevice, h->cs));
+            launch_gemm<T>(h, 6, cm<T>(V, mpad, 0), cm<T>(Vb, mpad, 0), cm<T>(W, TB, 0), TB, 0, Mt, b, b + 1, 0, 1, 1);
+            if (refine) {                       // res = Y_b - X_b L_bb ;  res <- res W_b ;  X_b += res
+                launch_gemm<T>(h, 6, cm<T>(Rs, mpad, 0), cm<T>(Vb, mpad, 0), cm<T>(L + (long)b * TS, TB, 0), TB, 0, Mt, 0, 1, 0, 1, 0);
+                launch_gemm<T>(h, 6, cm<T>(Rs, mpad, 0), cm<T>(Rs, mpad, 0), cm<T>(W + (long)b * TS, TB, 0), TB, 0, Mt, 0, 1, 0, 1, 1);
+                int gx = (int)((blk + 255) / 256);
+                if (gx > 2048) gx = 2048;
+                hipLaunchKernelGGL(add_rows_kernel<T>, dim3(gx), dim3(256), 0, h->cs, Vb, (const T*)Rs, blk);
+            }
             if (b > k0)                         // (the J operand is L(b, c) read transposed: tile (b, c) of the workspace)
-                launch_gemm<T>(h, 6, cm<T>(V, mpad, 0), cm<T>(V + (long)b * TB * mpad, mpad, 0), tl<T>(h, b, false), TB, 0, Mt, k0, b,
+                launch_gemm<T>(h, 6, cm<T>(V, mpad, 0), cm<T>(Vb, mpad, 0), tl<T>(h, b, false), TB, 0, Mt, k0, b,
                                0, 1, 0);
         }
         if (k0 > 0)                             // Y_c -= X[:, k0..k1) L(k0..k1, c) for every c < k0
@@ -2303,6 +2319,52 @@ int gphip_device_count(int* n) {
 
 const char* gphip_last_error(gphip_handle h) { return h ? h->err.c_str() : "null handle"; }
 
+// mid-range / half range of the training inputs xt [d][Npad] AS THE DEVICE HOLDS THEM (fp32 handles: rounded to float): what the
+// MFMA kernel build centres on and bounds its error with.  Non-finite inputs leave no centre (the direct form builds K).
+static int ctx_point_ranges(gphip_ctx* h, const std::vector<double>& xt) {
+    if (h->kernel_id == GPHIP_KERNEL_NULL || h->custom || mfma_family(h) < 0) return GPHIP_OK;
+    const int64_t d = h->d, N = h->N;
+    h->x_centre.assign((size_t)d, 0.0); h->x_half.assign((size_t)d, 0.0);
+    bool finite = true;
+    for (int64_t j = 0; j < d; ++j) {
+        double lo = 0.0, hi = 0.0;
+        for (int64_t i = 0; i < N; ++i) {
+            const double v = h->dtype == 64 ? xt[(size_t)j * h->Npad + i] : (double)(float)xt[(size_t)j * h->Npad + i];
+            if (i == 0 || v < lo) lo = v;
+            if (i == 0 || v > hi) hi = v;
+            if (!std::isfinite(v)) finite = false;
+        }
+        double c = 0.5 * lo + 0.5 * hi;
+        if (h->dtype == 32) c = (double)(float)c;
+        h->x_centre[(size_t)j] = c;
+        h->x_half[(size_t)j] = std::max(hi - c, c - lo);
+    }
+    if (finite) {
+        if (h->dCentre.grow((size_t)d * 8) != hipSuccess) return GPHIP_ERR_HIP;
+        if (hipMemcpyAsync(h->dCentre.p, h->x_centre.data(), (size_t)d * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+            hipStreamSynchronize(h->stream) != hipSuccess)
+            return GPHIP_ERR_HIP;
+    } else {
+        h->dCentre.release();
+    }
+    return GPHIP_OK;
+}
+
+// New training inputs X [N][d] for a context whose N, d, kernel and targets stay: the resident points and everything create_ctx
+// derives from them are replaced, buffers, streams, options and compiled programs are kept, the fit is dropped.
+static int ctx_replace_points(gphip_ctx* h, const double* X) {
+    if (!X) return GPHIP_ERR_ARG;
+    if (hipSetDevice(h->device) != hipSuccess) return GPHIP_ERR_HIP;
+    const int64_t N = h->N, d = h->d;
+    std::vector<double> xt((size_t)d * h->Npad, 0.0);
+    for (int64_t i = 0; i < N; ++i)
+        for (int64_t j = 0; j < d; ++j) xt[(size_t)j * h->Npad + i] = X[i * d + j];
+    invalidate_fit(h);
+    h->test_ratio = 0.0;
+    if (const int rc = DISPATCH(h, upload, h, h->dXt.p, xt, h->stream)) return rc;
+    return ctx_point_ranges(h, xt);
+}
+
 // one plain context on one device: data upload, streams, kernel attributes
 static int create_ctx(const void* X, const void* y, int64_t N, int64_t d, int kernel_id, int mean_id, int dtype,
                       int device /* < 0: current */, gphip_handle* out, const char* custom_body, int ncp, std::string* why) {
@@ -2411,30 +2473,7 @@ static int create_ctx(const void* X, const void* y, int64_t N, int64_t d, int ke
     }
     if (DISPATCH(h, upload, h, h->dXt.p, xt, h->stream) != GPHIP_OK) return bail(GPHIP_ERR_HIP);
     if (DISPATCH(h, upload, h, h->dY.p, yp, h->stream) != GPHIP_OK) return bail(GPHIP_ERR_HIP);
-    if (kernel_id != GPHIP_KERNEL_NULL && !custom_body && mfma_family(h) >= 0) {
-        // mid-range / half range of the inputs AS THE DEVICE HOLDS THEM (fp32 handles: rounded to float)
-        h->x_centre.assign((size_t)d, 0.0); h->x_half.assign((size_t)d, 0.0);
-        bool finite = true;
-        for (int64_t j = 0; j < d; ++j) {
-            double lo = 0.0, hi = 0.0;
-            for (int64_t i = 0; i < N; ++i) {
-                const double v = dtype == 64 ? xt[(size_t)j * h->Npad + i] : (double)(float)xt[(size_t)j * h->Npad + i];
-                if (i == 0 || v < lo) lo = v;
-                if (i == 0 || v > hi) hi = v;
-                if (!std::isfinite(v)) finite = false;
-            }
-            double c = 0.5 * lo + 0.5 * hi;
-            if (dtype == 32) c = (double)(float)c;
-            h->x_centre[(size_t)j] = c;
-            h->x_half[(size_t)j] = std::max(hi - c, c - lo);
-        }
-        if (finite) {
-            if (h->dCentre.grow((size_t)d * 8) != hipSuccess) return bail(GPHIP_ERR_HIP);
-            if (hipMemcpyAsync(h->dCentre.p, h->x_centre.data(), (size_t)d * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
-                hipStreamSynchronize(h->stream) != hipSuccess)
-                return bail(GPHIP_ERR_HIP);
-        }
-    }
+    if (const int rc = ctx_point_ranges(h, xt)) return bail(rc);
     if (DISPATCH(h, set_func_attrs, h) != GPHIP_OK) return bail(GPHIP_ERR_HIP);
     if (custom_body) {
         hipDeviceProp_t prop;

@@ -16,6 +16,9 @@
 //        per chunk, as before: V (kept from the evaluation when the call has one chunk), w = (r - V^T a) / sn^2,
 //        sparse_weight_kernel T = -2 (V S + w a^T) into b's dV, queue_backward_rows on it (G = L_u^-T T), the rectangular
 //        gradient reduction (rows = the chunk's points, columns = Z) into the same accumulators, chunks in order
+// Gradient in the inducing locations (gphip_sparse_bound_grad_inducing, DESIGN.md section 8e): the same pass; sparse_zgrad_kernel
+//   contracts -2 H (rows = Z) and every chunk's -2 G (rows = the chunk's points) per COLUMN with the coordinate differences,
+//   sparse_zgrad_finish_kernel adds the strip partials, H first and then chunk after chunk, into the m x d accumulator dZacc
 // Prediction: v1 = L_u^-1 k(Z, x*) by u's forward substitution, v2 = L_B^-1 v1 by b's, predict_partial_kernel on both and one
 // finishing kernel.  Everything of one evaluation up to B runs on u's stream; b's stream takes over after a host synchronisation.
 #include "gp_sparse.h"
@@ -36,6 +39,8 @@ struct gphip_sparse_ctx {
     Buf dAccP;                                 // typed [strip][tile][128 x 128]: strip partials of the accumulation
     Buf dSum; std::vector<double> hSum;        // double: [0] tr(V V^T), then the per-block partial sums of r^2 and of k(x_i, x_i)
     Buf dBc, dS, dH;                           // gradient, typed: B's tiles before its factorisation; S; the inner matrix of H (mpad x mpad)
+    Buf dLd, dRes;                             // refined backward substitutions with L_u: its diagonal tiles [Nt][128 x 128], one block column of residuals
+    Buf dZpart, dZacc;                         // gradient in Z, double: [part][term][mpad][d] strip partials; the [mpad][d] accumulator
     Buf dGw;                                   // gradient, double: [0] tr B^-1, [1] a^T a, per-block sums of w, w of a chunk, strip partials of V^T a
     // options
     int chunk = 0, split = 0, profile = 0;
@@ -44,8 +49,8 @@ struct gphip_sparse_ctx {
     int64_t last_chunk = 0;
     double last_jitter = 0.0;
     int grad_analytic = 0;                     // the last gphip_sparse_bound_grad: 1 = the analytic route, 0 = central differences
-    double ms[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};        // K_uu factor, cross build, forward substitution, accumulation, B factor;
-                                               // gradient: small m x m work, weights, backward substitution, reductions
+    double ms[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};    // K_uu factor, cross build, forward substitution, accumulation, B factor;
+                                               // gradient: small m x m work, weights, backward substitution, reductions, the reduction in Z
     // the resident fit
     bool fitted = false;
     double sn2_fit = 0, mu_fit = 0, kxx_fit = 0;
@@ -93,6 +98,15 @@ template <typename T>
 int sparse_func_attrs(gphip_sparse_ctx* h) {
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(sparse_accumulate_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)SPA_LDS));
+#define ZG_ATTR(DW)                                                                                                              \
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(sparse_zgrad_kernel<T, DW, false, false>),                          \
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)sparse_zgrad_lds<T, DW, false>(1)));             \
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(sparse_zgrad_kernel<T, DW, false, true>),                           \
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)sparse_zgrad_lds<T, DW, false>(2)));
+    ZG_ATTR(2) ZG_ATTR(4) ZG_ATTR(8) ZG_ATTR(16)
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(sparse_zgrad_kernel<T, 32, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)sparse_zgrad_lds<T, 32, false>(1)));
+#undef ZG_ATTR
     return GPHIP_OK;
 }
 
@@ -226,6 +240,53 @@ int sparse_mean_kzz(gphip_sparse_ctx* h, int64_t rows, double* out) {
     return GPHIP_OK;
 }
 
+// dZacc += scale x the column-wise contraction of the weight block W (nrows x u's columns, W(t, j) at W[j ldw + t]) whose rows are
+// the points xr / xr2 (scaled by term 1 / term 2, [d][ldr]).  Strips: whole slabs of 32 rows, strips x column tiles ~ 2 per CU.
+template <typename T>
+int sparse_queue_zgrad(gphip_sparse_ctx* h, const void* W, long ldw, const void* xr, const void* xr2, int64_t ldr, int64_t nrows, double scale) {
+    gphip_ctx* u = h->u;
+    SparseZGradArgs<T> a{};
+    a.W = (const T*)W; a.ldw = ldw;
+    a.xr = (const T*)xr; a.xr2 = (const T*)xr2; a.ldr = (int)ldr;
+    a.zs = (const T*)u->dXs.p; a.zs2 = (const T*)u->dXs2.p; a.ldz = (int)u->Npad;
+    a.nrows = (int)nrows; a.ncols = (int)u->N; a.d = (int)u->d; a.d0 = 0;
+    a.slotp = u->dSlotp.as<double>(); a.ks = u->ks;
+    a.mpad = (int)u->Npad;
+    const int Mt = (int)u->Nt, nterm = u->ks.op != 0 ? 2 : 1;
+    const int64_t nslabs = (nrows + ZG_TR - 1) / ZG_TR;
+    int64_t nstrips = std::min<int64_t>(nslabs, (2l * std::max(u->ncu, 1) + Mt - 1) / Mt);
+    const int64_t strip_slabs = (nslabs + nstrips - 1) / nstrips;
+    nstrips = (nslabs + strip_slabs - 1) / strip_slabs;
+    a.strip_rows = (int)(strip_slabs * ZG_TR);
+    const long md = (long)u->Npad * u->d;
+    HIPCHK(h->dZpart.grow((size_t)(2 * nstrips * nterm) * md * 8));
+    a.part = h->dZpart.as<double>();
+    const dim3 grid((unsigned)Mt, (unsigned)nstrips);
+    const int d = a.d;
+#define ZG_LAUNCH(DW)                                                                                                            \
+    do {                                                                                                                         \
+        if (nterm == 2) hipLaunchKernelGGL((sparse_zgrad_kernel<T, DW, false, true>), grid, dim3(256), (sparse_zgrad_lds<T, DW, false>(2)), u->stream, a); \
+        else hipLaunchKernelGGL((sparse_zgrad_kernel<T, DW, false, false>), grid, dim3(256), (sparse_zgrad_lds<T, DW, false>(1)), u->stream, a);           \
+    } while (0)
+    if (d <= 2) { ZG_LAUNCH(2); }
+    else if (d <= 4) { ZG_LAUNCH(4); }
+    else if (d <= 8) { ZG_LAUNCH(8); }
+    else if (d <= 16) { ZG_LAUNCH(16); }
+    else if (d <= KB_LDS_MAXD && nterm == 1)
+        hipLaunchKernelGGL((sparse_zgrad_kernel<T, 32, false, false>), grid, dim3(256), (sparse_zgrad_lds<T, 32, false>(1)), u->stream, a);
+    else                                       // (two terms beyond 16 dimensions: 2 x 32 accumulators would not stay in registers)
+                                               // the points from global memory, one launch per window of 16 coordinates
+        for (a.d0 = 0; a.d0 < d; a.d0 += 16) {
+            if (nterm == 2) hipLaunchKernelGGL((sparse_zgrad_kernel<T, 16, true, true>), grid, dim3(256), (sparse_zgrad_lds<T, 16, true>(2)), u->stream, a);
+            else hipLaunchKernelGGL((sparse_zgrad_kernel<T, 16, true, false>), grid, dim3(256), (sparse_zgrad_lds<T, 16, true>(1)), u->stream, a);
+        }
+#undef ZG_LAUNCH
+    hipLaunchKernelGGL(sparse_zgrad_finish_kernel, dim3((unsigned)((md + 255) / 256)), dim3(256), 0, u->stream, (const double*)a.part,
+                       (int)(2 * nstrips), nterm, md, d, (const double*)u->dInvEll.as<double>(),
+                       (const double*)(nterm == 2 ? u->dInvEll2.as<double>() : nullptr), scale, h->dZacc.as<double>());
+    return GPHIP_OK;
+}
+
 // what the evaluation hands on to the gradient phase
 struct SparseGradIn {
     const double* theta;
@@ -234,9 +295,10 @@ struct SparseGradIn {
 };
 
 // The gradient of the bound after a successful evaluation (u and b factored, both streams idle; the call's single chunk of V
-// still in u->dV when nchunks == 1).  grad: p derivatives in theta's layout.
+// still in u->dV when nchunks == 1).  grad: p derivatives in theta's layout (null: the reductions in theta are skipped);
+// gradZ: row-major m x d derivatives in the inducing locations (null: not wanted).
 template <typename T>
-int sparse_grad_phase(gphip_sparse_ctx* h, const SparseGradIn& in, std::vector<SparsePhase>& recs, double* grad) {
+int sparse_grad_phase(gphip_sparse_ctx* h, const SparseGradIn& in, std::vector<SparsePhase>& recs, double* grad, double* gradZ) {
     gphip_ctx *u = h->u, *b = h->b;
     const int64_t mpm = b->Npad;                // padded inducing points
     const int Mt = (int)b->Nt;
@@ -250,6 +312,16 @@ int sparse_grad_phase(gphip_sparse_ctx* h, const SparseGradIn& in, std::vector<S
     double* d_ws = d_tr + 2;
     double* d_w = d_ws + nblk;
     double* d_vta = d_w + in.rows;
+    // every backward substitution with L_u refines its diagonal solves (queue_backward_rows): G and H cancel in dF/dZ by up
+    // to 6e7, and a bare product with the explicit 128-block inverses costs it four digits at cond(K_uu) = 2e11
+    const int64_t rpad = std::max<int64_t>(mpm, (std::min<int64_t>(in.rows, h->N) + TB - 1) / TB * TB);
+    HIPCHK(h->dLd.grow((size_t)u->Nt * TS * sizeof(T)));
+    HIPCHK(h->dRes.grow((size_t)rpad * TB * sizeof(T)));
+    const size_t nz = (size_t)mpm * h->d;
+    if (gradZ) {
+        HIPCHK(h->dZacc.grow(nz * 8));
+        HIPCHK(hipMemsetAsync(h->dZacc.p, 0, nz * 8, u->stream));
+    }
     // ---- b: a, B^-1, S and the inner matrix of H
     {
         SparseScope ps(h, &recs, 5, b->stream);
@@ -275,14 +347,18 @@ int sparse_grad_phase(gphip_sparse_ctx* h, const SparseGradIn& in, std::vector<S
     HIPCHK(hipMemsetAsync(u->dGacc.p, 0, u->ngacc * 8, u->stream));
     {
         SparseScope ps(h, &recs, 5, u->stream);
-        queue_backward_rows<T>(u, mpm, h->dH.p);
+        if ((rc = queue_backward_rows<T>(u, mpm, h->dH.p, h->dLd.p, h->dRes.p))) return sfail(h, rc, u->err);
         hipLaunchKernelGGL(sparse_transpose_kernel<T>, dim3((unsigned)(mpm / 32), (unsigned)(mpm / 32)), dim3(256), 0, u->stream,
                            (const T*)h->dH.p, (long)mpm, (T*)b->dV.p, (long)mpm);
-        queue_backward_rows<T>(u, mpm, b->dV.p);
+        if ((rc = queue_backward_rows<T>(u, mpm, b->dV.p, h->dLd.p, h->dRes.p))) return sfail(h, rc, u->err);
     }
-    {
+    if (grad) {
         SparseScope ps(h, &recs, 8, u->stream);
         queue_grad_full<T>(u, b->dV.p, (long)mpm, nullptr);
+    }
+    if (gradZ) {                               // sum_l 2 H_lk dk(z_l, z_k)/dz_k: the rows are Z itself, nothing is halved
+        SparseScope ps(h, &recs, 9, u->stream);
+        if ((rc = sparse_queue_zgrad<T>(h, b->dV.p, (long)mpm, u->dXs.p, u->dXs2.p, mpm, u->N, 1.0))) return rc;
     }
     // ---- the chunks of data points, in the evaluation's order
     size_t used = 0;
@@ -320,9 +396,9 @@ int sparse_grad_phase(gphip_sparse_ctx* h, const SparseGradIn& in, std::vector<S
         }
         {
             SparseScope ps(h, &recs, 7, u->stream);
-            queue_backward_rows<T>(u, mpad, b->dV.p);
+            if ((rc = queue_backward_rows<T>(u, mpad, b->dV.p, h->dLd.p, h->dRes.p))) return sfail(h, rc, u->err);
         }
-        {
+        if (grad) {
             SparseScope ps(h, &recs, 8, u->stream);
             GradArgs<T> a = grad_args<T>(u, b->dV.p, (long)mpad, 0, mc);
             a.xr = (const T*)u->dXsS.p; a.xr2 = (const T*)u->dXsS2.p; a.npad_r = (int)mpad;
@@ -333,12 +409,19 @@ int sparse_grad_phase(gphip_sparse_ctx* h, const SparseGradIn& in, std::vector<S
                 launch_grad<T>(u, dg, dim3((unsigned)(mpad / TB), 1u));
             }
         }
+        if (gradZ) {                           // sum_i G_ki dk(z_k, x_i)/dz_k from -2 G: halved
+            SparseScope ps(h, &recs, 9, u->stream);
+            if ((rc = sparse_queue_zgrad<T>(h, b->dV.p, (long)mpad, u->dXsS.p, u->dXsS2.p, mpad, mc, 0.5))) return rc;
+        }
         used += nb;
     }
-    std::vector<double> gacc(u->ngacc), hw(2 + used);
+    std::vector<double> gacc(u->ngacc), hw(2 + used), zacc(gradZ ? nz : 0);
     HIPCHK(hipMemcpyAsync(gacc.data(), u->dGacc.p, gacc.size() * 8, hipMemcpyDeviceToHost, u->stream));
     HIPCHK(hipMemcpyAsync(hw.data(), h->dGw.p, hw.size() * 8, hipMemcpyDeviceToHost, u->stream));
+    if (gradZ) HIPCHK(hipMemcpyAsync(zacc.data(), h->dZacc.p, nz * 8, hipMemcpyDeviceToHost, u->stream));
     if ((rc = complete_call(u))) return sfail(h, rc, u->err);
+    if (gradZ) std::copy(zacc.begin(), zacc.begin() + (size_t)h->m * h->d, gradZ);
+    if (!grad) return GPHIP_OK;
     // ---- host: the diagonal term of a stationary family in closed form (weight -1 / sn^2 per point on the reductions' accumulators,
     // every family is 1 at r = 0 and dg/dalpha is 0 there), the noise derivative, the chain rule, the mean
     const int64_t d = h->d;
@@ -364,9 +447,10 @@ int sparse_grad_phase(gphip_sparse_ctx* h, const SparseGradIn& in, std::vector<S
     return GPHIP_OK;
 }
 
-// One evaluation: the bound (out, parts: null = not wanted) and the resident fit; grad (null = not wanted): the analytic gradient.
+// One evaluation: the bound (out, parts: null = not wanted) and the resident fit; grad (null = not wanted): the analytic gradient
+// in theta; gradZ (null = not wanted): the analytic gradient in the inducing locations, row-major m x d.
 int sparse_eval(gphip_sparse_ctx* h, const double* theta, int p, double jitter, double* out, double* parts, int* info,
-                double* grad = nullptr) {
+                double* grad = nullptr, double* gradZ = nullptr) {
     gphip_ctx *u = h->u, *b = h->b;
     if (p != u->p) return sfail(h, GPHIP_ERR_DIM, "theta has the wrong length for this kernel/mean");
     if (std::isnan(jitter) || std::isinf(jitter)) return sfail(h, GPHIP_ERR_ARG, "non-finite jitter");
@@ -378,6 +462,8 @@ int sparse_eval(gphip_sparse_ctx* h, const double* theta, int p, double jitter, 
         return GPHIP_OK;
     };
     if (grad) for (int k = 0; k < p; ++k) grad[k] = qnan;
+    if (gradZ) for (int64_t k = 0; k < h->m * h->d; ++k) gradZ[k] = qnan;
+    const bool wants_grad = grad || gradZ;
     h->fitted = false;
     for (double& v : h->ms) v = 0.0;
     for (int k = 0; k < p; ++k)
@@ -395,7 +481,7 @@ int sparse_eval(gphip_sparse_ctx* h, const double* theta, int p, double jitter, 
     int64_t rows = 0;
     const int64_t cap = h->chunk > 0 ? std::min<int64_t>(((int64_t)h->chunk + TB - 1) / TB * TB, h->Npad) : h->Npad;
     if ((rc = ensure_vchunk(u, cap, &rows))) { (void)hipGetLastError(); return sfail(h, rc, "no device memory for a chunk of V: " + u->err); }
-    if (grad) {
+    if (wants_grad) {
         // the second m x rows buffer (the weights T; also the scratch of the m x m work) is b's dV: the rows are halved while both do not fit
         rc = ensure_vbuf(b, std::max(rows, b->Npad));
         while (rc == GPHIP_ERR_HIP && rows > 2048) {
@@ -479,7 +565,7 @@ int sparse_eval(gphip_sparse_ctx* h, const double* theta, int p, double jitter, 
         }
     }
     DISPATCH(h, sparse_queue_diag, h, sn2, d_tr);
-    if (grad) {                                // B itself, before its factorisation overwrites it (the B / (2 sn^2) term of H)
+    if (wants_grad) {                          // B itself, before its factorisation overwrites it (the B / (2 sn^2) term of H)
         HIPCHK(h->dBc.grow((size_t)b->slot_elems * h->es));
         HIPCHK(hipMemcpyAsync(h->dBc.p, b->dA.p, (size_t)b->slot_elems * h->es, hipMemcpyDeviceToDevice, u->stream));
     }
@@ -505,10 +591,11 @@ int sparse_eval(gphip_sparse_ctx* h, const double* theta, int p, double jitter, 
     record_fit(b, *info == 0, thb, 3, logdet);
     h->fitted = *info == 0;
     h->sn2_fit = sn2; h->mu_fit = mu; h->kxx_fit = kxx;
-    if (grad && *info == 0) {
+    if (wants_grad && *info == 0) {
         const SparseGradIn in{theta, sn2, mu, rtr, ctc, trvv, skk, rows, nchunks};
-        rc = DISPATCH(h, sparse_grad_phase, h, in, recs, grad);
-        if (rc) for (int k = 0; k < p; ++k) grad[k] = qnan;
+        rc = DISPATCH(h, sparse_grad_phase, h, in, recs, grad, gradZ);
+        if (rc && grad) for (int k = 0; k < p; ++k) grad[k] = qnan;
+        if (rc && gradZ) for (int64_t k = 0; k < h->m * h->d; ++k) gradZ[k] = qnan;
     }
     sparse_harvest(h, recs);
     return rc;
@@ -585,7 +672,13 @@ int gphip_sparse_set_inducing(gphip_sparse_handle h, const void* Z, int64_t m) {
     if (!h || !Z) return sfail(h, GPHIP_ERR_ARG, "null argument");
     if (m < 1 || m > SPARSE_MAX_M) return sfail(h, GPHIP_ERR_DIM, "m < 1 or above GPHIP_SPARSE_MAX_M");
     std::lock_guard<std::recursive_mutex> lk(h->mu);
-    return sparse_make_children(h, static_cast<const double*>(Z), m);
+    if (m != h->m) return sparse_make_children(h, static_cast<const double*>(Z), m);
+    // the same number of inducing points: both contexts keep their buffers, streams, options and compiled programs; the points
+    // and what create_ctx derives from them are replaced, the fit is dropped
+    h->fitted = false;
+    for (gphip_ctx* c : {h->u, h->b})
+        if (const int rc = ctx_replace_points(c, static_cast<const double*>(Z))) return sfail(h, rc, "replacing the inducing points failed: " + c->err);
+    return GPHIP_OK;
 }
 
 int gphip_sparse_num_params(gphip_sparse_handle h, int* p) {
@@ -643,6 +736,20 @@ int gphip_sparse_bound_grad(gphip_sparse_handle h, const double* theta, int p, d
     if ((rc = sparse_eval(h, theta, p, jitter, out, parts, info))) return rc;
     if (*info == 0) for (int k = 0; k < p; ++k) grad[k] = g[(size_t)k];
     return GPHIP_OK;
+}
+
+int gphip_sparse_bound_grad_inducing(gphip_sparse_handle h, const double* theta, int p, double jitter, double* out, double* grad,
+                                     double* gradZ, double* parts, int* info) {
+    if (!h || !theta || !out || !gradZ || !info) return sfail(h, GPHIP_ERR_ARG, "null argument");
+    std::lock_guard<std::recursive_mutex> lk(h->mu);
+    if (p != h->u->p) return sfail(h, GPHIP_ERR_DIM, "theta has the wrong length for this kernel/mean");
+    if (std::isnan(jitter) || std::isinf(jitter)) return sfail(h, GPHIP_ERR_ARG, "non-finite jitter");
+    // (a run-time compiled function would need its dual-number program seeded in the coordinates: not built)
+    if (h->custom) return sfail(h, GPHIP_ERR_UNSUPPORTED, "no gradient in the inducing locations for a run-time compiled covariance function");
+    h->grad_analytic = 0;
+    const int rc = sparse_eval(h, theta, p, jitter, out, parts, info, grad, gradZ);
+    if (!rc && *info == 0 && grad) h->grad_analytic = 1;
+    return rc;
 }
 
 int gphip_sparse_fit(gphip_sparse_handle h, const double* theta, int p, double jitter, int* info) {
@@ -714,9 +821,9 @@ int gphip_sparse_set_option(gphip_sparse_handle h, const char* name, double valu
 int gphip_sparse_get_option(gphip_sparse_handle h, const char* name, double* value) {
     if (!h || !name || !value) return GPHIP_ERR_ARG;
     std::lock_guard<std::recursive_mutex> lk(h->mu);
-    static const char* const phases[9] = {"ms_kuu_factor", "ms_cross", "ms_forward", "ms_accumulate", "ms_b_factor",
-                                          "ms_grad_small", "ms_grad_weights", "ms_grad_backward", "ms_grad_reduce"};
-    for (int k = 0; k < 9; ++k)
+    static const char* const phases[10] = {"ms_kuu_factor", "ms_cross", "ms_forward", "ms_accumulate", "ms_b_factor",
+                                           "ms_grad_small", "ms_grad_weights", "ms_grad_backward", "ms_grad_reduce", "ms_grad_inducing"};
+    for (int k = 0; k < 10; ++k)
         if (!strcmp(name, phases[k])) { *value = h->ms[k]; return GPHIP_OK; }
     if (!strcmp(name, "sparse_chunk")) { *value = h->chunk; return GPHIP_OK; }
     if (!strcmp(name, "sparse_split")) { *value = h->split; return GPHIP_OK; }

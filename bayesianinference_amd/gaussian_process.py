@@ -799,8 +799,8 @@ def load_gaussian_process(path: str, variablePrior="Uniform", trust_kernel_sourc
 # ---------------------------------------------------------------------------------------------
 def selectInducingPoints(X, m: int, seed: int = 0):
     """m distinct rows of X, chosen by the counter-based generator of synthetic.py: a partial Fisher-Yates shuffle of the row
-    indices whose k-th swap partner comes from uniform k of stream STREAM_X at `seed`.  Deterministic; nothing cleverer
-    (optimising the inducing locations needs gradients of the bound, which the library does not have)."""
+    indices whose k-th swap partner comes from uniform k of stream STREAM_X at `seed`.  Deterministic; nothing cleverer: this
+    is the START of optimizeInducingPoints, which moves the locations along the gradient of the bound."""
     from . import synthetic
     X = np.atleast_2d(np.asarray(X, dtype=np.float64))
     n, m = len(X), int(m)
@@ -935,6 +935,69 @@ def defineSparseGaussianProcess(data, kernel, inducing, nugget="Constant", meanF
         "LogLikelihoodGradientFunction": log_likelihood_gradient if gradient == "analytic" else log_likelihood_gradient_differences,
         "LogLikelihoodFunction": loglik,
     })
+
+
+def optimizeInducingPoints(obj, theta, Joint: bool = False, MaxIterations: int = 200, Tolerance=None):
+    """Maximises the bound F of a sparse object over its inducing locations Z by L-BFGS-B with the device's gradient
+    (gphip_sparse_bound_grad_inducing): over Z alone at the given theta, or (Joint=True) over (theta, Z) with theta inside the
+    object's parameter box and Z unbounded.  Every evaluation is one set_inducing and one bound_grad_inducing; a failed one
+    (info != 0) is the 1e300 wall of laplace.selectHyperparameters.  The jitter is the object's "Jitter"; when that is the
+    default rule it is frozen at the value of the starting evaluation ("last_jitter"), so that the objective and the gradient
+    describe one function.  Tolerance: L-BFGS-B stops when the largest component of the projected gradient is at most this
+    (None: scipy's defaults).
+    Returns a new inferenceObject: "InducingPoints" replaced, the handle (shared with `obj`) left at the best Z found, and
+    "InducingOptimisation": {"Start": F0, "Maximum": F1, "Theta", "Iterations", "Evaluations", "Message"}; never a Z whose F is
+    below the start's.  ValueError for a run-time compiled kernel; None for an object that is not a sparse GP object or whose
+    starting evaluation fails."""
+    from scipy.optimize import minimize
+    if not isinstance(obj, inferenceObject) or obj.failed or "SparseGaussianProcessData" not in obj:
+        return None
+    if isinstance(obj["KernelName"], _lib.CustomKernel):
+        raise ValueError("a run-time compiled kernel has no gradient in the inducing locations")
+    handle = obj["SparseGaussianProcessData"]["HIPHandle"]
+    theta0 = np.asarray(theta, dtype=np.float64).ravel()
+    Z0 = np.array(obj["InducingPoints"], dtype=np.float64)
+    m, d = Z0.shape
+    p = len(theta0)
+    handle.set_inducing(Z0)
+    F0, _, _, info = handle.bound_grad_inducing(theta0, obj["Jitter"], with_theta=False)
+    if info != 0 or not math.isfinite(F0):
+        return None
+    jitter = float(obj["Jitter"]) if obj["Jitter"] >= 0.0 else handle.get_option("last_jitter")
+    if jitter != obj["Jitter"]:
+        F0 = handle.bound(theta0, jitter)[0]
+    best = {"F": F0, "theta": theta0.copy(), "Z": Z0.copy()}
+    count = [0]
+
+    def neg(x):
+        th = np.clip(x[:p], lo, hi) if Joint else theta0
+        Z = x[p if Joint else 0:].reshape(m, d)
+        count[0] += 1
+        handle.set_inducing(Z)
+        F, g, gz, info = handle.bound_grad_inducing(th, jitter, with_theta=Joint)
+        if info != 0 or not math.isfinite(F) or not np.all(np.isfinite(gz)) or (Joint and not np.all(np.isfinite(g))):
+            return 1e300, np.zeros_like(x)                    # the sentinel: a wall, never an exception
+        if F > best["F"]:
+            best.update(F=F, theta=np.array(th, dtype=np.float64), Z=Z.copy())
+        return -F, -(np.concatenate([g, gz.ravel()]) if Joint else gz.ravel())
+
+    options = {"maxiter": int(MaxIterations)}
+    if Tolerance is not None:
+        options.update(gtol=float(Tolerance), ftol=0.0)
+    if Joint:
+        lo = np.array([v[1] for v in obj["Parameters"]], dtype=np.float64)
+        hi = np.array([v[2] for v in obj["Parameters"]], dtype=np.float64)
+        x0 = np.concatenate([np.clip(theta0, lo, hi), Z0.ravel()])
+        bounds = list(zip(lo, hi)) + [(None, None)] * (m * d)
+    else:
+        lo = hi = None
+        x0, bounds = Z0.ravel(), None
+    res = minimize(neg, x0, jac=True, method="L-BFGS-B", bounds=bounds, options=options)
+    handle.set_inducing(best["Z"])                            # the handle is left at the best Z found (its fit is dropped)
+    msg = res.message.decode() if isinstance(res.message, bytes) else str(res.message)
+    return obj.append({"InducingPoints": best["Z"],
+                       "InducingOptimisation": {"Start": F0, "Maximum": best["F"], "Theta": best["theta"], "Iterations": int(res.nit),
+                                                "Evaluations": count[0], "Message": msg}})
 
 
 def predictFromSparseGaussianProcess(obj, pts, theta=None):

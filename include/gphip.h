@@ -505,6 +505,24 @@ int gphip_factor_bytes(gphip_handle h, int member, double* bytes);
  * the last call took.  (When device memory is so short that the second m x chunk buffer forces a smaller chunk than
  * gphip_sparse_bound would take, the two F differ by rounding.)
  *
+ * gphip_sparse_bound_grad_inducing: the bound, its gradient in theta and its gradient in the inducing LOCATIONS from the same pass.
+ * gradZ is row-major m x d, in the unscaled coordinates of Z as they were given:
+ *
+ *     dF/dz_k = sum_i G_ki dk(z_k, x_i)/dz_k + 2 sum_l H_kl dk(z_k, z_l)/dz_k                (a d-vector per inducing point)
+ *
+ * with G and H as above and, for one term k = sf^2 g(r^2), r^2 = sum_c ((a_c - b_c) / l_c)^2 of a named family,
+ * dk(a, b)/da_c = -sf^2 (-2 dg/dr^2) (a_c - b_c) / l_c^2 (finite at r = 0 for every family; the l = k term of the second sum is
+ * zero); sums and products of two terms by the product rule, each term with its own length scales.  sum_i k(x_i, x_i), the noise
+ * and the jitter do not depend on Z: the jitter is held fixed here as well.  *out is the same bytes gphip_sparse_bound returns;
+ * grad, when not NULL, the same bytes gphip_sparse_bound_grad returns (the new reduction only reads the weights G and H);
+ * grad == NULL skips the reductions in theta.  gradZ is all NaN when *info != 0; the fit stays resident.  Sums run in a fixed
+ * order without atomics: two calls with the same options return the same bytes.  NULL h / theta / out / gradZ / info and a
+ * non-finite jitter are GPHIP_ERR_ARG, a wrong p GPHIP_ERR_DIM, and a run-time compiled covariance function is
+ * GPHIP_ERR_UNSUPPORTED: it would need its dual-number program seeded in the coordinates, which is not built.
+ * gphip_sparse_set_inducing with an unchanged m replaces the points in place (same buffers, options and compiled programs, fit
+ * dropped); every later result is the same bytes as that of a fresh object created with the new Z.  A changed m recreates the
+ * two contexts.
+ *
  * Options (gphip_sparse_set_option / gphip_sparse_get_option):
  *   "sparse_chunk"  data points per pass over V (rounded up to 128); 0 (default) = as many as keep the chunk of V within ~8 GiB,
  *                   at least 2048, halved while it does not fit.  "last_sparse_chunk" (read-only): what the last call used.
@@ -514,6 +532,7 @@ int gphip_factor_bytes(gphip_handle h, int member, double* bytes);
  *                   "ms_kuu_factor", "ms_cross", "ms_forward", "ms_accumulate", "ms_b_factor"; of gphip_sparse_bound_grad also
  *                   "ms_grad_small" (the m x m work and the vector w), "ms_grad_weights" (sparse_weight_kernel alone),
  *                   "ms_grad_backward", "ms_grad_reduce" (its second pass over the data adds to "ms_cross" and "ms_forward").
+ *                   of gphip_sparse_bound_grad_inducing also "ms_grad_inducing" (the column-wise reductions for dF/dZ).
  *   every other name is handed on to the two contexts that factor K_uu and B (see gphip_set_option; e.g. "dataflow"). ---- */
 #define GPHIP_SPARSE_MAX_M 16384
 typedef struct gphip_sparse_ctx* gphip_sparse_handle;
@@ -527,6 +546,8 @@ int gphip_sparse_num_params(gphip_sparse_handle h, int* p);
 int gphip_sparse_bound(gphip_sparse_handle h, const double* theta, int p, double jitter, double* out, double* parts, int* info);
 int gphip_sparse_bound_grad(gphip_sparse_handle h, const double* theta, int p, double jitter, double* out, double* grad, double* parts,
                             int* info);
+int gphip_sparse_bound_grad_inducing(gphip_sparse_handle h, const double* theta, int p, double jitter, double* out,
+                                     double* grad /* p, may be NULL */, double* gradZ /* row-major m x d */, double* parts, int* info);
 int gphip_sparse_fit(gphip_sparse_handle h, const double* theta, int p, double jitter, int* info);
 int gphip_sparse_predict(gphip_sparse_handle h, const void* Xs, int64_t M, int latent, double* mean, double* var);
 int gphip_sparse_set_option(gphip_sparse_handle h, const char* name, double value);
