@@ -87,7 +87,7 @@ struct gphip_ctx {
     size_t es = 8;                     // element size of the device arithmetic type
     hipStream_t stream = nullptr;      // main stream: build, trailing updates, copies
     hipStream_t pstream = nullptr;     // panel stream (high priority): look-ahead panel factorisation
-    hipStream_t cs = nullptr;          // stream the launch helpers currently target
+    hipStream_t cs = nullptr;          // stream the launch helpers target: == stream, except inside a Scoped block (panel stream)
     std::vector<hipEvent_t> sync_events;
     size_t sync_used = 0;
     int dist_first_factored = -1;                // sharded evaluation: outer panel whose first diagonal block the last LA update factored
@@ -118,16 +118,14 @@ struct gphip_ctx {
     int dist_df_mode = 0;                        // .. and which form (dist_panel_df resolved: 0, 1, 2, 3; readable as option last_dist_panel_df)
     int bcast_two_hop = -1;                      // sharded evaluation over RCCL, world > 2: every broadcast as scatter (send / recv) + in-place all-gather;
                                                  // -1 (default) = on from 4 ranks when the loaded RCCL has send / recv / group calls (two_hop_ok)
-    std::vector<hipEvent_t>* col_events = nullptr;   // queue_panel: record "tile column final" events here (owner of a sharded panel)
+    std::vector<hipEvent_t>* col_events = nullptr;   // queue_panel: record "tile column final" events here (owner of a sharded panel; per call, Scoped)
     // dist_panel_df = 3: a dataflow panel launch counts finished tiles per tile column (DfArgs::colsig); the owner's communication
     // stream waits for a column's count with hipStreamWaitValue32.  Counters are cumulative over the panels of one evaluation
     // (zeroed in gphip_dist_begin): the target of a wait = everything counted before + the column's own tiles.
     Buf dColSig;                                     // unsigned int [64] counters (the first `panel` are used)
     unsigned int colsig_target[64] = {0};
-    std::vector<std::pair<unsigned int*, unsigned int>>* col_waits = nullptr;   // where gphip_dist_factor_panel reports (address, target) per tile column
+    std::vector<std::pair<unsigned int*, unsigned int>>* col_waits = nullptr;   // where gphip_dist_factor_panel reports (address, target) per tile column (per call, Scoped)
     int fuse_potrf = 1;                          // option: panel-stream updates factor the diagonal tile they have just updated
-    int fuse_b = -1;                             // launch_gemm: request (tile to factor) ...
-    bool fuse_done = false;                      // ... and answer (the launch took it)
     int dataflow_occ3 = -1;                      // 64-tile kernel built for three workgroups per CU: -1 auto (>= 8 000 tasks), 0 never, 1 always
     static constexpr int dataflow_park = 1;      // 64-tile dataflow, two workgroups per CU: park the neighbour of a chain task (round 5 retune: never worse)
     int dataflow_lds_kib = -1;                   // LDS request of the 64-tile dataflow kernel (> 80: ONE workgroup per CU); -1 auto, 0 off
@@ -251,7 +249,7 @@ struct gphip_ctx {
     int last_issue_us = 0;                       // read-only: host microseconds the last sharded evaluation spent issuing its schedule
     int debug_fail_hip = 0;                      // tests: make the n-th checked HIP call of the next collective sequence fail
     int fit_rank = 0, fit_world = 0;             // the layout a distributed fit was made in
-    bool in_group_call = false;                  // set on a member while the group handle runs a sharded call on it
+    bool in_group_call = false;                  // set (Scoped) on a member while the group handle runs a sharded call on it
     // Sharded evaluation (gphip_dist_*): where this rank keeps ITS outer panels.  replicate_factor = 0 (default): a
     // compact buffer holding only the owned panels (+ the corner tile on rank 0) -- memory per rank ~ 1 / world of the
     // workspace; 1: the dense workspace dA (every received panel is received in place: all ranks end up with all of L).
@@ -262,13 +260,13 @@ struct gphip_ctx {
     std::vector<long> dist_adj;                  // [nouter + 1] tiles to add to a dense tile index of panel slot q (owned slots)
     Buf dDistAdj;                                // long: device copy; null while every entry is 0 (dense)
     int lay_rank = -1, lay_world = 0, lay_panel = 0, lay_full = -1;   // what dist_adj / dOwn were laid out for
-    void* ws_override = nullptr;                 // tl<T>() / queue_panel address this base instead of dA (one owned panel)
+    void* ws_override = nullptr;                 // tl<T>() / queue_panel address this base instead of dA (one owned panel; per call, Scoped)
     bool dist_fit = false;                       // the factor of theta_fit is spread over the ranks (owned panels only)
     Buf dZ;                                      // typed [Npad]: z = L^-1 r gathered while the panels stream by (sharded prediction)
-    bool z_vector = false;                       // the prediction epilogue reads z from dZ (set only inside predict_streamed)
     bool null_fit = false;                       // fitted state of a null-kernel handle (no factor: K = diag(sn^2))
     // Point-dependent nugget / mean of the CURRENT call (gphip_*_pw, BGP:37, 113, 300, 408): host rows [B][N] (training
-    // points) and [S][M] (test points), null = the constant forms; device copies per workspace slot / prediction chunk
+    // points) and [S][M] (test points), null = the constant forms; device copies per workspace slot / prediction chunk.
+    // Installed by PwScope only (the call's arrays, or a group member's slice of them).
     const double *pw_mean_host = nullptr, *pw_nug_host = nullptr;
     const double *pw_mean_test = nullptr, *pw_nug_test = nullptr;
     long pw_test_stride = 0;                     // elements between the samples' rows of pw_*_test
@@ -320,6 +318,18 @@ void stamp_fit(gphip_ctx* h);
 void record_fit(gphip_ctx* h, bool ok, const double* theta, int p, double logdet);
 bool has_fit(const gphip_ctx* h) { return h->fitted && h->fit_gen == h->ws_gen; }
 
+// A context field that is an argument of the call in progress (cs, ws_override, col_events, ..): set for the length of a block,
+// the old value back on every exit path.
+template <typename T>
+struct Scoped {
+    T& ref;
+    const T old;
+    Scoped(T& r, T v) : ref(r), old(r) { ref = v; }
+    ~Scoped() { ref = old; }
+    Scoped(const Scoped&) = delete;
+    Scoped& operator=(const Scoped&) = delete;
+};
+
 struct FactorMode {                            // what the next factorisation leaves for its caller: set here, restored on every exit path
     gphip_ctx* h;
     const bool w, u;
@@ -327,6 +337,18 @@ struct FactorMode {                            // what the next factorisation le
     ~FactorMode() { h->want_w = w; h->want_u = u; }
     FactorMode(const FactorMode&) = delete;
     FactorMode& operator=(const FactorMode&) = delete;
+};
+
+// The point-dependent nugget / mean arrays of the current call (gphip_*_pw), or a group member's slice of them: installed here,
+// what was there before comes back on every exit path.
+struct PwScope {
+    gphip_ctx* h;
+    Scoped<const double*> mt, nt, ms, ns;
+    Scoped<long> stride;
+    PwScope(gphip_ctx* h_, const double* mt_, const double* nt_, const double* ms_, const double* ns_, long stride_)
+        : h(h_), mt(h_->pw_mean_host, mt_), nt(h_->pw_nug_host, nt_), ms(h_->pw_mean_test, ms_), ns(h_->pw_nug_test, ns_),
+          stride(h_->pw_test_stride, stride_) {}
+    ~PwScope() { h->pw_mean_on = h->pw_nug_on = false; }
 };
 
 double pivot_tol_rel(const gphip_ctx* h) {
@@ -647,9 +669,11 @@ Opnd<T> tl(const gphip_ctx* h, int k0 = 0, bool all_slots = true) {
 template <typename T>
 size_t potrf_lds();
 
+// fuse_b >= 0: a panel-stream update asked to factor the diagonal tile (fuse_b, fuse_b) it completes (queue_panel / queue_factor /
+// gphip_dist_update).  Returns whether the launch took that on (256-thread shape only).
 template <typename T>
-void launch_gemm(gphip_ctx* h, int cls, Opnd<T> Co, Opnd<T> Ao, Opnd<T> Bo, int K, int r0, int r1, int c0, int c1, int tri,
-                 int nslots, int mode = 0, int ktri = 0, int thin_row = -1, int groups = 1, int grp_stride = 0,
+bool launch_gemm(gphip_ctx* h, int cls, Opnd<T> Co, Opnd<T> Ao, Opnd<T> Bo, int K, int r0, int r1, int c0, int c1, int tri,
+                 int nslots, int mode = 0, int ktri = 0, int thin_row = -1, int fuse_b = -1, int groups = 1, int grp_stride = 0,
                  int grp_width = 0) {
     GemmArgs<T> g{};
     g.grp_stride = groups > 1 ? grp_stride : 0;
@@ -668,7 +692,7 @@ void launch_gemm(gphip_ctx* h, int cls, Opnd<T> Co, Opnd<T> Ao, Opnd<T> Bo, int 
     g.B = Bo.p; g.ldb = Bo.ld; g.b_bstride = Bo.bs; g.b_R = Bo.R; g.b_k0 = Bo.k0;
     g.K = K; g.r0 = r0; g.r1 = r1; g.c0 = c0; g.c1 = c1; g.tri = tri;
     const int H = r1 - r0, W = c1 - c0;
-    if (H <= 0 || W <= 0) return;
+    if (H <= 0 || W <= 0) return false;
     if (!tri) {
         g.nrect = H * W;
         g.ntiles = H * W;
@@ -727,18 +751,13 @@ void launch_gemm(gphip_ctx* h, int cls, Opnd<T> Co, Opnd<T> Ao, Opnd<T> Bo, int 
     // (measured: -8 % per evaluation at N=4096, neutral at 8192, +5 % at 32768 where its 147 KB of LDS keeps
     //  trailing-SYRK workgroups off the CU -- so it is used for small problems only)
     const bool lat = h->latency_gemm && !g.super && h->Nt <= h->latency_max_nt && (long)grid_x * nslots <= h->latency_tiles;
-    // a panel-stream update asked to factor the diagonal tile it updates (queue_panel / queue_factor): 256-thread shape only
     g.fuse_b = -1;
-    h->fuse_done = false;
     size_t lds2 = GEMM_LDS;
-    if (h->fuse_b >= 0 && cls == 3 && mode == 0 && !lat && !ktri && groups == 1 && tri && h->fuse_b >= c0 && h->fuse_b < c1 &&
-        h->fuse_b >= r0) {
-        g.fuse_b = h->fuse_b;
+    if (fuse_b >= 0 && cls == 3 && mode == 0 && !lat && !ktri && groups == 1 && tri && fuse_b >= c0 && fuse_b < c1 && fuse_b >= r0) {
+        g.fuse_b = fuse_b;
         g.fuse_W = (T*)h->dW.p; g.fuse_partial = h->dPartial.as<double>(); g.fuse_info = h->dInfo.as<int>(); g.fuse_slotp = h->dSlotp.as<double>(); g.fuse_nt = (int)h->Nt;
         lds2 = std::max(lds2, potrf_lds<T>());
-        h->fuse_done = true;
     }
-    h->fuse_b = -1;
 #define GEMM_LAUNCH(ROLE)                                                                                          \
     do {                                                                                                           \
         if (lat) hipLaunchKernelGGL((gemm_nt_kernel<T, ROLE, 4, 4, 4>), grid, dim3(1024), 2 * GEMM_LDS, h->cs, g);  \
@@ -750,6 +769,7 @@ void launch_gemm(gphip_ctx* h, int cls, Opnd<T> Co, Opnd<T> Ao, Opnd<T> Bo, int 
     else if (g.fuse_b >= 0) hipLaunchKernelGGL((gemm_nt_kernel<T, 4, 2, 2, 2>), grid, dim3(256), lds2, h->cs, g);
     else GEMM_LAUNCH(1);
 #undef GEMM_LAUNCH
+    return g.fuse_b >= 0;
 }
 
 hipEvent_t sync_event(gphip_ctx* h) {       // untimed events for cross-stream ordering
@@ -786,11 +806,8 @@ int queue_panel(gphip_ctx* h, int K0, int nin, int nslots, bool first_factored =
     bool factored = first_factored;
     for (int s = 0; s < nin; ++s) {
         const int b = K0 + s;
-        if (left && s > 0) {
-            if (fuse) h->fuse_b = b;
-            launch_gemm<T>(h, 3, tl<T>(h), tl<T>(h, K0), tl<T>(h, K0), s * TB, b, R, b, b + 1, 1, nslots, 0, 0, Nt);
-            factored = h->fuse_done;
-        }
+        if (left && s > 0)
+            factored = launch_gemm<T>(h, 3, tl<T>(h), tl<T>(h, K0), tl<T>(h, K0), s * TB, b, R, b, b + 1, 1, nslots, 0, 0, Nt, fuse ? b : -1);
         if (!factored) {
             ProfScope ps(h, 1, 2.0 * TB * TB * TB / 3.0 * nslots, 0.0);
             hipLaunchKernelGGL(potrf128_kernel<T>, dim3(nslots), dim3(256), potrf_lds<T>(), h->cs, A, bs, b, W,
@@ -804,11 +821,9 @@ int queue_panel(gphip_ctx* h, int K0, int nin, int nslots, bool first_factored =
             HIPCHK(hipEventRecord(e, h->cs));
             h->col_events->push_back(e);
         }
-        if (!left && s + 1 < nin) {
-            if (fuse) h->fuse_b = b + 1;
-            launch_gemm<T>(h, 3, tl<T>(h), tl<T>(h, b), tl<T>(h, b), TB, b + 1, R, b + 1, K0 + nin, 1, nslots, 0, 0, Nt);
-            factored = h->fuse_done;
-        }
+        if (!left && s + 1 < nin)
+            factored = launch_gemm<T>(h, 3, tl<T>(h), tl<T>(h, b), tl<T>(h, b), TB, b + 1, R, b + 1, K0 + nin, 1, nslots, 0, 0, Nt,
+                                      fuse ? b + 1 : -1);
     }
     return 0;
 }
@@ -870,11 +885,11 @@ bool use_dataflow(const gphip_ctx* h, int nslots) {
 void abort_hook(gphip_ctx* h, int kind) {
     if (h->debug_abort_word != kind) return;
     h->debug_abort_word = 0;
-    (void)hipMemsetAsync(h->dTicket.as<unsigned long long>() + 1, 1, 4, h->stream);
+    (void)hipMemsetAsync(h->dTicket.as<unsigned long long>() + 1, 1, 4, h->cs);
 }
 
 // c0 > 0 (128-tiles only): factor the trailing submatrix that starts at tile column c0 -- the tail of the
-// look-ahead schedule, already updated by every earlier panel.  No finalize here.
+// look-ahead schedule, already updated by every earlier panel.  No finalize here.  Queued on the targeted stream (h->cs).
 template <typename T, int TBX, int OCC = 2, int NST = 2, bool BUILD = false>
 void launch_dataflow(gphip_ctx* h, int nslots, int c0 = 0, double* part = nullptr, long pstride = 0, int ncols = 0, int nprev = 0,
                      const void* aprev = nullptr, unsigned int* colsig = nullptr) {
@@ -938,7 +953,7 @@ void launch_dataflow(gphip_ctx* h, int nslots, int c0 = 0, double* part = nullpt
         if (lds <= 80 * 1024 && h->dataflow_park) g.park = reinterpret_cast<int*>(h->dTicket.as<unsigned long long>() + 2);
     }
     abort_hook(h, 1);
-    hipLaunchKernelGGL((chol_dataflow_kernel<T, TBX, OCC, NST, BUILD>), dim3((unsigned)tasks), dim3(256), lds, h->stream, g, tp);
+    hipLaunchKernelGGL((chol_dataflow_kernel<T, TBX, OCC, NST, BUILD>), dim3((unsigned)tasks), dim3(256), lds, h->cs, g, tp);
 }
 
 // U = L^-T of the factor a single dataflow launch has just queued (one slot), by a second launch of the same kernel whose
@@ -1088,7 +1103,6 @@ void launch_finalize(gphip_ctx* h, int nslots, int nparts, int pstride = 0, cons
 
 template <typename T>
 int queue_factor_dataflow(gphip_ctx* h, int nslots) {
-    h->cs = h->stream;
     if constexpr (sizeof(T) == 8) {
         if (h->Nt <= h->dataflow_fine_nt) {
             // Throughput-bound launches (>= ~8 000 tile tasks: one theta from N = 8192 on) run the build of the same kernel
@@ -1144,29 +1158,25 @@ int queue_factor(gphip_ctx* h, int nslots) {
     const std::vector<int> bnd = panel_bounds(h);
     const int nouter = (int)bnd.size() - 1;
     auto k0 = [&](int k) { return bnd[(size_t)std::min(k, nouter)]; };
-    auto trailing = [&](int k, int c_lo, int c_hi, int cls) {      // apply panel k to tile columns [c_lo,c_hi)
-        launch_gemm<T>(h, cls, tl<T>(h), tl<T>(h, k0(k)), tl<T>(h, k0(k)), (k0(k + 1) - k0(k)) * TB, c_lo, R, c_lo, c_hi, 1,
-                       nslots, 0, 0, Nt);
+    auto trailing = [&](int k, int c_lo, int c_hi, int cls, int fuse_b = -1) {      // apply panel k to tile columns [c_lo,c_hi)
+        return launch_gemm<T>(h, cls, tl<T>(h), tl<T>(h, k0(k)), tl<T>(h, k0(k)), (k0(k + 1) - k0(k)) * TB, c_lo, R, c_lo, c_hi, 1,
+                              nslots, 0, 0, Nt, fuse_b);
     };
     if (use_dataflow(h, nslots)) return queue_factor_dataflow<T>(h, nslots);
     double* tail_part = nullptr;               // a 64-tile dataflow tail keeps its block partials here
     int tail_n = 0, tail_k0 = -1;
     // Option "panel_df" (one theta, fp64): every outer panel -- the look-ahead update by the panel before it AND its own
-    // factorisation -- is ONE 64-tile dataflow launch on the panel stream (the sharded schedule's dist_panel_df = 2 form).
+    // factorisation -- is ONE 64-tile dataflow launch on the targeted (panel) stream (the sharded schedule's dist_panel_df = 2 form).
     // All log-det partials are then per 64-block (dPartial[0 .. 2 Nt), the tail's too).
     bool pdf = false;
     if constexpr (sizeof(T) == 8) pdf = panel_df_on(h, nslots) && nouter >= 2;
     auto df_panel = [&](int kp, int kprev) {
         if constexpr (sizeof(T) == 8) {
-            hipStream_t keep = h->stream;
-            h->stream = h->pstream;
             const int c0 = 2 * (kprev >= 0 ? k0(kprev) : k0(kp));
             launch_dataflow<T, 64>(h, 1, c0, nullptr, 0, 2 * k0(kp + 1) - c0, kprev >= 0 ? 2 * (k0(kp) - k0(kprev)) : 0, h->dA.p);
-            h->stream = keep;
         }
     };
     if (!h->lookahead || nouter < 2) {
-        h->cs = h->stream;
         for (int k = 0; k < nouter; ++k) {
             queue_panel<T>(h, k0(k), k0(k + 1) - k0(k), nslots);
             trailing(k, k0(k + 1), R, 4);
@@ -1176,9 +1186,11 @@ int queue_factor(gphip_ctx* h, int nslots) {
         hipEvent_t built = sync_event(h);
         HIPCHK(hipEventRecord(built, h->stream));
         HIPCHK(hipStreamWaitEvent(h->pstream, built, 0));
-        h->cs = h->pstream;
-        if (pdf) df_panel(0, -1);
-        else queue_panel<T>(h, 0, k0(1), nslots);
+        {
+            Scoped<hipStream_t> on(h->cs, h->pstream);
+            if (pdf) df_panel(0, -1);
+            else queue_panel<T>(h, 0, k0(1), nslots);
+        }
         hipEvent_t ev_panel = sync_event(h);
         HIPCHK(hipEventRecord(ev_panel, h->pstream));
         hipEvent_t ev_rest = nullptr;
@@ -1194,7 +1206,6 @@ int queue_factor(gphip_ctx* h, int nslots) {
         for (int k = 0; k < nouter; ++k) {
             hipEvent_t ev_next = nullptr;
             if (k + 1 == kc) {                  // last multi-kernel panel: apply it to everything, then cut over
-                h->cs = h->stream;
                 HIPCHK(hipStreamWaitEvent(h->stream, ev_panel, 0));
                 trailing(k, k0(k + 1), R, 4);
                 const int rem = Nt - k0(kc);                       // tile columns left
@@ -1215,27 +1226,24 @@ int queue_factor(gphip_ctx* h, int nslots) {
                 break;
             }
             if (k + 1 < nouter) {
-                h->cs = h->pstream;
+                Scoped<hipStream_t> on(h->cs, h->pstream);
                 if (ev_rest) HIPCHK(hipStreamWaitEvent(h->pstream, ev_rest, 0));
                 if (pdf) {
                     df_panel(k + 1, k);                                        // LA(k) + factor panel k+1, one launch
                 } else {
-                    if (h->fuse_potrf && nslots <= 8 && h->dist_world == 0) h->fuse_b = k0(k + 1);  // ... whose first diagonal tile LA(k) also factors
-                    trailing(k, k0(k + 1), k0(k + 2), 3);                          // LA(k)
-                    const bool first_factored = h->fuse_done;
+                    const bool fuse = h->fuse_potrf && nslots <= 8 && h->dist_world == 0;      // LA(k) also factors panel k+1's first diagonal tile
+                    const bool first_factored = trailing(k, k0(k + 1), k0(k + 2), 3, fuse ? k0(k + 1) : -1);       // LA(k)
                     queue_panel<T>(h, k0(k + 1), k0(k + 2) - k0(k + 1), nslots, first_factored);    // factor panel k+1
                 }
                 ev_next = sync_event(h);
                 HIPCHK(hipEventRecord(ev_next, h->pstream));
             }
-            h->cs = h->stream;
             HIPCHK(hipStreamWaitEvent(h->stream, ev_panel, 0));
             trailing(k, k0(k + 2), R, 4);                                      // REST(k)
             ev_rest = sync_event(h);
             HIPCHK(hipEventRecord(ev_rest, h->stream));
             ev_panel = ev_next;
         }
-        h->cs = h->stream;
     }
     if (pdf) {
         launch_finalize<T>(h, nslots, 2 * Nt);
@@ -1513,7 +1521,6 @@ int eval_chunk(gphip_ctx* h, const double* Theta, int nb, double* out, double* p
     // inverses afterwards: the evaluation is ONE launch
     h->fused_eval = h->fuse_option && h->theta_packed && h->kt != 2 && h->dtype == 64 && !h->want_w && h->profile < 2 &&
                     !h->pw_mean_on && !h->pw_nug_on && use_dataflow(h, nb) && h->Nt <= h->dataflow_fine_nt;
-    h->cs = h->stream;
     {
         ProfScope ps(h, 5, 0.0, 0.0);
         if (!h->fused_eval) DISPATCH(h, queue_build, h, nb);
@@ -1824,6 +1831,24 @@ int upload_pw_test(gphip_ctx* h, int s0, int nb, int64_t m0, int64_t mc, int64_t
     return GPHIP_OK;
 }
 
+// One chunk of test points staged for the substitutions of a prediction: rows [m0, m0 + mc) of the row-major X, transposed and
+// zero-padded to [d][mpad] in the caller's xt (reused from chunk to chunk), go to dXsT, the same columns of the call's
+// point-dependent test rows (samples [s0, s0 + nslots)) next to them, and k(x*, X) of every slot is queued into dV.  Returns mpad;
+// *rc: the status.  ranged = false: the points are not measured against the training inputs' range (they count as far outside).
+int64_t stage_test_chunk(gphip_ctx* h, const double* X, int64_t m0, int64_t mc, int nslots, int s0, std::vector<double>& xt, int* rc,
+                         bool ranged = true) {
+    const int64_t d = h->d, mpad = (mc + TB - 1) / TB * TB;
+    xt.assign((size_t)d * mpad, 0.0);
+    for (int64_t i = 0; i < mc; ++i)
+        for (int64_t j = 0; j < d; ++j) xt[(size_t)j * mpad + i] = X[(m0 + i) * d + j];
+    if (ranged) note_test_range(h, xt, mc, mpad);
+    else h->test_ratio = HUGE_VAL;
+    *rc = DISPATCH(h, upload, h, h->dXsT.p, xt, h->stream);
+    if (!*rc) *rc = upload_pw_test(h, s0, nslots, m0, mc, mpad);
+    if (!*rc) DISPATCH(h, queue_cross, h, mc, mpad, nslots);
+    return mpad;
+}
+
 // run-time compiled covariance function: k(x*_t, x*_t) of the test points in dXsT for every slot -> dKss[slot][mpad] (fp64)
 int queue_custom_kss(gphip_ctx* h, int64_t mc, int64_t mpad, int nslots) {
     HIPCHK(h->dKss.grow((size_t)nslots * mpad * 8));
@@ -1838,9 +1863,10 @@ int queue_custom_kss(gphip_ctx* h, int64_t mc, int64_t mpad, int nslots) {
 }
 
 // mu*, var* from V and z: V streamed once (HBM bound) -- strips of columns x 128 test points per workgroup,
-// then the strips are added in order.  Profile class 6: bytes = V once.
+// then the strips are added in order.  Profile class 6: bytes = V once.  z_gathered: z is read from dZ (predict_streamed gathered
+// it there while the panels streamed by), not from the workspace's rhs row.
 template <typename T>
-int queue_predict_reduce(gphip_ctx* h, int64_t mc, int64_t mpad, int nslots) {
+int queue_predict_reduce(gphip_ctx* h, int64_t mc, int64_t mpad, int nslots, bool z_gathered = false) {
     const int Mt = (int)(mpad / TB), Nt = (int)h->Nt;
     int nstrips = (2048 + Mt * nslots - 1) / (Mt * nslots);          // enough workgroups to fill 256 CUs several times
     if (nstrips > Nt) nstrips = Nt;
@@ -1860,7 +1886,7 @@ int queue_predict_reduce(gphip_ctx* h, int64_t mc, int64_t mpad, int nslots) {
         ProfScope ps(h, 6, 4.0 * (double)mpad * h->Npad * nslots, (double)sizeof(T) * mpad * h->Npad * nslots);
         hipLaunchKernelGGL(predict_partial_kernel<T>, dim3((unsigned)Mt, (unsigned)nstrips, (unsigned)nslots), dim3(256),
                            (size_t)js * 8 + 8 * TB * 8, h->stream, (const T*)h->dV.p, (long)mpad, (long)mpad * h->Npad, (int)h->N,
-                           h->z_vector ? (const T*)h->dZ.p : (const T*)h->dA.p, h->z_vector ? 0 : (int)h->R, (long)h->slot_elems, js,
+                           z_gathered ? (const T*)h->dZ.p : (const T*)h->dA.p, z_gathered ? 0 : (int)h->R, (long)h->slot_elems, js,
                            h->dPart.as<double>(), nstrips);
         hipLaunchKernelGGL(predict_finish_kernel, dim3((unsigned)((mc + 255) / 256), (unsigned)nslots), dim3(256), 0, h->stream,
                            h->dPart.as<double>(), nstrips, (long)mpad, h->dSlotp.as<double>(), (int)mc, (long)mpad,
@@ -1870,18 +1896,18 @@ int queue_predict_reduce(gphip_ctx* h, int64_t mc, int64_t mpad, int nslots) {
     return 0;
 }
 
+// true: the launch also factored diagonal tile (fuse_b, fuse_b), as asked (launch_gemm)
 template <typename T>
-int queue_dist_update(gphip_ctx* h, const void* packed, long K0, long rows, long cols, int c_lo, int c_hi, int cls,
-                      int groups = 1, int grp_stride = 0) {
+bool queue_dist_update(gphip_ctx* h, const void* packed, long K0, long rows, long cols, int c_lo, int c_hi, int cls,
+                       int fuse_b = -1, int groups = 1, int grp_stride = 0) {
     // the packed panel is the panel's own contiguous range of the tile-major workspace: shifted base, global tile indices
     (void)rows;
     Opnd<T> pk{(const T*)packed - tile_index((int)K0, (int)K0, (int)h->R) * TS, TB, 0, (int)h->R, (int)K0};
     // C = this rank's own panels: the dense workspace, or its compact own-panel storage addressed through the adj table
     Opnd<T> co{(const T*)h->dist_base, TB, 0, (int)h->R, 0};
     co.adj = h->dDistAdj.as<long>(); co.adj_panel = h->panel;
-    launch_gemm<T>(h, cls, co, pk, pk, (int)cols, c_lo, (int)h->Nt + 1, c_lo, c_hi, 1, 1, 0, 0, (int)h->Nt, groups,
-                   grp_stride, h->panel);
-    return 0;
+    return launch_gemm<T>(h, cls, co, pk, pk, (int)cols, c_lo, (int)h->Nt + 1, c_lo, c_hi, 1, 1, 0, 0, (int)h->Nt, fuse_b, groups,
+                          grp_stride, h->panel);
 }
 
 template <typename T>
@@ -2448,14 +2474,13 @@ static int create_ctx(const void* X, const void* y, int64_t N, int64_t d, int ke
     if (int sr = 0, sw = 0; cu_slice(&sr, &sw)) {
         // developer experiment (scripts/gpu_cu_partition.py): this context runs on a slice of the chip's CUs
         if (make_slice_stream(&h->stream, sr, sw) != hipSuccess || make_slice_stream(&h->pstream, sr, sw) != hipSuccess) return bail(GPHIP_ERR_HIP);
-        h->cs = h->stream;
     } else {
         int least = 0, greatest = 0;                // numerically lower = higher priority
         (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
         if (hipStreamCreateWithPriority(&h->stream, hipStreamNonBlocking, least) != hipSuccess) return bail(GPHIP_ERR_HIP);
         if (hipStreamCreateWithPriority(&h->pstream, hipStreamNonBlocking, greatest) != hipSuccess) return bail(GPHIP_ERR_HIP);
-        h->cs = h->stream;
     }
+    h->cs = h->stream;                             // (from here on cs changes only through a Scoped block, and in gphip_set_streams)
     std::vector<double> xt((size_t)d * h->Npad, 0.0), yp((size_t)h->Npad, 0.0);
     for (int64_t i = 0; i < N; ++i) {
         for (int64_t j = 0; j < d; ++j) xt[(size_t)j * h->Npad + i] = Xd[i * d + j];
@@ -2773,7 +2798,6 @@ int gphip_loglik_grad(gphip_handle h, const double* theta, int p, double* out, d
     if ((rc = ensure_gacc(h))) return rc;
     int64_t MC = 0;                           // rows of K^-1 per pass (each pass a forward and a backward substitution)
     if (!potri && (rc = ensure_vchunk(h, Npad, &MC))) return rc;
-    h->cs = h->stream;
     const bool from_u = potri && inverse_launch_ran(h);       // alpha from the explicit U; else by a backward pass, whose scratch is dV:
     InvBufs ib{};                                             // U goes there only afterwards
     if (from_u) ib = DISPATCH(h, queue_u, h);
@@ -2874,7 +2898,6 @@ int gphip_covariance(gphip_handle h, const double* theta, int p, double* K) {
     if (!stage_theta(h, 0, theta)) return fail(h, GPHIP_ERR_ARG, "non-finite or zero hyper-parameter");
     rc = copy_theta(h, 1);
     if (rc) return rc;
-    h->cs = h->stream;
     DISPATCH(h, queue_build, h, 1);
     // the lower-triangle tiles of the packed workspace (tile (ti, tj) at tile_index(ti, tj, R), column-major inside)
     std::vector<double> tmp;
@@ -2897,7 +2920,7 @@ int gphip_cross_covariance(gphip_handle h, const double* theta, int p, const voi
     if (p != h->p) return fail(h, GPHIP_ERR_DIM, "theta has the wrong length");
     if (M < 1) return fail(h, GPHIP_ERR_DIM, "M < 1");
     std::lock_guard<std::recursive_mutex> lk(h->mu);
-    const int64_t N = h->N, d = h->d;
+    const int64_t N = h->N;
     if (h->kernel_id == GPHIP_KERNEL_NULL) {   // k = SparseArray[{}, {N, M}], kappa = nugget (BGP:72-80)
         for (int64_t i = 0; i < N * M; ++i) k[i] = 0.0;
         for (int64_t t = 0; t < M; ++t) kappa[t] = theta[0] * theta[0];
@@ -2910,7 +2933,6 @@ int gphip_cross_covariance(gphip_handle h, const double* theta, int p, const voi
     if (!stage_theta(h, 0, theta)) return fail(h, GPHIP_ERR_ARG, "non-finite or zero hyper-parameter");
     rc = copy_theta(h, 1);
     if (rc) return rc;
-    h->cs = h->stream;
     DISPATCH(h, queue_scale_train, h);
     const double* X = static_cast<const double*>(Xs);
     const int64_t MC = 2048;
@@ -2919,14 +2941,8 @@ int gphip_cross_covariance(gphip_handle h, const double* theta, int p, const voi
     std::vector<double> xt, v;
     for (int64_t m0 = 0; m0 < M; m0 += MC) {
         const int64_t mc = (M - m0 < MC) ? (M - m0) : MC;
-        const int64_t mpad = (mc + TB - 1) / TB * TB;
-        xt.assign((size_t)d * mpad, 0.0);
-        for (int64_t i = 0; i < mc; ++i)
-            for (int64_t j = 0; j < d; ++j) xt[(size_t)j * mpad + i] = X[(m0 + i) * d + j];
-        note_test_range(h, xt, mc, mpad);
-        rc = DISPATCH(h, upload, h, h->dXsT.p, xt, h->stream);
+        const int64_t mpad = stage_test_chunk(h, X, m0, mc, 1, 0, xt, &rc);
         if (rc) return rc;
-        DISPATCH(h, queue_cross, h, mc, mpad, 1);
         rc = DISPATCH(h, download, h, v, h->dV.p, (size_t)mpad * (size_t)N, h->stream);   // V(t, j) at j*mpad + t
         if (rc) return rc;
         HIPCHK(hipGetLastError());
@@ -2998,13 +3014,9 @@ int gphip_predict(gphip_handle h, const void* Xs, int64_t M, double* mean, doubl
             const int rc = group_parallel(h, [&](int i) {
                 const int64_t m0 = M * i / nl, m1 = M * (i + 1) / nl;
                 gphip_ctx* m = g->members[(size_t)i];
-                m->pw_mean_test = pm ? pm + m0 : nullptr;      // each member's shard of m(x*), nugget(x*)
-                m->pw_nug_test = pn ? pn + m0 : nullptr;
-                const int c = predict_local(m, X + m0 * d, m1 - m0, mean + m0, var + m0);
-                if (m != h) m->pw_mean_test = m->pw_nug_test = nullptr;
-                return c;
+                PwScope shard(m, m->pw_mean_host, m->pw_nug_host, pm ? pm + m0 : nullptr, pn ? pn + m0 : nullptr, m->pw_test_stride);   // of m(x*), nugget(x*)
+                return predict_local(m, X + m0 * d, m1 - m0, mean + m0, var + m0);
             });
-            h->pw_mean_test = pm; h->pw_nug_test = pn;
             return rc;
         }
     }
@@ -3015,24 +3027,14 @@ static int predict_local(gphip_handle h, const void* Xs, int64_t M, double* mean
     std::lock_guard<std::recursive_mutex> lk(h->mu);
     HIPCHK(hipSetDevice(h->device));
     const double* X = static_cast<const double*>(Xs);
-    const int64_t d = h->d;
     int64_t MC = 0;                                          // test points per chunk
     int rc = ensure_vchunk(h, std::min<int64_t>(32768, (M + TB - 1) / TB * TB), &MC);
     if (rc) return rc;
-    h->cs = h->stream;
     std::vector<double> xt;
     for (int64_t m0 = 0; m0 < M; m0 += MC) {
         const int64_t mc = (M - m0 < MC) ? (M - m0) : MC;
-        const int64_t mpad = (mc + TB - 1) / TB * TB;
-        xt.assign((size_t)d * mpad, 0.0);
-        for (int64_t i = 0; i < mc; ++i)
-            for (int64_t j = 0; j < d; ++j) xt[(size_t)j * mpad + i] = X[(m0 + i) * d + j];
-        note_test_range(h, xt, mc, mpad);
-        rc = DISPATCH(h, upload, h, h->dXsT.p, xt, h->stream);
+        const int64_t mpad = stage_test_chunk(h, X, m0, mc, 1, 0, xt, &rc);
         if (rc) return rc;
-        rc = upload_pw_test(h, 0, 1, m0, mc, mpad);
-        if (rc) return rc;
-        DISPATCH(h, queue_cross, h, mc, mpad, 1);
         queue_forward_fit(h, mpad);
         DISPATCH(h, queue_predict_reduce, h, mc, mpad, 1);
         HIPCHK(hipMemcpyAsync(mean + m0, h->dMean.p, (size_t)mc * 8, hipMemcpyDeviceToHost, h->stream));
@@ -3134,8 +3136,9 @@ static int predict_streamed(gphip_handle h, const void* Xs, int64_t M, double* m
         return failed;
     }
     std::vector<double> xt;
-    const double *pm0 = h->pw_mean_test, *pn0 = h->pw_nug_test;      // (member 0 IS the public handle: keep the call's pointers)
-    struct Restore { gphip_ctx* h; const double *a, *b; ~Restore() { h->pw_mean_test = a; h->pw_nug_test = b; } } restore{h, pm0, pn0};
+    const double *pm0 = h->pw_mean_test, *pn0 = h->pw_nug_test;
+    // a member's slice of the call's m(x*) / nugget(x*), from test point `a` on (member 0 IS the public handle)
+    auto pw_slice = [&](gphip_ctx* m, int64_t a) { return PwScope(m, m->pw_mean_host, m->pw_nug_host, pm0 ? pm0 + a : nullptr, pn0 ? pn0 + a : nullptr, m->pw_test_stride); };
     auto member_fail = [&](gphip_ctx* m, int code) { if (code) local_fail(code, m->err); };
     for (int pass = 0; pass < (int)passes; ++pass) {
         std::vector<int64_t> c0((size_t)nl, 0), mcv((size_t)nl, 0), mpadv((size_t)nl, 0);
@@ -3144,19 +3147,12 @@ static int predict_streamed(gphip_handle h, const void* Xs, int64_t M, double* m
             m->sync_used = 0;
             const int64_t a = lo[(size_t)i] + (int64_t)pass * MC[(size_t)i], b = std::min(lo[(size_t)i + 1], a + MC[(size_t)i]);
             if (b <= a) continue;
-            c0[(size_t)i] = a; mcv[(size_t)i] = b - a; mpadv[(size_t)i] = (b - a + TB - 1) / TB * TB;
-            const int64_t mc = b - a, mpad = mpadv[(size_t)i];
+            c0[(size_t)i] = a; mcv[(size_t)i] = b - a;
             if (!SOFT(hipSetDevice(m->device))) break;
-            m->cs = m->stream;
-            xt.assign((size_t)d * mpad, 0.0);
-            for (int64_t r = 0; r < mc; ++r)
-                for (int64_t j = 0; j < d; ++j) xt[(size_t)j * mpad + r] = X[(a + r) * d + j];
-            note_test_range(m, xt, mc, mpad);
-            member_fail(m, DISPATCH(m, upload, m, m->dXsT.p, xt, m->stream));
-            m->pw_mean_test = pm0 ? pm0 + a : nullptr;
-            m->pw_nug_test = pn0 ? pn0 + a : nullptr;
-            if (failed == GPHIP_OK) member_fail(m, upload_pw_test(m, 0, 1, 0, mc, mpad));
-            if (failed == GPHIP_OK) DISPATCH(m, queue_cross, m, mc, mpad, 1);
+            PwScope pw = pw_slice(m, a);
+            int c = GPHIP_OK;
+            mpadv[(size_t)i] = stage_test_chunk(m, X + a * d, 0, b - a, 1, 0, xt, &c);
+            member_fail(m, c);
         }
         std::vector<std::vector<hipEvent_t>> ev_used((size_t)nl, std::vector<hipEvent_t>((size_t)nouter, nullptr));
         for (int k = 0; k < nouter; ++k) {
@@ -3182,7 +3178,6 @@ static int predict_streamed(gphip_handle h, const void* Xs, int64_t M, double* m
                 const bool mine = o == g->ranks[(size_t)i];
                 // base through which this panel's tiles are addressed with their global indices
                 char* base = group_panel_ptr(g, i, k) - dist_panel_first(m, k) * TS * (long)m->es;
-                m->cs = m->stream;
                 if (m->dtype == 64) {
                     if (!mine) hipLaunchKernelGGL(trtri128_kernel<double>, dim3((unsigned)(K1 - K0), 1), dim3(256), potrf_lds<double>(),
                                                   m->stream, (const double*)base, 0l, (double*)m->dW.p, (int)m->Nt, K0);
@@ -3196,9 +3191,10 @@ static int predict_streamed(gphip_handle h, const void* Xs, int64_t M, double* m
                         hipLaunchKernelGGL(gather_rhs_row_kernel<float>, dim3((unsigned)(((K1 - K0) * TB + 255) / 256)), dim3(256), 0,
                                            m->stream, (const float*)base, (int)m->R, 0, K1 * TB, (float*)m->dZ.p, 1l, K0 * TB);
                 }
-                m->ws_override = base;
-                DISPATCH(m, queue_forward_panel, m, mpadv[(size_t)i], 1, K0, K1, 0, false);
-                m->ws_override = nullptr;
+                {
+                    Scoped<void*> ws(m->ws_override, base);
+                    DISPATCH(m, queue_forward_panel, m, mpadv[(size_t)i], 1, K0, K1, 0, false);
+                }
                 hipEvent_t eu = sync_event(m);
                 if (SOFT(hipEventRecord(eu, m->stream))) ev_used[(size_t)i][(size_t)k] = eu;
             }
@@ -3208,9 +3204,8 @@ static int predict_streamed(gphip_handle h, const void* Xs, int64_t M, double* m
             (void)hipSetDevice(m->device);
             if (mcv[(size_t)i] > 0 && failed == GPHIP_OK) {
                 const int64_t mc = mcv[(size_t)i], a = c0[(size_t)i];
-                m->z_vector = true;
-                DISPATCH(m, queue_predict_reduce, m, mc, mpadv[(size_t)i], 1);
-                m->z_vector = false;
+                PwScope pw = pw_slice(m, a);                               // (the epilogue asks which of the two are there)
+                DISPATCH(m, queue_predict_reduce, m, mc, mpadv[(size_t)i], 1, true);
                 SOFT(hipMemcpyAsync(mean + a, m->dMean.p, (size_t)mc * 8, hipMemcpyDeviceToHost, m->stream));
                 SOFT(hipMemcpyAsync(var + a, m->dVar.p, (size_t)mc * 8, hipMemcpyDeviceToHost, m->stream));
             }
@@ -3218,7 +3213,6 @@ static int predict_streamed(gphip_handle h, const void* Xs, int64_t M, double* m
             SOFT(hipStreamSynchronize(m->stream));
             SOFT(hipGetLastError());
             harvest(m);
-            m->pw_mean_test = m->pw_nug_test = nullptr;
         }
     }
 #undef SOFT
@@ -3254,24 +3248,18 @@ int gphip_predict_samples(gphip_handle h, const double* Thetas, int S, int p, co
         // posterior samples are independent units: contiguous blocks to the local devices, no collective
         gphip_group* g = h->group;
         const int nl = (int)g->members.size();
+        const double *a0 = h->pw_mean_host, *a1 = h->pw_nug_host, *a2 = h->pw_mean_test, *a3 = h->pw_nug_test;
+        const size_t N = (size_t)h->N, stride = (size_t)h->pw_test_stride;
         return group_parallel(h, [&](int i) {
             const int s0 = (int)((long)S * i / nl), s1 = (int)((long)S * (i + 1) / nl);
             if (s1 <= s0) return (int)GPHIP_OK;
             gphip_ctx* m = g->members[(size_t)i];
-            const double *a0 = h->pw_mean_host, *a1 = h->pw_nug_host, *a2 = h->pw_mean_test, *a3 = h->pw_nug_test;
-            if (m != h) {                                                  // the member's block of every per-sample row
-                m->pw_mean_host = a0 ? a0 + (size_t)s0 * h->N : nullptr;
-                m->pw_nug_host = a1 ? a1 + (size_t)s0 * h->N : nullptr;
-                m->pw_mean_test = a2 ? a2 + (size_t)s0 * h->pw_test_stride : nullptr;
-                m->pw_nug_test = a3 ? a3 + (size_t)s0 * h->pw_test_stride : nullptr;
-                m->pw_test_stride = h->pw_test_stride;
-            }
-            m->in_group_call = true;
-            const int c = gphip_predict_samples(m, Thetas + (size_t)s0 * p, s1 - s0, p, Xs, M, mean + (size_t)s0 * M,
-                                                var + (size_t)s0 * M, info + s0);
-            m->in_group_call = false;
-            if (m != h) m->pw_mean_host = m->pw_nug_host = m->pw_mean_test = m->pw_nug_test = nullptr;
-            return c;
+            // the member's block of every per-sample row (the public handle's own block starts at sample 0: what it holds already)
+            PwScope block(m, a0 ? a0 + s0 * N : nullptr, a1 ? a1 + s0 * N : nullptr, a2 ? a2 + s0 * stride : nullptr,
+                          a3 ? a3 + s0 * stride : nullptr, (long)stride);
+            Scoped<bool> member(m->in_group_call, true);
+            return gphip_predict_samples(m, Thetas + (size_t)s0 * p, s1 - s0, p, Xs, M, mean + (size_t)s0 * M, var + (size_t)s0 * M,
+                                         info + s0);
         });
     }
     HIPCHK(hipSetDevice(h->device));
@@ -3279,7 +3267,6 @@ int gphip_predict_samples(gphip_handle h, const double* Thetas, int S, int p, co
     if (rc) return rc;
     invalidate_fit(h);
     const double* X = static_cast<const double*>(Xs);
-    const int64_t d = h->d;
     std::vector<double> xt, hm, hv, scratch_out(1), scratch_parts;
     for (int s0 = 0; s0 < S; s0 += h->slots) {
         const int nb = (S - s0 < h->slots) ? (S - s0) : h->slots;
@@ -3296,19 +3283,10 @@ int gphip_predict_samples(gphip_handle h, const double* Thetas, int S, int p, co
         const int64_t MC = (M < mcap) ? (M + TB - 1) / TB * TB : mcap;
         rc = ensure_vbuf(h, (int64_t)nb * MC);
         if (rc) return rc;
-        h->cs = h->stream;
         for (int64_t m0 = 0; m0 < M; m0 += MC) {
             const int64_t mc = (M - m0 < MC) ? (M - m0) : MC;
-            const int64_t mpad = (mc + TB - 1) / TB * TB;
-            xt.assign((size_t)d * mpad, 0.0);
-            for (int64_t i = 0; i < mc; ++i)
-                for (int64_t j = 0; j < d; ++j) xt[(size_t)j * mpad + i] = X[(m0 + i) * d + j];
-            note_test_range(h, xt, mc, mpad);
-            rc = DISPATCH(h, upload, h, h->dXsT.p, xt, h->stream);
+            const int64_t mpad = stage_test_chunk(h, X, m0, mc, nb, s0, xt, &rc);
             if (rc) return rc;
-            rc = upload_pw_test(h, s0, nb, m0, mc, mpad);
-            if (rc) return rc;
-            DISPATCH(h, queue_cross, h, mc, mpad, nb);
             // few test points per sample: the forward substitutions of ALL samples as ONE dataflow launch (slot = sample) instead
             // of two launches per tile column (samples_forward_df)
             if (samples_forward_df(h, nb, mpad)) launch_dataflow_inverse<double, 64>(h, mpad, false, nb, h->dW64s.p);
@@ -3333,19 +3311,6 @@ int gphip_predict_samples(gphip_handle h, const double* Thetas, int S, int p, co
 // the test points, BGP:408 meanFunction /@ inputs): the host evaluates the two functions for the theta(s) of the call and
 // hands the VALUES over; a null pointer keeps the constant form (sn^2, mu) read from theta.  The arrays only have to
 // live for the duration of the call.
-namespace {
-struct PwScope {                               // installs the call's arrays on the handle, removes them on every exit path
-    gphip_ctx* h;
-    PwScope(gphip_ctx* h_, const double* mt, const double* nt, const double* ms, const double* ns, long stride) : h(h_) {
-        h->pw_mean_host = mt; h->pw_nug_host = nt; h->pw_mean_test = ms; h->pw_nug_test = ns; h->pw_test_stride = stride;
-    }
-    ~PwScope() {
-        h->pw_mean_host = h->pw_nug_host = h->pw_mean_test = h->pw_nug_test = nullptr;
-        h->pw_mean_on = h->pw_nug_on = false;
-    }
-};
-}  // namespace
-
 int gphip_loglik_batch_pw(gphip_handle h, const double* Theta, int B, int p, const double* mean_train, const double* nugget_train,
                           double* out, int* info) {
     if (!h) return GPHIP_ERR_ARG;
@@ -3418,7 +3383,6 @@ int gphip_solve(gphip_handle h, const double* rhs, int64_t nrhs, double* out) {
     for (int64_t i = 0; rhs_finite && i < nrhs * N; ++i) rhs_finite = std::isfinite(rhs[i]);
     if (rhs_finite && trsv_ok(h, (int)std::min<int64_t>(nrhs, TRSV_MAXR))) {
         // two launches per batch of <= 4 right-hand sides that stream the factor once each (gp_trsv.h) instead of a 128-row GEMM substitution
-        h->cs = h->stream;
         std::vector<double> b;
         std::vector<float> b32;
         for (int64_t m0 = 0; m0 < nrhs; m0 += TRSV_MAXR) {
@@ -3435,7 +3399,6 @@ int gphip_solve(gphip_handle h, const double* rhs, int64_t nrhs, double* out) {
     }
     int rc = ensure_vbuf(h, nrhs < MC ? (nrhs + TB - 1) / TB * TB : MC);
     if (rc) return rc;
-    h->cs = h->stream;
     std::vector<double> v;
     for (int64_t m0 = 0; m0 < nrhs; m0 += MC) {
         const int64_t mc = (nrhs - m0 < MC) ? (nrhs - m0) : MC;
@@ -3561,7 +3524,6 @@ int gphip_dist_begin(gphip_handle h, const double* theta, int p, int rank, int w
     h->dist_df_active = h->dist_df_mode != 0;
     h->df_prev_ptr = nullptr; h->df_prev_k = -2;
     HIPCHK(hipMemsetAsync(h->dPartial.p, 0, (size_t)2 * h->Nt * 8, h->stream));
-    h->cs = h->stream;
     DISPATCH(h, queue_build, h, 1);
     h->pw_mean_on = h->pw_nug_on = false;
     return GPHIP_OK;
@@ -3580,8 +3542,8 @@ int gphip_dist_factor_panel(gphip_handle h, int k, void* packed) {
     HIPCHK(hipSetDevice(h->device));
     const int64_t K0 = (int64_t)k * h->panel;
     const int64_t K1 = (K0 + h->panel < h->Nt) ? K0 + h->panel : h->Nt;
-    h->cs = h->pstream;
-    h->ws_override = dist_panel_base(h, k);
+    Scoped<hipStream_t> on(h->cs, h->pstream);
+    Scoped<void*> ws(h->ws_override, dist_panel_base(h, k));
     const bool first_factored = h->dist_first_factored == k;       // (by this rank's look-ahead update of the panel)
     h->dist_first_factored = -1;
     if (h->dist_df_active) {
@@ -3591,8 +3553,6 @@ int gphip_dist_factor_panel(gphip_handle h, int k, void* packed) {
         // dist_panel_df = 2: the look-ahead update of this panel by panel k - 1 rides in the SAME launch
         // (the tasks read panel k - 1 from where the broadcast put it, as 2 P more slabs): the update's MFMA work then fills
         // the chip around the panel's serial chain instead of preceding it.
-        hipStream_t keep = h->stream;
-        h->stream = h->pstream;
         if (h->df_prev_ptr && h->df_prev_k == k - 1 && k >= 1) {
             const int64_t Kp = K0 - h->panel;
             const char* pbase = static_cast<const char*>(h->df_prev_ptr) - dist_panel_first(h, k - 1) * TS * (long)h->es;
@@ -3623,20 +3583,17 @@ int gphip_dist_factor_panel(gphip_handle h, int k, void* packed) {
             }
         }
         h->df_prev_ptr = nullptr; h->df_prev_k = -2;
-        h->stream = keep;
         if (h->dist_df_mode >= 3) {
             // a launch that never ran would leave the column counters short of their targets and the waits on them pending for
             // ever: report it NOW (the caller then skips the waits: drain mode)
             const hipError_t le = hipGetLastError();
-            if (le != hipSuccess) { h->ws_override = nullptr; h->cs = h->stream; if (h->col_waits) h->col_waits->clear(); return fail(h, GPHIP_ERR_HIP, hipGetErrorString(le)); }
+            if (le != hipSuccess) { if (h->col_waits) h->col_waits->clear(); return fail(h, GPHIP_ERR_HIP, hipGetErrorString(le)); }
         }
     } else {
         DISPATCH(h, queue_panel, h, (int)K0, (int)(K1 - K0), 1, first_factored);
     }
-    h->ws_override = nullptr;
     if (packed && packed != (void*)dist_panel_range(h, k))
         HIPCHK(hipMemcpyAsync(packed, dist_panel_range(h, k), (size_t)rows * cols * h->es, hipMemcpyDeviceToDevice, h->pstream));
-    h->cs = h->stream;
     return GPHIP_OK;
 }
 
@@ -3654,7 +3611,7 @@ int gphip_dist_update(gphip_handle h, int k, const void* packed, int j_first, in
     const int nouter = (Nt + P - 1) / P;
     const long K0 = (long)k * P;
     cols = (std::min<long>(K0 + P, Nt) - K0) * TB;         // contraction length = the panel's width in columns
-    h->cs = on_panel_stream ? h->pstream : h->stream;
+    Scoped<hipStream_t> on(h->cs, on_panel_stream ? h->pstream : h->stream);
     // The owned panels j = j0, j0 + world, .. of this update go out as ONE grouped launch (blockIdx.y = owned panel;
     // gemm_nt decodes its own column range) instead of one launch per 512-column strip: a rank of an 8-GPU job owns
     // up to 8 strips per step, and a world of one owns them all (then they are adjacent: one plain triangular launch).
@@ -3669,7 +3626,6 @@ int gphip_dist_update(gphip_handle h, int k, const void* packed, int j_first, in
         // (gphip_dist_factor_panel), which reads panel k from `packed` -- the caller keeps it alive until then, as both the
         // in-library schedule (three rotating receive buffers) and dist_cholesky.py do.
         h->df_prev_ptr = packed; h->df_prev_k = k;
-        h->cs = h->stream;
         return GPHIP_OK;
     }
     // (dist_first_factored stays set until gphip_dist_factor_panel consumes it: the look-ahead update is the LAST update of
@@ -3678,22 +3634,20 @@ int gphip_dist_update(gphip_handle h, int k, const void* packed, int j_first, in
         // the look-ahead update of the NEXT panel (this rank owns it) also factors that panel's first diagonal block
         // (fuse_potrf): gphip_dist_factor_panel then starts at the panel solve
         const bool la_one = on_panel_stream && h->fuse_potrf && je - jb == 1 && !h->dist_df_active;
+        const int fuse_b = la_one ? j0 * P : -1;
         if (W == 1) {            // adjacent panels (and the corner tile right behind them): one triangular launch
-            if (la_one) h->fuse_b = j0 * P;
-            DISPATCH(h, queue_dist_update, h, packed, K0, (long)rows, (long)cols, j0 * P,
-                     (corner && je == nouter) ? R : std::min(je * P, Nt), cls);
-            if (la_one && h->fuse_done) h->dist_first_factored = j0;
+            if (DISPATCH(h, queue_dist_update, h, packed, K0, (long)rows, (long)cols, j0 * P,
+                         (corner && je == nouter) ? R : std::min(je * P, Nt), cls, fuse_b))
+                h->dist_first_factored = j0;
         } else if (cnt == 1) {
-            if (la_one) h->fuse_b = j0 * P;
-            DISPATCH(h, queue_dist_update, h, packed, K0, (long)rows, (long)cols, j0 * P, std::min(j0 * P + P, Nt), cls);
-            if (la_one && h->fuse_done) h->dist_first_factored = j0;
+            if (DISPATCH(h, queue_dist_update, h, packed, K0, (long)rows, (long)cols, j0 * P, std::min(j0 * P + P, Nt), cls, fuse_b))
+                h->dist_first_factored = j0;
         } else {
-            DISPATCH(h, queue_dist_update, h, packed, K0, (long)rows, (long)cols, j0 * P, Nt, cls, cnt, W * P);
+            DISPATCH(h, queue_dist_update, h, packed, K0, (long)rows, (long)cols, j0 * P, Nt, cls, -1, cnt, W * P);
         }
     }
     if (corner && !(cnt > 0 && W == 1 && je == nouter))
         DISPATCH(h, queue_dist_update, h, packed, K0, (long)rows, (long)cols, Nt, R, cls);
-    h->cs = h->stream;
     return GPHIP_OK;
 }
 

@@ -98,7 +98,6 @@ int queue_downdate(gphip_ctx* h, gphip_ctx* c, int64_t mpad) {
         HIPCHK(h->dJPart.grow((size_t)nsplit * g.ntiles * TS * sizeof(T)));
         g.P = (T*)h->dJPart.p;
     }
-    c->cs = c->stream;
     {
         // algorithmic flops M (M + 1) N (the lower triangle and the rhs row of an M x M downdate of contraction length N)
         ProfScope ps(c, 4, (double)mpad * (mpad + 1) * (double)h->N, (double)sizeof(T) * (mpad + TB) * (double)h->Npad);
@@ -114,19 +113,14 @@ int queue_downdate(gphip_ctx* h, gphip_ctx* c, int64_t mpad) {
 // diagonal carries k(x*, x*) + (noisy: sn^2) + (*jitter_io, which a negative value turns into the default first).
 int joint_sigma(gphip_ctx* h, const double* Xs, int64_t M, const double* ystar, bool noisy, double* jitter_io) {
     HIPCHK(hipSetDevice(h->device));
-    const int64_t mpad = (M + TB - 1) / TB * TB, d = h->d;
+    const int64_t mpad = (M + TB - 1) / TB * TB;
     int rc = ensure_vbuf(h, mpad);
     if (rc) { (void)hipGetLastError(); return fail(h, GPHIP_ERR_HIP, "joint prediction: no device memory for all M rows of V"); }
     HIPCHK(h->dJZ.grow((size_t)TB * h->Npad * h->es));
-    h->cs = h->stream;
     HIPCHK(hipMemsetAsync(h->dJZ.p, 0, (size_t)TB * h->Npad * h->es, h->stream));
-    std::vector<double> xt((size_t)d * mpad, 0.0);
-    for (int64_t i = 0; i < M; ++i)
-        for (int64_t j = 0; j < d; ++j) xt[(size_t)j * mpad + i] = Xs[i * d + j];
-    note_test_range(h, xt, M, mpad);
-    rc = DISPATCH(h, upload, h, h->dXsT.p, xt, h->stream);
+    std::vector<double> xt;
+    stage_test_chunk(h, Xs, 0, M, 1, 0, xt, &rc);         // all M rows as one chunk
     if (rc) return rc;
-    DISPATCH(h, queue_cross, h, M, mpad, 1);
     queue_forward_fit(h, mpad);
     if (h->dtype == 64)
         hipLaunchKernelGGL(gather_rhs_row_kernel<double>, dim3((unsigned)((h->Npad + 255) / 256)), dim3(256), 0, h->stream,
@@ -149,7 +143,6 @@ int joint_sigma(gphip_ctx* h, const double* Xs, int64_t M, const double* ystar, 
     c->hSlotp.as<double>()[SP_MFMA] = 0.0;
     if ((rc = copy_theta(c, 1))) return fail(h, rc, c->err.c_str());
     HIPCHK(hipMemsetAsync(c->dInfo.p, 0, 4, c->stream));
-    c->cs = c->stream;
     c->theta_packed = false; c->fused_eval = false;      // (want_w / want_u: no FactorMode is ever open on the child)
     DISPATCH(c, queue_build, c, 1);
     return DISPATCH(h, queue_downdate, h, c, mpad);

@@ -139,7 +139,6 @@ int loo_call(gphip_ctx* h, const double* theta, int p, double* mean, double* var
     if ((rc = loo_scratch(h, &s))) return rc;
     HIPCHK(h->dAlpha.grow((size_t)Npad * h->es));
     if (grad && (rc = ensure_gacc(h))) return rc;
-    h->cs = h->stream;
     const InvBufs ib = DISPATCH(h, queue_u, h);
     rc = DISPATCH(h, loo_queue_values, h, s, ib);
     if (rc) return rc;

@@ -448,11 +448,11 @@ int group_eval_run(gphip_ctx* h, const double* theta, int p, bool keep, double* 
                                                                        // (counter address, value it reaches when the column is final)
         if (lo >= 0 && failed == GPHIP_OK) {
             gphip_ctx* m = g->members[(size_t)lo];
-            m->col_events = h->bcast_chunks ? &colev : nullptr;
-            m->col_waits = h->bcast_chunks ? &colw : nullptr;
-            compute(m, gphip_dist_factor_panel(m, k, nullptr));
-            m->col_events = nullptr;
-            m->col_waits = nullptr;
+            {
+                Scoped<decltype(m->col_events)> ev(m->col_events, h->bcast_chunks ? &colev : nullptr);
+                Scoped<decltype(m->col_waits)> cw(m->col_waits, h->bcast_chunks ? &colw : nullptr);
+                compute(m, gphip_dist_factor_panel(m, k, nullptr));
+            }
             SOFT(hipSetDevice(m->device));
             factored = record(m, m->pstream);
             ev_fact[(size_t)k] = factored;

@@ -190,7 +190,6 @@ int sparse_queue_diag(gphip_sparse_ctx* h, double sn2, double* out) {
 int sparse_factor(gphip_sparse_ctx* h, gphip_ctx* c, bool build, const char* what, int* info) {
     {
         FactorMode mode(c, true);              // the forward substitutions that follow use the block inverses
-        c->cs = c->stream;
         c->theta_packed = false; c->fused_eval = false;
         if (build) DISPATCH(c, queue_build, c, 1);
         DISPATCH(c, queue_factor, c, 1);
@@ -325,7 +324,6 @@ int sparse_grad_phase(gphip_sparse_ctx* h, const SparseGradIn& in, std::vector<S
     // ---- b: a, B^-1, S and the inner matrix of H
     {
         SparseScope ps(h, &recs, 5, b->stream);
-        b->cs = b->stream;
         HIPCHK(b->dAlpha.grow((size_t)mpm * sizeof(T)));
         if ((rc = queue_alpha<T>(b))) return sfail(h, rc, b->err);
         int gx = (int)((mpm * mpm + 255) / 256);
@@ -340,7 +338,6 @@ int sparse_grad_phase(gphip_sparse_ctx* h, const SparseGradIn& in, std::vector<S
     }
     if ((rc = complete_call(b))) return sfail(h, rc, b->err);
     // ---- u: H = L_u^-T [..] L_u^-1 by two backward substitutions (the inner matrix is symmetric), then the K_uu term
-    u->cs = u->stream;
     HIPCHK(u->dAlpha.grow((size_t)u->Npad * sizeof(T)));
     HIPCHK(hipMemsetAsync(u->dAlpha.p, 0, (size_t)u->Npad * sizeof(T), u->stream));
     if ((rc = ensure_gacc(u))) return sfail(h, rc, u->err);
@@ -766,28 +763,22 @@ int gphip_sparse_predict(gphip_sparse_handle h, const void* Xs, int64_t M, int l
     if (!h->fitted || !has_fit(u) || !has_fit(b)) return sfail(h, GPHIP_ERR_STATE, "gphip_sparse_predict before a successful gphip_sparse_fit");
     HIPCHK(hipSetDevice(h->device));
     const double* X = static_cast<const double*>(Xs);
-    const int64_t d = h->d;
     int64_t MC = 0;
     int rc = ensure_vchunk(u, std::min<int64_t>(32768, (M + TB - 1) / TB * TB), &MC);
     if (rc) { (void)hipGetLastError(); return sfail(h, rc, "no device memory for the test points' V: " + u->err); }
     if ((rc = ensure_vbuf(b, MC))) { (void)hipGetLastError(); return sfail(h, rc, "no device memory for the test points' V: " + b->err); }
     std::vector<double> xt;
     for (int64_t m0 = 0; m0 < M; m0 += MC) {
-        const int64_t mc = std::min(MC, M - m0), mpad = (mc + TB - 1) / TB * TB;
-        xt.assign((size_t)d * mpad, 0.0);
-        for (int64_t i = 0; i < mc; ++i)
-            for (int64_t j = 0; j < d; ++j) xt[(size_t)j * mpad + i] = X[(m0 + i) * d + j];
-        if ((rc = DISPATCH(u, upload, u, u->dXsT.p, xt, u->stream))) return sfail(h, rc, u->err);
-        u->test_ratio = HUGE_VAL;
-        u->cs = u->stream;
-        DISPATCH(u, queue_cross, u, mc, mpad, 1);
+        const int64_t mc = std::min(MC, M - m0);
+        // (ranged = false: u builds k(x*, Z) with the direct form, kbuild_mfma = 0 -- no verdict of the MFMA kernel build to guard)
+        const int64_t mpad = stage_test_chunk(u, X, m0, mc, 1, 0, xt, &rc, false);
+        if (rc) return sfail(h, rc, u->err);
         queue_forward_fit(u, mpad);
         int ns1 = 0, ns2 = 0;
         if ((rc = DISPATCH(u, sparse_queue_partial, u, mpad, &ns1))) return sfail(h, rc, u->err);
         if (h->custom && (rc = queue_custom_kss(u, mc, mpad, 1))) return sfail(h, rc, u->err);
         if ((rc = complete_call(u))) return sfail(h, rc, u->err);
         // v2 = L_B^-1 v1: the same rows through b's factor
-        b->cs = b->stream;
         HIPCHK(hipMemcpyAsync(b->dV.p, u->dV.p, (size_t)mpad * u->Npad * h->es, hipMemcpyDeviceToDevice, b->stream));
         queue_forward_fit(b, mpad);
         if ((rc = DISPATCH(b, sparse_queue_partial, b, mpad, &ns2))) return sfail(h, rc, b->err);

@@ -3,7 +3,7 @@ like the reference's (BGP:228-330, 332-394) with the HIP closure installed."""
 import numpy as np
 import pytest
 
-from bayesianinference_amd import gaussian_process as gp, synthetic as syn
+from bayesianinference_amd import _lib, gaussian_process as gp, synthetic as syn
 from oracle import gp_oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -200,3 +200,78 @@ def test_define_gaussian_process_with_nugget_and_mean_functions_of_the_point():
                                       mean_fn=lambda x, t=t: mean(x[None, :], t)[0])
         np.testing.assert_allclose(res["Mean"][s], mo, rtol=1e-7, atol=1e-9)
         np.testing.assert_allclose(res["StandardDeviation"][s], so, rtol=1e-7)
+
+
+# ---- launch state of a call does not outlive the call ----
+_LS_N, _LS_D = 640, 3                              # 5 tile columns: panel = 2 gives three outer panels, panel = 1 five
+_LS_TH = syn.default_theta("se_ard", _LS_D)
+_LS_THS = _LS_TH[None, :] * (1.0 + 0.05 * np.arange(4))[:, None]
+_LS_XS = syn.make_test_points(3, _LS_D)
+
+
+def _ls_fit_predict(h):
+    assert h.fit(_LS_TH) == 0
+    return h.predict(_LS_XS)
+
+
+_LS_CALLS = {
+    "loglik": lambda h: h.loglik(_LS_TH),
+    "loglik_grad": lambda h: h.loglik_grad(_LS_TH),
+    "fit+predict": _ls_fit_predict,
+    "solve1": lambda h: (h.solve(np.random.default_rng(1).standard_normal(h.N)),),          # (after fit+predict: the fit is resident)
+    "solve8": lambda h: (h.solve(np.random.default_rng(8).standard_normal((h.N, 8))),),
+    "samples": lambda h: h.predict_samples(_LS_THS, _LS_XS),
+}
+
+
+def _ls_lookahead(h):
+    """a look-ahead multi-kernel factorisation: panel stream, fused first-tile factorisation, LA / REST alternation"""
+    assert h.loglik(_LS_TH)[1] == 0
+
+
+def _ls_sharded(h):
+    """a sharded evaluation over the two virtual ranks, a sharded fit and a streamed prediction from it; then local calls only"""
+    assert h.loglik(_LS_TH)[1] == 0
+    assert h.get_option("last_issue_us") > 0 and h.get_option("last_dist_panel_df") == h.get_option("dist_panel_df")
+    assert h.fit(_LS_TH) == 0
+    h.predict(_LS_XS)
+    h.set_option("shard_min_n", 1 << 30)
+
+
+@pytest.mark.parametrize("device,opts,retarget", [
+    (None, {"dataflow": 0, "panel": 2}, _ls_lookahead),
+    (None, {"dataflow": 0, "panel": 2, "latency_gemm": 0}, _ls_lookahead),      # (the 256-thread GEMM shape: the one that takes the fused tile)
+    ([0, 0], {"shard_min_n": 0, "panel": 1, "dist_panel_df": 0}, _ls_sharded),
+    ([0, 0], {"shard_min_n": 0, "panel": 1, "dist_panel_df": 3}, _ls_sharded),
+], ids=["lookahead", "lookahead-fused", "sharded-df0", "sharded-df3"])
+def test_launch_state_does_not_outlive_the_call_that_set_it(device, opts, retarget):
+    """The per-call fields of a context (targeted stream, workspace override, column-event sinks, fused-tile request, a
+    member's slices of the per-point arrays) are set through scopes and are back to their resting values when the call
+    returns.  So after calls that retarget launches -- the look-ahead schedule on the panel stream; a sharded evaluation,
+    a sharded fit and a streamed prediction over two virtual ranks on device 0 -- every ordinary call gives bit for bit
+    (np.array_equal) what a fresh handle with the same options gives; for the group the ordinary calls run locally
+    (shard_min_n raised).  Two fresh handles are compared with each other first: every route used here is bit-repeatable,
+    the multi-kernel one (dataflow = 0) included.  No fault is injected: the early-return paths are covered by the
+    scopes' destructors."""
+    X, y = syn.make_dataset(_LS_N, _LS_D)
+
+    def run(used):
+        h = _lib.Handle(X, y, "se_ard", device=device)
+        for k, v in opts.items():
+            h.set_option(k, v)
+        if used:
+            retarget(h)
+        elif "shard_min_n" in opts:
+            h.set_option("shard_min_n", 1 << 30)
+        res = {name: [np.asarray(a) for a in call(h)] for name, call in _LS_CALLS.items()}
+        assert (h.get_option("last_issue_us") > 0) == (used and device is not None)       # the ordinary calls did not shard
+        h.close()
+        return res
+
+    fresh, again, used = run(False), run(False), run(True)
+    for name in _LS_CALLS:
+        for a, b in zip(fresh[name], again[name]):
+            assert np.array_equal(a, b), ("two fresh handles differ", name, a, b)
+    for name in _LS_CALLS:
+        for a, b in zip(used[name], fresh[name]):
+            assert np.array_equal(a, b), (name, a, b)

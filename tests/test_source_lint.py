@@ -63,6 +63,21 @@ def test_factorisation_mode_flags_only_through_the_scope_type():
     assert not bad, bad
 
 
+def test_targeted_stream_changes_only_through_a_scope():
+    # `cs`, the stream the launch helpers queue on, rests at the main stream: it is assigned where a context's streams are made
+    # (create_ctx) and in gphip_set_streams, and retargeted only through `Scoped<hipStream_t>`, which puts it back on every exit
+    # path.  A by-hand `h->cs = h->pstream` that an early return skipped left every later call on the panel stream; the main
+    # stream itself is never swapped for another.
+    hits = {}
+    for name in sorted(os.listdir(CSRC)):
+        if name.endswith((".inc", ".hip")):
+            code = _code(os.path.join(CSRC, name))
+            hits[name] = (len(re.findall(r"->cs\s*=(?!=)", code)), len(re.findall(r"->stream\s*=(?!=)", code)))
+    assert hits.pop("gphip.hip") == (2, 1), "cs: create_ctx + gphip_set_streams; stream: gphip_set_streams"
+    assert all(v == (0, 0) for v in hits.values()), hits
+    assert "Scoped<hipStream_t>" in _code(os.path.join(CSRC, "gphip.hip"))
+
+
 def test_gfx950_only_no_compat_layers():
     for name in os.listdir(CSRC):
         code = _code(os.path.join(CSRC, name))
