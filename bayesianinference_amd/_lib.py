@@ -130,6 +130,9 @@ _SIGNATURES = {
     "gphip_sparse_set_inducing": (C.c_int, [_h, C.c_void_p, C.c_int64]),
     "gphip_sparse_num_params": (C.c_int, [_h, _ip]),
     "gphip_sparse_bound": (C.c_int, [_h, _dp, C.c_int, C.c_double, _dp, _dp, _ip]),
+    "gphip_sparse_bound_batch": (C.c_int, [_h, _dp, C.c_int, C.c_int, C.c_double, _dp, _dp, _ip]),
+    "gphip_sparse_nested_sampling": (C.c_int, [_h, C.c_double, _dp, _ip, C.c_void_p, C.c_void_p, C.c_void_p, _dp, C.c_int64, _dp, _dp, _dp,
+                                               _dp, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_int64)]),
     "gphip_sparse_bound_grad": (C.c_int, [_h, _dp, C.c_int, C.c_double, _dp, _dp, _dp, _ip]),
     "gphip_sparse_bound_grad_inducing": (C.c_int, [_h, _dp, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _ip]),
     "gphip_sparse_fit": (C.c_int, [_h, _dp, C.c_int, C.c_double, _ip]),
@@ -744,6 +747,46 @@ class SparseHandle:
         out, info = C.c_double(0.0), C.c_int(0)
         self._check(self._lib.gphip_sparse_bound(self._h, _d(th), th.size, float(jitter), C.byref(out), None, C.byref(info)))
         return out.value, info.value
+
+    def bound_batch(self, Theta, jitter: float = -1.0, parts: bool = False):
+        """gphip_sparse_bound_batch: (F[B], info[B]) -- with parts=True (F[B], info[B], parts[B, 5]) -- for the rows of Theta
+        [B, p] in ONE call; row s is `bound(Theta[s], jitter)` up to rounding, jitter < 0 the default rule per row.  A row that
+        fails has info != 0 and F (and its parts) NaN without disturbing the others.  No fit stays resident."""
+        Th = np.ascontiguousarray(np.asarray(Theta, dtype=np.float64))
+        if Th.ndim == 1:
+            Th = Th.reshape(1, -1)
+        B, p = Th.shape
+        out, info = np.zeros(B), np.zeros(B, dtype=np.int32)
+        pr = np.zeros((B, 5)) if parts else None
+        self._check(self._lib.gphip_sparse_bound_batch(self._h, _d(Th), B, p, float(jitter), _d(out), _d(pr) if parts else None,
+                                                       info.ctypes.data_as(_ip)))
+        return (out, info, pr) if parts else (out, info)
+
+    def nested_sampling(self, box, jitter: float = -1.0, prior_kind=None, logprior=None, start=None, cap=None, **options):
+        """gphip_sparse_nested_sampling: the native batched sampler with the bound F(theta; jitter) as the log-likelihood (one
+        bound_batch per Metropolis step).  Options and the returned dict as Handle.nested_sampling."""
+        o = NsOptions()
+        self._check(self._lib.gphip_ns_default_options(C.byref(o)))
+        for k, v in options.items():
+            if not hasattr(o, k):
+                raise GphipError(1, f"unknown sampler option {k!r}")
+            setattr(o, k, v)
+        box = np.ascontiguousarray(np.asarray(box, dtype=np.float64).reshape(self.p, 2))
+        kinds = None if prior_kind is None else np.ascontiguousarray(np.asarray(prior_kind, dtype=np.int32))
+        cb = None
+        if logprior is not None:
+            cb = LOGPRIOR_FN(lambda th, p, _u: float(logprior(np.ctypeslib.as_array(th, shape=(p,)).copy())))
+        st = None if start is None else np.ascontiguousarray(np.asarray(start, dtype=np.float64).reshape(o.pool, self.p))
+        cap = int(cap or (o.pool + max(o.max_iterations, o.min_iterations) + 1))
+        pts, ll, lp, ar = np.zeros((cap, self.p)), np.zeros(cap), np.zeros(cap), np.zeros(cap)
+        ns, ne, z = C.c_int64(0), C.c_int64(0), C.c_double(0.0)
+        self._check(self._lib.gphip_sparse_nested_sampling(
+            self._h, float(jitter), _d(box), None if kinds is None else kinds.ctypes.data_as(_ip), C.cast(cb, C.c_void_p) if cb else None,
+            None, C.byref(o), None if st is None else _d(st), cap, _d(pts), _d(ll), _d(lp), _d(ar), C.byref(ns), C.byref(z), C.byref(ne)))
+        m = ns.value
+        return {"Points": pts[:m].copy(), "LogLikelihood": ll[:m].copy(), "LogPriorPDF": lp[:m].copy(),
+                "AcceptanceRate": ar[:m].copy(), "SamplePoolSize": int(o.pool), "GeneratedNestedSamples": m - int(o.pool),
+                "TotalSamples": m, "CrudeLogEvidence": z.value, "LikelihoodEvaluations": ne.value, "Seed": int(o.seed)}
 
     def bound_grad(self, theta, jitter: float = -1.0):
         """(F(theta), dF/dtheta, info): the bound -- the same bytes as `bound` -- and its gradient in theta's layout, the jitter

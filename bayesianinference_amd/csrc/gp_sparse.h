@@ -1,6 +1,8 @@
 // gp_sparse.h -- device kernels of the sparse inducing-point GP (include/gphip.h: gphip_sparse_*, gphip_sparse.inc).
 //
 //   sparse_accumulate_kernel     C += V^T V and the rhs row += r^T V on the lower tiles of b's workspace (the hot path)
+//   (the first five kernels carry a slot dimension for gphip_sparse_bound_batch: one theta per workspace slot, slot = the grid's
+//    last index, every operand addressed as slot-0 base + slot x stride; the one-theta calls run them with one slot)
 //   sparse_reduce_kernel         C += the strip partials of one chunk, strips added in a fixed order
 //   sparse_resid_kernel          r = y - mu of a chunk into row 0 of the rhs operand + per-block partial sums of r^2
 //   sparse_blocksum_kernel       per-block partial sums of a double vector (k(x_i, x_i) of a run-time compiled kernel)
@@ -45,6 +47,7 @@ struct SparseAccArgs {
     int kstrip;                  // data points per strip (multiple of 128)
     int K;                       // padded data points of the chunk (multiple of 128)
     T* P;                        // [strip][tile][128 x 128] partial tiles; null: C += directly
+    long c_bstride, v_bstride, r_bstride, p_bstride;      // elements between the slots (blockIdx.z) of C, V, Rz and P
 };
 
 constexpr int SPA_OPND = TB * 128;             // bytes of one operand image of a stage: 128 rows x 128 bytes
@@ -75,8 +78,10 @@ __global__ __launch_bounds__(256, 2) void sparse_accumulate_kernel(SparseAccArgs
     const long lda = rhs ? g.ldr : g.ldv, ldb = g.ldv;
     // this lane's share of a DMA instruction: slot lane & 7 of row lane >> 3 of the instruction's eight rows
     const int lr = lane >> 3, lp = lane & 7;
-    const T* a_run = (rhs ? g.Rz : g.V + (long)ti * TB * g.ldv) + k0;
-    const T* b_run = g.V + (long)tj * TB * g.ldv + k0;
+    const long slot = blockIdx.z;
+    const T* Vs = g.V + slot * g.v_bstride;
+    const T* a_run = (rhs ? g.Rz + slot * g.r_bstride : Vs + (long)ti * TB * g.ldv) + k0;
+    const T* b_run = Vs + (long)tj * TB * g.ldv + k0;
     auto stage = [&](int st) {
         char* Is = smem + st * SPA_STAGE;
         char* Js = Is + SPA_OPND;
@@ -97,8 +102,8 @@ __global__ __launch_bounds__(256, 2) void sparse_accumulate_kernel(SparseAccArgs
     const bool direct = g.P == nullptr;
     // lane holds i = wi*64 + y*16 + (lane&15), j = wj*64 + x*16 + drow(lane>>4, r) of the tile (column-major, ld 128)
     const long toff = (long)(wj * 16 * FJ) * TB + wi * (16 * FI) + (lane & 15);
-    T* Cg = g.C + tile_index(ti, tj, g.R) * TS + toff;
-    T* Pg = direct ? nullptr : g.P + ((long)split * g.ntiles + t) * TS + toff;
+    T* Cg = g.C + slot * g.c_bstride + tile_index(ti, tj, g.R) * TS + toff;
+    T* Pg = direct ? nullptr : g.P + slot * g.p_bstride + ((long)split * g.ntiles + t) * TS + toff;
     const int l4 = lane >> 4, l15 = lane & 15;
     const int nk = (int)(klen / GK);
     // rows this wave computes (wave-uniform), as in downdate_kernel: ONE 16-row group of an rhs tile, nothing of the strictly-upper
@@ -191,12 +196,14 @@ __global__ __launch_bounds__(256, 2) void sparse_accumulate_kernel(SparseAccArgs
     else pipeline(std::integral_constant<int, 0>{});
 }
 
-// C += P[0] + P[1] + .. + P[nsplit-1], elementwise, strips in order (fp64 sums).  grid = (ntiles, 16), 256 threads x 4 elements.
+// C += P[0] + P[1] + .. + P[nsplit-1], elementwise, strips in order (fp64 sums).  grid = (ntiles, 16, slots), 256 threads x 4 elements.
 // Only what sparse_accumulate_kernel wrote: the first 16 rows of an rhs tile, a diagonal tile without its strictly-upper quadrant.
 template <typename T>
 __global__ __launch_bounds__(256) void sparse_reduce_kernel(T* __restrict__ C, int R, int ntri, int Mt, int ntiles,
-                                                            const T* __restrict__ P, int nsplit) {
+                                                            const T* __restrict__ P, int nsplit, long c_bstride, long p_bstride) {
     const int t = blockIdx.x;
+    C += (long)blockIdx.z * c_bstride;
+    P += (long)blockIdx.z * p_bstride;
     int ti, tj;
     if (t < ntri) tri_decode(t, Mt, ti, tj);
     else { ti = Mt; tj = t - ntri; }
@@ -225,31 +232,45 @@ __device__ __forceinline__ double sparse_block_sum(double v, double* red) {
 }
 
 // rz[t] = y[t] - mu for t < n, 0 for n <= t < npad (the residual in the handle's arithmetic type), part[block] = sum of the
-// block's rz^2 in fp64.  grid = ceil(npad / 256).
+// block's rz^2 in fp64.  grid = (ceil(npad / 256), slots): slot s subtracts mu[s mu_stride] and writes rz + s r_bstride,
+// part + s p_bstride.
 template <typename T>
-__global__ __launch_bounds__(256) void sparse_resid_kernel(const T* __restrict__ y, int n, int npad, double mu, T* __restrict__ rz,
-                                                           double* __restrict__ part) {
+__global__ __launch_bounds__(256) void sparse_resid_kernel(const T* __restrict__ y, int n, int npad, const double* __restrict__ muv,
+                                                           int mu_stride, T* __restrict__ rz, long r_bstride, double* __restrict__ part,
+                                                           long p_bstride) {
     __shared__ double red[256];
     const int t = blockIdx.x * 256 + threadIdx.x;
+    const double mu = muv[(long)blockIdx.y * mu_stride];
+    rz += (long)blockIdx.y * r_bstride;
+    part += (long)blockIdx.y * p_bstride;
     const T r = t < n ? (T)(y[t] - (T)mu) : (T)0;
     if (t < npad) rz[t] = r;
     const double s = sparse_block_sum((double)r * (double)r, red);
     if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
-// part[block] = sum of v[t], t < n, over the block's 256 entries
-__global__ __launch_bounds__(256) void sparse_blocksum_kernel(const double* __restrict__ v, int n, double* __restrict__ part) {
+// part[block] = sum of v[t], t < n, over the block's 256 entries.  grid = (blocks, slots): slot s reads v + s v_bstride
+__global__ __launch_bounds__(256) void sparse_blocksum_kernel(const double* __restrict__ v, long v_bstride, int n, double* __restrict__ part,
+                                                              long p_bstride) {
     __shared__ double red[256];
     const int t = blockIdx.x * 256 + threadIdx.x;
+    v += (long)blockIdx.y * v_bstride;
+    part += (long)blockIdx.y * p_bstride;
     const double s = sparse_block_sum(t < n ? v[t] : 0.0, red);
     if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
 // The diagonal of the accumulated V V^T in b's workspace: out[0] = its sum over the m inducing points (fixed order), then
-// C(k, k) += sn2 for k < m and C(k, k) = 1 on the pad (k < 128 Mt).  One workgroup.
+// C(k, k) += sn2 for k < m and C(k, k) = 1 on the pad (k < 128 Mt).  One workgroup per slot: slot s works on C + s c_bstride
+// with sn2 = sn2v[s sn2_stride] and writes out[s o_bstride].
 template <typename T>
-__global__ __launch_bounds__(256) void sparse_diag_kernel(T* __restrict__ C, int R, int m, int mpad, double sn2, double* __restrict__ out) {
+__global__ __launch_bounds__(256) void sparse_diag_kernel(T* __restrict__ C, long c_bstride, int R, int m, int mpad,
+                                                          const double* __restrict__ sn2v, int sn2_stride, double* __restrict__ out,
+                                                          long o_bstride) {
     __shared__ double red[256];
+    const double sn2 = sn2v[(long)blockIdx.x * sn2_stride];
+    C += (long)blockIdx.x * c_bstride;
+    out += (long)blockIdx.x * o_bstride;
     double s = 0.0;
     for (int k = threadIdx.x; k < mpad; k += 256) {
         T* p = C + tile_index(k >> 7, k >> 7, R) * TS + (long)(k & 127) * (TB + 1);

@@ -159,12 +159,14 @@ struct NsPrior {
     }
 };
 
-// likelihood of a batch with the reference's failure convention: info != 0 / non-finite -> the sentinel
-int ns_loglik(gphip_handle h, const double* Theta, int B, int p, std::vector<double>& out, std::vector<int>& info, int64_t* n_evals) {
+// likelihood of a batch with the reference's failure convention: info != 0 / non-finite -> the sentinel.  eval: the batched
+// evaluator (Theta, B, p, out, info) -> status -- gphip_loglik_batch of an exact GP, gphip_sparse_bound_batch of a sparse one
+template <typename Eval>
+int ns_loglik(Eval& eval, const double* Theta, int B, int p, std::vector<double>& out, std::vector<int>& info, int64_t* n_evals) {
     out.resize((size_t)B);
     info.resize((size_t)B);
     if (B == 0) return GPHIP_OK;
-    const int rc = gphip_loglik_batch(h, Theta, B, p, out.data(), info.data());
+    const int rc = eval(Theta, B, p, out.data(), info.data());
     if (rc) return rc;
     for (int i = 0; i < B; ++i)
         if (info[(size_t)i] != 0 || !std::isfinite(out[(size_t)i])) out[(size_t)i] = NS_LOG_ZERO;
@@ -173,39 +175,19 @@ int ns_loglik(gphip_handle h, const double* Theta, int B, int p, std::vector<dou
     return GPHIP_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int gphip_ns_default_options(gphip_ns_options* o) {          // BS:833-855
-    if (!o) return GPHIP_ERR_ARG;
-    o->pool = 100; o->max_iterations = 10000; o->min_iterations = 100; o->mc_steps = 200; o->walkers = 32;
-    o->termination_fraction = 0.01; o->min_accept = 0.0; o->max_accept = 1.0; o->seed = 0;
-    return GPHIP_OK;
-}
-
-// deterministic pieces, exported for the tests (compared value for value with nested_sampling.calculate_weights_crude)
-int gphip_ns_crude_weights(const double* points, const double* loglik, int64_t m, int p, int pool, int64_t* order, double* logx,
-                           double* logw, double* log_evidence) {
-    if (!points || !loglik || !order || !logx || !logw || m < 2 || p < 1 || pool < 1 || pool > m) return GPHIP_ERR_ARG;
-    std::vector<int64_t> o;
-    std::vector<double> x, w;
-    ns_crude_weights(points, loglik, m, p, pool, o, x, w);
-    for (int64_t i = 0; i < m; ++i) { order[i] = o[(size_t)i]; logx[i] = x[(size_t)i]; logw[i] = w[(size_t)i]; }
-    if (log_evidence) *log_evidence = ns_log_sum_exp(w);
-    return GPHIP_OK;
-}
-
-int gphip_nested_sampling(gphip_handle h, const double* box, const int* prior_kind, gphip_logprior_fn logprior, void* user,
-                          const gphip_ns_options* opts, const double* start, int64_t cap, double* points, double* loglik,
-                          double* logprior_out, double* accept_rate, int64_t* n_samples, double* log_evidence, int64_t* n_evals) {
-    if (!h || !box || !opts || !points || !loglik || !n_samples) return fail(h, GPHIP_ERR_ARG, "null argument");
-    const int p = h->p, n = opts->pool, W = std::max(1, opts->walkers);
-    if (n < 2 || cap < n + 1 || opts->mc_steps < 1) return fail(h, GPHIP_ERR_ARG, "pool < 2, cap <= pool or mc_steps < 1");
+// The driver itself, shared by the exact GP (gphip_nested_sampling) and the sparse one (gphip_sparse_nested_sampling): eval is the
+// batched evaluator of ns_loglik over p hyper-parameters, failf(code, message) records an error with the caller's handle and
+// returns the code.  The caller holds its handle's lock.
+template <typename Eval, typename Fail>
+int ns_run(int p, Eval&& eval, Fail&& failf, const double* box, const int* prior_kind, gphip_logprior_fn logprior, void* user,
+           const gphip_ns_options* opts, const double* start, int64_t cap, double* points, double* loglik, double* logprior_out,
+           double* accept_rate, int64_t* n_samples, double* log_evidence, int64_t* n_evals) {
+    if (!box || !opts || !points || !loglik || !n_samples) return failf(GPHIP_ERR_ARG, "null argument");
+    const int n = opts->pool, W = std::max(1, opts->walkers);
+    if (n < 2 || cap < n + 1 || opts->mc_steps < 1) return failf(GPHIP_ERR_ARG, "pool < 2, cap <= pool or mc_steps < 1");
     for (int j = 0; j < p; ++j)
         if (!(box[2 * j] < box[2 * j + 1]) || (prior_kind && prior_kind[j] == 1 && !(box[2 * j] > 0.0)))
-            return fail(h, GPHIP_ERR_ARG, "parameter box must have lo < hi (and lo > 0 for a log-uniform prior)");
-    std::lock_guard<std::recursive_mutex> lk(h->mu);
+            return failf(GPHIP_ERR_ARG, "parameter box must have lo < hi (and lo > 0 for a log-uniform prior)");
     NsPrior prior{box, prior_kind, logprior, user, p};
     NsRng rng(opts->seed);
     int64_t evals = 0;
@@ -213,7 +195,7 @@ int gphip_nested_sampling(gphip_handle h, const double* box, const int* prior_ki
     std::vector<int> info;
     if (start) std::copy(start, start + (size_t)n * p, pts.begin());          // generateStartingPoints is host business (BS:1046-1068)
     else for (int i = 0; i < n; ++i) prior.draw(rng, &pts[(size_t)i * p]);
-    int rc = ns_loglik(h, pts.data(), n, p, ll, info, &evals);                // initial sweep, BS:902-916: ONE batched call
+    int rc = ns_loglik(eval, pts.data(), n, p, ll, info, &evals);                // initial sweep, BS:902-916: ONE batched call
     if (rc) return rc;
     for (int i = 0; i < n; ++i) lpr[(size_t)i] = prior.logpdf(&pts[(size_t)i * p]);
     std::vector<int64_t> idx((size_t)n);
@@ -255,7 +237,7 @@ int gphip_nested_sampling(gphip_handle h, const double* box, const int* prior_ki
         double factor = 1.0;
         while (cand_ll.empty()) {
             const int steps = (int)std::ceil(factor * opts->mc_steps);
-            if (!ns_proposal_factor(cov, p, L)) return fail(h, GPHIP_ERR_ARG, "nested sampling: the live points are degenerate (singular covariance)");
+            if (!ns_proposal_factor(cov, p, L)) return failf(GPHIP_ERR_ARG, "nested sampling: the live points are degenerate (singular covariance)");
             // W walkers in lock step: random live points, Metropolis on the prior restricted to {L > threshold, box}
             std::vector<double> x((size_t)W * p), lx((size_t)W, std::nan("")), lp((size_t)W), prop((size_t)W * p), lpp((size_t)W);
             for (int w = 0; w < W; ++w) {
@@ -281,7 +263,7 @@ int gphip_nested_sampling(gphip_handle h, const double* box, const int* prior_ki
                         batch.insert(batch.end(), &prop[(size_t)w * p], &prop[(size_t)w * p] + p);
                     }
                 }
-                rc = ns_loglik(h, batch.data(), (int)which.size(), p, bl, info, &evals);   // ONE batched likelihood call per step
+                rc = ns_loglik(eval, batch.data(), (int)which.size(), p, bl, info, &evals);   // ONE batched likelihood call per step
                 if (rc) return rc;
                 std::vector<double> lnew((size_t)W, NS_LOG_ZERO);
                 for (size_t c = 0; c < which.size(); ++c) lnew[(size_t)which[c]] = bl[c];
@@ -305,7 +287,7 @@ int gphip_nested_sampling(gphip_handle h, const double* box, const int* prior_ki
                         cand_pts.insert(cand_pts.end(), &x[(size_t)w * p], &x[(size_t)w * p] + p);
                     }
             factor *= 1.25;                                                                // BS:1003
-            if (factor > 50) return fail(h, GPHIP_ERR_ARG, "nested sampling: no walker could move (\"Bad likelihood function\", BS:917-921)");
+            if (factor > 50) return failf(GPHIP_ERR_ARG, "nested sampling: no walker could move (\"Bad likelihood function\", BS:917-921)");
         }
         pts.insert(pts.end(), cand_pts.begin(), cand_pts.begin() + p);                     // BS:1012 (value carried from the chain)
         ll.push_back(cand_ll[0]);
@@ -330,6 +312,39 @@ int gphip_nested_sampling(gphip_handle h, const double* box, const int* prior_ki
     }
     if (n_evals) *n_evals = evals;
     return GPHIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gphip_ns_default_options(gphip_ns_options* o) {          // BS:833-855
+    if (!o) return GPHIP_ERR_ARG;
+    o->pool = 100; o->max_iterations = 10000; o->min_iterations = 100; o->mc_steps = 200; o->walkers = 32;
+    o->termination_fraction = 0.01; o->min_accept = 0.0; o->max_accept = 1.0; o->seed = 0;
+    return GPHIP_OK;
+}
+
+// deterministic pieces, exported for the tests (compared value for value with nested_sampling.calculate_weights_crude)
+int gphip_ns_crude_weights(const double* points, const double* loglik, int64_t m, int p, int pool, int64_t* order, double* logx,
+                           double* logw, double* log_evidence) {
+    if (!points || !loglik || !order || !logx || !logw || m < 2 || p < 1 || pool < 1 || pool > m) return GPHIP_ERR_ARG;
+    std::vector<int64_t> o;
+    std::vector<double> x, w;
+    ns_crude_weights(points, loglik, m, p, pool, o, x, w);
+    for (int64_t i = 0; i < m; ++i) { order[i] = o[(size_t)i]; logx[i] = x[(size_t)i]; logw[i] = w[(size_t)i]; }
+    if (log_evidence) *log_evidence = ns_log_sum_exp(w);
+    return GPHIP_OK;
+}
+
+int gphip_nested_sampling(gphip_handle h, const double* box, const int* prior_kind, gphip_logprior_fn logprior, void* user,
+                          const gphip_ns_options* opts, const double* start, int64_t cap, double* points, double* loglik,
+                          double* logprior_out, double* accept_rate, int64_t* n_samples, double* log_evidence, int64_t* n_evals) {
+    if (!h) return GPHIP_ERR_ARG;
+    std::lock_guard<std::recursive_mutex> lk(h->mu);
+    return ns_run(h->p, [h](const double* Theta, int B, int p, double* out, int* info) { return gphip_loglik_batch(h, Theta, B, p, out, info); },
+                  [h](int code, const char* msg) { return fail(h, code, msg); }, box, prior_kind, logprior, user, opts, start, cap, points,
+                  loglik, logprior_out, accept_rate, n_samples, log_evidence, n_evals);
 }
 
 }  // extern "C"

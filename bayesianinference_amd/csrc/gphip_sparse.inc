@@ -35,17 +35,20 @@ struct gphip_sparse_ctx {
     int ncp = 0;
     std::vector<std::pair<std::string, double>> forwarded;    // options handed on to u and b (replayed after gphip_sparse_set_inducing)
     Buf dXt, dY;                               // typed [d][Npad], [Npad]: the data, resident
-    Buf dRz; int64_t rcap = 0;                 // typed [16][rcap]: row 0 = r of the current chunk, the other rows zero
-    Buf dAccP;                                 // typed [strip][tile][128 x 128]: strip partials of the accumulation
-    Buf dSum; std::vector<double> hSum;        // double: [0] tr(V V^T), then the per-block partial sums of r^2 and of k(x_i, x_i)
+    Buf dRz; int64_t rcap = 0; int rz_slots = 0;   // typed [slot][16][rcap]: row 0 = r of the current chunk, the other rows zero
+    Buf dPar, hPar;                            // double [slot][2]: mu and sn^2 of every slot's theta (device; pinned staging copy)
+    Buf dAccP;                                 // typed [slot][strip][tile][128 x 128]: strip partials of the accumulation
+    Buf dSum; std::vector<double> hSum;        // double, per slot: [0] tr(V V^T), then the per-block partial sums of r^2 and of k(x_i, x_i)
     Buf dBc, dS, dH;                           // gradient, typed: B's tiles before its factorisation; S; the inner matrix of H (mpad x mpad)
     Buf dLd, dRes;                             // refined backward substitutions with L_u: its diagonal tiles [Nt][128 x 128], one block column of residuals
     Buf dZpart, dZacc;                         // gradient in Z, double: [part][term][mpad][d] strip partials; the [mpad][d] accumulator
     Buf dGw;                                   // gradient, double: [0] tr B^-1, [1] a^T a, per-block sums of w, w of a chunk, strip partials of V^T a
     // options
     int chunk = 0, split = 0, profile = 0;
+    int batch_slots = 0;                       // gphip_sparse_bound_batch: most thetas per group (0 = by the group rule)
     // read-only results of the last call
     int last_nsplit = 0;
+    int last_slots = 0;                        // thetas in the last group of the last gphip_sparse_bound_batch
     int64_t last_chunk = 0;
     double last_jitter = 0.0;
     int grad_analytic = 0;                     // the last gphip_sparse_bound_grad: 1 = the analytic route, 0 = central differences
@@ -142,10 +145,35 @@ int sparse_load_points(gphip_sparse_ctx* h, const void* xt, int64_t ld, int64_t 
     return GPHIP_OK;
 }
 
-// C += V^T V, rhs row += r^T V for the chunk of mpad rows in u->dV.  Split rule (queue_downdate's): while the output tiles are
-// fewer than two per CU the chunk is cut into strips of whole 128-rows so that tiles x strips >= 2 per CU.
+// [slot][16][rcap] residual rows for nb slots of `rows` data points each (zeroed whenever they are laid out again)
+int sparse_ensure_rz(gphip_sparse_ctx* h, int nb, int64_t rows) {
+    if (rows <= h->rcap && nb <= h->rz_slots) return GPHIP_OK;
+    const int64_t rcap = std::max(rows, h->rcap);
+    const int ns = std::max(nb, h->rz_slots);
+    h->rcap = 0; h->rz_slots = 0;
+    const size_t bytes = (size_t)ns * 16 * rcap * h->es;
+    HIPCHK(h->dRz.grow(bytes));
+    HIPCHK(hipMemsetAsync(h->dRz.p, 0, bytes, h->u->stream));
+    h->rcap = rcap; h->rz_slots = ns;
+    return GPHIP_OK;
+}
+
+// mu and sn^2 of the first nb slots, staged in hPar -> device, on u's stream
+int sparse_copy_par(gphip_sparse_ctx* h, int nb) {
+    HIPCHK(hipMemcpyAsync(h->dPar.p, h->hPar.p, (size_t)nb * 16, hipMemcpyHostToDevice, h->u->stream));
+    return GPHIP_OK;
+}
+int sparse_ensure_par(gphip_sparse_ctx* h, int nb) {
+    HIPCHK(h->dPar.grow((size_t)nb * 16));
+    HIPCHK(h->hPar.grow((size_t)nb * 16, true));
+    return GPHIP_OK;
+}
+
+// C += V^T V, rhs row += r^T V for the chunk of mpad rows in u->dV, for every one of nb slots by ONE launch (slot s: V at
+// dV + s mpad Npad, C = b's workspace slot s).  Split rule (queue_downdate's, counting WORKGROUPS): while output tiles x slots
+// are fewer than two per CU the chunk is cut into strips of whole 128-rows so that tiles x slots x strips >= 2 per CU.
 template <typename T>
-int sparse_queue_accumulate(gphip_sparse_ctx* h, int64_t mpad) {
+int sparse_queue_accumulate(gphip_sparse_ctx* h, int64_t mpad, int nb = 1) {
     gphip_ctx *u = h->u, *b = h->b;
     SparseAccArgs<T> g{};
     g.C = (T*)b->dA.p; g.R = (int)b->R;
@@ -153,36 +181,42 @@ int sparse_queue_accumulate(gphip_sparse_ctx* h, int64_t mpad) {
     g.Rz = (const T*)h->dRz.p; g.ldr = (long)h->rcap;
     g.Mt = (int)u->Nt; g.ntri = g.Mt * (g.Mt + 1) / 2; g.ntiles = g.ntri + g.Mt;
     g.K = (int)mpad;
-    const long target = 2l * std::max(u->ncu, 1);
+    g.c_bstride = (long)b->slot_elems; g.v_bstride = (long)mpad * u->Npad; g.r_bstride = 16l * h->rcap;
+    const long target = 2l * std::max(u->ncu, 1), wgs = (long)g.ntiles * nb;
     const int kt = (int)(mpad / TB);
-    int nsplit = g.ntiles >= target ? 1 : (int)std::min<long>(kt, (target + g.ntiles - 1) / g.ntiles);
+    int nsplit = wgs >= target ? 1 : (int)std::min<long>(kt, (target + wgs - 1) / wgs);
     if (h->split > 0) nsplit = std::min(h->split, kt);
     const int strip_tiles = (kt + nsplit - 1) / nsplit;
     nsplit = (kt + strip_tiles - 1) / strip_tiles;
     g.kstrip = strip_tiles * TB;
     h->last_nsplit = nsplit;
     if (nsplit > 1) {
-        HIPCHK(h->dAccP.grow((size_t)nsplit * g.ntiles * TS * sizeof(T)));
+        g.p_bstride = (long)nsplit * g.ntiles * TS;
+        HIPCHK(h->dAccP.grow((size_t)nb * g.p_bstride * sizeof(T)));
         g.P = (T*)h->dAccP.p;
     }
-    hipLaunchKernelGGL(sparse_accumulate_kernel<T>, dim3((unsigned)g.ntiles, (unsigned)nsplit), dim3(256), SPA_LDS, u->stream, g);
+    hipLaunchKernelGGL(sparse_accumulate_kernel<T>, dim3((unsigned)g.ntiles, (unsigned)nsplit, (unsigned)nb), dim3(256), SPA_LDS, u->stream, g);
     if (nsplit > 1)
-        hipLaunchKernelGGL(sparse_reduce_kernel<T>, dim3((unsigned)g.ntiles, 16), dim3(256), 0, u->stream, (T*)b->dA.p, (int)b->R, g.ntri,
-                           g.Mt, g.ntiles, (const T*)g.P, nsplit);
+        hipLaunchKernelGGL(sparse_reduce_kernel<T>, dim3((unsigned)g.ntiles, 16, (unsigned)nb), dim3(256), 0, u->stream, (T*)b->dA.p, (int)b->R,
+                           g.ntri, g.Mt, g.ntiles, (const T*)g.P, nsplit, g.c_bstride, g.p_bstride);
     return GPHIP_OK;
 }
 
+// r = y - mu_s of the chunk for nb slots (mu_s from dPar); slot s's partial sums go to part + s pstride
 template <typename T>
-int sparse_queue_resid(gphip_sparse_ctx* h, int64_t c0, int64_t mc, int64_t mpad, double mu, double* part) {
-    hipLaunchKernelGGL(sparse_resid_kernel<T>, dim3((unsigned)((mpad + 255) / 256)), dim3(256), 0, h->u->stream, (const T*)h->dY.p + c0, (int)mc,
-                       (int)mpad, mu, (T*)h->dRz.p, part);
+int sparse_queue_resid(gphip_sparse_ctx* h, int64_t c0, int64_t mc, int64_t mpad, double* part, int nb = 1, long pstride = 0) {
+    hipLaunchKernelGGL(sparse_resid_kernel<T>, dim3((unsigned)((mpad + 255) / 256), (unsigned)nb), dim3(256), 0, h->u->stream,
+                       (const T*)h->dY.p + c0, (int)mc, (int)mpad, (const double*)h->dPar.as<double>(), 2, (T*)h->dRz.p, 16l * h->rcap, part,
+                       pstride);
     return GPHIP_OK;
 }
 
+// the trace and B = sn_s^2 I + V V^T of nb slots (sn_s^2 from dPar); slot s's trace goes to out[s ostride]
 template <typename T>
-int sparse_queue_diag(gphip_sparse_ctx* h, double sn2, double* out) {
+int sparse_queue_diag(gphip_sparse_ctx* h, double* out, int nb = 1, long ostride = 0) {
     gphip_ctx* b = h->b;
-    hipLaunchKernelGGL(sparse_diag_kernel<T>, dim3(1), dim3(256), 0, h->u->stream, (T*)b->dA.p, (int)b->R, (int)b->N, (int)b->Npad, sn2, out);
+    hipLaunchKernelGGL(sparse_diag_kernel<T>, dim3((unsigned)nb), dim3(256), 0, h->u->stream, (T*)b->dA.p, (long)b->slot_elems, (int)b->R,
+                       (int)b->N, (int)b->Npad, (const double*)h->dPar.as<double>() + 1, 2, out, ostride);
     return GPHIP_OK;
 }
 
@@ -220,22 +254,23 @@ int sparse_queue_partial(gphip_ctx* h, int64_t mpad, int* nstrips_out) {
     return GPHIP_OK;
 }
 
-// mean of k(z, z) over the inducing points of a run-time compiled kernel (the default jitter's scale); theta is on the device
-int sparse_mean_kzz(gphip_sparse_ctx* h, int64_t rows, double* out) {
+// mean of k(z, z) over the inducing points of a run-time compiled kernel (the default jitter's scale) for the thetas of the
+// first nb slots, which are on the device; out [nb]
+int sparse_mean_kzz(gphip_sparse_ctx* h, int64_t rows, double* out, int nb = 1) {
     gphip_ctx* u = h->u;
-    std::vector<double> k;
-    double s = 0.0;
+    std::vector<double> k, s((size_t)nb, 0.0);
     for (int64_t c0 = 0; c0 < u->N; c0 += rows) {
         const int64_t mc = std::min(rows, u->N - c0), mpad = (mc + TB - 1) / TB * TB;
         int rc = sparse_load_points(h, u->dXt.p, u->Npad, c0, mpad);
-        if (!rc) rc = queue_custom_kss(u, mc, mpad, 1);
+        if (!rc) rc = queue_custom_kss(u, mc, mpad, nb);
         if (rc) return rc == GPHIP_ERR_HIP && !u->err.empty() ? sfail(h, rc, u->err) : rc;
-        k.resize((size_t)mc);
-        HIPCHK(hipMemcpyAsync(k.data(), u->dKss.p, (size_t)mc * 8, hipMemcpyDeviceToHost, u->stream));
+        k.resize((size_t)nb * mpad);
+        HIPCHK(hipMemcpyAsync(k.data(), u->dKss.p, k.size() * 8, hipMemcpyDeviceToHost, u->stream));
         HIPCHK(hipStreamSynchronize(u->stream));
-        for (double v : k) s += v;
+        for (int q = 0; q < nb; ++q)
+            for (int64_t t = 0; t < mc; ++t) s[(size_t)q] += k[(size_t)q * mpad + t];
     }
-    *out = s / (double)u->N;
+    for (int q = 0; q < nb; ++q) out[q] = s[(size_t)q] / (double)u->N;
     return GPHIP_OK;
 }
 
@@ -372,7 +407,7 @@ int sparse_grad_phase(gphip_sparse_ctx* h, const SparseGradIn& in, std::vector<S
                 SparseScope ps(h, &recs, 2, u->stream);
                 queue_forward_fit(u, mpad);
             }
-            sparse_queue_resid<T>(h, c0, mc, mpad, in.mu, h->dSum.as<double>() + 1);       // (its sums of r^2 are not read again)
+            sparse_queue_resid<T>(h, c0, mc, mpad, h->dSum.as<double>() + 1);       // (mu is still in dPar; its sums of r^2 are not read again)
         }
         {
             SparseScope ps(h, &recs, 5, u->stream);
@@ -490,11 +525,8 @@ int sparse_eval(gphip_sparse_ctx* h, const double* theta, int p, double jitter, 
         if (rc) { (void)hipGetLastError(); return sfail(h, rc, "no device memory for the gradient's weights: " + b->err); }
     }
     h->last_chunk = rows;
-    if (rows > h->rcap) {
-        HIPCHK(h->dRz.grow((size_t)16 * rows * h->es));
-        HIPCHK(hipMemsetAsync(h->dRz.p, 0, (size_t)16 * rows * h->es, u->stream));
-        h->rcap = rows;
-    }
+    if ((rc = sparse_ensure_rz(h, 1, rows))) return rc;
+    if ((rc = sparse_ensure_par(h, 1))) return rc;
     double jit = jitter;
     if (jit < 0.0) {                           // default: joint_jitter_rel x k(x, x) (run-time compiled kernels: the mean of k(z, z))
         double scale = kxx;
@@ -513,6 +545,8 @@ int sparse_eval(gphip_sparse_ctx* h, const double* theta, int p, double jitter, 
     else sp[3] = pivot_tol_rel(u) * (std::fabs(kxx) + jit);
     if ((rc = copy_theta(u, 1))) return sfail(h, rc, u->err);
     HIPCHK(hipMemsetAsync(u->dInfo.p, 0, 4, u->stream));
+    h->hPar.as<double>()[0] = mu; h->hPar.as<double>()[1] = sn2;
+    if ((rc = sparse_copy_par(h, 1))) return rc;
     std::vector<SparsePhase> recs;
     int inf = 0;
     {
@@ -549,11 +583,11 @@ int sparse_eval(gphip_sparse_ctx* h, const double* theta, int p, double jitter, 
             SparseScope ps(h, &recs, 2, u->stream);
             queue_forward_fit(u, mpad);
         }
-        DISPATCH(h, sparse_queue_resid, h, c0, mc, mpad, mu, d_r2 + used);
+        DISPATCH(h, sparse_queue_resid, h, c0, mc, mpad, d_r2 + used);
         if (h->custom) {                       // k(x_i, x_i) per point for a run-time compiled kernel (u->dXsT still holds the chunk)
             if ((rc = queue_custom_kss(u, mc, mpad, 1))) return sfail(h, rc, u->err);
-            hipLaunchKernelGGL(sparse_blocksum_kernel, dim3((unsigned)((mpad + 255) / 256)), dim3(256), 0, u->stream, u->dKss.as<double>(), (int)mc,
-                               d_kk + used);
+            hipLaunchKernelGGL(sparse_blocksum_kernel, dim3((unsigned)((mpad + 255) / 256)), dim3(256), 0, u->stream, u->dKss.as<double>(), 0l,
+                               (int)mc, d_kk + used, 0l);
         }
         used += (size_t)((mpad + 255) / 256);
         {
@@ -561,7 +595,7 @@ int sparse_eval(gphip_sparse_ctx* h, const double* theta, int p, double jitter, 
             if ((rc = DISPATCH(h, sparse_queue_accumulate, h, mpad))) return rc;
         }
     }
-    DISPATCH(h, sparse_queue_diag, h, sn2, d_tr);
+    DISPATCH(h, sparse_queue_diag, h, d_tr);
     if (wants_grad) {                          // B itself, before its factorisation overwrites it (the B / (2 sn^2) term of H)
         HIPCHK(h->dBc.grow((size_t)b->slot_elems * h->es));
         HIPCHK(hipMemcpyAsync(h->dBc.p, b->dA.p, (size_t)b->slot_elems * h->es, hipMemcpyDeviceToDevice, u->stream));
@@ -596,6 +630,186 @@ int sparse_eval(gphip_sparse_ctx* h, const double* theta, int p, double jitter, 
     }
     sparse_harvest(h, recs);
     return rc;
+}
+
+// gphip_sparse_bound_batch (DESIGN.md section 8f): the bound for the B rows of Theta, one theta per workspace slot, group after
+// group.  Per group of nb rows: u builds and factors nb K_uu at once; every chunk of data points is loaded once and crossed,
+// substituted, reduced and accumulated for all nb slots by launches whose last grid index is the slot; b factors nb matrices B at
+// once.  No fit is left resident.  A row that fails keeps its slot (a non-finite theta is staged as stage_theta's stand-in values
+// with a unit nugget, so its slot factors) and only its own info / out.
+int sparse_eval_batch(gphip_sparse_ctx* h, const double* Theta, int B, int p, double jitter, double* out, double* parts, int* info) {
+    gphip_ctx *u = h->u, *b = h->b;
+    const double qnan = std::nan("");
+    h->fitted = false;
+    for (double& v : h->ms) v = 0.0;
+    HIPCHK(hipSetDevice(h->device));
+    // ---- the group: as many rows as u and b give slots, as keep 2048 data points of V per slot within the ~8 GiB of a chunk
+    const int64_t mpm = u->Npad;
+    const double budget = 8.0 * (1 << 30);
+    int want = (int)std::min<int64_t>(B, std::max<int64_t>(1, (int64_t)(budget / ((double)mpm * 2048 * h->es))));
+    if (h->batch_slots > 0) want = std::min(want, h->batch_slots);
+    int rc = ensure_slots(u, want);
+    if (rc) return sfail(h, rc, u->err);
+    if ((rc = ensure_slots(b, want))) return sfail(h, rc, b->err);
+    invalidate_fit(u);
+    invalidate_fit(b);
+    int G = std::min(want, std::min(u->slots, b->slots));
+    // rows of V per slot and pass: the chunk of all slots within the budget, at least 2048, at most the option / the data;
+    // halved while the buffer does not fit, then the group is
+    const int64_t cap = h->chunk > 0 ? std::min<int64_t>(((int64_t)h->chunk + TB - 1) / TB * TB, h->Npad) : h->Npad;
+    int64_t rows = (int64_t)(budget / ((double)G * mpm * h->es)) / TB * TB;
+    rows = std::min(std::max<int64_t>(rows, 2048), cap);
+    rc = ensure_vbuf(u, (int64_t)G * rows);
+    while (rc == GPHIP_ERR_HIP && (rows > 2048 || G > 1)) {
+        (void)hipGetLastError();
+        if (rows > 2048) rows = std::min(cap, std::max<int64_t>(2048, (rows / 2 + TB - 1) / TB * TB));
+        else G = (G + 1) / 2;
+        u->vcap = 0;
+        rc = ensure_vbuf(u, (int64_t)G * rows);
+    }
+    if (rc) { (void)hipGetLastError(); return sfail(h, rc, "no device memory for a chunk of V: " + u->err); }
+    h->last_chunk = rows;
+    if ((rc = sparse_ensure_rz(h, G, rows))) return rc;
+    if ((rc = sparse_ensure_par(h, G))) return rc;
+    // partial sums per slot: [0] the trace, then one per 256 data points of every chunk for r^2, then the same for k(x_i, x_i)
+    const int64_t nchunks = (h->N + rows - 1) / rows;
+    const size_t nblk = (size_t)(h->Npad / 256 + nchunks + 1), ss = 1 + 2 * nblk;
+    HIPCHK(h->dSum.grow((size_t)G * ss * 8));
+    std::vector<SparsePhase> recs;
+    std::vector<char> ok((size_t)G);
+    std::vector<double> sn2v((size_t)G), kxxv((size_t)G), jitv((size_t)G);
+    std::vector<int> uinfo((size_t)G);
+    for (int s0 = 0; s0 < B; s0 += G) {
+        const int nb = std::min(G, B - s0);
+        h->last_slots = nb;
+        double* par = h->hPar.as<double>();
+        for (int s = 0; s < nb; ++s) {
+            ok[(size_t)s] = stage_theta(u, s, Theta + (size_t)(s0 + s) * p);
+            const double* sp = u->hSlotp.as<double>() + (size_t)s * SLOTP;
+            sn2v[(size_t)s] = sp[1]; kxxv[(size_t)s] = sp[SP_KXX];
+            par[2 * s] = sp[2]; par[2 * s + 1] = sp[1];
+            jitv[(size_t)s] = jitter;
+        }
+        if (jitter < 0.0) {                    // default: joint_jitter_rel x the row's k(x, x) (run-time compiled kernels: its mean of k(z, z))
+            std::vector<double> scale(kxxv.begin(), kxxv.begin() + nb);
+            if (h->custom) {
+                if ((rc = copy_theta(u, nb))) return sfail(h, rc, u->err);
+                if ((rc = sparse_mean_kzz(h, rows, scale.data(), nb))) return rc;
+            }
+            for (int s = 0; s < nb; ++s) jitv[(size_t)s] = joint_jitter_rel(u) * scale[(size_t)s];
+        }
+        for (int s = 0; s < nb; ++s) {
+            double* sp = u->hSlotp.as<double>() + (size_t)s * SLOTP;
+            double jit = jitv[(size_t)s];
+            if (!std::isfinite(jit) || jit < 0.0) ok[(size_t)s] = 0;
+            if (ok[(size_t)s]) h->last_jitter = jit;
+            else jit = 1.0;                    // (the stand-in theta of a row that is given up: K_uu + I factors)
+            // u: the nugget slot carries the jitter; the pivot tolerance follows it
+            sp[1] = jit;
+            sp[SP_MFMA] = 0.0;
+            if (h->custom) sp[SP_SF2B] = jit;
+            else sp[3] = pivot_tol_rel(u) * (std::fabs(kxxv[(size_t)s]) + jit);
+        }
+        if ((rc = copy_theta(u, nb))) return sfail(h, rc, u->err);
+        HIPCHK(hipMemsetAsync(u->dInfo.p, 0, (size_t)nb * 4, u->stream));
+        if ((rc = sparse_copy_par(h, nb))) return rc;
+        {
+            SparseScope ps(h, &recs, 0, u->stream);
+            FactorMode mode(u, true);          // the forward substitutions that follow use the block inverses
+            u->theta_packed = false; u->fused_eval = false;
+            DISPATCH(u, queue_build, u, nb);
+            DISPATCH(u, queue_factor, u, nb);
+        }
+        u->abort_unread = "sparse GP: the factorisation of K_uu timed out (set option dataflow=0 and report)";
+        if ((rc = complete_call(u))) { sparse_harvest(h, recs); return sfail(h, rc, u->err); }
+        bool all_factored = true;
+        for (int s = 0; s < nb; ++s) {
+            uinfo[(size_t)s] = u->hInfo.as<int>()[s];
+            if (uinfo[(size_t)s] != 0) all_factored = false;
+        }
+        // b: empty bordered workspaces; the nugget scalar of slot s is sn_s^2, its pivot tolerance relative to sn_s^2
+        for (int s = 0; s < nb; ++s) {
+            const double sn2 = sn2v[(size_t)s];
+            const double thb[3] = {1.0, 1.0, std::sqrt(sn2)};
+            (void)stage_theta(b, s, thb);
+            double* spb = b->hSlotp.as<double>() + (size_t)s * SLOTP;
+            spb[1] = sn2; spb[3] = pivot_tol_rel(b) * sn2; spb[4] = 0.0; spb[SP_MFMA] = 0.0;
+        }
+        if ((rc = copy_theta(b, nb))) return sfail(h, rc, b->err);
+        HIPCHK(hipMemsetAsync(b->dInfo.p, 0, (size_t)nb * 4, b->stream));
+        HIPCHK(hipMemsetAsync(b->dA.p, 0, (size_t)nb * b->slot_elems * h->es, u->stream));
+        double* d_r2 = h->dSum.as<double>() + 1;
+        double* d_kk = d_r2 + nblk;
+        size_t used = 0;
+        for (int64_t c0 = 0; c0 < h->N; c0 += rows) {
+            const int64_t mc = std::min(rows, h->N - c0), mpad = (mc + TB - 1) / TB * TB;
+            {
+                SparseScope ps(h, &recs, 1, u->stream);
+                if ((rc = sparse_load_points(h, h->dXt.p, h->Npad, c0, mpad))) return rc;
+                DISPATCH(u, queue_cross, u, mc, mpad, nb);
+            }
+            {
+                // every slot's substitution in one pass: ONE dataflow launch (slot = row) where gphip_predict_samples would take it
+                // and every slot of the group has a factor (a slot whose factorisation was abandoned has no block inverses to hand
+                // to the launch's chain), else the batched GEMM substitution, which has no waits
+                SparseScope ps(h, &recs, 2, u->stream);
+                if (all_factored && samples_forward_df(u, nb, mpad)) launch_dataflow_inverse<double, 64>(u, mpad, false, nb, u->dW64s.p);
+                else DISPATCH(u, queue_forward_rows, u, mpad, nb);
+            }
+            DISPATCH(h, sparse_queue_resid, h, c0, mc, mpad, d_r2 + used, nb, (long)ss);
+            if (h->custom) {                   // k(x_i, x_i) per point and slot (u->dXsT still holds the chunk)
+                if ((rc = queue_custom_kss(u, mc, mpad, nb))) return sfail(h, rc, u->err);
+                hipLaunchKernelGGL(sparse_blocksum_kernel, dim3((unsigned)((mpad + 255) / 256), (unsigned)nb), dim3(256), 0, u->stream,
+                                   u->dKss.as<double>(), (long)mpad, (int)mc, d_kk + used, (long)ss);
+            }
+            used += (size_t)((mpad + 255) / 256);
+            {
+                SparseScope ps(h, &recs, 3, u->stream);
+                if ((rc = DISPATCH(h, sparse_queue_accumulate, h, mpad, nb))) return rc;
+            }
+        }
+        // a slot without a factor of K_uu accumulated whatever its V held: B = sn^2 I in its place, so that b factors numbers
+        for (int s = 0; s < nb; ++s)
+            if (uinfo[(size_t)s] != 0)
+                HIPCHK(hipMemsetAsync(static_cast<char*>(b->dA.p) + (size_t)s * b->slot_elems * h->es, 0, (size_t)b->slot_elems * h->es, u->stream));
+        DISPATCH(h, sparse_queue_diag, h, h->dSum.as<double>(), nb, (long)ss);
+        h->hSum.assign((size_t)nb * ss, 0.0);
+        HIPCHK(hipMemcpyAsync(h->hSum.data(), h->dSum.p, (size_t)nb * ss * 8, hipMemcpyDeviceToHost, u->stream));
+        if ((rc = complete_call(u))) { sparse_harvest(h, recs); return sfail(h, rc, u->err); }      // (the forward substitutions' abort word)
+        {
+            SparseScope ps(h, &recs, 4, b->stream);
+            FactorMode mode(b, false);         // (nothing substitutes with L_B here)
+            b->theta_packed = false; b->fused_eval = false;
+            DISPATCH(b, queue_factor, b, nb);
+        }
+        b->abort_unread = "sparse GP: the factorisation of B timed out (set option dataflow=0 and report)";
+        if ((rc = complete_call(b))) { sparse_harvest(h, recs); return sfail(h, rc, b->err); }
+        for (int s = 0; s < nb; ++s) {
+            const double* hs = h->hSum.data() + (size_t)s * ss;
+            const double sn2 = sn2v[(size_t)s];
+            const double logdet = b->hRes.as<double>()[2 * s], ctc = b->hRes.as<double>()[2 * s + 1];
+            double rtr = 0.0, skk = 0.0;
+            for (size_t k = 0; k < used; ++k) rtr += hs[1 + k];
+            if (h->custom) for (size_t k = 0; k < used; ++k) skk += hs[1 + nblk + k];
+            else skk = (double)h->N * kxxv[(size_t)s];
+            const double trvv = hs[0];
+            const double F = -0.5 * ((double)h->N * LOG_TWO_PI + (double)(h->N - h->m) * std::log(sn2) + logdet + (rtr - ctc) / sn2) -
+                             (skk - trvv) / (2.0 * sn2);
+            int inf = b->hInfo.as<int>()[s];
+            if (uinfo[(size_t)s] != 0) inf = uinfo[(size_t)s];                 // (a failure of u comes first)
+            if (!ok[(size_t)s]) inf = GPHIP_INFO_NAN;
+            else if (inf == 0 && !std::isfinite(F)) inf = GPHIP_INFO_NAN;
+            info[s0 + s] = inf;
+            out[s0 + s] = inf == 0 ? F : qnan;
+            if (parts) {
+                double* ps = parts + (size_t)(s0 + s) * 5;
+                ps[0] = logdet; ps[1] = ctc; ps[2] = rtr; ps[3] = trvv; ps[4] = skk;
+                if (inf != 0) for (int k = 0; k < 5; ++k) ps[k] = qnan;
+            }
+        }
+        sparse_harvest(h, recs);
+    }
+    return GPHIP_OK;
 }
 
 int sparse_create(const void* X, const void* y, int64_t N, int64_t d, const void* Z, int64_t m, int kernel_id, const char* body, int ncp,
@@ -688,6 +902,30 @@ int gphip_sparse_bound(gphip_sparse_handle h, const double* theta, int p, double
     if (!h || !theta || !out || !info) return sfail(h, GPHIP_ERR_ARG, "null argument");
     std::lock_guard<std::recursive_mutex> lk(h->mu);
     return sparse_eval(h, theta, p, jitter, out, parts, info);
+}
+
+int gphip_sparse_bound_batch(gphip_sparse_handle h, const double* Theta, int B, int p, double jitter, double* out, double* parts,
+                             int* info) {
+    if (!h || !Theta || !out || !info) return sfail(h, GPHIP_ERR_ARG, "null argument");
+    if (std::isnan(jitter) || std::isinf(jitter)) return sfail(h, GPHIP_ERR_ARG, "non-finite jitter");
+    std::lock_guard<std::recursive_mutex> lk(h->mu);
+    if (p != h->u->p) return sfail(h, GPHIP_ERR_DIM, "theta has the wrong length for this kernel/mean");
+    if (B <= 0) return GPHIP_OK;
+    return sparse_eval_batch(h, Theta, B, p, jitter, out, parts, info);
+}
+
+int gphip_sparse_nested_sampling(gphip_sparse_handle h, double jitter, const double* box, const int* prior_kind, gphip_logprior_fn logprior,
+                                 void* user, const gphip_ns_options* opts, const double* start, int64_t cap, double* points, double* loglik,
+                                 double* logprior_out, double* accept_rate, int64_t* n_samples, double* log_evidence, int64_t* n_evals) {
+    if (!h) return GPHIP_ERR_ARG;
+    if (std::isnan(jitter) || std::isinf(jitter)) return sfail(h, GPHIP_ERR_ARG, "non-finite jitter");
+    std::lock_guard<std::recursive_mutex> lk(h->mu);
+    return ns_run(h->u->p,
+                  [&](const double* Theta, int B, int p, double* out, int* info) {
+                      return gphip_sparse_bound_batch(h, Theta, B, p, jitter, out, nullptr, info);
+                  },
+                  [&](int code, const char* msg) { return sfail(h, code, msg); }, box, prior_kind, logprior, user, opts, start, cap, points,
+                  loglik, logprior_out, accept_rate, n_samples, log_evidence, n_evals);
 }
 
 int gphip_sparse_bound_grad(gphip_sparse_handle h, const double* theta, int p, double jitter, double* out, double* grad, double* parts,
@@ -799,6 +1037,7 @@ int gphip_sparse_set_option(gphip_sparse_handle h, const char* name, double valu
     if (!strcmp(name, "sparse_chunk")) { if (v < 0) return sfail(h, GPHIP_ERR_ARG, "sparse_chunk < 0"); h->chunk = v; return GPHIP_OK; }
     if (!strcmp(name, "sparse_split")) { if (v < 0) return sfail(h, GPHIP_ERR_ARG, "sparse_split < 0"); h->split = v; return GPHIP_OK; }
     if (!strcmp(name, "profile")) { h->profile = v; return GPHIP_OK; }
+    if (!strcmp(name, "sparse_batch_slots")) { if (v < 0) return sfail(h, GPHIP_ERR_ARG, "sparse_batch_slots < 0"); h->batch_slots = v; return GPHIP_OK; }
     int rc = gphip_set_option(h->u, name, value);
     if (!rc) rc = gphip_set_option(h->b, name, value);
     if (rc) return sfail(h, rc, "unknown option");
@@ -823,6 +1062,8 @@ int gphip_sparse_get_option(gphip_sparse_handle h, const char* name, double* val
     if (!strcmp(name, "grad_analytic")) { *value = h->grad_analytic; return GPHIP_OK; }
     if (!strcmp(name, "last_sparse_chunk")) { *value = (double)h->last_chunk; return GPHIP_OK; }
     if (!strcmp(name, "last_sparse_nsplit")) { *value = h->last_nsplit; return GPHIP_OK; }
+    if (!strcmp(name, "sparse_batch_slots")) { *value = h->batch_slots; return GPHIP_OK; }
+    if (!strcmp(name, "last_sparse_slots")) { *value = h->last_slots; return GPHIP_OK; }
     const int rc = gphip_get_option(h->u, name, value);
     return rc ? sfail(h, rc, "unknown option") : GPHIP_OK;
 }

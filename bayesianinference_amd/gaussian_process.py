@@ -816,7 +816,8 @@ def selectInducingPoints(X, m: int, seed: int = 0):
 
 def make_sparse_log_likelihood(handle: "_lib.SparseHandle", jitter: float = -1.0):
     """The closure for "LogLikelihoodFunction" of a sparse object: theta -> F(theta), the collapsed lower bound on the log
-    marginal likelihood; $MachineLogZero on numerical failure (info != 0), B x p -> B for a batch, like make_log_likelihood."""
+    marginal likelihood; $MachineLogZero on numerical failure (info != 0), B x p -> B for a batch, like make_log_likelihood.
+    A batch is ONE device call (SparseHandle.bound_batch), so every Metropolis step of nestedSampling is one call."""
     def one(theta):
         val, info = handle.bound(theta, jitter)
         if info != 0 or not math.isfinite(val):
@@ -826,7 +827,12 @@ def make_sparse_log_likelihood(handle: "_lib.SparseHandle", jitter: float = -1.0
     def log_likelihood(theta):
         theta = np.asarray(theta, dtype=np.float64)
         if theta.ndim == 2:
-            return np.array([one(t) for t in theta], dtype=np.float64)
+            if theta.shape[0] == 0:
+                return np.zeros(0, dtype=np.float64)
+            val, info = handle.bound_batch(theta, jitter)
+            val = np.asarray(val, dtype=np.float64)
+            bad = (np.asarray(info) != 0) | ~np.isfinite(val)
+            return np.where(bad, MACHINE_LOG_ZERO, np.clip(np.where(bad, 0.0, val), MACHINE_LOG_ZERO, -MACHINE_LOG_ZERO))
         return one(theta)
     return log_likelihood
 

@@ -523,11 +523,33 @@ int gphip_factor_bytes(gphip_handle h, int member, double* bytes);
  * dropped); every later result is the same bytes as that of a fresh object created with the new Z.  A changed m recreates the
  * two contexts.
  *
+ * gphip_sparse_bound_batch: the bound for the B rows of the row-major B x p array Theta in one call; row s has the semantics of
+ * gphip_sparse_bound(h, Theta + s p, p, jitter, ..): out[s] = F, parts (NULL or B x 5) as there, info[s] as there.  jitter < 0 is
+ * the default rule applied PER ROW (it scales with that row's k(x, x); run-time compiled kernels: that row's mean of k(z, z));
+ * "last_jitter" reads the last usable row's value.  A row that fails -- non-finite theta, a K_uu or a B that does not factor --
+ * sets only its own info[s] and gets out[s] (and its parts) NaN; the other rows of the call are not disturbed.  NULL h / Theta /
+ * out / info and a non-finite jitter are GPHIP_ERR_ARG, a wrong p GPHIP_ERR_DIM, B <= 0 returns GPHIP_OK and touches nothing.
+ * The rows are evaluated in groups, one theta per workspace slot: a group's K_uu are built and factored together, every chunk of
+ * data points is loaded once and crossed, substituted and accumulated for all slots of the group by launches that carry the slot
+ * as a grid dimension, and the group's B are factored together.  A group holds as many rows as the two
+ * contexts give slots, as keep 2048 data points of V per slot within the ~8 GiB of a chunk, and as option "sparse_batch_slots"
+ * allows.  The call drops any resident fit, as gphip_loglik_batch does: a following gphip_sparse_predict is GPHIP_ERR_STATE.
+ * Every row's sums run in a fixed order without atomics: two calls with the same arguments and options return the same bytes, and
+ * a row's bytes do not depend on its position in Theta while the group sizes stay the same.  Against gphip_sparse_bound of the
+ * same theta the result differs by rounding (the factorisations of several slots take another schedule).
+ *
+ * gphip_sparse_nested_sampling: gphip_nested_sampling (above) on a sparse object -- the same driver, arguments, outputs and seed
+ * behaviour, with F(theta; jitter) in the place of the log-likelihood: every Metropolis step is ONE gphip_sparse_bound_batch call
+ * of up to `walkers` rows at the given jitter (< 0: the default rule per row).  Errors go to gphip_sparse_last_error.
+ *
  * Options (gphip_sparse_set_option / gphip_sparse_get_option):
  *   "sparse_chunk"  data points per pass over V (rounded up to 128); 0 (default) = as many as keep the chunk of V within ~8 GiB,
  *                   at least 2048, halved while it does not fit.  "last_sparse_chunk" (read-only): what the last call used.
  *   "sparse_split"  strips the accumulation kernel cuts a chunk into; 0 (default) = by the split rule (output tiles x strips
- *                   >= two per CU).  "last_sparse_nsplit" (read-only): strips of the last chunk of the last call.
+ *                   >= two per CU; gphip_sparse_bound_batch: output tiles x slots x strips).  "last_sparse_nsplit" (read-only):
+ *                   strips of the last chunk of the last call (of its last group).
+ *   "sparse_batch_slots"  most rows gphip_sparse_bound_batch evaluates together in one group; 0 (default) = by the group rule
+ *                   above.  "last_sparse_slots" (read-only): rows in the last group of the last gphip_sparse_bound_batch.
  *   "profile"       0 / 1: time the phases of gphip_sparse_bound / _fit with HIP events; read-only milliseconds of the last call:
  *                   "ms_kuu_factor", "ms_cross", "ms_forward", "ms_accumulate", "ms_b_factor"; of gphip_sparse_bound_grad also
  *                   "ms_grad_small" (the m x m work and the vector w), "ms_grad_weights" (sparse_weight_kernel alone),
@@ -544,6 +566,12 @@ int gphip_sparse_destroy(gphip_sparse_handle h);
 int gphip_sparse_set_inducing(gphip_sparse_handle h, const void* Z, int64_t m);
 int gphip_sparse_num_params(gphip_sparse_handle h, int* p);
 int gphip_sparse_bound(gphip_sparse_handle h, const double* theta, int p, double jitter, double* out, double* parts, int* info);
+int gphip_sparse_bound_batch(gphip_sparse_handle h, const double* Theta, int B, int p, double jitter, double* out /* B */,
+                             double* parts /* NULL or B x 5 */, int* info /* B */);
+int gphip_sparse_nested_sampling(gphip_sparse_handle h, double jitter, const double* box, const int* prior_kind,
+                                 gphip_logprior_fn logprior, void* user, const gphip_ns_options* opts, const double* start, int64_t cap,
+                                 double* points, double* loglik, double* logprior_out, double* accept_rate, int64_t* n_samples,
+                                 double* log_evidence, int64_t* n_evals);
 int gphip_sparse_bound_grad(gphip_sparse_handle h, const double* theta, int p, double jitter, double* out, double* grad, double* parts,
                             int* info);
 int gphip_sparse_bound_grad_inducing(gphip_sparse_handle h, const double* theta, int p, double jitter, double* out,
