@@ -137,6 +137,9 @@ _SIGNATURES = {
     "gphip_sparse_bound_grad_inducing": (C.c_int, [_h, _dp, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _ip]),
     "gphip_sparse_fit": (C.c_int, [_h, _dp, C.c_int, C.c_double, _ip]),
     "gphip_sparse_predict": (C.c_int, [_h, C.c_void_p, C.c_int64, C.c_int, _dp, _dp]),
+    "gphip_sparse_predict_cov": (C.c_int, [_h, C.c_void_p, C.c_int64, C.c_int, _dp, _dp]),
+    "gphip_sparse_predict_draws": (C.c_int, [_h, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_uint64, _dp, C.c_double, _dp, _ip]),
+    "gphip_sparse_predict_logpdf": (C.c_int, [_h, C.c_void_p, C.c_int64, _dp, _dp, _ip]),
     "gphip_sparse_set_option": (C.c_int, [_h, C.c_char_p, C.c_double]),
     "gphip_sparse_get_option": (C.c_int, [_h, C.c_char_p, C.POINTER(C.c_double)]),
     "gphip_sparse_last_error": (C.c_char_p, [_h]),
@@ -662,6 +665,7 @@ SPARSE_PARTS = ("logdet_B", "ctc", "rtr", "tr_VVt", "sum_kxx")
 SPARSE_PHASES = ("ms_kuu_factor", "ms_cross", "ms_forward", "ms_accumulate", "ms_b_factor")
 SPARSE_GRAD_PHASES = ("ms_grad_small", "ms_grad_weights", "ms_grad_backward", "ms_grad_reduce")
 SPARSE_ZGRAD_PHASES = ("ms_grad_inducing",)
+SPARSE_JOINT_PHASES = ("ms_joint_v", "ms_joint_build", "ms_joint_downdate", "ms_joint_factor")
 
 
 class SparseHandle:
@@ -826,3 +830,46 @@ class SparseHandle:
         mean, var = np.zeros(M), np.zeros(M)
         self._check(self._lib.gphip_sparse_predict(self._h, Xs.ctypes.data, M, 1 if latent else 0, _d(mean), _d(var)))
         return mean, var
+
+    def _test_points(self, Xs):
+        Xs = np.ascontiguousarray(np.atleast_2d(np.asarray(Xs, dtype=np.float64)))
+        if Xs.shape[1] != self.d:
+            raise GphipError(2, "test points and data differ in dimension")
+        return Xs
+
+    def predict_cov(self, Xs, latent: bool = False):
+        """Joint predictive distribution at Xs[M, d] from the resident fit: (mean[M], cov[M, M]).  latent=False: covariance of
+        noisy observations (its diagonal is predict()'s var); latent=True: of the latent function.  The fit stays resident."""
+        Xs = self._test_points(Xs)
+        M = Xs.shape[0]
+        mean, cov = np.zeros(M), np.zeros((M, M))
+        self._check(self._lib.gphip_sparse_predict_cov(self._h, Xs.ctypes.data, M, int(bool(latent)), _d(mean), _d(cov)))
+        return mean, cov
+
+    def predict_draws(self, Xs, S: int, seed: int = 0, z=None, latent: bool = True, jitter: float = -1.0):
+        """S draws from the joint predictive distribution: (out[S, M], info).  z: the caller's standard normals [S, M]
+        (None: generated on the device from (seed, s, j)); jitter < 0: the library's default, 0: none."""
+        Xs = self._test_points(Xs)
+        M, S = Xs.shape[0], int(S)
+        zp = None
+        if z is not None:
+            z = np.ascontiguousarray(np.asarray(z, dtype=np.float64))
+            if z.shape != (S, M):
+                raise GphipError(2, f"z must have shape ({S}, {M})")
+            zp = _d(z)
+        out = np.zeros((max(S, 0), M))
+        info = C.c_int(0)
+        self._check(self._lib.gphip_sparse_predict_draws(self._h, Xs.ctypes.data, M, int(bool(latent)), S, int(seed) & (2**64 - 1), zp,
+                                                         float(jitter), _d(out), C.byref(info)))
+        return out, info.value
+
+    def predict_logpdf(self, Xs, ystar):
+        """log N(ystar | mean, cov) with the noisy-observation covariance at Xs: (value, info)."""
+        Xs = self._test_points(Xs)
+        M = Xs.shape[0]
+        ys = np.ascontiguousarray(np.asarray(ystar, dtype=np.float64).ravel())
+        if ys.shape != (M,):
+            raise GphipError(2, f"ystar must have length {M}")
+        out, info = C.c_double(0.0), C.c_int(0)
+        self._check(self._lib.gphip_sparse_predict_logpdf(self._h, Xs.ctypes.data, M, _d(ys), C.byref(out), C.byref(info)))
+        return out.value, info.value

@@ -1,9 +1,11 @@
 // gp_joint.h -- device kernels of the joint predictive path (gphip_predict_cov / _draws / _logpdf, gphip_joint.inc).
 //
 //   downdate_kernel         C -= [V; z^T] V^T on the lower tiles of a tile-major M x M workspace (the hot path)
+//                           (SEG: the two-segment form of the sparse object, C -= V1 V1^T - sn^2 V2 V2^T over a stacked index)
 //   downdate_reduce_kernel  C -= sum of the K-strip partials, strips added in a fixed order
 //   joint_unpack_kernel     lower tiles -> dense row-major M x M, both triangles (exactly symmetric)
 //   joint_rhs_kernel        the workspace's rhs row -> a vector
+//   joint_cblock_kernel     the sparse object's rhs-row operand: -c / sn^2 gathered from a factor's rhs tile row
 //   joint_normal_kernel     counter-based standard normals (Philox4x32-10, Box-Muller in fp64), keyed by (seed, s, j)
 //   joint_trmm_kernel       out = mean + Z L^T with L lower triangular in the tile-major factor
 #pragma once
@@ -22,6 +24,15 @@ namespace gphip {
 // downdate_reduce_kernel adds the strips in order -- no atomics, bit-repeatable.  nsplit = 1 (P null): the accumulators start
 // at C and take the negated J fragment, the epilogue is stores only (the trailing-SYRK form of gemm_nt_kernel).
 // Staging, MFMA shape and the software pipeline are gemm_nt_kernel's 2 x 2-wave, two-stage form.
+//
+// SEG (the sparse object's joint prediction, gphip_sparse.inc): the same pipeline over a STACKED contraction index of length
+// K = 2 kseg.  V is [V1 | V2], V1 = L_u^-1 k(Z, X*) in columns [0, kseg) and V2 = L_B^-1 V1 in columns [kseg, 2 kseg), and
+//     C -= V1 V1^T - sn^2 V2 V2^T,      rhs row -= c^T V2^T
+// A stage of GK columns lies in one segment (GK divides 128, kseg is a multiple of 128), so the segment's factor is a
+// wave-uniform scalar per stage: the J fragments take s1 in the first segment and s2 in the second -- one VALU multiply per J
+// fragment where the plain form has its negation.  The host sets (s1, s2) = (-1, +sn^2) when the accumulators start at C and
+// (+1, -sn^2) when the strip's product goes to a partial tile that downdate_reduce_kernel subtracts.  Z then is 128 x 2 kseg
+// with row 0 = 0 in the first segment and -c / sn^2 in the second, which serves both signs.  A strip may span the boundary.
 // ---------------------------------------------------------------------------------------------
 template <typename T>
 struct DowndateArgs {
@@ -34,6 +45,8 @@ struct DowndateArgs {
     int kstrip;                  // contraction columns per strip (multiple of 128)
     int K;                       // contraction length (Npad of the training points)
     T* P;                        // [strip][tile][128 x 128] partial tiles; null: C -= directly
+    int kseg;                    // SEG: columns of the first segment
+    T s1, s2;                    // SEG: factor of the J fragments in the first / second segment
 };
 
 template <typename T>
@@ -42,7 +55,7 @@ __device__ __forceinline__ void downdate_tile(int t, int ntri, int Mt, int& ti, 
     else { ti = Mt; tj = t - ntri; }
 }
 
-template <typename T>
+template <typename T, bool SEG = false>
 __global__ __launch_bounds__(256, 2) void downdate_kernel(DowndateArgs<T> g) {
     constexpr int FI = 4, FJ = 4;
     extern __shared__ double smem_raw[];
@@ -118,10 +131,11 @@ __global__ __launch_bounds__(256, 2) void downdate_kernel(DowndateArgs<T> g) {
     auto pipeline = [&](auto nyc) {
         constexpr int NY = decltype(nyc)::value;
         constexpr int NKK = GK / 4;
+        T sc = g.s1;                      // SEG: the factor of the stage the MFMAs are reading
         auto mfma_block = [&](const T* fi, const T* fj) {
             T nj[FJ];
 #pragma unroll
-            for (int f = 0; f < FJ; ++f) nj[f] = direct ? -fj[f] : fj[f];
+            for (int f = 0; f < FJ; ++f) nj[f] = SEG ? sc * fj[f] : (direct ? -fj[f] : fj[f]);
 #pragma unroll
             for (int x = 0; x < FJ; ++x)
 #pragma unroll
@@ -146,6 +160,7 @@ __global__ __launch_bounds__(256, 2) void downdate_kernel(DowndateArgs<T> g) {
         for (int kb = 0; kb < nk; ++kb) {
             const int cur = kb & 1;
             if (kb + 1 < nk) stage(cur ^ 1);
+            if (SEG) sc = k0 + (long)kb * GK < g.kseg ? g.s1 : g.s2;
             if (NY > 0) {
 #pragma unroll
                 for (int kk = 0; kk + 1 < NKK; ++kk) {
@@ -220,6 +235,14 @@ __global__ void joint_rhs_kernel(const T* __restrict__ C, int R, int M, const do
     if (j >= M) return;
     const double r = (double)C[tile_index(R - 1, j >> 7, R) * TS + (long)(j & 127) * TB];
     out[j] = (ystar ? ystar[j] : 0.0) - r;
+}
+
+// The sparse object's rhs-row operand: out[(k0 + j) * 128] = -c_j / sn2, j < npad, with c in row 0 of the rhs tile row of the
+// tile-major factor A (R tile rows).  out is a zeroed 128 x (k0 + npad) column-major block (ld 128).
+template <typename T>
+__global__ void joint_cblock_kernel(const T* __restrict__ A, int R, int npad, double sn2, T* __restrict__ out, long k0) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < npad) out[(k0 + j) * TB] = (T)(-(double)A[tile_index(R - 1, j >> 7, R) * TS + (long)(j & 127) * TB] / sn2);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -9,6 +9,8 @@
 //                                queue_factor        L_Sigma, log det Sigma, (y* - mu)^T Sigma^-1 (y* - mu)   (draws / logpdf)
 // The child is made on the first call and kept while M stays the same (its points and y are uploaded again per call); it dies
 // with the parent.  It never runs the fused single-launch evaluation (h->fused_eval: that one builds K inside the factorisation).
+// The sparse object (gphip_sparse.inc) owns such a child through its inducing-point context: joint_build, queue_downdate_any
+// and the joint_*_tail functions below take the owning context, whichever object it belongs to.
 #include "gp_joint.h"
 
 namespace {
@@ -79,33 +81,65 @@ int joint_mean_kss(gphip_ctx* h, int64_t M, int64_t mpad, double* out) {
 
 // C -= [V; z^T] V^T on the child's workspace.  Split rule: while the output tiles (incl. the rhs row) are fewer than two per CU,
 // the contraction is cut into strips of whole 128-columns so that tiles x strips >= 2 per CU; strips are equal but the last.
-template <typename T>
-int queue_downdate(gphip_ctx* h, gphip_ctx* c, int64_t mpad) {
+// SEG (the sparse object): h->dV holds [V1 | V2], the contraction runs over the stacked index of 2 x h->Npad columns and sn2
+// scales the second segment (gp_joint.h); split > 0 forces that many strips; *nsplit_out: the strips used.
+template <typename T, bool SEG>
+int queue_downdate_any(gphip_ctx* h, gphip_ctx* c, int64_t mpad, int split, int* nsplit_out, double sn2) {
     DowndateArgs<T> g{};
     g.C = (T*)c->dA.p; g.R = (int)c->R;
     g.V = (const T*)h->dV.p; g.ldv = (long)mpad; g.Z = (const T*)h->dJZ.p;
     g.Mt = (int)(mpad / TB); g.ntri = g.Mt * (g.Mt + 1) / 2; g.ntiles = g.ntri + g.Mt;
-    g.K = (int)h->Npad;
+    g.K = (int)(SEG ? 2 * h->Npad : h->Npad);
     const long target = 2l * std::max(h->ncu, 1);
-    const int kt = (int)h->Nt;
+    const int kt = (int)(SEG ? 2 * h->Nt : h->Nt);
     int nsplit = g.ntiles >= target ? 1 : (int)std::min<long>(kt, (target + g.ntiles - 1) / g.ntiles);
-    if (h->joint_split > 0) nsplit = std::min(h->joint_split, kt);
+    if (split > 0) nsplit = std::min(split, kt);
     const int strip_tiles = (kt + nsplit - 1) / nsplit;
     nsplit = (kt + strip_tiles - 1) / strip_tiles;
     g.kstrip = strip_tiles * TB;
-    h->joint_nsplit = nsplit;
+    *nsplit_out = nsplit;
     if (nsplit > 1) {
         HIPCHK(h->dJPart.grow((size_t)nsplit * g.ntiles * TS * sizeof(T)));
         g.P = (T*)h->dJPart.p;
     }
+    if (SEG) {                                 // accumulators that start at C take the update itself, a partial tile its negative
+        g.kseg = (int)h->Npad;
+        g.s1 = (T)(nsplit > 1 ? 1.0 : -1.0);
+        g.s2 = (T)(nsplit > 1 ? -sn2 : sn2);
+    }
     {
         // algorithmic flops M (M + 1) N (the lower triangle and the rhs row of an M x M downdate of contraction length N)
-        ProfScope ps(c, 4, (double)mpad * (mpad + 1) * (double)h->N, (double)sizeof(T) * (mpad + TB) * (double)h->Npad);
-        hipLaunchKernelGGL(downdate_kernel<T>, dim3((unsigned)g.ntiles, (unsigned)nsplit), dim3(256), GEMM_LDS, c->stream, g);
+        ProfScope ps(c, 4, (double)mpad * (mpad + 1) * (double)(SEG ? 2 * h->N : h->N), (double)sizeof(T) * (mpad + TB) * (double)g.K);
+        hipLaunchKernelGGL((downdate_kernel<T, SEG>), dim3((unsigned)g.ntiles, (unsigned)nsplit), dim3(256), GEMM_LDS, c->stream, g);
         if (nsplit > 1)
             hipLaunchKernelGGL(downdate_reduce_kernel<T>, dim3((unsigned)g.ntiles, 16), dim3(256), 0, c->stream, (T*)c->dA.p, (int)c->R,
                                g.ntri, g.Mt, g.ntiles, (const T*)g.P, nsplit);
     }
+    return GPHIP_OK;
+}
+template <typename T>
+int queue_downdate(gphip_ctx* h, gphip_ctx* c, int64_t mpad) {
+    return queue_downdate_any<T, false>(h, c, mpad, h->joint_split, &h->joint_nsplit, 0.0);
+}
+
+// The child of h (made by joint_child): K(X*, X*) at h's fitted theta with (noisy: sn^2) + (*jitter_io, which a negative value
+// turns into the default first; kss_mean: the mean of k(x*, x*) of a run-time compiled kernel) on the diagonal, rhs row
+// y* - m(X*), queued on the child's stream.
+int joint_build(gphip_ctx* h, bool noisy, double* jitter_io, double kss_mean) {
+    int rc;
+    gphip_ctx* c = h->joint;
+    HIPCHK(hipSetDevice(c->device));
+    invalidate_fit(c);
+    if (!stage_theta(c, 0, h->theta_fit.data())) return fail(h, GPHIP_ERR_ARG, "the fitted theta does not stage");
+    const double sn2 = c->hSlotp.as<double>()[1];
+    if (jitter_io && *jitter_io < 0.0)                // default jitter: relative to the prior variance k(x*, x*) + sn^2
+        *jitter_io = joint_jitter_rel(h) * ((h->custom ? kss_mean : c->hSlotp.as<double>()[SP_KXX]) + sn2);
+    c->hSlotp.as<double>()[1] = (noisy ? sn2 : 0.0) + (jitter_io ? *jitter_io : 0.0);
+    c->hSlotp.as<double>()[SP_MFMA] = 0.0;
+    if ((rc = copy_theta(c, 1))) return fail(h, rc, c->err.c_str());
+    HIPCHK(hipMemsetAsync(c->dInfo.p, 0, 4, c->stream));
+    c->theta_packed = false; c->fused_eval = false;      // (want_w / want_u: no FactorMode is ever open on the child)
+    DISPATCH(c, queue_build, c, 1);
     return GPHIP_OK;
 }
 
@@ -132,20 +166,8 @@ int joint_sigma(gphip_ctx* h, const double* Xs, int64_t M, const double* ystar, 
     if (jitter_io && *jitter_io < 0.0 && h->custom && (rc = joint_mean_kss(h, M, mpad, &kss_mean))) return rc;
     if ((rc = complete_call(h))) return rc;           // (the forward substitution's abort word)
     if ((rc = joint_child(h, Xs, M, ystar))) return rc;
-    gphip_ctx* c = h->joint;
-    HIPCHK(hipSetDevice(c->device));
-    invalidate_fit(c);
-    if (!stage_theta(c, 0, h->theta_fit.data())) return fail(h, GPHIP_ERR_ARG, "the fitted theta does not stage");
-    const double sn2 = c->hSlotp.as<double>()[1];
-    if (jitter_io && *jitter_io < 0.0)                // default jitter: relative to the prior variance k(x*, x*) + sn^2
-        *jitter_io = joint_jitter_rel(h) * ((h->custom ? kss_mean : c->hSlotp.as<double>()[SP_KXX]) + sn2);
-    c->hSlotp.as<double>()[1] = (noisy ? sn2 : 0.0) + (jitter_io ? *jitter_io : 0.0);
-    c->hSlotp.as<double>()[SP_MFMA] = 0.0;
-    if ((rc = copy_theta(c, 1))) return fail(h, rc, c->err.c_str());
-    HIPCHK(hipMemsetAsync(c->dInfo.p, 0, 4, c->stream));
-    c->theta_packed = false; c->fused_eval = false;      // (want_w / want_u: no FactorMode is ever open on the child)
-    DISPATCH(c, queue_build, c, 1);
-    return DISPATCH(h, queue_downdate, h, c, mpad);
+    if ((rc = joint_build(h, noisy, jitter_io, kss_mean))) return rc;
+    return DISPATCH(h, queue_downdate, h, h->joint, mpad);
 }
 
 // the child's rhs row -> out[M] (y* = 0: the predictive mean)
@@ -156,10 +178,12 @@ int queue_joint_rhs(gphip_ctx* c, int64_t M, double* out) {
     return GPHIP_OK;
 }
 
-// the child's factorisation; *info as gphip_loglik's
-int joint_factor(gphip_ctx* h, int* info) {
+// the child's factorisation; *info as gphip_loglik's (ev: two events to record around it on the child's stream, or null)
+int joint_factor(gphip_ctx* h, int* info, hipEvent_t* ev = nullptr) {
     gphip_ctx* c = h->joint;
+    if (ev) (void)hipEventRecord(ev[0], c->stream);
     DISPATCH(c, queue_factor, c, 1);
+    if (ev) (void)hipEventRecord(ev[1], c->stream);
     c->abort_unread = "joint prediction: the factorisation of Sigma timed out (set option dataflow=0 and report)";
     const int rc = complete_call(c);
     if (rc) return fail(h, rc, c->err.c_str());
@@ -173,25 +197,8 @@ int joint_download(gphip_ctx* h, gphip_ctx* c, double* dst, const double* src, s
     return rc ? fail(h, rc, c->err.c_str()) : GPHIP_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int gphip_predict_cov(gphip_handle h, const void* Xs, int64_t M, int latent, double* mean, double* cov) {
-    if (!h || !Xs || !mean || !cov) return fail(h, GPHIP_ERR_ARG, "null argument");
-    if (int rc = joint_dim_check(h, M)) return rc;
-    std::lock_guard<std::recursive_mutex> lk(h->mu);
-    if (int rc = joint_common_checks(h)) return rc;
-    if (h->null_fit) {                             // null kernel: k = 0, Sigma = diag(nugget) (latent: 0)
-        for (int64_t i = 0; i < M; ++i) {
-            mean[i] = h->mu_fit;
-            for (int64_t j = 0; j < M; ++j) cov[i * M + j] = (i == j && !latent) ? h->kappa_fit : 0.0;
-        }
-        return GPHIP_OK;
-    }
-    const double* X = static_cast<const double*>(Xs);
-    int rc = joint_sigma(h, X, M, nullptr, !latent, nullptr);
-    if (rc) return rc;
+// Sigma and the rhs row in h's child -> dense cov [M][M] (both triangles) and mean [M] on the host
+int joint_cov_tail(gphip_ctx* h, int64_t M, double* mean, double* cov) {
     gphip_ctx* c = h->joint;
     HIPCHK(h->dJOut.grow(((size_t)M * M + (size_t)M) * 8));
     const long n = (long)M * M;
@@ -207,45 +214,16 @@ int gphip_predict_cov(gphip_handle h, const void* Xs, int64_t M, int latent, dou
     return joint_download(h, c, cov, h->dJOut.as<double>(), (size_t)n);
 }
 
-int gphip_predict_draws(gphip_handle h, const void* Xs, int64_t M, int latent, int S, uint64_t seed, const double* z, double jitter,
-                        double* out, int* info) {
-    if (!h || !Xs || !out || !info) return fail(h, GPHIP_ERR_ARG, "null argument");
-    if (!std::isfinite(jitter)) return fail(h, GPHIP_ERR_ARG, "non-finite jitter");
-    if (int rc = joint_dim_check(h, M)) return rc;
-    if (S < 1) return fail(h, GPHIP_ERR_DIM, "S < 1");
-    std::lock_guard<std::recursive_mutex> lk(h->mu);
-    if (int rc = joint_common_checks(h)) return rc;
-    *info = GPHIP_INFO_OK;
+// Sigma (+ jitter) and the rhs row (-mu, y* = 0) in h's child -> S draws [S][M] on the host; *info as gphip_predict_draws'
+int joint_draws_tail(gphip_ctx* h, int64_t M, int S, uint64_t seed, const double* z, double* out, int* info, hipEvent_t* ev = nullptr) {
     const size_t total = (size_t)S * (size_t)M;
-    if (h->null_fit) {                             // Sigma = diag(nugget) (latent: 0) + jitter: independent draws
-        const double jit = jitter < 0.0 ? joint_jitter_rel(h) * h->kappa_fit : jitter;
-        const double v = (latent ? 0.0 : h->kappa_fit) + jit;
-        if (!(v > 0.0)) {
-            *info = GPHIP_INFO_NOT_SPD;
-            for (size_t e = 0; e < total; ++e) out[e] = NAN;
-            return GPHIP_OK;
-        }
-        const double sd = std::sqrt(v);
-        for (int s = 0; s < S; ++s)
-            for (int64_t j = 0; j < M; ++j) {
-                const double zz = z ? z[(size_t)s * M + j] : philox_normal(seed, (uint32_t)s, (uint32_t)j);
-                out[(size_t)s * M + j] = h->mu_fit + sd * zz;
-            }
-        for (size_t e = 0; e < total; ++e)
-            if (!std::isfinite(out[e])) *info = GPHIP_INFO_NAN;
-        return GPHIP_OK;
-    }
-    const double* X = static_cast<const double*>(Xs);
-    double jit = jitter;
-    int rc = joint_sigma(h, X, M, nullptr, !latent, &jit);
-    if (rc) return rc;
     gphip_ctx* c = h->joint;
     const int64_t mpad = (M + TB - 1) / TB * TB;
     // the mean (rhs row = -mu with y* = 0) before the factorisation overwrites that row
     HIPCHK(h->dJOut.grow((size_t)mpad * 8));
     DISPATCH(c, queue_joint_rhs, c, M, h->dJOut.as<double>());
-    int inf = 0;
-    if ((rc = joint_factor(h, &inf))) return rc;
+    int inf = 0, rc;
+    if ((rc = joint_factor(h, &inf, ev))) return rc;
     if (inf != 0) {
         *info = inf;
         for (size_t e = 0; e < total; ++e) out[e] = NAN;
@@ -287,6 +265,74 @@ int gphip_predict_draws(gphip_handle h, const void* Xs, int64_t M, int latent, i
     return GPHIP_OK;
 }
 
+// Sigma (noisy) and the rhs row y* - mu in h's child -> the joint log density
+int joint_logpdf_tail(gphip_ctx* h, int64_t M, double* out, int* info, hipEvent_t* ev = nullptr) {
+    int inf = 0;
+    if (const int rc = joint_factor(h, &inf, ev)) return rc;
+    const gphip_ctx* c = h->joint;
+    const double logdet = c->hRes.as<double>()[0], quad = c->hRes.as<double>()[1];
+    *out = -0.5 * ((double)M * LOG_TWO_PI + logdet + quad);
+    *info = inf != 0 ? inf : (std::isfinite(*out) ? GPHIP_INFO_OK : GPHIP_INFO_NAN);
+    return GPHIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gphip_predict_cov(gphip_handle h, const void* Xs, int64_t M, int latent, double* mean, double* cov) {
+    if (!h || !Xs || !mean || !cov) return fail(h, GPHIP_ERR_ARG, "null argument");
+    if (int rc = joint_dim_check(h, M)) return rc;
+    std::lock_guard<std::recursive_mutex> lk(h->mu);
+    if (int rc = joint_common_checks(h)) return rc;
+    if (h->null_fit) {                             // null kernel: k = 0, Sigma = diag(nugget) (latent: 0)
+        for (int64_t i = 0; i < M; ++i) {
+            mean[i] = h->mu_fit;
+            for (int64_t j = 0; j < M; ++j) cov[i * M + j] = (i == j && !latent) ? h->kappa_fit : 0.0;
+        }
+        return GPHIP_OK;
+    }
+    const double* X = static_cast<const double*>(Xs);
+    int rc = joint_sigma(h, X, M, nullptr, !latent, nullptr);
+    if (rc) return rc;
+    return joint_cov_tail(h, M, mean, cov);
+}
+
+int gphip_predict_draws(gphip_handle h, const void* Xs, int64_t M, int latent, int S, uint64_t seed, const double* z, double jitter,
+                        double* out, int* info) {
+    if (!h || !Xs || !out || !info) return fail(h, GPHIP_ERR_ARG, "null argument");
+    if (!std::isfinite(jitter)) return fail(h, GPHIP_ERR_ARG, "non-finite jitter");
+    if (int rc = joint_dim_check(h, M)) return rc;
+    if (S < 1) return fail(h, GPHIP_ERR_DIM, "S < 1");
+    std::lock_guard<std::recursive_mutex> lk(h->mu);
+    if (int rc = joint_common_checks(h)) return rc;
+    *info = GPHIP_INFO_OK;
+    const size_t total = (size_t)S * (size_t)M;
+    if (h->null_fit) {                             // Sigma = diag(nugget) (latent: 0) + jitter: independent draws
+        const double jit = jitter < 0.0 ? joint_jitter_rel(h) * h->kappa_fit : jitter;
+        const double v = (latent ? 0.0 : h->kappa_fit) + jit;
+        if (!(v > 0.0)) {
+            *info = GPHIP_INFO_NOT_SPD;
+            for (size_t e = 0; e < total; ++e) out[e] = NAN;
+            return GPHIP_OK;
+        }
+        const double sd = std::sqrt(v);
+        for (int s = 0; s < S; ++s)
+            for (int64_t j = 0; j < M; ++j) {
+                const double zz = z ? z[(size_t)s * M + j] : philox_normal(seed, (uint32_t)s, (uint32_t)j);
+                out[(size_t)s * M + j] = h->mu_fit + sd * zz;
+            }
+        for (size_t e = 0; e < total; ++e)
+            if (!std::isfinite(out[e])) *info = GPHIP_INFO_NAN;
+        return GPHIP_OK;
+    }
+    const double* X = static_cast<const double*>(Xs);
+    double jit = jitter;
+    int rc = joint_sigma(h, X, M, nullptr, !latent, &jit);
+    if (rc) return rc;
+    return joint_draws_tail(h, M, S, seed, z, out, info);
+}
+
 int gphip_predict_logpdf(gphip_handle h, const void* Xs, int64_t M, const double* ystar, double* out, int* info) {
     if (!h || !Xs || !ystar || !out || !info) return fail(h, GPHIP_ERR_ARG, "null argument");
     if (int rc = joint_dim_check(h, M)) return rc;
@@ -304,13 +350,7 @@ int gphip_predict_logpdf(gphip_handle h, const void* Xs, int64_t M, const double
     }
     int rc = joint_sigma(h, static_cast<const double*>(Xs), M, ystar, true, nullptr);
     if (rc) return rc;
-    int inf = 0;
-    if ((rc = joint_factor(h, &inf))) return rc;
-    const gphip_ctx* c = h->joint;
-    const double logdet = c->hRes.as<double>()[0], quad = c->hRes.as<double>()[1];
-    *out = -0.5 * ((double)M * LOG_TWO_PI + logdet + quad);
-    *info = inf != 0 ? inf : (std::isfinite(*out) ? GPHIP_INFO_OK : GPHIP_INFO_NAN);
-    return GPHIP_OK;
+    return joint_logpdf_tail(h, M, out, info);
 }
 
 }  // extern "C"

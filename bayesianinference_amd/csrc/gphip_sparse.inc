@@ -21,6 +21,11 @@
 //   sparse_zgrad_finish_kernel adds the strip partials, H first and then chunk after chunk, into the m x d accumulator dZacc
 // Prediction: v1 = L_u^-1 k(Z, x*) by u's forward substitution, v2 = L_B^-1 v1 by b's, predict_partial_kernel on both and one
 // finishing kernel.  Everything of one evaluation up to B runs on u's stream; b's stream takes over after a host synchronisation.
+// Joint prediction (gphip_sparse_predict_cov / _draws / _logpdf, DESIGN.md section 8g): all M rows of V1 = L_u^-1 k(Z, X*) and
+//   V2 = L_B^-1 V1 side by side in u's dV, the rhs-row operand -c / sn^2 in u's dJZ; u owns the child context of the exact
+//   path (u->joint, gphip_joint.inc: training points X*, K(X*, X*) by the direct build) and the two-segment downdate_kernel turns
+//   the child's workspace into Sigma = K(X*, X*) - V1^T V1 + sn^2 V2^T V2 and its rhs row into y* - mu.  Cov, draws and the log
+//   density then are the exact path's own code on that child.
 #include "gp_sparse.h"
 
 struct gphip_sparse_ctx {
@@ -45,15 +50,18 @@ struct gphip_sparse_ctx {
     Buf dGw;                                   // gradient, double: [0] tr B^-1, [1] a^T a, per-block sums of w, w of a chunk, strip partials of V^T a
     // options
     int chunk = 0, split = 0, profile = 0;
+    int joint_split = 0;                       // joint prediction: strips of the stacked contraction (0 = by the split rule)
     int batch_slots = 0;                       // gphip_sparse_bound_batch: most thetas per group (0 = by the group rule)
     // read-only results of the last call
     int last_nsplit = 0;
+    int joint_nsplit = 0;                      // strips the last joint prediction's downdate used
     int last_slots = 0;                        // thetas in the last group of the last gphip_sparse_bound_batch
     int64_t last_chunk = 0;
     double last_jitter = 0.0;
     int grad_analytic = 0;                     // the last gphip_sparse_bound_grad: 1 = the analytic route, 0 = central differences
-    double ms[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};    // K_uu factor, cross build, forward substitution, accumulation, B factor;
-                                               // gradient: small m x m work, weights, backward substitution, reductions, the reduction in Z
+    double ms[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};    // K_uu factor, cross build, forward substitution, accumulation, B factor;
+                                               // gradient: small m x m work, weights, backward substitution, reductions, the reduction in Z;
+                                               // joint prediction: V1 and V2, K(X*, X*), the downdate, the factorisation of Sigma
     // the resident fit
     bool fitted = false;
     double sn2_fit = 0, mu_fit = 0, kxx_fit = 0;
@@ -497,7 +505,7 @@ int sparse_eval(gphip_sparse_ctx* h, const double* theta, int p, double jitter, 
     if (gradZ) for (int64_t k = 0; k < h->m * h->d; ++k) gradZ[k] = qnan;
     const bool wants_grad = grad || gradZ;
     h->fitted = false;
-    for (double& v : h->ms) v = 0.0;
+    for (int k = 0; k < 10; ++k) h->ms[k] = 0.0;
     for (int k = 0; k < p; ++k)
         if (!std::isfinite(theta[k])) return give_up(GPHIP_INFO_NAN);
     HIPCHK(hipSetDevice(h->device));
@@ -641,7 +649,7 @@ int sparse_eval_batch(gphip_sparse_ctx* h, const double* Theta, int B, int p, do
     gphip_ctx *u = h->u, *b = h->b;
     const double qnan = std::nan("");
     h->fitted = false;
-    for (double& v : h->ms) v = 0.0;
+    for (int k = 0; k < 10; ++k) h->ms[k] = 0.0;
     HIPCHK(hipSetDevice(h->device));
     // ---- the group: as many rows as u and b give slots, as keep 2048 data points of V per slot within the ~8 GiB of a chunk
     const int64_t mpm = u->Npad;
@@ -847,6 +855,87 @@ int sparse_create(const void* X, const void* y, int64_t N, int64_t d, const void
     return GPHIP_OK;
 }
 
+
+// ---- joint prediction (DESIGN.md section 8g)
+
+int sparse_joint_dim_check(gphip_sparse_ctx* h, int64_t M) {
+    if (M < 1) return sfail(h, GPHIP_ERR_DIM, "M < 1");
+    if (M > JOINT_MAX_M) return sfail(h, GPHIP_ERR_DIM, "M above GPHIP_JOINT_MAX_M (all rows of V1 and V2 must be resident at once)");
+    return GPHIP_OK;
+}
+
+int sparse_joint_state_check(gphip_sparse_ctx* h) {
+    if (!h->fitted || !has_fit(h->u) || !has_fit(h->b)) return sfail(h, GPHIP_ERR_STATE, "joint prediction before a successful gphip_sparse_fit");
+    return GPHIP_OK;
+}
+
+// Everything up to Sigma in the workspace of u's child: V1 on u, V2 and the rhs-row operand on b, then build + downdate on the
+// child.  The child's diagonal carries k(x*, x*) + (noisy: sn^2) + (*jitter_io, which a negative value turns into the default).
+int sparse_joint_sigma(gphip_sparse_ctx* h, const double* Xs, int64_t M, const double* ystar, bool noisy, double* jitter_io,
+                       std::vector<SparsePhase>& recs) {
+    gphip_ctx *u = h->u, *b = h->b;
+    HIPCHK(hipSetDevice(h->device));
+    for (int k = 10; k < 14; ++k) h->ms[k] = 0.0;
+    const int64_t mpad = (M + TB - 1) / TB * TB, kseg = u->Npad;
+    const size_t seg_bytes = (size_t)mpad * kseg * h->es;
+    int rc = ensure_vbuf(u, 2 * mpad);         // u's dV takes both segments: [V1 | V2], mpad x 2 kseg with ld mpad
+    if (!rc) rc = ensure_vbuf(b, mpad);
+    if (rc) { (void)hipGetLastError(); return sfail(h, GPHIP_ERR_HIP, "joint prediction: no device memory for all M rows of V1 and V2"); }
+    HIPCHK(u->dJZ.grow((size_t)TB * 2 * kseg * h->es));
+    HIPCHK(hipMemsetAsync(u->dJZ.p, 0, (size_t)TB * 2 * kseg * h->es, u->stream));
+    std::vector<double> xt;
+    {
+        SparseScope ps(h, &recs, 10, u->stream);
+        stage_test_chunk(u, Xs, 0, M, 1, 0, xt, &rc, false);      // all M rows as one chunk
+        if (rc) return sfail(h, rc, u->err);
+        queue_forward_fit(u, mpad);
+    }
+    double kss_mean = 0.0;                     // (run-time compiled kernels: k(x*, x*) is a function of the point)
+    if (jitter_io && *jitter_io < 0.0 && h->custom && (rc = joint_mean_kss(u, M, mpad, &kss_mean))) return sfail(h, rc, u->err);
+    if ((rc = complete_call(u))) return sfail(h, rc, u->err);
+    {
+        // V2 = L_B^-1 V1: the same rows through b's factor, then next to V1; the rhs-row operand from b's rhs row
+        SparseScope ps(h, &recs, 10, b->stream);
+        HIPCHK(hipMemcpyAsync(b->dV.p, u->dV.p, seg_bytes, hipMemcpyDeviceToDevice, b->stream));
+        queue_forward_fit(b, mpad);
+        HIPCHK(hipMemcpyAsync(static_cast<char*>(u->dV.p) + seg_bytes, b->dV.p, seg_bytes, hipMemcpyDeviceToDevice, b->stream));
+        const dim3 grid((unsigned)((kseg + 255) / 256));
+        if (h->dtype == 64)
+            hipLaunchKernelGGL(joint_cblock_kernel<double>, grid, dim3(256), 0, b->stream, (const double*)b->dA.p, (int)b->R, (int)kseg,
+                               h->sn2_fit, (double*)u->dJZ.p, (long)kseg);
+        else
+            hipLaunchKernelGGL(joint_cblock_kernel<float>, grid, dim3(256), 0, b->stream, (const float*)b->dA.p, (int)b->R, (int)kseg,
+                               h->sn2_fit, (float*)u->dJZ.p, (long)kseg);
+    }
+    if ((rc = complete_call(b))) return sfail(h, rc, b->err);
+    if ((rc = joint_child(u, Xs, M, ystar))) return sfail(h, rc, u->err);
+    gphip_ctx* c = u->joint;
+    {
+        SparseScope ps(h, &recs, 11, c->stream);
+        rc = joint_build(u, noisy, jitter_io, kss_mean);
+    }
+    if (rc) return sfail(h, rc, u->err);
+    {
+        SparseScope ps(h, &recs, 12, c->stream);
+        rc = h->dtype == 64 ? queue_downdate_any<double, true>(u, c, mpad, h->joint_split, &h->joint_nsplit, h->sn2_fit)
+                            : queue_downdate_any<float, true>(u, c, mpad, h->joint_split, &h->joint_nsplit, h->sn2_fit);
+    }
+    return rc ? sfail(h, rc, u->err) : GPHIP_OK;
+}
+
+// the event pair of the factorisation of Sigma while option "profile" is on (phase 13)
+struct SparseFactorEvents {
+    hipEvent_t ev[2];
+    bool on;
+    SparseFactorEvents(gphip_sparse_ctx* h) : on(h->profile > 0) {
+        if (on) { ev[0] = get_event(h->u); ev[1] = get_event(h->u); }
+    }
+    hipEvent_t* get() { return on ? ev : nullptr; }
+    void hand_over(std::vector<SparsePhase>& recs) {
+        if (on) recs.push_back(SparsePhase{13, ev[0], ev[1]});
+    }
+};
+
 }  // namespace
 
 extern "C" {
@@ -1030,6 +1119,53 @@ int gphip_sparse_predict(gphip_sparse_handle h, const void* Xs, int64_t M, int l
     return GPHIP_OK;
 }
 
+int gphip_sparse_predict_cov(gphip_sparse_handle h, const void* Xs, int64_t M, int latent, double* mean, double* cov) {
+    if (!h || !Xs || !mean || !cov) return sfail(h, GPHIP_ERR_ARG, "null argument");
+    if (int rc = sparse_joint_dim_check(h, M)) return rc;
+    std::lock_guard<std::recursive_mutex> lk(h->mu);
+    if (int rc = sparse_joint_state_check(h)) return rc;
+    std::vector<SparsePhase> recs;
+    int rc = sparse_joint_sigma(h, static_cast<const double*>(Xs), M, nullptr, !latent, nullptr, recs);
+    if (!rc && (rc = joint_cov_tail(h->u, M, mean, cov))) (void)sfail(h, rc, h->u->err);
+    sparse_harvest(h, recs);
+    return rc;
+}
+
+int gphip_sparse_predict_draws(gphip_sparse_handle h, const void* Xs, int64_t M, int latent, int S, uint64_t seed, const double* z,
+                               double jitter, double* out, int* info) {
+    if (!h || !Xs || !out || !info) return sfail(h, GPHIP_ERR_ARG, "null argument");
+    if (!std::isfinite(jitter)) return sfail(h, GPHIP_ERR_ARG, "non-finite jitter");
+    if (int rc = sparse_joint_dim_check(h, M)) return rc;
+    if (S < 1) return sfail(h, GPHIP_ERR_DIM, "S < 1");
+    std::lock_guard<std::recursive_mutex> lk(h->mu);
+    if (int rc = sparse_joint_state_check(h)) return rc;
+    *info = GPHIP_INFO_OK;
+    std::vector<SparsePhase> recs;
+    SparseFactorEvents fev(h);
+    double jit = jitter;
+    int rc = sparse_joint_sigma(h, static_cast<const double*>(Xs), M, nullptr, !latent, &jit, recs);
+    if (!rc && (rc = joint_draws_tail(h->u, M, S, seed, z, out, info, fev.get()))) (void)sfail(h, rc, h->u->err);
+    fev.hand_over(recs);
+    sparse_harvest(h, recs);
+    return rc;
+}
+
+int gphip_sparse_predict_logpdf(gphip_sparse_handle h, const void* Xs, int64_t M, const double* ystar, double* out, int* info) {
+    if (!h || !Xs || !ystar || !out || !info) return sfail(h, GPHIP_ERR_ARG, "null argument");
+    if (int rc = sparse_joint_dim_check(h, M)) return rc;
+    std::lock_guard<std::recursive_mutex> lk(h->mu);
+    if (int rc = sparse_joint_state_check(h)) return rc;
+    for (int64_t j = 0; j < M; ++j)
+        if (!std::isfinite(ystar[j])) { *out = NAN; *info = GPHIP_INFO_NAN; return GPHIP_OK; }
+    std::vector<SparsePhase> recs;
+    SparseFactorEvents fev(h);
+    int rc = sparse_joint_sigma(h, static_cast<const double*>(Xs), M, ystar, true, nullptr, recs);
+    if (!rc && (rc = joint_logpdf_tail(h->u, M, out, info, fev.get()))) (void)sfail(h, rc, h->u->err);
+    fev.hand_over(recs);
+    sparse_harvest(h, recs);
+    return rc;
+}
+
 int gphip_sparse_set_option(gphip_sparse_handle h, const char* name, double value) {
     if (!h || !name) return GPHIP_ERR_ARG;
     std::lock_guard<std::recursive_mutex> lk(h->mu);
@@ -1037,6 +1173,7 @@ int gphip_sparse_set_option(gphip_sparse_handle h, const char* name, double valu
     if (!strcmp(name, "sparse_chunk")) { if (v < 0) return sfail(h, GPHIP_ERR_ARG, "sparse_chunk < 0"); h->chunk = v; return GPHIP_OK; }
     if (!strcmp(name, "sparse_split")) { if (v < 0) return sfail(h, GPHIP_ERR_ARG, "sparse_split < 0"); h->split = v; return GPHIP_OK; }
     if (!strcmp(name, "profile")) { h->profile = v; return GPHIP_OK; }
+    if (!strcmp(name, "sparse_joint_split")) { if (v < 0) return sfail(h, GPHIP_ERR_ARG, "sparse_joint_split < 0"); h->joint_split = v; return GPHIP_OK; }
     if (!strcmp(name, "sparse_batch_slots")) { if (v < 0) return sfail(h, GPHIP_ERR_ARG, "sparse_batch_slots < 0"); h->batch_slots = v; return GPHIP_OK; }
     int rc = gphip_set_option(h->u, name, value);
     if (!rc) rc = gphip_set_option(h->b, name, value);
@@ -1051,9 +1188,10 @@ int gphip_sparse_set_option(gphip_sparse_handle h, const char* name, double valu
 int gphip_sparse_get_option(gphip_sparse_handle h, const char* name, double* value) {
     if (!h || !name || !value) return GPHIP_ERR_ARG;
     std::lock_guard<std::recursive_mutex> lk(h->mu);
-    static const char* const phases[10] = {"ms_kuu_factor", "ms_cross", "ms_forward", "ms_accumulate", "ms_b_factor",
-                                           "ms_grad_small", "ms_grad_weights", "ms_grad_backward", "ms_grad_reduce", "ms_grad_inducing"};
-    for (int k = 0; k < 10; ++k)
+    static const char* const phases[14] = {"ms_kuu_factor", "ms_cross", "ms_forward", "ms_accumulate", "ms_b_factor",
+                                           "ms_grad_small", "ms_grad_weights", "ms_grad_backward", "ms_grad_reduce", "ms_grad_inducing",
+                                           "ms_joint_v", "ms_joint_build", "ms_joint_downdate", "ms_joint_factor"};
+    for (int k = 0; k < 14; ++k)
         if (!strcmp(name, phases[k])) { *value = h->ms[k]; return GPHIP_OK; }
     if (!strcmp(name, "sparse_chunk")) { *value = h->chunk; return GPHIP_OK; }
     if (!strcmp(name, "sparse_split")) { *value = h->split; return GPHIP_OK; }
@@ -1064,6 +1202,8 @@ int gphip_sparse_get_option(gphip_sparse_handle h, const char* name, double* val
     if (!strcmp(name, "last_sparse_nsplit")) { *value = h->last_nsplit; return GPHIP_OK; }
     if (!strcmp(name, "sparse_batch_slots")) { *value = h->batch_slots; return GPHIP_OK; }
     if (!strcmp(name, "last_sparse_slots")) { *value = h->last_slots; return GPHIP_OK; }
+    if (!strcmp(name, "sparse_joint_split")) { *value = h->joint_split; return GPHIP_OK; }
+    if (!strcmp(name, "last_sparse_joint_nsplit")) { *value = h->joint_nsplit; return GPHIP_OK; }
     const int rc = gphip_get_option(h->u, name, value);
     return rc ? sfail(h, rc, "unknown option") : GPHIP_OK;
 }

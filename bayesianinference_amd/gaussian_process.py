@@ -579,12 +579,18 @@ def gaussianProcessFunctionSamples(obj, pts, n: int, seed: int = 0, latent: bool
     distribution of that theta (one fit and one gphip_predict_draws per distinct theta).  latent = True: draws of f;
     False: of noisy observations.  Returns {"Points" [M,d], "Sample" [n] (index into "Samples"), "Values" [n,M]}; rows of a
     theta that does not factor are NaN.  None for an unsampled object and for objects with a point-dependent nugget or
-    mean function (not supported by the joint path).  pts may be an int > 1 as for predictFromGaussianProcess."""
-    if not isinstance(obj, inferenceObject) or obj.failed or "GaussianProcessData" not in obj or "Samples" not in obj:
+    mean function (not supported by the joint path).  pts may be an int > 1 as for predictFromGaussianProcess.
+    A sampled sparse object (defineSparseGaussianProcess) is taken as well: the same draw-to-sample assignment and per-theta
+    seeds, one fit(theta, obj["Jitter"]) and one gphip_sparse_predict_draws per distinct theta."""
+    if not isinstance(obj, inferenceObject) or obj.failed or "Samples" not in obj:
         return None
-    mf = obj["GaussianProcessData"]["ModelFunctions"]
-    if callable(mf["NuggetFunction"]) or callable(mf["MeanFunction"]):
-        return None
+    sparse = "SparseGaussianProcessData" in obj
+    if not sparse:
+        if "GaussianProcessData" not in obj:
+            return None
+        mf = obj["GaussianProcessData"]["ModelFunctions"]
+        if callable(mf["NuggetFunction"]) or callable(mf["MeanFunction"]):
+            return None
     X = obj["Data"][0]
     if isinstance(pts, (int, np.integer)):
         if pts <= 1 or X.shape[1] != 1:
@@ -593,7 +599,7 @@ def gaussianProcessFunctionSamples(obj, pts, n: int, seed: int = 0, latent: bool
     P = dataNormalForm(pts)
     if P is None or isinstance(P, tuple) or int(n) < 1:
         return None
-    handle = obj["GaussianProcessData"]["HIPHandle"]
+    handle = obj["SparseGaussianProcessData" if sparse else "GaussianProcessData"]["HIPHandle"]
     samples = obj["Samples"]
     points = np.array([s["Point"] for s in samples], dtype=np.float64)
     w = np.array([s["CrudePosteriorWeight"] for s in samples], dtype=np.float64)
@@ -601,7 +607,7 @@ def gaussianProcessFunctionSamples(obj, pts, n: int, seed: int = 0, latent: bool
     values = np.full((int(n), len(P)), np.nan)
     for k in np.unique(which):
         rows = np.flatnonzero(which == k)
-        if handle.fit(points[k]) != 0:
+        if (handle.fit(points[k], obj["Jitter"]) if sparse else handle.fit(points[k])) != 0:
             continue
         key = int(np.random.SeedSequence([int(seed) & (2**63 - 1), int(k)]).generate_state(1, np.uint64)[0])
         out, info = handle.predict_draws(P, len(rows), seed=key, latent=latent)
@@ -1037,3 +1043,41 @@ def predictFromSparseGaussianProcess(obj, pts, theta=None):
     with np.errstate(invalid="ignore"):
         sd = np.sqrt(var)
     return {"Points": P, "Weights": weights, "Mean": mean, "StandardDeviation": sd}
+
+
+def predictJointFromSparseGaussianProcess(obj, pts, theta):
+    """Joint form of predictFromSparseGaussianProcess(obj, pts, theta) for one theta: duplicates in pts are removed first (as
+    predictJointFromGaussianProcess does), then {"Points" [M,d], "Mean" [M], "Covariance" [M,M]} -- the MultinormalDistribution
+    of noisy observations at the points under the sparse posterior, whose diagonal is the per-point variance of
+    predictFromSparseGaussianProcess.  None where the object is not a sparse GP object, on bad points or a theta whose fit fails."""
+    if not isinstance(obj, inferenceObject) or obj.failed or "SparseGaussianProcessData" not in obj:
+        return None
+    P = dataNormalForm(pts)
+    if P is None or isinstance(P, tuple):
+        return None
+    _, first = np.unique(P, axis=0, return_index=True)
+    P = P[np.sort(first)]
+    handle = obj["SparseGaussianProcessData"]["HIPHandle"]
+    if handle.fit(np.asarray(theta, dtype=np.float64).ravel(), obj["Jitter"]) != 0:
+        return None
+    mean, cov = handle.predict_cov(P, latent=False)
+    return {"Points": P, "Mean": mean, "Covariance": cov}
+
+
+def sparsePredictiveLogDensity(obj, heldout, theta):
+    """log N(ys | mean, Covariance) of held-out data heldout = (Xs, ys) under the sparse posterior of obj at theta: the joint
+    predictive log density (the correlations between the held-out points included).  None where the object is not a sparse GP
+    object, on bad data or a failed fit / factorisation."""
+    if not isinstance(obj, inferenceObject) or obj.failed or "SparseGaussianProcessData" not in obj:
+        return None
+    P = dataNormalForm(heldout[0])
+    if P is None or isinstance(P, tuple):
+        return None
+    ys = np.asarray(heldout[1], dtype=np.float64).ravel()
+    if ys.shape != (len(P),):
+        return None
+    handle = obj["SparseGaussianProcessData"]["HIPHandle"]
+    if handle.fit(np.asarray(theta, dtype=np.float64).ravel(), obj["Jitter"]) != 0:
+        return None
+    value, info = handle.predict_logpdf(P, ys)
+    return value if info == 0 else None

@@ -542,6 +542,27 @@ int gphip_factor_bytes(gphip_handle h, int member, double* bytes);
  * behaviour, with F(theta; jitter) in the place of the log-likelihood: every Metropolis step is ONE gphip_sparse_bound_batch call
  * of up to `walkers` rows at the given jitter (< 0: the default rule per row).  Errors go to gphip_sparse_last_error.
  *
+ * gphip_sparse_predict_cov / _draws / _logpdf: the JOINT predictive distribution of M test points from the resident fit, with the
+ * semantics of gphip_predict_cov / _draws / _logpdf (above), point for point.  With V1 = L_u^-1 k(Z, X*) (m x M) and V2 = L_B^-1 V1
+ *
+ *     mu = m(X*) + V2^T c        Sigma = k(X*, X*) [+ sn^2 I unless latent] - V1^T V1 + sn^2 V2^T V2
+ *
+ * whose diagonal is gphip_sparse_predict's variance.  The jitter j of the model belongs to K_uu only; it is not added to k(X*, X*).
+ * cov is row-major M x M with both triangles, exactly symmetric.  draws: out is S x M; z == NULL uses the device's Philox normals
+ * keyed by (seed, s, j), so the first S' draws of a call are those of a call with S = S'; z != NULL is S x M standard normals of the
+ * caller; latent selects the draws of f* (1) or of y* (0); jitter (absolute, >= 0) is added to Sigma's diagonal before its
+ * factorisation, jitter < 0 is the default 1e-10 (fp64) / 1e-4 (fp32) x (k(x*, x*) + sn^2) (run-time compiled kernels: k(x*, x*) is its
+ * mean over the test points) -- a latent Sigma is singular to rounding and needs it.  *info is GPHIP_INFO_NOT_SPD when Sigma (+ jitter)
+ * does not factor and GPHIP_INFO_NAN for non-finite results; the outputs are NaN then.  logpdf: the log density of ystar under
+ * N(mu, Sigma) with the noisy Sigma; a non-finite ystar entry gives *info = GPHIP_INFO_NAN.
+ * Statuses, all decided before any device work: NULL pointers and a non-finite jitter GPHIP_ERR_ARG; M < 1, M > GPHIP_JOINT_MAX_M
+ * and S < 1 GPHIP_ERR_DIM; no successful fit (also after gphip_sparse_bound_batch or gphip_sparse_set_inducing) GPHIP_ERR_STATE.
+ * The calls never invalidate the fit: gphip_sparse_predict and gphip_sparse_bound return the same bytes before and after them.
+ * All M rows of V1 and V2 are resident at once (2 M m elements); Sigma is assembled in a context whose training points are X*
+ * (kept while M stays the same, dies with the object) by one launch of the two-segment downdate kernel over the stacked index
+ * [V1 | V2]; cov, draws and the log density then run the exact path's code on it.  Two calls with the same
+ * options return the same bytes.
+ *
  * Options (gphip_sparse_set_option / gphip_sparse_get_option):
  *   "sparse_chunk"  data points per pass over V (rounded up to 128); 0 (default) = as many as keep the chunk of V within ~8 GiB,
  *                   at least 2048, halved while it does not fit.  "last_sparse_chunk" (read-only): what the last call used.
@@ -555,6 +576,11 @@ int gphip_factor_bytes(gphip_handle h, int member, double* bytes);
  *                   "ms_grad_small" (the m x m work and the vector w), "ms_grad_weights" (sparse_weight_kernel alone),
  *                   "ms_grad_backward", "ms_grad_reduce" (its second pass over the data adds to "ms_cross" and "ms_forward").
  *                   of gphip_sparse_bound_grad_inducing also "ms_grad_inducing" (the column-wise reductions for dF/dZ).
+ *                   of the joint prediction calls "ms_joint_v" (V1 and V2), "ms_joint_build" (K(X*, X*)), "ms_joint_downdate" (the
+ *                   two-segment downdate and its strip reduction) and "ms_joint_factor" (Sigma's factorisation; draws / logpdf).
+ *   "sparse_joint_split"  strips the joint prediction's downdate cuts the stacked index of 2 m_pad columns into; 0 (default) = by
+ *                   gphip_predict_cov's split rule (output tiles x strips >= 2 per CU, strips of whole 128-columns; a strip may
+ *                   span the V1 / V2 boundary), n = n strips.  "last_sparse_joint_nsplit" (read-only): strips of the last call.
  *   every other name is handed on to the two contexts that factor K_uu and B (see gphip_set_option; e.g. "dataflow"). ---- */
 #define GPHIP_SPARSE_MAX_M 16384
 typedef struct gphip_sparse_ctx* gphip_sparse_handle;
@@ -578,6 +604,10 @@ int gphip_sparse_bound_grad_inducing(gphip_sparse_handle h, const double* theta,
                                      double* grad /* p, may be NULL */, double* gradZ /* row-major m x d */, double* parts, int* info);
 int gphip_sparse_fit(gphip_sparse_handle h, const double* theta, int p, double jitter, int* info);
 int gphip_sparse_predict(gphip_sparse_handle h, const void* Xs, int64_t M, int latent, double* mean, double* var);
+int gphip_sparse_predict_cov(gphip_sparse_handle h, const void* Xs, int64_t M, int latent, double* mean /* M */, double* cov /* M x M */);
+int gphip_sparse_predict_draws(gphip_sparse_handle h, const void* Xs, int64_t M, int latent, int S, uint64_t seed,
+                               const double* z /* NULL or S x M */, double jitter, double* out /* S x M */, int* info);
+int gphip_sparse_predict_logpdf(gphip_sparse_handle h, const void* Xs, int64_t M, const double* ystar, double* out, int* info);
 int gphip_sparse_set_option(gphip_sparse_handle h, const char* name, double value);
 int gphip_sparse_get_option(gphip_sparse_handle h, const char* name, double* value);
 const char* gphip_sparse_last_error(gphip_sparse_handle h);   /* owned by the library */
