@@ -1,10 +1,14 @@
 // gphip_sparse.inc -- sparse inducing-point GP: the collapsed variational bound of Titsias (2009), its fit and prediction
 // (include/gphip.h: gphip_sparse_*; kernels: gp_sparse.h).  Included at the end of gphip.hip.
 //
+// The forward pass of the bound exists once, in sparse_group: nb thetas in workspace slots 0 .. nb - 1 of u and b, every launch
+// with the slot as its last grid index.  sparse_eval (gphip_sparse_bound / _fit / _bound_grad / _bound_grad_inducing) is the group
+// of ONE slot in resident mode (SparseKeep::fit), sparse_eval_batch (gphip_sparse_bound_batch, the native sampler) loops groups in
+// batch mode (SparseKeep::nothing); DESIGN.md section 8f lists what the mode decides.  Per slot:
 //   u (a context whose TRAINING points are Z, y = 0; its nugget slot scalar carries the jitter j)
 //        queue_build + queue_factor        L_u L_u^T = k(Z, Z) + j I, direct-difference kernel build
 //        per chunk of data points, treated as test points of u:
-//        queue_cross + queue_forward_fit   the chunk of V = L_u^-1 k(Z, X) in u->dV, V(t, k) at V[t + k ld]
+//        queue_cross + sparse_queue_forward   the chunk of V = L_u^-1 k(Z, X) in u->dV, V(t, k) at V[t + k ld]
 //        sparse_resid_kernel               r = y - mu of the chunk (row 0 of the rhs operand), partial sums of r^2
 //        sparse_accumulate_kernel          b's workspace: lower tiles += V^T V, rhs tile row += r^T V  (chunks in order)
 //   b (a context of m points whose workspace is filled by hand)
@@ -27,6 +31,20 @@
 //   the child's workspace into Sigma = K(X*, X*) - V1^T V1 + sn^2 V2^T V2 and its rhs row into y* - mu.  Cov, draws and the log
 //   density then are the exact path's own code on that child.
 #include "gp_sparse.h"
+
+// The phases timed by HIP events while option "profile" is on, and the options that read them (gphip_sparse_get_option).
+// PH_KUU_FACTOR .. PH_GRAD_INDUCING are reset by every evaluation of the bound, PH_JOINT_V .. by every joint prediction.
+enum SparsePhaseId {
+    PH_KUU_FACTOR, PH_CROSS, PH_FORWARD, PH_ACCUMULATE, PH_B_FACTOR,                               // the bound
+    PH_GRAD_SMALL, PH_GRAD_WEIGHTS, PH_GRAD_BACKWARD, PH_GRAD_REDUCE, PH_GRAD_INDUCING,            // its gradients
+    PH_JOINT_V, PH_JOINT_BUILD, PH_JOINT_DOWNDATE, PH_JOINT_FACTOR,                                // joint prediction
+    PH_COUNT
+};
+static const char* const SPARSE_PHASE_OPTION[] = {
+    "ms_kuu_factor", "ms_cross", "ms_forward", "ms_accumulate", "ms_b_factor",
+    "ms_grad_small", "ms_grad_weights", "ms_grad_backward", "ms_grad_reduce", "ms_grad_inducing",
+    "ms_joint_v", "ms_joint_build", "ms_joint_downdate", "ms_joint_factor"};
+static_assert(sizeof SPARSE_PHASE_OPTION / sizeof SPARSE_PHASE_OPTION[0] == PH_COUNT, "one option name per phase");
 
 struct gphip_sparse_ctx {
     std::recursive_mutex mu;
@@ -59,7 +77,7 @@ struct gphip_sparse_ctx {
     int64_t last_chunk = 0;
     double last_jitter = 0.0;
     int grad_analytic = 0;                     // the last gphip_sparse_bound_grad: 1 = the analytic route, 0 = central differences
-    double ms[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};    // K_uu factor, cross build, forward substitution, accumulation, B factor;
+    double ms[PH_COUNT] = {};                  // K_uu factor, cross build, forward substitution, accumulation, B factor;
                                                // gradient: small m x m work, weights, backward substitution, reductions, the reduction in Z;
                                                // joint prediction: V1 and V2, K(X*, X*), the downdate, the factorisation of Sigma
     // the resident fit
@@ -77,33 +95,48 @@ int sfail(gphip_sparse_ctx* h, int code, const std::string& msg) {
     return code;
 }
 
-struct SparsePhase { int phase; hipEvent_t e0, e1; };
+void sparse_reset_phases(gphip_sparse_ctx* h, SparsePhaseId first, SparsePhaseId end) {
+    for (int k = first; k < end; ++k) h->ms[k] = 0.0;
+}
 
-// HIP-event pair around a phase of the evaluation while option "profile" is on (the events come from u's pool)
+struct SparsePhase { SparsePhaseId phase; hipEvent_t e0, e1; };
+
+// The event pairs of one call.  They come from u's pool and go back to it when the call ends, on every exit path: declare the
+// owner BEFORE the call's scopes, so that every scope has closed when it is destroyed.
+struct SparsePhases {
+    gphip_sparse_ctx* h;
+    std::vector<SparsePhase> recs;
+    explicit SparsePhases(gphip_sparse_ctx* h_) : h(h_) {}
+    SparsePhases(const SparsePhases&) = delete;
+    SparsePhases& operator=(const SparsePhases&) = delete;
+    ~SparsePhases() { harvest(); }
+    void harvest() {                           // adds the times to h->ms (waits for each closing event)
+        for (const SparsePhase& r : recs) {
+            float ms = 0.f;
+            (void)hipEventSynchronize(r.e1);   // (a scope's closing event may have been recorded after the call's last synchronisation)
+            if (hipEventElapsedTime(&ms, r.e0, r.e1) == hipSuccess) h->ms[r.phase] += ms;
+            else (void)hipGetLastError();
+            h->u->pool.push_back(r.e0);
+            h->u->pool.push_back(r.e1);
+        }
+        recs.clear();
+    }
+};
+
+// HIP-event pair around a phase of the evaluation while option "profile" is on
 struct SparseScope {
-    gphip_sparse_ctx* h; std::vector<SparsePhase>* recs; SparsePhase r; hipStream_t st; bool on;
-    SparseScope(gphip_sparse_ctx* h_, std::vector<SparsePhase>* recs_, int phase, hipStream_t st_) : h(h_), recs(recs_), st(st_), on(h_->profile > 0) {
+    SparsePhases& ph; SparsePhase r; hipStream_t st; bool on;
+    SparseScope(SparsePhases& ph_, SparsePhaseId phase, hipStream_t st_) : ph(ph_), st(st_), on(ph_.h->profile > 0) {
         if (!on) return;
-        r.phase = phase; r.e0 = get_event(h->u); r.e1 = get_event(h->u);
+        r.phase = phase; r.e0 = get_event(ph.h->u); r.e1 = get_event(ph.h->u);
         (void)hipEventRecord(r.e0, st);
     }
     ~SparseScope() {
         if (!on) return;
         (void)hipEventRecord(r.e1, st);
-        recs->push_back(r);
+        ph.recs.push_back(r);
     }
 };
-void sparse_harvest(gphip_sparse_ctx* h, std::vector<SparsePhase>& recs) {      // after the streams' synchronisation
-    for (const SparsePhase& r : recs) {
-        float ms = 0.f;
-        (void)hipEventSynchronize(r.e1);       // (a scope's closing event may have been recorded after the call's last synchronisation)
-        if (hipEventElapsedTime(&ms, r.e0, r.e1) == hipSuccess) h->ms[r.phase] += ms;
-        else (void)hipGetLastError();
-        h->u->pool.push_back(r.e0);
-        h->u->pool.push_back(r.e1);
-    }
-    recs.clear();
-}
 
 template <typename T>
 int sparse_func_attrs(gphip_sparse_ctx* h) {
@@ -131,7 +164,6 @@ int sparse_make_children(gphip_sparse_ctx* h, const double* Z, int64_t m) {
     if (rc) return sfail(h, rc, "creating the inducing-point context failed " + why);
     rc = create_ctx(Z, y0.data(), m, h->d, GPHIP_KERNEL_SE, GPHIP_MEAN_ZERO, h->dtype, u->device, &b);
     if (rc) { gphip_destroy(u); return sfail(h, rc, "creating the context of B failed"); }
-    u->kbuild_mfma = 0;                        // K_uu and k(Z, X) from the same, direct-difference form of the kernel build
     if (h->u) gphip_destroy(h->u);
     if (h->b) gphip_destroy(h->b);
     h->u = u; h->b = b; h->m = m; h->device = u->device;
@@ -140,7 +172,7 @@ int sparse_make_children(gphip_sparse_ctx* h, const double* Z, int64_t m) {
         (void)gphip_set_option(u, o.first.c_str(), o.second);
         (void)gphip_set_option(b, o.first.c_str(), o.second);
     }
-    u->kbuild_mfma = 0;
+    u->kbuild_mfma = 0;                        // K_uu and k(Z, X) from the same, direct-difference form of the kernel build
     return GPHIP_OK;
 }
 
@@ -228,19 +260,18 @@ int sparse_queue_diag(gphip_sparse_ctx* h, double* out, int nb = 1, long ostride
     return GPHIP_OK;
 }
 
-// queue_factor on a context whose workspace is ready, leaving what the substitutions need; *info as gphip_loglik's
-int sparse_factor(gphip_sparse_ctx* h, gphip_ctx* c, bool build, const char* what, int* info) {
+// queue_factor on nb slots of a context whose workspaces are ready (build: after queue_build), to the end of the call; want_w:
+// it leaves the block inverses that forward substitutions with the factor use.  Slot s's info, as gphip_loglik's, is c->hInfo[s].
+int sparse_factor(gphip_sparse_ctx* h, gphip_ctx* c, int nb, bool build, bool want_w, const char* what) {
     {
-        FactorMode mode(c, true);              // the forward substitutions that follow use the block inverses
+        FactorMode mode(c, want_w);
         c->theta_packed = false; c->fused_eval = false;
-        if (build) DISPATCH(c, queue_build, c, 1);
-        DISPATCH(c, queue_factor, c, 1);
+        if (build) DISPATCH(c, queue_build, c, nb);
+        DISPATCH(c, queue_factor, c, nb);
     }
     c->abort_unread = what;
     const int rc = complete_call(c);
-    if (rc) return sfail(h, rc, c->err);
-    *info = c->hInfo.as<int>()[0];
-    return GPHIP_OK;
+    return rc ? sfail(h, rc, c->err) : GPHIP_OK;
 }
 
 // strip partials of predict_partial_kernel for the mpad rows in c->dV against c's rhs row (queue_predict_reduce's first stage)
@@ -340,7 +371,7 @@ struct SparseGradIn {
 // still in u->dV when nchunks == 1).  grad: p derivatives in theta's layout (null: the reductions in theta are skipped);
 // gradZ: row-major m x d derivatives in the inducing locations (null: not wanted).
 template <typename T>
-int sparse_grad_phase(gphip_sparse_ctx* h, const SparseGradIn& in, std::vector<SparsePhase>& recs, double* grad, double* gradZ) {
+int sparse_grad_phase(gphip_sparse_ctx* h, const SparseGradIn& in, SparsePhases& ph, double* grad, double* gradZ) {
     gphip_ctx *u = h->u, *b = h->b;
     const int64_t mpm = b->Npad;                // padded inducing points
     const int Mt = (int)b->Nt;
@@ -366,7 +397,7 @@ int sparse_grad_phase(gphip_sparse_ctx* h, const SparseGradIn& in, std::vector<S
     }
     // ---- b: a, B^-1, S and the inner matrix of H
     {
-        SparseScope ps(h, &recs, 5, b->stream);
+        SparseScope ps(ph, PH_GRAD_SMALL, b->stream);
         HIPCHK(b->dAlpha.grow((size_t)mpm * sizeof(T)));
         if ((rc = queue_alpha<T>(b))) return sfail(h, rc, b->err);
         int gx = (int)((mpm * mpm + 255) / 256);
@@ -386,18 +417,18 @@ int sparse_grad_phase(gphip_sparse_ctx* h, const SparseGradIn& in, std::vector<S
     if ((rc = ensure_gacc(u))) return sfail(h, rc, u->err);
     HIPCHK(hipMemsetAsync(u->dGacc.p, 0, u->ngacc * 8, u->stream));
     {
-        SparseScope ps(h, &recs, 5, u->stream);
+        SparseScope ps(ph, PH_GRAD_SMALL, u->stream);
         if ((rc = queue_backward_rows<T>(u, mpm, h->dH.p, h->dLd.p, h->dRes.p))) return sfail(h, rc, u->err);
         hipLaunchKernelGGL(sparse_transpose_kernel<T>, dim3((unsigned)(mpm / 32), (unsigned)(mpm / 32)), dim3(256), 0, u->stream,
                            (const T*)h->dH.p, (long)mpm, (T*)b->dV.p, (long)mpm);
         if ((rc = queue_backward_rows<T>(u, mpm, b->dV.p, h->dLd.p, h->dRes.p))) return sfail(h, rc, u->err);
     }
     if (grad) {
-        SparseScope ps(h, &recs, 8, u->stream);
+        SparseScope ps(ph, PH_GRAD_REDUCE, u->stream);
         queue_grad_full<T>(u, b->dV.p, (long)mpm, nullptr);
     }
     if (gradZ) {                               // sum_l 2 H_lk dk(z_l, z_k)/dz_k: the rows are Z itself, nothing is halved
-        SparseScope ps(h, &recs, 9, u->stream);
+        SparseScope ps(ph, PH_GRAD_INDUCING, u->stream);
         if ((rc = sparse_queue_zgrad<T>(h, b->dV.p, (long)mpm, u->dXs.p, u->dXs2.p, mpm, u->N, 1.0))) return rc;
     }
     // ---- the chunks of data points, in the evaluation's order
@@ -407,25 +438,25 @@ int sparse_grad_phase(gphip_sparse_ctx* h, const SparseGradIn& in, std::vector<S
         const unsigned nb = (unsigned)((mpad + 255) / 256);
         if (in.nchunks > 1) {
             {
-                SparseScope ps(h, &recs, 1, u->stream);
+                SparseScope ps(ph, PH_CROSS, u->stream);
                 if ((rc = sparse_load_points(h, h->dXt.p, h->Npad, c0, mpad))) return rc;
                 queue_cross<T>(u, mc, mpad, 1);
             }
             {
-                SparseScope ps(h, &recs, 2, u->stream);
+                SparseScope ps(ph, PH_FORWARD, u->stream);
                 queue_forward_fit(u, mpad);
             }
             sparse_queue_resid<T>(h, c0, mc, mpad, h->dSum.as<double>() + 1);       // (mu is still in dPar; its sums of r^2 are not read again)
         }
         {
-            SparseScope ps(h, &recs, 5, u->stream);
+            SparseScope ps(ph, PH_GRAD_SMALL, u->stream);
             hipLaunchKernelGGL(sparse_vta_kernel<T>, dim3(nb, (unsigned)Mt), dim3(256), 0, u->stream, (const T*)u->dV.p, (long)mpad,
                                (const T*)b->dAlpha.p, (int)mpad, d_vta);
             hipLaunchKernelGGL(sparse_w_kernel<T>, dim3(nb), dim3(256), 0, u->stream, (const T*)h->dRz.p, (const double*)d_vta, Mt, (int)mc,
                                (int)mpad, sn2, d_w, d_ws + used);
         }
         {
-            SparseScope ps(h, &recs, 6, u->stream);
+            SparseScope ps(ph, PH_GRAD_WEIGHTS, u->stream);
             SparseWeightArgs<T> g{};
             g.V = (const T*)u->dV.p; g.ldv = (long)mpad;
             g.S = (const T*)h->dS.p; g.lds = (long)mpm;
@@ -435,11 +466,11 @@ int sparse_grad_phase(gphip_sparse_ctx* h, const SparseGradIn& in, std::vector<S
             hipLaunchKernelGGL(sparse_weight_kernel<T>, dim3((unsigned)(mpad / TB), (unsigned)Mt), dim3(256), 0, u->stream, g);
         }
         {
-            SparseScope ps(h, &recs, 7, u->stream);
+            SparseScope ps(ph, PH_GRAD_BACKWARD, u->stream);
             if ((rc = queue_backward_rows<T>(u, mpad, b->dV.p, h->dLd.p, h->dRes.p))) return sfail(h, rc, u->err);
         }
         if (grad) {
-            SparseScope ps(h, &recs, 8, u->stream);
+            SparseScope ps(ph, PH_GRAD_REDUCE, u->stream);
             GradArgs<T> a = grad_args<T>(u, b->dV.p, (long)mpad, 0, mc);
             a.xr = (const T*)u->dXsS.p; a.xr2 = (const T*)u->dXsS2.p; a.npad_r = (int)mpad;
             launch_grad<T>(u, a, dim3((unsigned)(mpad / TB), (unsigned)u->Nt));
@@ -450,7 +481,7 @@ int sparse_grad_phase(gphip_sparse_ctx* h, const SparseGradIn& in, std::vector<S
             }
         }
         if (gradZ) {                           // sum_i G_ki dk(z_k, x_i)/dz_k from -2 G: halved
-            SparseScope ps(h, &recs, 9, u->stream);
+            SparseScope ps(ph, PH_GRAD_INDUCING, u->stream);
             if ((rc = sparse_queue_zgrad<T>(h, b->dV.p, (long)mpad, u->dXsS.p, u->dXsS2.p, mpad, mc, 0.5))) return rc;
         }
         used += nb;
@@ -487,13 +518,181 @@ int sparse_grad_phase(gphip_sparse_ctx* h, const SparseGradIn& in, std::vector<S
     return GPHIP_OK;
 }
 
-// One evaluation: the bound (out, parts: null = not wanted) and the resident fit; grad (null = not wanted): the analytic gradient
-// in theta; gradZ (null = not wanted): the analytic gradient in the inducing locations, row-major m x d.
+// theta's length and the jitter of an entry point (called under the object's lock: gphip_sparse_set_inducing replaces u)
+int sparse_check_args(gphip_sparse_ctx* h, int p, double jitter) {
+    if (p != h->u->p) return sfail(h, GPHIP_ERR_DIM, "theta has the wrong length for this kernel/mean");
+    if (std::isnan(jitter) || std::isinf(jitter)) return sfail(h, GPHIP_ERR_ARG, "non-finite jitter");
+    return GPHIP_OK;
+}
+
+// What a group evaluation is for (DESIGN.md section 8f).  fit: a one-theta entry point -- the factors of u and b stay resident
+// for the substitutions that follow (prediction, the gradient phase), u substitutes with queue_forward_fit, and a theta that
+// cannot be evaluated ends the call before the chunk loop.  nothing: a batch -- every row keeps its slot whatever becomes of it,
+// and no factor outlives the call.  The mode is the caller's, never the number of rows: a group of one row of a batch is a batch.
+enum class SparseKeep { fit, nothing };
+
+// one theta's slot of a group evaluation
+struct SparseSlot {
+    bool ok = false;                           // theta and its jitter are usable (else stand-in values were staged)
+    bool evaluated = false;                    // B was factored and F formed (SparseKeep::fit stops before that on a failure)
+    int info = 0, uinfo = 0;                   // the row's info as gphip_loglik's; that of K_uu's factorisation alone
+    double sn2 = 0, mu = 0, kxx = 0, jit = 0;
+    double F = 0, logdet = 0, ctc = 0, rtr = 0, trvv = 0, skk = 0;
+    void put_parts(double* out) const { out[0] = logdet; out[1] = ctc; out[2] = rtr; out[3] = trvv; out[4] = skk; }
+};
+
+// the chunk's mpad rows of every slot: V <- L_u^-1 k(Z, X).  Resident: the fitted factor's route.  Batch: ONE dataflow launch
+// (slot = row) where gphip_predict_samples would take it and every slot of the group has a factor (a slot whose factorisation
+// was abandoned has no block inverses to hand to the launch's chain), else the batched GEMM substitution, which has no waits
+void sparse_queue_forward(gphip_ctx* u, int64_t mpad, int nb, SparseKeep keep, bool all_factored) {
+    if (keep == SparseKeep::fit) queue_forward_fit(u, mpad);
+    else if (all_factored && samples_forward_df(u, nb, mpad)) launch_dataflow_inverse<double, 64>(u, mpad, false, nb, u->dW64s.p);
+    else DISPATCH(u, queue_forward_rows, u, mpad, nb);
+}
+
+// The bound for the nb rows of Theta in slots 0 .. nb - 1 of u and b, `rows` data points per chunk (the callers size u's dV, dRz
+// and dPar for nb slots of them).  u builds and factors nb K_uu at once; every chunk of data points is loaded once and crossed,
+// substituted, reduced and accumulated for all nb slots by launches whose last grid index is the slot; b factors nb matrices B at
+// once.  A row that fails keeps its slot (a non-finite theta is staged as stage_theta's stand-in values with a unit nugget, so
+// its slot factors) and only its own res[s] tells -- unless keep says that it ends the call.  keepB (null: not wanted): slot
+// 0's B before its factorisation overwrites it.
+int sparse_group(gphip_sparse_ctx* h, const double* Theta, int nb, int p, double jitter, int64_t rows, SparseKeep keep, Buf* keepB,
+                 SparsePhases& ph, SparseSlot* res) {
+    gphip_ctx *u = h->u, *b = h->b;
+    const bool resident = keep == SparseKeep::fit;
+    int rc;
+    double* par = h->hPar.as<double>();
+    for (int s = 0; s < nb; ++s) {
+        SparseSlot& r = res[s];
+        r = SparseSlot{};
+        r.ok = stage_theta(u, s, Theta + (size_t)s * p);
+        const double* sp = u->hSlotp.as<double>() + (size_t)s * SLOTP;
+        r.sn2 = sp[1]; r.mu = sp[2]; r.kxx = sp[SP_KXX]; r.jit = jitter;
+        par[2 * s] = r.mu; par[2 * s + 1] = r.sn2;
+    }
+    if (jitter < 0.0) {                        // default: joint_jitter_rel x the row's k(x, x) (run-time compiled kernels: its mean of k(z, z))
+        std::vector<double> scale((size_t)nb);
+        for (int s = 0; s < nb; ++s) scale[(size_t)s] = res[s].kxx;
+        if (h->custom) {
+            if ((rc = copy_theta(u, nb))) return sfail(h, rc, u->err);
+            if ((rc = sparse_mean_kzz(h, rows, scale.data(), nb))) return rc;
+        }
+        for (int s = 0; s < nb; ++s) res[s].jit = joint_jitter_rel(u) * scale[(size_t)s];
+    }
+    for (int s = 0; s < nb; ++s) {
+        SparseSlot& r = res[s];
+        if (!std::isfinite(r.jit) || r.jit < 0.0) r.ok = false;
+        if (!r.ok && resident) { r.info = GPHIP_INFO_NAN; return GPHIP_OK; }
+        if (r.ok) h->last_jitter = r.jit;
+        else r.jit = 1.0;                      // (the stand-in theta of a row that is given up: K_uu + I factors)
+        // u: the nugget slot carries the jitter; the pivot tolerance follows it
+        double* sp = u->hSlotp.as<double>() + (size_t)s * SLOTP;
+        sp[1] = r.jit;
+        sp[SP_MFMA] = 0.0;
+        if (h->custom) sp[SP_SF2B] = r.jit;
+        else sp[3] = pivot_tol_rel(u) * (std::fabs(r.kxx) + r.jit);
+    }
+    if ((rc = copy_theta(u, nb))) return sfail(h, rc, u->err);
+    HIPCHK(hipMemsetAsync(u->dInfo.p, 0, (size_t)nb * 4, u->stream));
+    if ((rc = sparse_copy_par(h, nb))) return rc;
+    {
+        SparseScope ps(ph, PH_KUU_FACTOR, u->stream);
+        rc = sparse_factor(h, u, nb, true, true, "sparse GP: the factorisation of K_uu timed out (set option dataflow=0 and report)");
+    }
+    if (rc) return rc;
+    bool all_factored = true;
+    for (int s = 0; s < nb; ++s)
+        if ((res[s].uinfo = u->hInfo.as<int>()[s]) != 0) all_factored = false;
+    if (resident) {
+        if (!all_factored) { res[0].info = res[0].uinfo; return GPHIP_OK; }
+        record_fit(u, true, Theta, p, u->hRes.as<double>()[0]);       // (queue_forward_fit asks for it)
+    }
+    // b: empty bordered workspaces; the nugget scalar of slot s is sn_s^2, its pivot tolerance relative to sn_s^2 (B >= sn_s^2 I)
+    for (int s = 0; s < nb; ++s) {
+        const double sn2 = res[s].sn2, thb[3] = {1.0, 1.0, std::sqrt(sn2)};
+        (void)stage_theta(b, s, thb);
+        double* spb = b->hSlotp.as<double>() + (size_t)s * SLOTP;
+        spb[1] = sn2; spb[3] = pivot_tol_rel(b) * sn2; spb[4] = 0.0; spb[SP_MFMA] = 0.0;
+    }
+    if ((rc = copy_theta(b, nb))) return sfail(h, rc, b->err);
+    HIPCHK(hipMemsetAsync(b->dInfo.p, 0, (size_t)nb * 4, b->stream));
+    HIPCHK(hipMemsetAsync(b->dA.p, 0, (size_t)nb * b->slot_elems * h->es, u->stream));
+    // partial sums per slot: [0] the trace, then one per 256 data points of every chunk for r^2, then the same for k(x_i, x_i)
+    const int64_t nchunks = (h->N + rows - 1) / rows;
+    const size_t nblk = (size_t)(h->Npad / 256 + nchunks + 1), ss = 1 + 2 * nblk;
+    HIPCHK(h->dSum.grow((size_t)nb * ss * 8));
+    double* d_r2 = h->dSum.as<double>() + 1;
+    double* d_kk = d_r2 + nblk;
+    size_t used = 0;
+    for (int64_t c0 = 0; c0 < h->N; c0 += rows) {
+        const int64_t mc = std::min(rows, h->N - c0), mpad = (mc + TB - 1) / TB * TB;
+        {
+            SparseScope ps(ph, PH_CROSS, u->stream);
+            if ((rc = sparse_load_points(h, h->dXt.p, h->Npad, c0, mpad))) return rc;
+            DISPATCH(u, queue_cross, u, mc, mpad, nb);
+        }
+        {
+            SparseScope ps(ph, PH_FORWARD, u->stream);
+            sparse_queue_forward(u, mpad, nb, keep, all_factored);
+        }
+        DISPATCH(h, sparse_queue_resid, h, c0, mc, mpad, d_r2 + used, nb, (long)ss);
+        if (h->custom) {                       // k(x_i, x_i) per point and slot (u->dXsT still holds the chunk)
+            if ((rc = queue_custom_kss(u, mc, mpad, nb))) return sfail(h, rc, u->err);
+            hipLaunchKernelGGL(sparse_blocksum_kernel, dim3((unsigned)((mpad + 255) / 256), (unsigned)nb), dim3(256), 0, u->stream,
+                               u->dKss.as<double>(), (long)mpad, (int)mc, d_kk + used, (long)ss);
+        }
+        used += (size_t)((mpad + 255) / 256);
+        {
+            SparseScope ps(ph, PH_ACCUMULATE, u->stream);
+            if ((rc = DISPATCH(h, sparse_queue_accumulate, h, mpad, nb))) return rc;
+        }
+    }
+    // a slot without a factor of K_uu accumulated whatever its V held: B = sn^2 I in its place, so that b factors numbers
+    for (int s = 0; s < nb; ++s)
+        if (res[s].uinfo != 0)
+            HIPCHK(hipMemsetAsync(static_cast<char*>(b->dA.p) + (size_t)s * b->slot_elems * h->es, 0, (size_t)b->slot_elems * h->es, u->stream));
+    DISPATCH(h, sparse_queue_diag, h, h->dSum.as<double>(), nb, (long)ss);
+    if (keepB) {
+        HIPCHK(keepB->grow((size_t)b->slot_elems * h->es));
+        HIPCHK(hipMemcpyAsync(keepB->p, b->dA.p, (size_t)b->slot_elems * h->es, hipMemcpyDeviceToDevice, u->stream));
+    }
+    h->hSum.assign((size_t)nb * ss, 0.0);
+    HIPCHK(hipMemcpyAsync(h->hSum.data(), h->dSum.p, (size_t)nb * ss * 8, hipMemcpyDeviceToHost, u->stream));
+    if ((rc = complete_call(u))) return sfail(h, rc, u->err);          // (the forward substitutions' abort word)
+    {
+        SparseScope ps(ph, PH_B_FACTOR, b->stream);    // (resident: substitutions with L_B follow, so it leaves its block inverses)
+        rc = sparse_factor(h, b, nb, false, resident, "sparse GP: the factorisation of B timed out (set option dataflow=0 and report)");
+    }
+    if (rc) return rc;
+    for (int s = 0; s < nb; ++s) {
+        SparseSlot& r = res[s];
+        const double* hs = h->hSum.data() + (size_t)s * ss;
+        r.logdet = b->hRes.as<double>()[2 * s]; r.ctc = b->hRes.as<double>()[2 * s + 1];
+        for (size_t k = 0; k < used; ++k) r.rtr += hs[1 + k];
+        if (h->custom) for (size_t k = 0; k < used; ++k) r.skk += hs[1 + nblk + k];
+        else r.skk = (double)h->N * r.kxx;
+        r.trvv = hs[0];
+        r.F = -0.5 * ((double)h->N * LOG_TWO_PI + (double)(h->N - h->m) * std::log(r.sn2) + r.logdet + (r.rtr - r.ctc) / r.sn2) -
+              (r.skk - r.trvv) / (2.0 * r.sn2);
+        r.info = r.uinfo != 0 ? r.uinfo : b->hInfo.as<int>()[s];        // (a failure of u comes first)
+        if (!r.ok || (r.info == 0 && !std::isfinite(r.F))) r.info = GPHIP_INFO_NAN;
+        r.evaluated = true;
+    }
+    if (resident) {
+        const double thb[3] = {1.0, 1.0, std::sqrt(res[0].sn2)};
+        record_fit(b, res[0].info == 0, thb, 3, res[0].logdet);
+    }
+    return GPHIP_OK;
+}
+
+// One evaluation: the group evaluator with one slot, the fit left resident.  out, parts: the bound (null = not wanted); grad
+// (null = not wanted): the analytic gradient in theta; gradZ (null = not wanted): the analytic gradient in the inducing
+// locations, row-major m x d.
 int sparse_eval(gphip_sparse_ctx* h, const double* theta, int p, double jitter, double* out, double* parts, int* info,
                 double* grad = nullptr, double* gradZ = nullptr) {
     gphip_ctx *u = h->u, *b = h->b;
-    if (p != u->p) return sfail(h, GPHIP_ERR_DIM, "theta has the wrong length for this kernel/mean");
-    if (std::isnan(jitter) || std::isinf(jitter)) return sfail(h, GPHIP_ERR_ARG, "non-finite jitter");
+    int rc = sparse_check_args(h, p, jitter);
+    if (rc) return rc;
     const double qnan = std::nan("");
     auto give_up = [&](int inf) {
         *info = inf;
@@ -505,18 +704,15 @@ int sparse_eval(gphip_sparse_ctx* h, const double* theta, int p, double jitter, 
     if (gradZ) for (int64_t k = 0; k < h->m * h->d; ++k) gradZ[k] = qnan;
     const bool wants_grad = grad || gradZ;
     h->fitted = false;
-    for (int k = 0; k < 10; ++k) h->ms[k] = 0.0;
+    sparse_reset_phases(h, PH_KUU_FACTOR, PH_JOINT_V);
     for (int k = 0; k < p; ++k)
         if (!std::isfinite(theta[k])) return give_up(GPHIP_INFO_NAN);
     HIPCHK(hipSetDevice(h->device));
-    int rc = ensure_slots(u, 1);
-    if (rc) return sfail(h, rc, u->err);
+    if ((rc = ensure_slots(u, 1))) return sfail(h, rc, u->err);
     if ((rc = ensure_slots(b, 1))) return sfail(h, rc, b->err);
     invalidate_fit(u);
     invalidate_fit(b);
-    if (!stage_theta(u, 0, theta)) return give_up(GPHIP_INFO_NAN);
-    double* sp = u->hSlotp.as<double>();
-    const double sn2 = sp[1], mu = sp[2], kxx = sp[SP_KXX];
+    if (!stage_theta(u, 0, theta)) return give_up(GPHIP_INFO_NAN);     // (an unusable theta: before any buffer is sized; the group stages it again)
     // rows of V per pass: ensure_vchunk's rule (V within ~8 GiB, at least 2048 rows, halved while it does not fit) and the option
     int64_t rows = 0;
     const int64_t cap = h->chunk > 0 ? std::min<int64_t>(((int64_t)h->chunk + TB - 1) / TB * TB, h->Npad) : h->Npad;
@@ -535,121 +731,32 @@ int sparse_eval(gphip_sparse_ctx* h, const double* theta, int p, double jitter, 
     h->last_chunk = rows;
     if ((rc = sparse_ensure_rz(h, 1, rows))) return rc;
     if ((rc = sparse_ensure_par(h, 1))) return rc;
-    double jit = jitter;
-    if (jit < 0.0) {                           // default: joint_jitter_rel x k(x, x) (run-time compiled kernels: the mean of k(z, z))
-        double scale = kxx;
-        if (h->custom) {
-            if ((rc = copy_theta(u, 1))) return sfail(h, rc, u->err);
-            if ((rc = sparse_mean_kzz(h, rows, &scale))) return rc;
-        }
-        jit = joint_jitter_rel(u) * scale;
-    }
-    if (!std::isfinite(jit) || jit < 0.0) return give_up(GPHIP_INFO_NAN);
-    h->last_jitter = jit;
-    // u: the nugget slot carries the jitter; the pivot tolerance follows it
-    sp[1] = jit;
-    sp[SP_MFMA] = 0.0;
-    if (h->custom) sp[SP_SF2B] = jit;
-    else sp[3] = pivot_tol_rel(u) * (std::fabs(kxx) + jit);
-    if ((rc = copy_theta(u, 1))) return sfail(h, rc, u->err);
-    HIPCHK(hipMemsetAsync(u->dInfo.p, 0, 4, u->stream));
-    h->hPar.as<double>()[0] = mu; h->hPar.as<double>()[1] = sn2;
-    if ((rc = sparse_copy_par(h, 1))) return rc;
-    std::vector<SparsePhase> recs;
-    int inf = 0;
-    {
-        SparseScope ps(h, &recs, 0, u->stream);
-        rc = sparse_factor(h, u, true, "sparse GP: the factorisation of K_uu timed out (set option dataflow=0 and report)", &inf);
-    }
-    if (rc) return rc;
-    if (inf != 0) { sparse_harvest(h, recs); return give_up(inf); }
-    record_fit(u, true, theta, p, u->hRes.as<double>()[0]);
-    // b: an empty bordered workspace; its nugget scalar is sn^2, its pivot tolerance relative to sn^2 (B >= sn^2 I)
-    const double thb[3] = {1.0, 1.0, std::sqrt(sn2)};
-    (void)stage_theta(b, 0, thb);
-    double* spb = b->hSlotp.as<double>();
-    spb[1] = sn2; spb[3] = pivot_tol_rel(b) * sn2; spb[4] = 0.0; spb[SP_MFMA] = 0.0;
-    if ((rc = copy_theta(b, 1))) return sfail(h, rc, b->err);
-    HIPCHK(hipMemsetAsync(b->dInfo.p, 0, 4, b->stream));
-    HIPCHK(hipMemsetAsync(b->dA.p, 0, (size_t)b->slot_elems * h->es, u->stream));
-    // partial sums: [0] the trace, then one per 256 data points of every chunk for r^2, then the same for k(x_i, x_i)
-    const int64_t nchunks = (h->N + rows - 1) / rows;
-    const size_t nblk = (size_t)(h->Npad / 256 + nchunks + 1);
-    HIPCHK(h->dSum.grow((1 + 2 * nblk) * 8));
-    double* d_tr = h->dSum.as<double>();
-    double* d_r2 = d_tr + 1;
-    double* d_kk = d_r2 + nblk;
-    size_t used = 0;
-    for (int64_t c0 = 0; c0 < h->N; c0 += rows) {
-        const int64_t mc = std::min(rows, h->N - c0), mpad = (mc + TB - 1) / TB * TB;
-        {
-            SparseScope ps(h, &recs, 1, u->stream);
-            if ((rc = sparse_load_points(h, h->dXt.p, h->Npad, c0, mpad))) return rc;
-            DISPATCH(u, queue_cross, u, mc, mpad, 1);
-        }
-        {
-            SparseScope ps(h, &recs, 2, u->stream);
-            queue_forward_fit(u, mpad);
-        }
-        DISPATCH(h, sparse_queue_resid, h, c0, mc, mpad, d_r2 + used);
-        if (h->custom) {                       // k(x_i, x_i) per point for a run-time compiled kernel (u->dXsT still holds the chunk)
-            if ((rc = queue_custom_kss(u, mc, mpad, 1))) return sfail(h, rc, u->err);
-            hipLaunchKernelGGL(sparse_blocksum_kernel, dim3((unsigned)((mpad + 255) / 256)), dim3(256), 0, u->stream, u->dKss.as<double>(), 0l,
-                               (int)mc, d_kk + used, 0l);
-        }
-        used += (size_t)((mpad + 255) / 256);
-        {
-            SparseScope ps(h, &recs, 3, u->stream);
-            if ((rc = DISPATCH(h, sparse_queue_accumulate, h, mpad))) return rc;
-        }
-    }
-    DISPATCH(h, sparse_queue_diag, h, d_tr);
-    if (wants_grad) {                          // B itself, before its factorisation overwrites it (the B / (2 sn^2) term of H)
-        HIPCHK(h->dBc.grow((size_t)b->slot_elems * h->es));
-        HIPCHK(hipMemcpyAsync(h->dBc.p, b->dA.p, (size_t)b->slot_elems * h->es, hipMemcpyDeviceToDevice, u->stream));
-    }
-    h->hSum.assign(1 + 2 * nblk, 0.0);
-    HIPCHK(hipMemcpyAsync(h->hSum.data(), h->dSum.p, (1 + (h->custom ? 2 * nblk : nblk)) * 8, hipMemcpyDeviceToHost, u->stream));
-    if ((rc = complete_call(u))) { sparse_harvest(h, recs); return sfail(h, rc, u->err); }      // (the forward substitutions' abort word)
-    {
-        SparseScope ps(h, &recs, 4, b->stream);
-        rc = sparse_factor(h, b, false, "sparse GP: the factorisation of B timed out (set option dataflow=0 and report)", &inf);
-    }
-    if (rc) { sparse_harvest(h, recs); return rc; }
-    const double logdet = b->hRes.as<double>()[0], ctc = b->hRes.as<double>()[1];
-    double rtr = 0.0, skk = 0.0;
-    for (size_t k = 0; k < used; ++k) rtr += h->hSum[1 + k];
-    if (h->custom) for (size_t k = 0; k < used; ++k) skk += h->hSum[1 + nblk + k];
-    else skk = (double)h->N * kxx;
-    const double trvv = h->hSum[0];
-    const double F = -0.5 * ((double)h->N * LOG_TWO_PI + (double)(h->N - h->m) * std::log(sn2) + logdet + (rtr - ctc) / sn2) -
-                     (skk - trvv) / (2.0 * sn2);
-    if (parts) { parts[0] = logdet; parts[1] = ctc; parts[2] = rtr; parts[3] = trvv; parts[4] = skk; }
-    if (out) *out = F;
-    *info = inf != 0 ? inf : (std::isfinite(F) ? GPHIP_INFO_OK : GPHIP_INFO_NAN);
-    record_fit(b, *info == 0, thb, 3, logdet);
+    SparsePhases ph(h);
+    SparseSlot r;
+    // (the gradient wants B itself, before its factorisation overwrites it: the B / (2 sn^2) term of H)
+    if ((rc = sparse_group(h, theta, 1, p, jitter, rows, SparseKeep::fit, wants_grad ? &h->dBc : nullptr, ph, &r))) return rc;
+    if (!r.evaluated) return give_up(r.info);
+    if (parts) r.put_parts(parts);
+    if (out) *out = r.F;
+    *info = r.info;
     h->fitted = *info == 0;
-    h->sn2_fit = sn2; h->mu_fit = mu; h->kxx_fit = kxx;
+    h->sn2_fit = r.sn2; h->mu_fit = r.mu; h->kxx_fit = r.kxx;
     if (wants_grad && *info == 0) {
-        const SparseGradIn in{theta, sn2, mu, rtr, ctc, trvv, skk, rows, nchunks};
-        rc = DISPATCH(h, sparse_grad_phase, h, in, recs, grad, gradZ);
+        const SparseGradIn in{theta, r.sn2, r.mu, r.rtr, r.ctc, r.trvv, r.skk, rows, (h->N + rows - 1) / rows};
+        rc = DISPATCH(h, sparse_grad_phase, h, in, ph, grad, gradZ);
         if (rc && grad) for (int k = 0; k < p; ++k) grad[k] = qnan;
         if (rc && gradZ) for (int64_t k = 0; k < h->m * h->d; ++k) gradZ[k] = qnan;
     }
-    sparse_harvest(h, recs);
     return rc;
 }
 
-// gphip_sparse_bound_batch (DESIGN.md section 8f): the bound for the B rows of Theta, one theta per workspace slot, group after
-// group.  Per group of nb rows: u builds and factors nb K_uu at once; every chunk of data points is loaded once and crossed,
-// substituted, reduced and accumulated for all nb slots by launches whose last grid index is the slot; b factors nb matrices B at
-// once.  No fit is left resident.  A row that fails keeps its slot (a non-finite theta is staged as stage_theta's stand-in values
-// with a unit nugget, so its slot factors) and only its own info / out.
+// gphip_sparse_bound_batch (DESIGN.md section 8f): the bound for the B rows of Theta, one theta per workspace slot, the group
+// evaluator on group after group.  No fit is left resident; a row that fails has only its own info / out to show for it.
 int sparse_eval_batch(gphip_sparse_ctx* h, const double* Theta, int B, int p, double jitter, double* out, double* parts, int* info) {
     gphip_ctx *u = h->u, *b = h->b;
     const double qnan = std::nan("");
     h->fitted = false;
-    for (int k = 0; k < 10; ++k) h->ms[k] = 0.0;
+    sparse_reset_phases(h, PH_KUU_FACTOR, PH_JOINT_V);
     HIPCHK(hipSetDevice(h->device));
     // ---- the group: as many rows as u and b give slots, as keep 2048 data points of V per slot within the ~8 GiB of a chunk
     const int64_t mpm = u->Npad;
@@ -679,143 +786,23 @@ int sparse_eval_batch(gphip_sparse_ctx* h, const double* Theta, int B, int p, do
     h->last_chunk = rows;
     if ((rc = sparse_ensure_rz(h, G, rows))) return rc;
     if ((rc = sparse_ensure_par(h, G))) return rc;
-    // partial sums per slot: [0] the trace, then one per 256 data points of every chunk for r^2, then the same for k(x_i, x_i)
-    const int64_t nchunks = (h->N + rows - 1) / rows;
-    const size_t nblk = (size_t)(h->Npad / 256 + nchunks + 1), ss = 1 + 2 * nblk;
-    HIPCHK(h->dSum.grow((size_t)G * ss * 8));
-    std::vector<SparsePhase> recs;
-    std::vector<char> ok((size_t)G);
-    std::vector<double> sn2v((size_t)G), kxxv((size_t)G), jitv((size_t)G);
-    std::vector<int> uinfo((size_t)G);
+    SparsePhases ph(h);
+    std::vector<SparseSlot> res((size_t)G);
     for (int s0 = 0; s0 < B; s0 += G) {
         const int nb = std::min(G, B - s0);
         h->last_slots = nb;
-        double* par = h->hPar.as<double>();
+        if ((rc = sparse_group(h, Theta + (size_t)s0 * p, nb, p, jitter, rows, SparseKeep::nothing, nullptr, ph, res.data()))) return rc;
         for (int s = 0; s < nb; ++s) {
-            ok[(size_t)s] = stage_theta(u, s, Theta + (size_t)(s0 + s) * p);
-            const double* sp = u->hSlotp.as<double>() + (size_t)s * SLOTP;
-            sn2v[(size_t)s] = sp[1]; kxxv[(size_t)s] = sp[SP_KXX];
-            par[2 * s] = sp[2]; par[2 * s + 1] = sp[1];
-            jitv[(size_t)s] = jitter;
-        }
-        if (jitter < 0.0) {                    // default: joint_jitter_rel x the row's k(x, x) (run-time compiled kernels: its mean of k(z, z))
-            std::vector<double> scale(kxxv.begin(), kxxv.begin() + nb);
-            if (h->custom) {
-                if ((rc = copy_theta(u, nb))) return sfail(h, rc, u->err);
-                if ((rc = sparse_mean_kzz(h, rows, scale.data(), nb))) return rc;
-            }
-            for (int s = 0; s < nb; ++s) jitv[(size_t)s] = joint_jitter_rel(u) * scale[(size_t)s];
-        }
-        for (int s = 0; s < nb; ++s) {
-            double* sp = u->hSlotp.as<double>() + (size_t)s * SLOTP;
-            double jit = jitv[(size_t)s];
-            if (!std::isfinite(jit) || jit < 0.0) ok[(size_t)s] = 0;
-            if (ok[(size_t)s]) h->last_jitter = jit;
-            else jit = 1.0;                    // (the stand-in theta of a row that is given up: K_uu + I factors)
-            // u: the nugget slot carries the jitter; the pivot tolerance follows it
-            sp[1] = jit;
-            sp[SP_MFMA] = 0.0;
-            if (h->custom) sp[SP_SF2B] = jit;
-            else sp[3] = pivot_tol_rel(u) * (std::fabs(kxxv[(size_t)s]) + jit);
-        }
-        if ((rc = copy_theta(u, nb))) return sfail(h, rc, u->err);
-        HIPCHK(hipMemsetAsync(u->dInfo.p, 0, (size_t)nb * 4, u->stream));
-        if ((rc = sparse_copy_par(h, nb))) return rc;
-        {
-            SparseScope ps(h, &recs, 0, u->stream);
-            FactorMode mode(u, true);          // the forward substitutions that follow use the block inverses
-            u->theta_packed = false; u->fused_eval = false;
-            DISPATCH(u, queue_build, u, nb);
-            DISPATCH(u, queue_factor, u, nb);
-        }
-        u->abort_unread = "sparse GP: the factorisation of K_uu timed out (set option dataflow=0 and report)";
-        if ((rc = complete_call(u))) { sparse_harvest(h, recs); return sfail(h, rc, u->err); }
-        bool all_factored = true;
-        for (int s = 0; s < nb; ++s) {
-            uinfo[(size_t)s] = u->hInfo.as<int>()[s];
-            if (uinfo[(size_t)s] != 0) all_factored = false;
-        }
-        // b: empty bordered workspaces; the nugget scalar of slot s is sn_s^2, its pivot tolerance relative to sn_s^2
-        for (int s = 0; s < nb; ++s) {
-            const double sn2 = sn2v[(size_t)s];
-            const double thb[3] = {1.0, 1.0, std::sqrt(sn2)};
-            (void)stage_theta(b, s, thb);
-            double* spb = b->hSlotp.as<double>() + (size_t)s * SLOTP;
-            spb[1] = sn2; spb[3] = pivot_tol_rel(b) * sn2; spb[4] = 0.0; spb[SP_MFMA] = 0.0;
-        }
-        if ((rc = copy_theta(b, nb))) return sfail(h, rc, b->err);
-        HIPCHK(hipMemsetAsync(b->dInfo.p, 0, (size_t)nb * 4, b->stream));
-        HIPCHK(hipMemsetAsync(b->dA.p, 0, (size_t)nb * b->slot_elems * h->es, u->stream));
-        double* d_r2 = h->dSum.as<double>() + 1;
-        double* d_kk = d_r2 + nblk;
-        size_t used = 0;
-        for (int64_t c0 = 0; c0 < h->N; c0 += rows) {
-            const int64_t mc = std::min(rows, h->N - c0), mpad = (mc + TB - 1) / TB * TB;
-            {
-                SparseScope ps(h, &recs, 1, u->stream);
-                if ((rc = sparse_load_points(h, h->dXt.p, h->Npad, c0, mpad))) return rc;
-                DISPATCH(u, queue_cross, u, mc, mpad, nb);
-            }
-            {
-                // every slot's substitution in one pass: ONE dataflow launch (slot = row) where gphip_predict_samples would take it
-                // and every slot of the group has a factor (a slot whose factorisation was abandoned has no block inverses to hand
-                // to the launch's chain), else the batched GEMM substitution, which has no waits
-                SparseScope ps(h, &recs, 2, u->stream);
-                if (all_factored && samples_forward_df(u, nb, mpad)) launch_dataflow_inverse<double, 64>(u, mpad, false, nb, u->dW64s.p);
-                else DISPATCH(u, queue_forward_rows, u, mpad, nb);
-            }
-            DISPATCH(h, sparse_queue_resid, h, c0, mc, mpad, d_r2 + used, nb, (long)ss);
-            if (h->custom) {                   // k(x_i, x_i) per point and slot (u->dXsT still holds the chunk)
-                if ((rc = queue_custom_kss(u, mc, mpad, nb))) return sfail(h, rc, u->err);
-                hipLaunchKernelGGL(sparse_blocksum_kernel, dim3((unsigned)((mpad + 255) / 256), (unsigned)nb), dim3(256), 0, u->stream,
-                                   u->dKss.as<double>(), (long)mpad, (int)mc, d_kk + used, (long)ss);
-            }
-            used += (size_t)((mpad + 255) / 256);
-            {
-                SparseScope ps(h, &recs, 3, u->stream);
-                if ((rc = DISPATCH(h, sparse_queue_accumulate, h, mpad, nb))) return rc;
-            }
-        }
-        // a slot without a factor of K_uu accumulated whatever its V held: B = sn^2 I in its place, so that b factors numbers
-        for (int s = 0; s < nb; ++s)
-            if (uinfo[(size_t)s] != 0)
-                HIPCHK(hipMemsetAsync(static_cast<char*>(b->dA.p) + (size_t)s * b->slot_elems * h->es, 0, (size_t)b->slot_elems * h->es, u->stream));
-        DISPATCH(h, sparse_queue_diag, h, h->dSum.as<double>(), nb, (long)ss);
-        h->hSum.assign((size_t)nb * ss, 0.0);
-        HIPCHK(hipMemcpyAsync(h->hSum.data(), h->dSum.p, (size_t)nb * ss * 8, hipMemcpyDeviceToHost, u->stream));
-        if ((rc = complete_call(u))) { sparse_harvest(h, recs); return sfail(h, rc, u->err); }      // (the forward substitutions' abort word)
-        {
-            SparseScope ps(h, &recs, 4, b->stream);
-            FactorMode mode(b, false);         // (nothing substitutes with L_B here)
-            b->theta_packed = false; b->fused_eval = false;
-            DISPATCH(b, queue_factor, b, nb);
-        }
-        b->abort_unread = "sparse GP: the factorisation of B timed out (set option dataflow=0 and report)";
-        if ((rc = complete_call(b))) { sparse_harvest(h, recs); return sfail(h, rc, b->err); }
-        for (int s = 0; s < nb; ++s) {
-            const double* hs = h->hSum.data() + (size_t)s * ss;
-            const double sn2 = sn2v[(size_t)s];
-            const double logdet = b->hRes.as<double>()[2 * s], ctc = b->hRes.as<double>()[2 * s + 1];
-            double rtr = 0.0, skk = 0.0;
-            for (size_t k = 0; k < used; ++k) rtr += hs[1 + k];
-            if (h->custom) for (size_t k = 0; k < used; ++k) skk += hs[1 + nblk + k];
-            else skk = (double)h->N * kxxv[(size_t)s];
-            const double trvv = hs[0];
-            const double F = -0.5 * ((double)h->N * LOG_TWO_PI + (double)(h->N - h->m) * std::log(sn2) + logdet + (rtr - ctc) / sn2) -
-                             (skk - trvv) / (2.0 * sn2);
-            int inf = b->hInfo.as<int>()[s];
-            if (uinfo[(size_t)s] != 0) inf = uinfo[(size_t)s];                 // (a failure of u comes first)
-            if (!ok[(size_t)s]) inf = GPHIP_INFO_NAN;
-            else if (inf == 0 && !std::isfinite(F)) inf = GPHIP_INFO_NAN;
-            info[s0 + s] = inf;
-            out[s0 + s] = inf == 0 ? F : qnan;
+            const SparseSlot& r = res[(size_t)s];
+            info[s0 + s] = r.info;
+            out[s0 + s] = r.info == 0 ? r.F : qnan;
             if (parts) {
                 double* ps = parts + (size_t)(s0 + s) * 5;
-                ps[0] = logdet; ps[1] = ctc; ps[2] = rtr; ps[3] = trvv; ps[4] = skk;
-                if (inf != 0) for (int k = 0; k < 5; ++k) ps[k] = qnan;
+                r.put_parts(ps);
+                if (r.info != 0) for (int k = 0; k < 5; ++k) ps[k] = qnan;
             }
         }
-        sparse_harvest(h, recs);
+        ph.harvest();                          // (group by group: the events go back to the pool for the next one)
     }
     return GPHIP_OK;
 }
@@ -869,13 +856,27 @@ int sparse_joint_state_check(gphip_sparse_ctx* h) {
     return GPHIP_OK;
 }
 
+// the rhs-row operand -c / sn^2 of the V2 segment: from b's rhs tile row into u's dJZ, on b's stream
+template <typename T>
+void sparse_queue_cblock(gphip_sparse_ctx* h, int64_t kseg) {
+    gphip_ctx *u = h->u, *b = h->b;
+    hipLaunchKernelGGL(joint_cblock_kernel<T>, dim3((unsigned)((kseg + 255) / 256)), dim3(256), 0, b->stream, (const T*)b->dA.p, (int)b->R,
+                       (int)kseg, h->sn2_fit, (T*)u->dJZ.p, (long)kseg);
+}
+
+// the two-segment downdate of the child's workspace: Sigma = K(X*, X*) - V1^T V1 + sn^2 V2^T V2
+template <typename T>
+int sparse_queue_joint_downdate(gphip_sparse_ctx* h, int64_t mpad) {
+    return queue_downdate_any<T, true>(h->u, h->u->joint, mpad, h->joint_split, &h->joint_nsplit, h->sn2_fit);
+}
+
 // Everything up to Sigma in the workspace of u's child: V1 on u, V2 and the rhs-row operand on b, then build + downdate on the
 // child.  The child's diagonal carries k(x*, x*) + (noisy: sn^2) + (*jitter_io, which a negative value turns into the default).
 int sparse_joint_sigma(gphip_sparse_ctx* h, const double* Xs, int64_t M, const double* ystar, bool noisy, double* jitter_io,
-                       std::vector<SparsePhase>& recs) {
+                       SparsePhases& ph) {
     gphip_ctx *u = h->u, *b = h->b;
     HIPCHK(hipSetDevice(h->device));
-    for (int k = 10; k < 14; ++k) h->ms[k] = 0.0;
+    sparse_reset_phases(h, PH_JOINT_V, PH_COUNT);
     const int64_t mpad = (M + TB - 1) / TB * TB, kseg = u->Npad;
     const size_t seg_bytes = (size_t)mpad * kseg * h->es;
     int rc = ensure_vbuf(u, 2 * mpad);         // u's dV takes both segments: [V1 | V2], mpad x 2 kseg with ld mpad
@@ -885,7 +886,7 @@ int sparse_joint_sigma(gphip_sparse_ctx* h, const double* Xs, int64_t M, const d
     HIPCHK(hipMemsetAsync(u->dJZ.p, 0, (size_t)TB * 2 * kseg * h->es, u->stream));
     std::vector<double> xt;
     {
-        SparseScope ps(h, &recs, 10, u->stream);
+        SparseScope ps(ph, PH_JOINT_V, u->stream);
         stage_test_chunk(u, Xs, 0, M, 1, 0, xt, &rc, false);      // all M rows as one chunk
         if (rc) return sfail(h, rc, u->err);
         queue_forward_fit(u, mpad);
@@ -895,35 +896,28 @@ int sparse_joint_sigma(gphip_sparse_ctx* h, const double* Xs, int64_t M, const d
     if ((rc = complete_call(u))) return sfail(h, rc, u->err);
     {
         // V2 = L_B^-1 V1: the same rows through b's factor, then next to V1; the rhs-row operand from b's rhs row
-        SparseScope ps(h, &recs, 10, b->stream);
+        SparseScope ps(ph, PH_JOINT_V, b->stream);
         HIPCHK(hipMemcpyAsync(b->dV.p, u->dV.p, seg_bytes, hipMemcpyDeviceToDevice, b->stream));
         queue_forward_fit(b, mpad);
         HIPCHK(hipMemcpyAsync(static_cast<char*>(u->dV.p) + seg_bytes, b->dV.p, seg_bytes, hipMemcpyDeviceToDevice, b->stream));
-        const dim3 grid((unsigned)((kseg + 255) / 256));
-        if (h->dtype == 64)
-            hipLaunchKernelGGL(joint_cblock_kernel<double>, grid, dim3(256), 0, b->stream, (const double*)b->dA.p, (int)b->R, (int)kseg,
-                               h->sn2_fit, (double*)u->dJZ.p, (long)kseg);
-        else
-            hipLaunchKernelGGL(joint_cblock_kernel<float>, grid, dim3(256), 0, b->stream, (const float*)b->dA.p, (int)b->R, (int)kseg,
-                               h->sn2_fit, (float*)u->dJZ.p, (long)kseg);
+        DISPATCH(h, sparse_queue_cblock, h, kseg);
     }
     if ((rc = complete_call(b))) return sfail(h, rc, b->err);
     if ((rc = joint_child(u, Xs, M, ystar))) return sfail(h, rc, u->err);
     gphip_ctx* c = u->joint;
     {
-        SparseScope ps(h, &recs, 11, c->stream);
+        SparseScope ps(ph, PH_JOINT_BUILD, c->stream);
         rc = joint_build(u, noisy, jitter_io, kss_mean);
     }
     if (rc) return sfail(h, rc, u->err);
     {
-        SparseScope ps(h, &recs, 12, c->stream);
-        rc = h->dtype == 64 ? queue_downdate_any<double, true>(u, c, mpad, h->joint_split, &h->joint_nsplit, h->sn2_fit)
-                            : queue_downdate_any<float, true>(u, c, mpad, h->joint_split, &h->joint_nsplit, h->sn2_fit);
+        SparseScope ps(ph, PH_JOINT_DOWNDATE, c->stream);
+        rc = DISPATCH(h, sparse_queue_joint_downdate, h, mpad);
     }
     return rc ? sfail(h, rc, u->err) : GPHIP_OK;
 }
 
-// the event pair of the factorisation of Sigma while option "profile" is on (phase 13)
+// the event pair of the factorisation of Sigma while option "profile" is on
 struct SparseFactorEvents {
     hipEvent_t ev[2];
     bool on;
@@ -931,8 +925,8 @@ struct SparseFactorEvents {
         if (on) { ev[0] = get_event(h->u); ev[1] = get_event(h->u); }
     }
     hipEvent_t* get() { return on ? ev : nullptr; }
-    void hand_over(std::vector<SparsePhase>& recs) {
-        if (on) recs.push_back(SparsePhase{13, ev[0], ev[1]});
+    void hand_over(SparsePhases& ph) {
+        if (on) ph.recs.push_back(SparsePhase{PH_JOINT_FACTOR, ev[0], ev[1]});
     }
 };
 
@@ -996,9 +990,8 @@ int gphip_sparse_bound(gphip_sparse_handle h, const double* theta, int p, double
 int gphip_sparse_bound_batch(gphip_sparse_handle h, const double* Theta, int B, int p, double jitter, double* out, double* parts,
                              int* info) {
     if (!h || !Theta || !out || !info) return sfail(h, GPHIP_ERR_ARG, "null argument");
-    if (std::isnan(jitter) || std::isinf(jitter)) return sfail(h, GPHIP_ERR_ARG, "non-finite jitter");
     std::lock_guard<std::recursive_mutex> lk(h->mu);
-    if (p != h->u->p) return sfail(h, GPHIP_ERR_DIM, "theta has the wrong length for this kernel/mean");
+    if (const int rc = sparse_check_args(h, p, jitter)) return rc;
     if (B <= 0) return GPHIP_OK;
     return sparse_eval_batch(h, Theta, B, p, jitter, out, parts, info);
 }
@@ -1007,8 +1000,8 @@ int gphip_sparse_nested_sampling(gphip_sparse_handle h, double jitter, const dou
                                  void* user, const gphip_ns_options* opts, const double* start, int64_t cap, double* points, double* loglik,
                                  double* logprior_out, double* accept_rate, int64_t* n_samples, double* log_evidence, int64_t* n_evals) {
     if (!h) return GPHIP_ERR_ARG;
-    if (std::isnan(jitter) || std::isinf(jitter)) return sfail(h, GPHIP_ERR_ARG, "non-finite jitter");
     std::lock_guard<std::recursive_mutex> lk(h->mu);
+    if (const int rc = sparse_check_args(h, h->u->p, jitter)) return rc;
     return ns_run(h->u->p,
                   [&](const double* Theta, int B, int p, double* out, int* info) {
                       return gphip_sparse_bound_batch(h, Theta, B, p, jitter, out, nullptr, info);
@@ -1022,8 +1015,7 @@ int gphip_sparse_bound_grad(gphip_sparse_handle h, const double* theta, int p, d
     if (!h || !theta || !out || !grad || !info) return sfail(h, GPHIP_ERR_ARG, "null argument");
     std::lock_guard<std::recursive_mutex> lk(h->mu);
     gphip_ctx* u = h->u;
-    if (p != u->p) return sfail(h, GPHIP_ERR_DIM, "theta has the wrong length for this kernel/mean");
-    if (std::isnan(jitter) || std::isinf(jitter)) return sfail(h, GPHIP_ERR_ARG, "non-finite jitter");
+    if (const int rc = sparse_check_args(h, p, jitter)) return rc;
     h->grad_analytic = 0;
     if (h->custom) {
         if (const int rc = ensure_custom_grad(u)) return sfail(h, rc, u->err);
@@ -1066,8 +1058,7 @@ int gphip_sparse_bound_grad_inducing(gphip_sparse_handle h, const double* theta,
                                      double* gradZ, double* parts, int* info) {
     if (!h || !theta || !out || !gradZ || !info) return sfail(h, GPHIP_ERR_ARG, "null argument");
     std::lock_guard<std::recursive_mutex> lk(h->mu);
-    if (p != h->u->p) return sfail(h, GPHIP_ERR_DIM, "theta has the wrong length for this kernel/mean");
-    if (std::isnan(jitter) || std::isinf(jitter)) return sfail(h, GPHIP_ERR_ARG, "non-finite jitter");
+    if (const int rc = sparse_check_args(h, p, jitter)) return rc;
     // (a run-time compiled function would need its dual-number program seeded in the coordinates: not built)
     if (h->custom) return sfail(h, GPHIP_ERR_UNSUPPORTED, "no gradient in the inducing locations for a run-time compiled covariance function");
     h->grad_analytic = 0;
@@ -1124,10 +1115,9 @@ int gphip_sparse_predict_cov(gphip_sparse_handle h, const void* Xs, int64_t M, i
     if (int rc = sparse_joint_dim_check(h, M)) return rc;
     std::lock_guard<std::recursive_mutex> lk(h->mu);
     if (int rc = sparse_joint_state_check(h)) return rc;
-    std::vector<SparsePhase> recs;
-    int rc = sparse_joint_sigma(h, static_cast<const double*>(Xs), M, nullptr, !latent, nullptr, recs);
+    SparsePhases ph(h);
+    int rc = sparse_joint_sigma(h, static_cast<const double*>(Xs), M, nullptr, !latent, nullptr, ph);
     if (!rc && (rc = joint_cov_tail(h->u, M, mean, cov))) (void)sfail(h, rc, h->u->err);
-    sparse_harvest(h, recs);
     return rc;
 }
 
@@ -1140,13 +1130,12 @@ int gphip_sparse_predict_draws(gphip_sparse_handle h, const void* Xs, int64_t M,
     std::lock_guard<std::recursive_mutex> lk(h->mu);
     if (int rc = sparse_joint_state_check(h)) return rc;
     *info = GPHIP_INFO_OK;
-    std::vector<SparsePhase> recs;
+    SparsePhases ph(h);
     SparseFactorEvents fev(h);
     double jit = jitter;
-    int rc = sparse_joint_sigma(h, static_cast<const double*>(Xs), M, nullptr, !latent, &jit, recs);
+    int rc = sparse_joint_sigma(h, static_cast<const double*>(Xs), M, nullptr, !latent, &jit, ph);
     if (!rc && (rc = joint_draws_tail(h->u, M, S, seed, z, out, info, fev.get()))) (void)sfail(h, rc, h->u->err);
-    fev.hand_over(recs);
-    sparse_harvest(h, recs);
+    fev.hand_over(ph);
     return rc;
 }
 
@@ -1157,12 +1146,11 @@ int gphip_sparse_predict_logpdf(gphip_sparse_handle h, const void* Xs, int64_t M
     if (int rc = sparse_joint_state_check(h)) return rc;
     for (int64_t j = 0; j < M; ++j)
         if (!std::isfinite(ystar[j])) { *out = NAN; *info = GPHIP_INFO_NAN; return GPHIP_OK; }
-    std::vector<SparsePhase> recs;
+    SparsePhases ph(h);
     SparseFactorEvents fev(h);
-    int rc = sparse_joint_sigma(h, static_cast<const double*>(Xs), M, ystar, true, nullptr, recs);
+    int rc = sparse_joint_sigma(h, static_cast<const double*>(Xs), M, ystar, true, nullptr, ph);
     if (!rc && (rc = joint_logpdf_tail(h->u, M, out, info, fev.get()))) (void)sfail(h, rc, h->u->err);
-    fev.hand_over(recs);
-    sparse_harvest(h, recs);
+    fev.hand_over(ph);
     return rc;
 }
 
@@ -1188,11 +1176,8 @@ int gphip_sparse_set_option(gphip_sparse_handle h, const char* name, double valu
 int gphip_sparse_get_option(gphip_sparse_handle h, const char* name, double* value) {
     if (!h || !name || !value) return GPHIP_ERR_ARG;
     std::lock_guard<std::recursive_mutex> lk(h->mu);
-    static const char* const phases[14] = {"ms_kuu_factor", "ms_cross", "ms_forward", "ms_accumulate", "ms_b_factor",
-                                           "ms_grad_small", "ms_grad_weights", "ms_grad_backward", "ms_grad_reduce", "ms_grad_inducing",
-                                           "ms_joint_v", "ms_joint_build", "ms_joint_downdate", "ms_joint_factor"};
-    for (int k = 0; k < 14; ++k)
-        if (!strcmp(name, phases[k])) { *value = h->ms[k]; return GPHIP_OK; }
+    for (int k = 0; k < PH_COUNT; ++k)
+        if (!strcmp(name, SPARSE_PHASE_OPTION[k])) { *value = h->ms[k]; return GPHIP_OK; }
     if (!strcmp(name, "sparse_chunk")) { *value = h->chunk; return GPHIP_OK; }
     if (!strcmp(name, "sparse_split")) { *value = h->split; return GPHIP_OK; }
     if (!strcmp(name, "profile")) { *value = h->profile; return GPHIP_OK; }

@@ -78,6 +78,29 @@ def test_targeted_stream_changes_only_through_a_scope():
     assert "Scoped<hipStream_t>" in _code(os.path.join(CSRC, "gphip.hip"))
 
 
+def test_sparse_bound_has_one_forward_pass_and_owned_phase_records():
+    # The collapsed bound's forward pass exists once, in the group evaluator the one-theta and the batched entry points share
+    # (DESIGN.md section 8f): a second copy of the chunk loop or of the formula for F drifts.  Phases are named by the
+    # SparsePhaseId enum, and the HIP-event records of a call belong to `struct SparsePhases`, whose destructor hands the
+    # events back to the pool on every exit path: nothing else harvests them.
+    code = _code(os.path.join(CSRC, "gphip_sparse.inc"))
+    for fn in ("sparse_queue_accumulate", "sparse_queue_diag"):
+        uses = re.findall(r"\b%s\b.{0,24}" % fn, code)              # its definition `int fn(gphip_sparse_ctx* h, ..` and its call sites
+        sites = [u for u in uses if not u.startswith(fn + "(gphip_sparse_ctx*")]
+        assert len(uses) == 2 and len(sites) == 1, (fn, uses)
+    assert len(re.findall(r"\bsparse_blocksum_kernel\b", code)) == 1          # (defined in gp_sparse.h)
+    assert len(re.findall(r"\bLOG_TWO_PI\b", code)) == 1
+    scopes = re.findall(r"\bSparseScope\s+\w+\s*\(([^;]*)\);", code)
+    assert len(scopes) >= 15, scopes
+    for args in scopes:                                              # (owner, phase, stream)
+        assert re.fullmatch(r"PH_[A-Z_]+", args.split(",")[1].strip()), args
+    owner = re.search(r"\nstruct SparsePhases \{.*?\n\};", code, flags=re.S)
+    assert owner and "~SparsePhases() { harvest(); }" in owner.group(0), "the owner of the phase records (struct SparsePhases) is missing"
+    rest = code[:owner.start()] + code[owner.end():]
+    assert "sparse_harvest" not in rest
+    assert all(re.fullmatch(r"\w+\.harvest\(\)", m) for m in re.findall(r"[\w.>-]*\bharvest\b(?:\(\))?", rest)), "harvest outside the owner"
+
+
 def test_gfx950_only_no_compat_layers():
     for name in os.listdir(CSRC):
         code = _code(os.path.join(CSRC, name))
