@@ -137,6 +137,7 @@ _SIGNATURES = {
     "gphip_sparse_bound_grad_inducing": (C.c_int, [_h, _dp, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _ip]),
     "gphip_sparse_fit": (C.c_int, [_h, _dp, C.c_int, C.c_double, _ip]),
     "gphip_sparse_predict": (C.c_int, [_h, C.c_void_p, C.c_int64, C.c_int, _dp, _dp]),
+    "gphip_sparse_predict_samples": (C.c_int, [_h, _dp, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_int64, C.c_int, _dp, _dp, _dp, _ip]),
     "gphip_sparse_predict_cov": (C.c_int, [_h, C.c_void_p, C.c_int64, C.c_int, _dp, _dp]),
     "gphip_sparse_predict_draws": (C.c_int, [_h, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_uint64, _dp, C.c_double, _dp, _ip]),
     "gphip_sparse_predict_logpdf": (C.c_int, [_h, C.c_void_p, C.c_int64, _dp, _dp, _ip]),
@@ -666,6 +667,7 @@ SPARSE_PHASES = ("ms_kuu_factor", "ms_cross", "ms_forward", "ms_accumulate", "ms
 SPARSE_GRAD_PHASES = ("ms_grad_small", "ms_grad_weights", "ms_grad_backward", "ms_grad_reduce")
 SPARSE_ZGRAD_PHASES = ("ms_grad_inducing",)
 SPARSE_JOINT_PHASES = ("ms_joint_v", "ms_joint_build", "ms_joint_downdate", "ms_joint_factor")
+SPARSE_SAMPLES_PHASES = ("ms_samples_v1", "ms_samples_handover", "ms_samples_v2", "ms_samples_reduce")
 
 
 class SparseHandle:
@@ -830,6 +832,23 @@ class SparseHandle:
         mean, var = np.zeros(M), np.zeros(M)
         self._check(self._lib.gphip_sparse_predict(self._h, Xs.ctypes.data, M, 1 if latent else 0, _d(mean), _d(var)))
         return mean, var
+
+    def predict_samples(self, Thetas, Xs, jitter: float = -1.0, latent: bool = False, bound: bool = False):
+        """gphip_sparse_predict_samples: (mean[S, M], var[S, M], info[S]) -- with bound=True also F[S] -- at Xs for the rows of
+        Thetas [S, p] in ONE call; row s is `fit(Thetas[s], jitter)` followed by `predict(Xs, latent)` up to rounding, jitter < 0
+        the default rule per row.  A row that fails has info != 0 and its rows of mean and var (and its F) NaN without disturbing
+        the others.  No fit stays resident."""
+        Th = np.ascontiguousarray(np.asarray(Thetas, dtype=np.float64))
+        if Th.ndim == 1:
+            Th = Th.reshape(1, -1)
+        Xs = self._test_points(Xs)
+        S, p = Th.shape
+        M = Xs.shape[0]
+        mean, var, info = np.zeros((S, M)), np.zeros((S, M)), np.zeros(S, dtype=np.int32)
+        F = np.zeros(S) if bound else None
+        self._check(self._lib.gphip_sparse_predict_samples(self._h, _d(Th), S, p, float(jitter), Xs.ctypes.data, M, int(bool(latent)),
+                                                           _d(mean), _d(var), _d(F) if bound else None, info.ctypes.data_as(_ip)))
+        return (mean, var, info, F) if bound else (mean, var, info)
 
     def _test_points(self, Xs):
         Xs = np.ascontiguousarray(np.atleast_2d(np.asarray(Xs, dtype=np.float64)))

@@ -7,13 +7,16 @@
 //   sparse_resid_kernel          r = y - mu of a chunk into row 0 of the rhs operand + per-block partial sums of r^2
 //   sparse_blocksum_kernel       per-block partial sums of a double vector (k(x_i, x_i) of a run-time compiled kernel)
 //   sparse_diag_kernel           tr(V V^T) from C's diagonal, then + sn^2 on it (identity on the pad)
-//   sparse_predict_finish_kernel mean and variance of a chunk of test points from the strip partials of v1 and v2
+//   sparse_predict_finish_kernel mean and variance of a chunk of test points from the strip partials of v1 and v2, per slot
+//   sparse_handover_kernel       gphip_sparse_predict_samples: V1 of every slot from u's dV into b's + the strip partials of |v1|^2
 //   sparse_small / _trace / _vta / _w / _weight / _transpose_kernel   the gradient of the bound, see the second half of this file
 //   sparse_zgrad_kernel / sparse_zgrad_finish_kernel   the gradient of the bound in the inducing LOCATIONS, see the end of this file
 #pragma once
 #include "gp_kernels.h"
 
 namespace gphip {
+
+constexpr int SPARSE_PAR = 4;                  // doubles per slot of the sparse object's own scalars: mu, sn^2, k(x, x), unused
 
 // ---------------------------------------------------------------------------------------------
 // Accumulation.  V is the chunk of L_u^-1 k(Z, X) the forward substitution leaves: column-major, V(t, k) at V[t + k ldv],
@@ -286,22 +289,81 @@ __global__ __launch_bounds__(256) void sparse_diag_kernel(T* __restrict__ C, lon
     if (threadIdx.x == 0) out[0] = s;
 }
 
-// Prediction epilogue.  part1 / part2: the strip partials predict_partial_kernel leaves for v1 = L_u^-1 k(Z, x*) (its norms)
-// and for v2 = L_B^-1 v1 against c (dots and norms), [strip][2][mpad] each.
+// Prediction epilogue, one slot per blockIdx.y (the one-theta call: one slot).  part1: strip partials of |v1|^2, v1 = L_u^-1 k(Z, x*),
+// strip s of slot q at part1[q p1_bstride + s p1_sstride + t] (predict_partial_kernel's norm rows of u, or what
+// sparse_handover_kernel leaves); part2: predict_partial_kernel's [slot][strip][2][mpad] for v2 = L_B^-1 v1 against c (dots and
+// norms).  par: [slot][SPARSE_PAR] = mu, sn^2 and the scalar k(x, x) of the slot's theta; kss [slot][mpad] (run-time compiled
+// kernels): k(x*, x*) per point in its place.  mean, var: [slot][mpad].
 //     mean = mu + v2^T c        var = k(x*, x*) [+ sn2] - |v1|^2 + sn2 |v2|^2
-__global__ void sparse_predict_finish_kernel(const double* __restrict__ part1, int nstrips1, const double* __restrict__ part2, int nstrips2,
-                                             long mpad, int mc, double mu, double kxx, const double* __restrict__ kss, double sn2, int latent,
-                                             double* __restrict__ mean, double* __restrict__ var) {
+__global__ void sparse_predict_finish_kernel(const double* __restrict__ part1, int nstrips1, long p1_sstride, long p1_bstride,
+                                             const double* __restrict__ part2, int nstrips2, long mpad, int mc,
+                                             const double* __restrict__ par, const double* __restrict__ kss, int latent, double* __restrict__ mean, double* __restrict__ var) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    const int slot = blockIdx.y;
     if (t >= mc) return;
+    const double mu = par[SPARSE_PAR * slot], sn2 = par[SPARSE_PAR * slot + 1];
+    part1 += (long)slot * p1_bstride;
+    part2 += (long)slot * nstrips2 * 2 * mpad;
     double n1 = 0.0, dot = 0.0, n2 = 0.0;
-    for (int s = 0; s < nstrips1; ++s) n1 += part1[((long)s * 2 + 1) * mpad + t];
+    for (int s = 0; s < nstrips1; ++s) n1 += part1[(long)s * p1_sstride + t];
     for (int s = 0; s < nstrips2; ++s) {
         dot += part2[((long)s * 2 + 0) * mpad + t];
         n2 += part2[((long)s * 2 + 1) * mpad + t];
     }
-    mean[t] = mu + dot;
-    var[t] = (kss ? kss[t] : kxx) + (latent ? 0.0 : sn2) - n1 + sn2 * n2;
+    const long o = (long)slot * mpad + t;
+    mean[o] = mu + dot;
+    var[o] = (kss ? kss[o] : par[SPARSE_PAR * slot + 2]) + (latent ? 0.0 : sn2) - n1 + sn2 * n2;
+}
+
+// gphip_sparse_predict_samples: V1 = L_u^-1 k(Z, X*) of every slot of a group goes from u's dV into b's, and the norms |v1|^2 are
+// taken on the way -- ONE pass that reads V1 once (the one-theta call copies device to device and then runs
+// predict_partial_kernel on u: two reads, one write).  predict_partial_kernel's access pattern: one workgroup per 128 test points
+// x strip of js columns x slot, wave w takes columns w, w + 4, .. of the strip, a lane moves 2 adjacent test points per column
+// (fp64: one 16-byte load and store), four columns in flight per wave, fp64 partial sums that meet in LDS in a fixed order.
+// Columns [ncols, ncols_pad) are the pad of the inducing points: copied (b substitutes over whole tiles), not summed.
+// grid = (mpad / 128, nstrips, nslots); V (both): V(t, j) at V[slot bstride + t + j ldv]; part: [slot][strip][mpad].
+template <typename T>
+__global__ __launch_bounds__(256) void sparse_handover_kernel(const T* __restrict__ V, T* __restrict__ out, long ldv, long bstride,
+                                                              int ncols, int ncols_pad, int js, double* __restrict__ part, int nstrips) {
+    __shared__ double red[4 * TB];
+    typedef typename Num<T>::pair_t pair_t;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tb = blockIdx.x, strip = blockIdx.y, slot = blockIdx.z;
+    const int j0 = strip * js;
+    const int jn = (ncols - j0 < js) ? (ncols - j0) : js;           // columns of this strip that are summed (<= 0: none)
+    const int jc = (ncols_pad - j0 < js) ? (ncols_pad - j0) : js;   // columns of this strip that are copied
+    const long base = (long)slot * bstride + (long)tb * TB + 2 * lane;
+    V += base;
+    out += base;
+    double n0 = 0.0, n1 = 0.0;
+    int j = wave;
+    for (; j + 12 < jn; j += 16) {                // four independent 16-byte loads in flight per lane
+        pair_t v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const pair_t*>(V + (long)(j0 + j + 4 * u) * ldv);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            *reinterpret_cast<pair_t*>(out + (long)(j0 + j + 4 * u) * ldv) = v[u];
+            const double a = (double)v[u].x, b = (double)v[u].y;
+            n0 = __builtin_fma(a, a, n0); n1 = __builtin_fma(b, b, n1);
+        }
+    }
+    for (; j < jn; j += 4) {
+        const pair_t v = *reinterpret_cast<const pair_t*>(V + (long)(j0 + j) * ldv);
+        *reinterpret_cast<pair_t*>(out + (long)(j0 + j) * ldv) = v;
+        const double a = (double)v.x, b = (double)v.y;
+        n0 = __builtin_fma(a, a, n0); n1 = __builtin_fma(b, b, n1);
+    }
+    for (; j < jc; j += 4)
+        *reinterpret_cast<pair_t*>(out + (long)(j0 + j) * ldv) = *reinterpret_cast<const pair_t*>(V + (long)(j0 + j) * ldv);
+    red[wave * TB + 2 * lane] = n0; red[wave * TB + 2 * lane + 1] = n1;
+    __syncthreads();
+    if (tid < TB) {
+        double s = 0.0;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) s += red[w * TB + tid];
+        part[((long)slot * nstrips + strip) * ldv + (long)tb * TB + tid] = s;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------

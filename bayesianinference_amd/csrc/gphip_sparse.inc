@@ -4,7 +4,8 @@
 // The forward pass of the bound exists once, in sparse_group: nb thetas in workspace slots 0 .. nb - 1 of u and b, every launch
 // with the slot as its last grid index.  sparse_eval (gphip_sparse_bound / _fit / _bound_grad / _bound_grad_inducing) is the group
 // of ONE slot in resident mode (SparseKeep::fit), sparse_eval_batch (gphip_sparse_bound_batch, the native sampler) loops groups in
-// batch mode (SparseKeep::nothing); DESIGN.md section 8f lists what the mode decides.  Per slot:
+// batch mode (SparseKeep::nothing), sparse_predict_samples (gphip_sparse_predict_samples) loops them in SparseKeep::group and
+// substitutes with the factors each group leaves; DESIGN.md sections 8f and 8h list what the mode decides.  Per slot:
 //   u (a context whose TRAINING points are Z, y = 0; its nugget slot scalar carries the jitter j)
 //        queue_build + queue_factor        L_u L_u^T = k(Z, Z) + j I, direct-difference kernel build
 //        per chunk of data points, treated as test points of u:
@@ -25,6 +26,9 @@
 //   sparse_zgrad_finish_kernel adds the strip partials, H first and then chunk after chunk, into the m x d accumulator dZacc
 // Prediction: v1 = L_u^-1 k(Z, x*) by u's forward substitution, v2 = L_B^-1 v1 by b's, predict_partial_kernel on both and one
 // finishing kernel.  Everything of one evaluation up to B runs on u's stream; b's stream takes over after a host synchronisation.
+// Prediction over samples (gphip_sparse_predict_samples, DESIGN.md section 8h): the same per chunk of test points for all slots of
+//   a group at once; sparse_handover_kernel takes V1 from u's dV to b's and the norms |v1|^2 on the way, b's stream waits for an
+//   event of u's.
 // Joint prediction (gphip_sparse_predict_cov / _draws / _logpdf, DESIGN.md section 8g): all M rows of V1 = L_u^-1 k(Z, X*) and
 //   V2 = L_B^-1 V1 side by side in u's dV, the rhs-row operand -c / sn^2 in u's dJZ; u owns the child context of the exact
 //   path (u->joint, gphip_joint.inc: training points X*, K(X*, X*) by the direct build) and the two-segment downdate_kernel turns
@@ -33,17 +37,20 @@
 #include "gp_sparse.h"
 
 // The phases timed by HIP events while option "profile" is on, and the options that read them (gphip_sparse_get_option).
-// PH_KUU_FACTOR .. PH_GRAD_INDUCING are reset by every evaluation of the bound, PH_JOINT_V .. by every joint prediction.
+// PH_KUU_FACTOR .. PH_GRAD_INDUCING are reset by every evaluation of the bound, PH_JOINT_V .. PH_JOINT_FACTOR by every joint
+// prediction, PH_SAMPLES_VU .. by every gphip_sparse_predict_samples (which also evaluates the bound).
 enum SparsePhaseId {
     PH_KUU_FACTOR, PH_CROSS, PH_FORWARD, PH_ACCUMULATE, PH_B_FACTOR,                               // the bound
     PH_GRAD_SMALL, PH_GRAD_WEIGHTS, PH_GRAD_BACKWARD, PH_GRAD_REDUCE, PH_GRAD_INDUCING,            // its gradients
     PH_JOINT_V, PH_JOINT_BUILD, PH_JOINT_DOWNDATE, PH_JOINT_FACTOR,                                // joint prediction
+    PH_SAMPLES_VU, PH_SAMPLES_HANDOVER, PH_SAMPLES_VB, PH_SAMPLES_REDUCE,                          // prediction over samples
     PH_COUNT
 };
 static const char* const SPARSE_PHASE_OPTION[] = {
     "ms_kuu_factor", "ms_cross", "ms_forward", "ms_accumulate", "ms_b_factor",
     "ms_grad_small", "ms_grad_weights", "ms_grad_backward", "ms_grad_reduce", "ms_grad_inducing",
-    "ms_joint_v", "ms_joint_build", "ms_joint_downdate", "ms_joint_factor"};
+    "ms_joint_v", "ms_joint_build", "ms_joint_downdate", "ms_joint_factor",
+    "ms_samples_v1", "ms_samples_handover", "ms_samples_v2", "ms_samples_reduce"};
 static_assert(sizeof SPARSE_PHASE_OPTION / sizeof SPARSE_PHASE_OPTION[0] == PH_COUNT, "one option name per phase");
 
 struct gphip_sparse_ctx {
@@ -59,7 +66,7 @@ struct gphip_sparse_ctx {
     std::vector<std::pair<std::string, double>> forwarded;    // options handed on to u and b (replayed after gphip_sparse_set_inducing)
     Buf dXt, dY;                               // typed [d][Npad], [Npad]: the data, resident
     Buf dRz; int64_t rcap = 0; int rz_slots = 0;   // typed [slot][16][rcap]: row 0 = r of the current chunk, the other rows zero
-    Buf dPar, hPar;                            // double [slot][2]: mu and sn^2 of every slot's theta (device; pinned staging copy)
+    Buf dPar, hPar;                            // double [slot][SPARSE_PAR]: mu, sn^2 and k(x, x) of every slot's theta (device; pinned staging copy)
     Buf dAccP;                                 // typed [slot][strip][tile][128 x 128]: strip partials of the accumulation
     Buf dSum; std::vector<double> hSum;        // double, per slot: [0] tr(V V^T), then the per-block partial sums of r^2 and of k(x_i, x_i)
     Buf dBc, dS, dH;                           // gradient, typed: B's tiles before its factorisation; S; the inner matrix of H (mpad x mpad)
@@ -69,17 +76,21 @@ struct gphip_sparse_ctx {
     // options
     int chunk = 0, split = 0, profile = 0;
     int joint_split = 0;                       // joint prediction: strips of the stacked contraction (0 = by the split rule)
-    int batch_slots = 0;                       // gphip_sparse_bound_batch: most thetas per group (0 = by the group rule)
+    int batch_slots = 0;                       // gphip_sparse_bound_batch / _predict_samples: most thetas per group (0 = by the group rule)
+    int samples_chunk = 0;                     // gphip_sparse_predict_samples: test points per pass (0 = by the rule)
+    int samples_handover = 1;                  // gphip_sparse_predict_samples: 1 = sparse_handover_kernel, 0 = copy + norm launch (measurement)
     // read-only results of the last call
     int last_nsplit = 0;
     int joint_nsplit = 0;                      // strips the last joint prediction's downdate used
     int last_slots = 0;                        // thetas in the last group of the last gphip_sparse_bound_batch
     int64_t last_chunk = 0;
+    int64_t last_samples_chunk = 0;            // test points per pass of the last gphip_sparse_predict_samples
     double last_jitter = 0.0;
     int grad_analytic = 0;                     // the last gphip_sparse_bound_grad: 1 = the analytic route, 0 = central differences
     double ms[PH_COUNT] = {};                  // K_uu factor, cross build, forward substitution, accumulation, B factor;
                                                // gradient: small m x m work, weights, backward substitution, reductions, the reduction in Z;
-                                               // joint prediction: V1 and V2, K(X*, X*), the downdate, the factorisation of Sigma
+                                               // joint prediction: V1 and V2, K(X*, X*), the downdate, the factorisation of Sigma;
+                                               // prediction over samples: V1, the handover to b, V2, the reductions
     // the resident fit
     bool fitted = false;
     double sn2_fit = 0, mu_fit = 0, kxx_fit = 0;
@@ -198,14 +209,14 @@ int sparse_ensure_rz(gphip_sparse_ctx* h, int nb, int64_t rows) {
     return GPHIP_OK;
 }
 
-// mu and sn^2 of the first nb slots, staged in hPar -> device, on u's stream
+// mu, sn^2 and k(x, x) of the first nb slots, staged in hPar -> device, on u's stream
 int sparse_copy_par(gphip_sparse_ctx* h, int nb) {
-    HIPCHK(hipMemcpyAsync(h->dPar.p, h->hPar.p, (size_t)nb * 16, hipMemcpyHostToDevice, h->u->stream));
+    HIPCHK(hipMemcpyAsync(h->dPar.p, h->hPar.p, (size_t)nb * SPARSE_PAR * 8, hipMemcpyHostToDevice, h->u->stream));
     return GPHIP_OK;
 }
 int sparse_ensure_par(gphip_sparse_ctx* h, int nb) {
-    HIPCHK(h->dPar.grow((size_t)nb * 16));
-    HIPCHK(h->hPar.grow((size_t)nb * 16, true));
+    HIPCHK(h->dPar.grow((size_t)nb * SPARSE_PAR * 8));
+    HIPCHK(h->hPar.grow((size_t)nb * SPARSE_PAR * 8, true));
     return GPHIP_OK;
 }
 
@@ -246,7 +257,7 @@ int sparse_queue_accumulate(gphip_sparse_ctx* h, int64_t mpad, int nb = 1) {
 template <typename T>
 int sparse_queue_resid(gphip_sparse_ctx* h, int64_t c0, int64_t mc, int64_t mpad, double* part, int nb = 1, long pstride = 0) {
     hipLaunchKernelGGL(sparse_resid_kernel<T>, dim3((unsigned)((mpad + 255) / 256), (unsigned)nb), dim3(256), 0, h->u->stream,
-                       (const T*)h->dY.p + c0, (int)mc, (int)mpad, (const double*)h->dPar.as<double>(), 2, (T*)h->dRz.p, 16l * h->rcap, part,
+                       (const T*)h->dY.p + c0, (int)mc, (int)mpad, (const double*)h->dPar.as<double>(), SPARSE_PAR, (T*)h->dRz.p, 16l * h->rcap, part,
                        pstride);
     return GPHIP_OK;
 }
@@ -256,7 +267,7 @@ template <typename T>
 int sparse_queue_diag(gphip_sparse_ctx* h, double* out, int nb = 1, long ostride = 0) {
     gphip_ctx* b = h->b;
     hipLaunchKernelGGL(sparse_diag_kernel<T>, dim3((unsigned)nb), dim3(256), 0, h->u->stream, (T*)b->dA.p, (long)b->slot_elems, (int)b->R,
-                       (int)b->N, (int)b->Npad, (const double*)h->dPar.as<double>() + 1, 2, out, ostride);
+                       (int)b->N, (int)b->Npad, (const double*)h->dPar.as<double>() + 1, SPARSE_PAR, out, ostride);
     return GPHIP_OK;
 }
 
@@ -274,21 +285,44 @@ int sparse_factor(gphip_sparse_ctx* h, gphip_ctx* c, int nb, bool build, bool wa
     return rc ? sfail(h, rc, c->err) : GPHIP_OK;
 }
 
-// strip partials of predict_partial_kernel for the mpad rows in c->dV against c's rhs row (queue_predict_reduce's first stage)
-template <typename T>
-int sparse_queue_partial(gphip_ctx* h, int64_t mpad, int* nstrips_out) {
+// the strips of a pass over the mpad rows x Npad columns of nb slots of c->dV (queue_predict_reduce's rule): columns per strip
+int sparse_partial_strips(const gphip_ctx* h, int64_t mpad, int nb, int* nstrips_out) {
     const int Mt = (int)(mpad / TB), Nt = (int)h->Nt;
-    int nstrips = (2048 + Mt - 1) / Mt;
+    int nstrips = (2048 + Mt * nb - 1) / (Mt * nb);
     if (nstrips > Nt) nstrips = Nt;
     if (nstrips > 64) nstrips = 64;
     if (nstrips < 1) nstrips = 1;
     int js = (Nt + nstrips - 1) / nstrips * TB;
     if (js > 4096) js = 4096;
-    nstrips = (int)((h->Npad + js - 1) / js);
-    HIPCHK(h->dPart.grow((size_t)nstrips * 2 * mpad * 8));
-    hipLaunchKernelGGL(predict_partial_kernel<T>, dim3((unsigned)Mt, (unsigned)nstrips, 1u), dim3(256), (size_t)js * 8 + 8 * TB * 8, h->stream,
-                       (const T*)h->dV.p, (long)mpad, (long)mpad * h->Npad, (int)h->N, (const T*)h->dA.p, (int)h->R, (long)h->slot_elems, js,
-                       h->dPart.as<double>(), nstrips);
+    *nstrips_out = (int)((h->Npad + js - 1) / js);
+    return js;
+}
+
+// strip partials of predict_partial_kernel for the mpad rows of nb slots in c->dV against each slot's rhs row
+// (queue_predict_reduce's first stage): c->dPart [slot][strip][2][mpad]
+template <typename T>
+int sparse_queue_partial(gphip_ctx* h, int64_t mpad, int* nstrips_out, int nb = 1) {
+    int nstrips = 0;
+    const int js = sparse_partial_strips(h, mpad, nb, &nstrips);
+    HIPCHK(h->dPart.grow((size_t)nb * nstrips * 2 * mpad * 8));
+    hipLaunchKernelGGL(predict_partial_kernel<T>, dim3((unsigned)(mpad / TB), (unsigned)nstrips, (unsigned)nb), dim3(256),
+                       (size_t)js * 8 + 8 * TB * 8, h->stream, (const T*)h->dV.p, (long)mpad, (long)mpad * h->Npad, (int)h->N,
+                       (const T*)h->dA.p, (int)h->R, (long)h->slot_elems, js, h->dPart.as<double>(), nstrips);
+    *nstrips_out = nstrips;
+    return GPHIP_OK;
+}
+
+// gphip_sparse_predict_samples: the mpad rows of V1 of nb slots from u's dV into b's, the strip partials of |v1|^2 into u->dPart
+// [slot][strip][mpad] on the way (sparse_handover_kernel), on u's stream
+template <typename T>
+int sparse_queue_handover(gphip_sparse_ctx* h, int64_t mpad, int nb, int* nstrips_out) {
+    gphip_ctx *u = h->u, *b = h->b;
+    int nstrips = 0;
+    const int js = sparse_partial_strips(u, mpad, nb, &nstrips);
+    HIPCHK(u->dPart.grow((size_t)nb * nstrips * mpad * 8));
+    hipLaunchKernelGGL(sparse_handover_kernel<T>, dim3((unsigned)(mpad / TB), (unsigned)nstrips, (unsigned)nb), dim3(256), 0, u->stream,
+                       (const T*)u->dV.p, (T*)b->dV.p, (long)mpad, (long)mpad * u->Npad, (int)u->N, (int)u->Npad, js, u->dPart.as<double>(),
+                       nstrips);
     *nstrips_out = nstrips;
     return GPHIP_OK;
 }
@@ -525,11 +559,13 @@ int sparse_check_args(gphip_sparse_ctx* h, int p, double jitter) {
     return GPHIP_OK;
 }
 
-// What a group evaluation is for (DESIGN.md section 8f).  fit: a one-theta entry point -- the factors of u and b stay resident
-// for the substitutions that follow (prediction, the gradient phase), u substitutes with queue_forward_fit, and a theta that
-// cannot be evaluated ends the call before the chunk loop.  nothing: a batch -- every row keeps its slot whatever becomes of it,
-// and no factor outlives the call.  The mode is the caller's, never the number of rows: a group of one row of a batch is a batch.
-enum class SparseKeep { fit, nothing };
+// What a group evaluation is for (DESIGN.md sections 8f and 8h).  fit: a one-theta entry point -- the factors of u and b stay
+// resident for the substitutions that follow (prediction, the gradient phase), u substitutes with queue_forward_fit, and a theta
+// that cannot be evaluated ends the call before the chunk loop.  nothing: a batch -- every row keeps its slot whatever becomes of
+// it, and no factor outlives the call.  group: a batch whose caller substitutes with the factors of every slot of u and b before
+// the next group overwrites them (gphip_sparse_predict_samples) -- it differs from nothing in one thing: B factors with its
+// block inverses.  The mode is the caller's, never the number of rows: a group of one row of a batch is a batch.
+enum class SparseKeep { fit, nothing, group };
 
 // one theta's slot of a group evaluation
 struct SparseSlot {
@@ -568,7 +604,8 @@ int sparse_group(gphip_sparse_ctx* h, const double* Theta, int nb, int p, double
         r.ok = stage_theta(u, s, Theta + (size_t)s * p);
         const double* sp = u->hSlotp.as<double>() + (size_t)s * SLOTP;
         r.sn2 = sp[1]; r.mu = sp[2]; r.kxx = sp[SP_KXX]; r.jit = jitter;
-        par[2 * s] = r.mu; par[2 * s + 1] = r.sn2;
+        double* ps = par + (size_t)SPARSE_PAR * s;
+        ps[0] = r.mu; ps[1] = r.sn2; ps[2] = r.kxx; ps[3] = 0.0;
     }
     if (jitter < 0.0) {                        // default: joint_jitter_rel x the row's k(x, x) (run-time compiled kernels: its mean of k(z, z))
         std::vector<double> scale((size_t)nb);
@@ -660,8 +697,8 @@ int sparse_group(gphip_sparse_ctx* h, const double* Theta, int nb, int p, double
     HIPCHK(hipMemcpyAsync(h->hSum.data(), h->dSum.p, (size_t)nb * ss * 8, hipMemcpyDeviceToHost, u->stream));
     if ((rc = complete_call(u))) return sfail(h, rc, u->err);          // (the forward substitutions' abort word)
     {
-        SparseScope ps(ph, PH_B_FACTOR, b->stream);    // (resident: substitutions with L_B follow, so it leaves its block inverses)
-        rc = sparse_factor(h, b, nb, false, resident, "sparse GP: the factorisation of B timed out (set option dataflow=0 and report)");
+        SparseScope ps(ph, PH_B_FACTOR, b->stream);    // (fit, group: substitutions with L_B follow, so it leaves its block inverses)
+        rc = sparse_factor(h, b, nb, false, keep != SparseKeep::nothing, "sparse GP: the factorisation of B timed out (set option dataflow=0 and report)");
     }
     if (rc) return rc;
     for (int s = 0; s < nb; ++s) {
@@ -750,14 +787,10 @@ int sparse_eval(gphip_sparse_ctx* h, const double* theta, int p, double jitter, 
     return rc;
 }
 
-// gphip_sparse_bound_batch (DESIGN.md section 8f): the bound for the B rows of Theta, one theta per workspace slot, the group
-// evaluator on group after group.  No fit is left resident; a row that fails has only its own info / out to show for it.
-int sparse_eval_batch(gphip_sparse_ctx* h, const double* Theta, int B, int p, double jitter, double* out, double* parts, int* info) {
+// The group and chunk rule of the batched calls (gphip_sparse_bound_batch, gphip_sparse_predict_samples) for B rows: *G rows per
+// group, *rows data points of V per slot and pass; u and b get their slots, u's dV, dRz and dPar their sizes.  Drops any fit.
+int sparse_size_groups(gphip_sparse_ctx* h, int B, int* G_out, int64_t* rows_out) {
     gphip_ctx *u = h->u, *b = h->b;
-    const double qnan = std::nan("");
-    h->fitted = false;
-    sparse_reset_phases(h, PH_KUU_FACTOR, PH_JOINT_V);
-    HIPCHK(hipSetDevice(h->device));
     // ---- the group: as many rows as u and b give slots, as keep 2048 data points of V per slot within the ~8 GiB of a chunk
     const int64_t mpm = u->Npad;
     const double budget = 8.0 * (1 << 30);
@@ -786,6 +819,21 @@ int sparse_eval_batch(gphip_sparse_ctx* h, const double* Theta, int B, int p, do
     h->last_chunk = rows;
     if ((rc = sparse_ensure_rz(h, G, rows))) return rc;
     if ((rc = sparse_ensure_par(h, G))) return rc;
+    *G_out = G; *rows_out = rows;
+    return GPHIP_OK;
+}
+
+// gphip_sparse_bound_batch (DESIGN.md section 8f): the bound for the B rows of Theta, one theta per workspace slot, the group
+// evaluator on group after group.  No fit is left resident; a row that fails has only its own info / out to show for it.
+int sparse_eval_batch(gphip_sparse_ctx* h, const double* Theta, int B, int p, double jitter, double* out, double* parts, int* info) {
+    const double qnan = std::nan("");
+    h->fitted = false;
+    sparse_reset_phases(h, PH_KUU_FACTOR, PH_JOINT_V);
+    HIPCHK(hipSetDevice(h->device));
+    int G = 0;
+    int64_t rows = 0;
+    int rc = sparse_size_groups(h, B, &G, &rows);
+    if (rc) return rc;
     SparsePhases ph(h);
     std::vector<SparseSlot> res((size_t)G);
     for (int s0 = 0; s0 < B; s0 += G) {
@@ -800,6 +848,116 @@ int sparse_eval_batch(gphip_sparse_ctx* h, const double* Theta, int B, int p, do
                 double* ps = parts + (size_t)(s0 + s) * 5;
                 r.put_parts(ps);
                 if (r.info != 0) for (int k = 0; k < 5; ++k) ps[k] = qnan;
+            }
+        }
+        ph.harvest();                          // (group by group: the events go back to the pool for the next one)
+    }
+    return GPHIP_OK;
+}
+
+// gphip_sparse_predict_samples (DESIGN.md section 8h): mean and variance at the M test points for the S rows of Thetas.  Group
+// after group (sparse_eval_batch's rule) the group evaluator leaves the factors of every slot of u and b (SparseKeep::group);
+// the test points then go through in chunks of MC points, every launch with the slot as its last grid index:
+//   u   stage_test_chunk (k_s(X*, Z) of all slots), the forward substitution of all slots, k_s(x*, x*) of a run-time compiled
+//       kernel, sparse_handover_kernel: V1 into b's dV and the strip partials of |v1|^2
+//   b   (after an event of u's stream) the forward substitution of all slots, predict_partial_kernel, the finishing kernel
+// and one download per chunk.  A launch that spin-waits (the dataflow substitution) runs on a context only when every slot of
+// the group has a factor there: a slot whose factorisation was abandoned has no block inverses to hand to the launch's chain.
+int sparse_predict_samples(gphip_sparse_ctx* h, const double* Thetas, int S, int p, double jitter, const double* X, int64_t M, int latent,
+                           double* mean, double* var, double* bound, int* info) {
+    gphip_ctx *u = h->u, *b = h->b;
+    const double qnan = std::nan("");
+    h->fitted = false;
+    sparse_reset_phases(h, PH_KUU_FACTOR, PH_JOINT_V);
+    sparse_reset_phases(h, PH_SAMPLES_VU, PH_COUNT);
+    HIPCHK(hipSetDevice(h->device));
+    int G = 0;
+    int64_t rows = 0;
+    int rc = sparse_size_groups(h, S, &G, &rows);
+    if (rc) return rc;
+    // test points per pass (gphip_predict_samples' rule): at most 2048, the group's V within the ~8 GiB budget in u's dV and in
+    // b's, at most the option; halved while the two buffers do not fit
+    const int64_t mpm = u->Npad;
+    int64_t MC = (int64_t)((8.0 * (1 << 30)) / ((double)G * mpm * h->es)) / TB * TB;
+    MC = std::min<int64_t>(std::max<int64_t>(MC, TB), 2048);
+    MC = std::min(MC, (M + TB - 1) / TB * TB);
+    if (h->samples_chunk > 0) MC = std::min(MC, ((int64_t)h->samples_chunk + TB - 1) / TB * TB);
+    for (;;) {
+        if (!(rc = ensure_vbuf(u, (int64_t)G * MC))) rc = ensure_vbuf(b, (int64_t)G * MC);
+        if (rc != GPHIP_ERR_HIP || MC <= TB) break;
+        (void)hipGetLastError();
+        MC = (MC / 2 + TB - 1) / TB * TB;
+    }
+    if (rc) { (void)hipGetLastError(); return sfail(h, rc, "no device memory for the test points' V of a group"); }
+    h->last_samples_chunk = MC;
+    SparsePhases ph(h);
+    std::vector<SparseSlot> res((size_t)G);
+    std::vector<double> xt, hm, hv;
+    hipEvent_t handed = get_event(u);          // u's part of a chunk is queued: b's stream waits for it, not the host
+    struct Back { gphip_ctx* u; hipEvent_t e; ~Back() { u->pool.push_back(e); } } back{u, handed};
+    for (int s0 = 0; s0 < S; s0 += G) {
+        const int nb = std::min(G, S - s0);
+        h->last_slots = nb;
+        if ((rc = sparse_group(h, Thetas + (size_t)s0 * p, nb, p, jitter, rows, SparseKeep::group, nullptr, ph, res.data()))) return rc;
+        bool u_factored = true, b_factored = true;
+        for (int s = 0; s < nb; ++s) {
+            const SparseSlot& r = res[(size_t)s];
+            info[s0 + s] = r.info;
+            if (bound) bound[s0 + s] = r.info == 0 ? r.F : qnan;
+            if (r.uinfo != 0) u_factored = false;
+            if (b->hInfo.as<int>()[s] != 0) b_factored = false;
+        }
+        for (int64_t m0 = 0; m0 < M; m0 += MC) {
+            const int64_t mc = std::min(MC, M - m0);
+            int64_t mpad = 0;
+            int ns1 = 0, ns2 = 0;
+            {
+                SparseScope ps(ph, PH_SAMPLES_VU, u->stream);
+                mpad = stage_test_chunk(u, X, m0, mc, nb, 0, xt, &rc, false);
+                if (rc) return sfail(h, rc, u->err);
+                sparse_queue_forward(u, mpad, nb, SparseKeep::nothing, u_factored);
+                if (h->custom && (rc = queue_custom_kss(u, mc, mpad, nb))) return sfail(h, rc, u->err);
+            }
+            long p1_sstride = (long)mpad, p1_off = 0;
+            {
+                SparseScope ps(ph, PH_SAMPLES_HANDOVER, u->stream);
+                if (h->samples_handover) {
+                    if ((rc = DISPATCH(h, sparse_queue_handover, h, mpad, nb, &ns1))) return rc;
+                } else {                       // the two launches it replaces: a copy, and predict_partial_kernel on u for its norm rows
+                    HIPCHK(hipMemcpyAsync(b->dV.p, u->dV.p, (size_t)nb * mpad * mpm * h->es, hipMemcpyDeviceToDevice, u->stream));
+                    if ((rc = DISPATCH(u, sparse_queue_partial, u, mpad, &ns1, nb))) return sfail(h, rc, u->err);
+                    p1_sstride = 2l * mpad; p1_off = (long)mpad;
+                }
+            }
+            HIPCHK(hipEventRecord(handed, u->stream));
+            HIPCHK(hipStreamWaitEvent(b->stream, handed, 0));
+            {
+                SparseScope ps(ph, PH_SAMPLES_VB, b->stream);
+                if (b_factored && samples_forward_df(b, nb, mpad)) launch_dataflow_inverse<double, 64>(b, mpad, false, nb, b->dW64s.p);
+                else DISPATCH(b, queue_forward_rows, b, mpad, nb);
+            }
+            {
+                SparseScope ps(ph, PH_SAMPLES_REDUCE, b->stream);
+                if ((rc = DISPATCH(b, sparse_queue_partial, b, mpad, &ns2, nb))) return sfail(h, rc, b->err);
+                hipLaunchKernelGGL(sparse_predict_finish_kernel, dim3((unsigned)((mc + 255) / 256), (unsigned)nb), dim3(256), 0, b->stream,
+                                   u->dPart.as<double>() + p1_off, ns1, p1_sstride, (long)ns1 * p1_sstride, b->dPart.as<double>(), ns2,
+                                   (long)mpad, (int)mc, h->dPar.as<double>(), h->custom ? u->dKss.as<double>() : nullptr, latent ? 1 : 0,
+                                   b->dMean.as<double>(), b->dVar.as<double>());
+            }
+            hm.resize((size_t)nb * mpad);
+            hv.resize((size_t)nb * mpad);
+            HIPCHK(hipMemcpyAsync(hm.data(), b->dMean.p, hm.size() * 8, hipMemcpyDeviceToHost, b->stream));
+            HIPCHK(hipMemcpyAsync(hv.data(), b->dVar.p, hv.size() * 8, hipMemcpyDeviceToHost, b->stream));
+            if ((rc = complete_call(b))) return sfail(h, rc, b->err);      // (b's stream waited for u's: both are idle)
+            if ((rc = complete_call(u))) return sfail(h, rc, u->err);      // (the abort word of u's substitution)
+            for (int s = 0; s < nb; ++s) {
+                const bool good = info[s0 + s] == 0;
+                double* ms = mean + (size_t)(s0 + s) * M + m0;
+                double* vs = var + (size_t)(s0 + s) * M + m0;
+                for (int64_t t = 0; t < mc; ++t) {
+                    ms[t] = good ? hm[(size_t)s * mpad + t] : qnan;
+                    vs[t] = good ? hv[(size_t)s * mpad + t] : qnan;
+                }
             }
         }
         ph.harvest();                          // (group by group: the events go back to the pool for the next one)
@@ -876,7 +1034,7 @@ int sparse_joint_sigma(gphip_sparse_ctx* h, const double* Xs, int64_t M, const d
                        SparsePhases& ph) {
     gphip_ctx *u = h->u, *b = h->b;
     HIPCHK(hipSetDevice(h->device));
-    sparse_reset_phases(h, PH_JOINT_V, PH_COUNT);
+    sparse_reset_phases(h, PH_JOINT_V, PH_SAMPLES_VU);
     const int64_t mpad = (M + TB - 1) / TB * TB, kseg = u->Npad;
     const size_t seg_bytes = (size_t)mpad * kseg * h->es;
     int rc = ensure_vbuf(u, 2 * mpad);         // u's dV takes both segments: [V1 | V2], mpad x 2 kseg with ld mpad
@@ -1100,14 +1258,25 @@ int gphip_sparse_predict(gphip_sparse_handle h, const void* Xs, int64_t M, int l
         HIPCHK(hipMemcpyAsync(b->dV.p, u->dV.p, (size_t)mpad * u->Npad * h->es, hipMemcpyDeviceToDevice, b->stream));
         queue_forward_fit(b, mpad);
         if ((rc = DISPATCH(b, sparse_queue_partial, b, mpad, &ns2))) return sfail(h, rc, b->err);
-        hipLaunchKernelGGL(sparse_predict_finish_kernel, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, b->stream, u->dPart.as<double>(), ns1,
-                           b->dPart.as<double>(), ns2, (long)mpad, (int)mc, h->mu_fit, h->kxx_fit, h->custom ? u->dKss.as<double>() : nullptr,
-                           h->sn2_fit, latent ? 1 : 0, b->dMean.as<double>(), b->dVar.as<double>());
+        // (one slot of the finishing kernel: u's norm rows; mu, sn^2 and k(x, x) of the fit are slot 0 of dPar since the evaluation)
+        hipLaunchKernelGGL(sparse_predict_finish_kernel, dim3((unsigned)((mc + 255) / 256), 1u), dim3(256), 0, b->stream,
+                           u->dPart.as<double>() + mpad, ns1, 2l * mpad, 0l, b->dPart.as<double>(), ns2, (long)mpad, (int)mc,
+                           h->dPar.as<double>(), h->custom ? u->dKss.as<double>() : nullptr, latent ? 1 : 0, b->dMean.as<double>(),
+                           b->dVar.as<double>());
         HIPCHK(hipMemcpyAsync(mean + m0, b->dMean.p, (size_t)mc * 8, hipMemcpyDeviceToHost, b->stream));
         HIPCHK(hipMemcpyAsync(var + m0, b->dVar.p, (size_t)mc * 8, hipMemcpyDeviceToHost, b->stream));
         if ((rc = complete_call(b))) return sfail(h, rc, b->err);
     }
     return GPHIP_OK;
+}
+
+int gphip_sparse_predict_samples(gphip_sparse_handle h, const double* Thetas, int S, int p, double jitter, const void* Xs, int64_t M,
+                                 int latent, double* mean, double* var, double* bound, int* info) {
+    if (!h || !Thetas || !Xs || !mean || !var || !info) return sfail(h, GPHIP_ERR_ARG, "null argument");
+    std::lock_guard<std::recursive_mutex> lk(h->mu);
+    if (const int rc = sparse_check_args(h, p, jitter)) return rc;
+    if (S < 1 || M < 1) return sfail(h, GPHIP_ERR_DIM, "S < 1 or M < 1");
+    return sparse_predict_samples(h, Thetas, S, p, jitter, static_cast<const double*>(Xs), M, latent, mean, var, bound, info);
 }
 
 int gphip_sparse_predict_cov(gphip_sparse_handle h, const void* Xs, int64_t M, int latent, double* mean, double* cov) {
@@ -1163,6 +1332,8 @@ int gphip_sparse_set_option(gphip_sparse_handle h, const char* name, double valu
     if (!strcmp(name, "profile")) { h->profile = v; return GPHIP_OK; }
     if (!strcmp(name, "sparse_joint_split")) { if (v < 0) return sfail(h, GPHIP_ERR_ARG, "sparse_joint_split < 0"); h->joint_split = v; return GPHIP_OK; }
     if (!strcmp(name, "sparse_batch_slots")) { if (v < 0) return sfail(h, GPHIP_ERR_ARG, "sparse_batch_slots < 0"); h->batch_slots = v; return GPHIP_OK; }
+    if (!strcmp(name, "sparse_samples_chunk")) { if (v < 0) return sfail(h, GPHIP_ERR_ARG, "sparse_samples_chunk < 0"); h->samples_chunk = v; return GPHIP_OK; }
+    if (!strcmp(name, "sparse_samples_handover")) { h->samples_handover = v != 0; return GPHIP_OK; }
     int rc = gphip_set_option(h->u, name, value);
     if (!rc) rc = gphip_set_option(h->b, name, value);
     if (rc) return sfail(h, rc, "unknown option");
@@ -1187,6 +1358,9 @@ int gphip_sparse_get_option(gphip_sparse_handle h, const char* name, double* val
     if (!strcmp(name, "last_sparse_nsplit")) { *value = h->last_nsplit; return GPHIP_OK; }
     if (!strcmp(name, "sparse_batch_slots")) { *value = h->batch_slots; return GPHIP_OK; }
     if (!strcmp(name, "last_sparse_slots")) { *value = h->last_slots; return GPHIP_OK; }
+    if (!strcmp(name, "sparse_samples_chunk")) { *value = h->samples_chunk; return GPHIP_OK; }
+    if (!strcmp(name, "last_sparse_samples_chunk")) { *value = (double)h->last_samples_chunk; return GPHIP_OK; }
+    if (!strcmp(name, "sparse_samples_handover")) { *value = h->samples_handover; return GPHIP_OK; }
     if (!strcmp(name, "sparse_joint_split")) { *value = h->joint_split; return GPHIP_OK; }
     if (!strcmp(name, "last_sparse_joint_nsplit")) { *value = h->joint_nsplit; return GPHIP_OK; }
     const int rc = gphip_get_option(h->u, name, value);

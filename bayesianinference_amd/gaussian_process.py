@@ -1016,7 +1016,9 @@ def predictFromSparseGaussianProcess(obj, pts, theta=None):
     """Prediction from a sparse object: for one theta, or (theta=None) the posterior mixture of a sampled object -- one Normal
     per posterior sample, mixed with the CrudePosteriorWeights.  Returns the dict of predictFromGaussianProcess: "Points" [M,d],
     "Weights" [S], "Mean" [S,M], "StandardDeviation" [S,M] (S = 1 for one theta); the variance includes the noise sn^2.  Samples
-    whose fit fails give NaN rows.  None where the object is not a sparse GP object (or unsampled without a theta)."""
+    whose fit fails give NaN rows.  The mixture is ONE device call over all samples (SparseHandle.predict_samples), which leaves no
+    fit resident; the theta= form is fit + predict and leaves its fit resident.  None where the object is not a sparse GP object
+    (or unsampled without a theta)."""
     if not isinstance(obj, inferenceObject) or obj.failed or "SparseGaussianProcessData" not in obj:
         return None
     X = obj["Data"][0]
@@ -1030,16 +1032,19 @@ def predictFromSparseGaussianProcess(obj, pts, theta=None):
     handle = obj["SparseGaussianProcessData"]["HIPHandle"]
     if theta is not None:
         points, weights = np.atleast_2d(np.asarray(theta, dtype=np.float64)), np.ones(1)
+        mean = np.full((len(points), len(P)), np.nan)
+        var = np.full((len(points), len(P)), np.nan)
+        for s, th in enumerate(points):
+            if handle.fit(th, obj["Jitter"]) == 0:
+                mean[s], var[s] = handle.predict(P)
     elif "Samples" in obj:
         points = np.array([s["Point"] for s in obj["Samples"]], dtype=np.float64)
         weights = np.array([s["CrudePosteriorWeight"] for s in obj["Samples"]], dtype=np.float64)
+        mean, var, info = handle.predict_samples(points, P, obj["Jitter"])
+        mean[info != 0] = np.nan
+        var[info != 0] = np.nan
     else:
         return None
-    mean = np.full((len(points), len(P)), np.nan)
-    var = np.full((len(points), len(P)), np.nan)
-    for s, th in enumerate(points):
-        if handle.fit(th, obj["Jitter"]) == 0:
-            mean[s], var[s] = handle.predict(P)
     with np.errstate(invalid="ignore"):
         sd = np.sqrt(var)
     return {"Points": P, "Weights": weights, "Mean": mean, "StandardDeviation": sd}

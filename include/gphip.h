@@ -563,14 +563,40 @@ int gphip_factor_bytes(gphip_handle h, int member, double* bytes);
  * [V1 | V2]; cov, draws and the log density then run the exact path's code on it.  Two calls with the same
  * options return the same bytes.
  *
+ * gphip_sparse_predict_samples: mean and variance at the M test points Xs for the S rows of the row-major S x p array Thetas --
+ * one Normal per posterior sample -- in one call; mean and var are row-major S x M.  Row s has the semantics of
+ * gphip_sparse_fit(h, Thetas + s p, p, jitter, ..) followed by gphip_sparse_predict(h, Xs, M, latent, ..): mean = m(x*) + v2^T c,
+ * var = k(x*, x*) [+ sn^2 unless latent] - |v1|^2 + sn^2 |v2|^2 with v1 = L_u^-1 k(Z, x*), v2 = L_B^-1 v1, all of that row's theta
+ * (k(x*, x*) of a run-time compiled kernel is a function of the point AND the row).  bound (NULL or S): bound[s] = F(theta_s; jitter)
+ * as gphip_sparse_bound_batch defines it.  jitter < 0 is the default rule applied PER ROW as there; "last_jitter" reads the last
+ * usable row's value.  A row that fails -- non-finite theta, an unusable jitter, a K_uu or a B that does not factor -- sets only its
+ * own info[s] (GPHIP_INFO_NAN / GPHIP_INFO_NOT_SPD; a failure of K_uu takes precedence) and gets its rows of mean and var and its
+ * bound[s] NaN; the other rows of the call are not disturbed.  Statuses, all decided before any device work: NULL h / Thetas / Xs /
+ * mean / var / info and a non-finite jitter GPHIP_ERR_ARG; a wrong p, S < 1 and M < 1 GPHIP_ERR_DIM.
+ * The rows are evaluated in the groups of gphip_sparse_bound_batch (the same rule, "sparse_batch_slots" included) by the same
+ * group evaluator, which here leaves the factors of every slot of u and b in place; the test points then go through in chunks:
+ * k(X*, Z) and u's forward substitution for all slots of the group at once, one pass that hands V1 to the context of B and takes
+ * |v1|^2 on the way, B's forward substitution and the reductions for all slots at once, one download per chunk (DESIGN.md section
+ * 8h).  The call drops any resident fit: a following gphip_sparse_predict is GPHIP_ERR_STATE.  Every sum runs in a fixed order
+ * without atomics: two calls with the same arguments and options return the same bytes, and permuting the rows of Thetas permutes
+ * the rows of every output bit for bit while the group sizes stay the same.  Against fit + predict of the same theta a row differs
+ * by rounding (the factorisations of several slots take another schedule).  One device.
+ *
  * Options (gphip_sparse_set_option / gphip_sparse_get_option):
  *   "sparse_chunk"  data points per pass over V (rounded up to 128); 0 (default) = as many as keep the chunk of V within ~8 GiB,
  *                   at least 2048, halved while it does not fit.  "last_sparse_chunk" (read-only): what the last call used.
  *   "sparse_split"  strips the accumulation kernel cuts a chunk into; 0 (default) = by the split rule (output tiles x strips
  *                   >= two per CU; gphip_sparse_bound_batch: output tiles x slots x strips).  "last_sparse_nsplit" (read-only):
  *                   strips of the last chunk of the last call (of its last group).
- *   "sparse_batch_slots"  most rows gphip_sparse_bound_batch evaluates together in one group; 0 (default) = by the group rule
- *                   above.  "last_sparse_slots" (read-only): rows in the last group of the last gphip_sparse_bound_batch.
+ *   "sparse_batch_slots"  most rows gphip_sparse_bound_batch / gphip_sparse_predict_samples evaluate together in one group; 0
+ *                   (default) = by the group rule above.  "last_sparse_slots" (read-only): rows in the last group of the last call.
+ *   "sparse_samples_chunk"  test points per pass of gphip_sparse_predict_samples; 0 (default) = by the rule: at most 2048, the
+ *                   group's slots x points x m_pad elements within ~8 GiB in both contexts, halved while the buffers do not fit;
+ *                   n = n points rounded up to 128, within the same caps.  "last_sparse_samples_chunk" (read-only): what the
+ *                   last call used.
+ *   "sparse_samples_handover"  1 (default): V1 reaches the context of B through sparse_handover_kernel (one read, one write, the
+ *                   norms on the way); 0: through a device-to-device copy and a separate norm launch, the form it replaced (kept
+ *                   for measurement, scripts/gpu_sparse_samples_time.py).
  *   "profile"       0 / 1: time the phases of gphip_sparse_bound / _fit with HIP events; read-only milliseconds of the last call:
  *                   "ms_kuu_factor", "ms_cross", "ms_forward", "ms_accumulate", "ms_b_factor"; of gphip_sparse_bound_grad also
  *                   "ms_grad_small" (the m x m work and the vector w), "ms_grad_weights" (sparse_weight_kernel alone),
@@ -578,6 +604,9 @@ int gphip_factor_bytes(gphip_handle h, int member, double* bytes);
  *                   of gphip_sparse_bound_grad_inducing also "ms_grad_inducing" (the column-wise reductions for dF/dZ).
  *                   of the joint prediction calls "ms_joint_v" (V1 and V2), "ms_joint_build" (K(X*, X*)), "ms_joint_downdate" (the
  *                   two-segment downdate and its strip reduction) and "ms_joint_factor" (Sigma's factorisation; draws / logpdf).
+ *                   of gphip_sparse_predict_samples, next to the bound's five, "ms_samples_v1" (k(X*, Z) and u's substitution),
+ *                   "ms_samples_handover" (V1 to b and |v1|^2), "ms_samples_v2" (b's substitution) and "ms_samples_reduce"
+ *                   (the dots and norms of v2 and the finishing kernel), summed over groups and chunks.
  *   "sparse_joint_split"  strips the joint prediction's downdate cuts the stacked index of 2 m_pad columns into; 0 (default) = by
  *                   gphip_predict_cov's split rule (output tiles x strips >= 2 per CU, strips of whole 128-columns; a strip may
  *                   span the V1 / V2 boundary), n = n strips.  "last_sparse_joint_nsplit" (read-only): strips of the last call.
@@ -604,6 +633,9 @@ int gphip_sparse_bound_grad_inducing(gphip_sparse_handle h, const double* theta,
                                      double* grad /* p, may be NULL */, double* gradZ /* row-major m x d */, double* parts, int* info);
 int gphip_sparse_fit(gphip_sparse_handle h, const double* theta, int p, double jitter, int* info);
 int gphip_sparse_predict(gphip_sparse_handle h, const void* Xs, int64_t M, int latent, double* mean, double* var);
+int gphip_sparse_predict_samples(gphip_sparse_handle h, const double* Thetas, int S, int p, double jitter, const void* Xs, int64_t M,
+                                 int latent, double* mean /* S x M */, double* var /* S x M */, double* bound /* NULL or S */,
+                                 int* info /* S */);
 int gphip_sparse_predict_cov(gphip_sparse_handle h, const void* Xs, int64_t M, int latent, double* mean /* M */, double* cov /* M x M */);
 int gphip_sparse_predict_draws(gphip_sparse_handle h, const void* Xs, int64_t M, int latent, int S, uint64_t seed,
                                const double* z /* NULL or S x M */, double jitter, double* out /* S x M */, int* info);
