@@ -1,221 +1,43 @@
 // gp_joint.h -- device kernels of the joint predictive path (gphip_predict_cov / _draws / _logpdf, gphip_joint.inc).
 //
-//   downdate_kernel         C -= [V; z^T] V^T on the lower tiles of a tile-major M x M workspace (the hot path)
+//   downdate_kernel         C -= [V; z^T] V^T on the lower tiles of a tile-major M x M workspace (the hot path; gp_contract.h)
 //                           (SEG: the two-segment form of the sparse object, C -= V1 V1^T - sn^2 V2 V2^T over a stacked index)
-//   downdate_reduce_kernel  C -= sum of the K-strip partials, strips added in a fixed order
 //   joint_unpack_kernel     lower tiles -> dense row-major M x M, both triangles (exactly symmetric)
 //   joint_rhs_kernel        the workspace's rhs row -> a vector
 //   joint_cblock_kernel     the sparse object's rhs-row operand: -c / sn^2 gathered from a factor's rhs tile row
 //   joint_normal_kernel     counter-based standard normals (Philox4x32-10, Box-Muller in fp64), keyed by (seed, s, j)
 //   joint_trmm_kernel       out = mean + Z L^T with L lower triangular in the tile-major factor
 #pragma once
-#include "gp_kernels.h"
+#include "gp_contract.h"
 
 #include <stdint.h>
 
 namespace gphip {
 
 // ---------------------------------------------------------------------------------------------
-// Downdate.  V = L^-1 K(X, X*) is the column-major mpad x Npad block the forward substitution leaves (row t = test point t,
-// ld = mpad); Z is a 128 x Npad column-major block (ld = 128) whose row 0 is z = L^-1 r and whose other rows are zero: it is
-// the I operand of the workspace's right-hand-side tile row, so that row turns from y* - m(X*) into y* - mu in the same launch.
-// One workgroup = one 128 x 128 output tile x one strip of the contraction.  The few output tiles of a typical call (M = 1000:
-// 44) cannot fill 256 CUs, so K is split into nsplit strips (grid.y); each strip's product goes to its own partial tile and
-// downdate_reduce_kernel adds the strips in order -- no atomics, bit-repeatable.  nsplit = 1 (P null): the accumulators start
-// at C and take the negated J fragment, the epilogue is stores only (the trailing-SYRK form of gemm_nt_kernel).
-// Staging, MFMA shape and the software pipeline are gemm_nt_kernel's 2 x 2-wave, two-stage form.
+// Downdate: strip_contract (gp_contract.h) with the strided-k operands.  V = L^-1 K(X, X*) is the column-major mpad x Npad block
+// the forward substitution leaves (row t = test point t, ld = mpad); Z is a 128 x Npad column-major block (ld = 128) whose row 0
+// is z = L^-1 r and whose other rows are zero: it is the I operand of the workspace's right-hand-side tile row, so that row
+// turns from y* - m(X*) into y* - mu in the same launch.  One slot: the slot strides are zero.
 //
-// SEG (the sparse object's joint prediction, gphip_sparse.inc): the same pipeline over a STACKED contraction index of length
+// SEG (the sparse object's joint prediction, gphip_sparse.inc): the same over a STACKED contraction index of length
 // K = 2 kseg.  V is [V1 | V2], V1 = L_u^-1 k(Z, X*) in columns [0, kseg) and V2 = L_B^-1 V1 in columns [kseg, 2 kseg), and
 //     C -= V1 V1^T - sn^2 V2 V2^T,      rhs row -= c^T V2^T
-// A stage of GK columns lies in one segment (GK divides 128, kseg is a multiple of 128), so the segment's factor is a
-// wave-uniform scalar per stage: the J fragments take s1 in the first segment and s2 in the second -- one VALU multiply per J
-// fragment where the plain form has its negation.  The host sets (s1, s2) = (-1, +sn^2) when the accumulators start at C and
-// (+1, -sn^2) when the strip's product goes to a partial tile that downdate_reduce_kernel subtracts.  Z then is 128 x 2 kseg
-// with row 0 = 0 in the first segment and -c / sn^2 in the second, which serves both signs.  A strip may span the boundary.
+// The J fragments take s1 in the first segment and s2 in the second -- one VALU multiply per J fragment where the plain form
+// has its negation.  The host sets (s1, s2) = (-1, +sn^2) when the accumulators start at C and (+1, -sn^2) when the strip's
+// product goes to a partial tile that strip_reduce_kernel subtracts.  Z then is 128 x 2 kseg with row 0 = 0 in the first
+// segment and -c / sn^2 in the second, which serves both signs.  A strip may span the boundary.
 // ---------------------------------------------------------------------------------------------
 template <typename T>
-struct DowndateArgs {
-    T* C; int R;                 // workspace (slot 0 base) of R = Mt + 1 tile rows
-    const T* V; long ldv;        // V(t, k) at V[t + k ldv]
-    const T* Z;                  // 128 x K, ld 128: row 0 = z
-    int Mt;                      // tile rows of V
-    int ntri;                    // Mt (Mt + 1) / 2: tiles 0 .. ntri-1 = the lower triangle (column-major), then the rhs row's Mt tiles
-    int ntiles;                  // ntri + Mt
-    int kstrip;                  // contraction columns per strip (multiple of 128)
-    int K;                       // contraction length (Npad of the training points)
-    T* P;                        // [strip][tile][128 x 128] partial tiles; null: C -= directly
+struct DowndateArgs : ContractArgs<T> {
     int kseg;                    // SEG: columns of the first segment
     T s1, s2;                    // SEG: factor of the J fragments in the first / second segment
 };
 
-template <typename T>
-__device__ __forceinline__ void downdate_tile(int t, int ntri, int Mt, int& ti, int& tj) {
-    if (t < ntri) tri_decode(t, Mt, ti, tj);
-    else { ti = Mt; tj = t - ntri; }
-}
-
 template <typename T, bool SEG = false>
 __global__ __launch_bounds__(256, 2) void downdate_kernel(DowndateArgs<T> g) {
-    constexpr int FI = 4, FJ = 4;
-    extern __shared__ double smem_raw[];
-    T* smem = reinterpret_cast<T*>(smem_raw);
-    typedef typename Num<T>::acc_t acc_t;
-    constexpr int GK = Num<T>::GK;
-    constexpr int STAGE = STAGE_BYTES / (int)sizeof(T);
-    constexpr int JOFF = STAGE / 2;
-    constexpr bool F64 = sizeof(T) == 8;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int uw = __builtin_amdgcn_readfirstlane(wave);
-    const int wi = uw & 1, wj = uw >> 1;
-    const int t = blockIdx.x, split = blockIdx.y;
-    int ti, tj;
-    downdate_tile<T>(t, g.ntri, g.Mt, ti, tj);
-    ti = __builtin_amdgcn_readfirstlane(ti);
-    tj = __builtin_amdgcn_readfirstlane(tj);
-    const long k0 = (long)split * g.kstrip;
-    const long klen = (g.K - k0 < g.kstrip) ? g.K - k0 : g.kstrip;
-    const bool rhs = ti == g.Mt;
-    const long lda = rhs ? (long)TB : g.ldv, ldb = g.ldv;
-    const T* a_run = rhs ? g.Z + k0 * TB : g.V + (long)ti * TB + k0 * g.ldv;
-    const T* b_run = g.V + (long)tj * TB + k0 * g.ldv;
-    auto stage = [&](int st) {
-        T* Is = smem + st * STAGE;
-        T* Js = Is + JOFF;
-        const T* Ag = a_run;
-        const T* Bg = b_run;
-        a_run += (long)GK * lda;
-        b_run += (long)GK * ldb;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const int q = uw + 4 * s;             // instruction index 0..15 within the stage
-            if (F64) {
-                __builtin_amdgcn_global_load_lds((glb_void*)(Ag + (long)q * lda + 2 * lane), (lds_void*)(Is + q * LDT), 16, 0, 0);
-                __builtin_amdgcn_global_load_lds((glb_void*)(Bg + (long)q * ldb + 2 * lane), (lds_void*)(Js + q * LDT), 16, 0, 0);
-            } else {
-                const long kcol = 4 * (q >> 1) + (q & 1) + 2 * (lane >> 5);
-                const int row = 4 * (lane & 31);
-                __builtin_amdgcn_global_load_lds((glb_void*)(Ag + kcol * lda + row), (lds_void*)(Is + q * LDP), 16, 0, 0);
-                __builtin_amdgcn_global_load_lds((glb_void*)(Bg + kcol * ldb + row), (lds_void*)(Js + q * LDP), 16, 0, 0);
-            }
-        }
-    };
-    const bool direct = g.P == nullptr;
-    // lane holds i = wi*64 + y*16 + (lane&15), j = wj*64 + x*16 + drow(lane>>4, r) of the tile (column-major, ld 128)
-    const long toff = (long)(wj * 16 * FJ) * TB + wi * (16 * FI) + (lane & 15);
-    T* Cg = g.C + tile_index(ti, tj, g.R) * TS + toff;
-    T* Pg = direct ? nullptr : g.P + ((long)split * g.ntiles + t) * TS + toff;
-    const int l4 = lane >> 4;
-    const int nk = (int)(klen / GK);
-    // rows this wave computes (wave-uniform): the rhs tile row has ONE real row (the first 16-row group of wave column 0), and
-    // nothing reads the strictly-upper 64 x 64 quadrant of a diagonal tile
-    int ny = FI;
-    if (rhs) ny = wi == 0 ? 1 : 0;
-    else if (ti == tj && wi == 0 && wj == 1) ny = 0;
-    acc_t acc[FJ][FI];
-    auto load_frags = [&](int buf, int kk, T* fi, T* fj) {
-        const T* Is = smem + buf * STAGE + wi * (16 * FI) + (lane & 15);
-        const T* Js = smem + buf * STAGE + JOFF;
-        const int k = 4 * kk + l4;
-#pragma unroll
-        for (int f = 0; f < FI; ++f) fi[f] = Is[lds_off<T>(k, f * 16)];
-#pragma unroll
-        for (int f = 0; f < FJ; ++f) fj[f] = Js[lds_off<T>(k, wj * (16 * FJ) + f * 16 + (lane & 15))];
-    };
-    auto pin_frags = [&](T* fi, T* fj) {
-#pragma unroll
-        for (int f = 0; f < FI; ++f) asm volatile("" : "+v"(fi[f]));
-#pragma unroll
-        for (int f = 0; f < FJ; ++f) asm volatile("" : "+v"(fj[f]));
-    };
-    auto pipeline = [&](auto nyc) {
-        constexpr int NY = decltype(nyc)::value;
-        constexpr int NKK = GK / 4;
-        T sc = g.s1;                      // SEG: the factor of the stage the MFMAs are reading
-        auto mfma_block = [&](const T* fi, const T* fj) {
-            T nj[FJ];
-#pragma unroll
-            for (int f = 0; f < FJ; ++f) nj[f] = SEG ? sc * fj[f] : (direct ? -fj[f] : fj[f]);
-#pragma unroll
-            for (int x = 0; x < FJ; ++x)
-#pragma unroll
-                for (int y = 0; y < NY; ++y) acc[x][y] = Num<T>::mfma(nj[x], fi[y], acc[x][y]);
-        };
-        T fa[2][FI], fb[2][FJ];
-        stage(0);
-#pragma unroll
-        for (int x = 0; x < FJ; ++x)
-#pragma unroll
-            for (int y = 0; y < FI; ++y) {
-                if (!direct || y >= NY) {
-                    acc[x][y] = (acc_t){0, 0, 0, 0};
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) acc[x][y][r] = Cg[(long)(x * 16 + Num<T>::drow(l4, r)) * TB + y * 16];
-                }
-            }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (NY > 0) load_frags(0, 0, fa[0], fb[0]);
-        for (int kb = 0; kb < nk; ++kb) {
-            const int cur = kb & 1;
-            if (kb + 1 < nk) stage(cur ^ 1);
-            if (SEG) sc = k0 + (long)kb * GK < g.kseg ? g.s1 : g.s2;
-            if (NY > 0) {
-#pragma unroll
-                for (int kk = 0; kk + 1 < NKK; ++kk) {
-                    pin_frags(fa[kk & 1], fb[kk & 1]);
-                    __builtin_amdgcn_sched_barrier(0);
-                    load_frags(cur, kk + 1, fa[(kk + 1) & 1], fb[(kk + 1) & 1]);
-                    __builtin_amdgcn_sched_barrier(0);
-                    mfma_block(fa[kk & 1], fb[kk & 1]);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                pin_frags(fa[(NKK - 1) & 1], fb[(NKK - 1) & 1]);
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            if (NY > 0) {
-                if (kb + 1 < nk) load_frags(cur ^ 1, 0, fa[0], fb[0]);
-                __builtin_amdgcn_sched_barrier(0);
-                mfma_block(fa[(NKK - 1) & 1], fb[(NKK - 1) & 1]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        T* out = direct ? Cg : Pg;
-#pragma unroll
-        for (int x = 0; x < FJ; ++x)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                T* cp = out + (long)(x * 16 + Num<T>::drow(l4, r)) * TB;
-#pragma unroll
-                for (int y = 0; y < NY; ++y) cp[y * 16] = acc[x][y][r];
-            }
-    };
-    if (ny == FI) pipeline(std::integral_constant<int, FI>{});
-    else if (ny == 1) pipeline(std::integral_constant<int, 1>{});
-    else pipeline(std::integral_constant<int, 0>{});
-}
-
-// C -= P[0] + P[1] + .. + P[nsplit-1], elementwise, strips in order (fp64 sums).  grid = (ntiles, 16), 256 threads x 4 elements.
-// Only what downdate_kernel wrote: the first 16 rows of an rhs tile, a diagonal tile without its strictly-upper quadrant.
-template <typename T>
-__global__ __launch_bounds__(256) void downdate_reduce_kernel(T* __restrict__ C, int R, int ntri, int Mt, int ntiles,
-                                                              const T* __restrict__ P, int nsplit) {
-    const int t = blockIdx.x;
-    int ti, tj;
-    downdate_tile<T>(t, ntri, Mt, ti, tj);
-    T* Ct = C + tile_index(ti, tj, R) * TS;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const int e = (blockIdx.y * 4 + u) * 256 + threadIdx.x;          // element of the tile: row e % 128, column e / 128
-        const int i = e & 127, j = e >> 7;
-        if (ti == Mt && i >= 16) continue;
-        if (ti == tj && i < 64 && j >= 64) continue;
-        double s = 0.0;
-        for (int q = 0; q < nsplit; ++q) s += (double)P[((long)q * ntiles + t) * TS + e];
-        Ct[e] = (T)((double)Ct[e] - s);
-    }
+    if constexpr (SEG) strip_contract<T>(g, StridedK<T>{}, JSegment<T>(g.kseg, g.s1, g.s2));
+    else strip_contract<T>(g, StridedK<T>{}, JNegate<T>{});
 }
 
 // dense row-major out[i * M + j] = C(max(i, j), min(i, j)): both triangles read the same element

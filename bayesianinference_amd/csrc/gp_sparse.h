@@ -1,9 +1,8 @@
 // gp_sparse.h -- device kernels of the sparse inducing-point GP (include/gphip.h: gphip_sparse_*, gphip_sparse.inc).
 //
-//   sparse_accumulate_kernel     C += V^T V and the rhs row += r^T V on the lower tiles of b's workspace (the hot path)
-//   (the first five kernels carry a slot dimension for gphip_sparse_bound_batch: one theta per workspace slot, slot = the grid's
-//    last index, every operand addressed as slot-0 base + slot x stride; the one-theta calls run them with one slot)
-//   sparse_reduce_kernel         C += the strip partials of one chunk, strips added in a fixed order
+//   sparse_accumulate_kernel     C += V^T V and the rhs row += r^T V on the lower tiles of b's workspace (the hot path; gp_contract.h)
+//   (the first four kernels and strip_reduce_kernel carry a slot dimension for gphip_sparse_bound_batch: one theta per workspace
+//    slot, slot = the grid's last index, every operand addressed as slot-0 base + slot x stride; the one-theta calls run them with one slot)
 //   sparse_resid_kernel          r = y - mu of a chunk into row 0 of the rhs operand + per-block partial sums of r^2
 //   sparse_blocksum_kernel       per-block partial sums of a double vector (k(x_i, x_i) of a run-time compiled kernel)
 //   sparse_diag_kernel           tr(V V^T) from C's diagonal, then + sn^2 on it (identity on the pad)
@@ -12,215 +11,28 @@
 //   sparse_small / _trace / _vta / _w / _weight / _transpose_kernel   the gradient of the bound, see the second half of this file
 //   sparse_zgrad_kernel / sparse_zgrad_finish_kernel   the gradient of the bound in the inducing LOCATIONS, see the end of this file
 #pragma once
-#include "gp_kernels.h"
+#include "gp_contract.h"
 
 namespace gphip {
 
 constexpr int SPARSE_PAR = 4;                  // doubles per slot of the sparse object's own scalars: mu, sn^2, k(x, x), unused
 
 // ---------------------------------------------------------------------------------------------
-// Accumulation.  V is the chunk of L_u^-1 k(Z, X) the forward substitution leaves: column-major, V(t, k) at V[t + k ldv],
-// t = data point of the chunk, k = inducing index.  Output tile (ti, tj) of b's tile-major workspace takes
+// Accumulation: strip_contract (gp_contract.h) with the contiguous-k operands.  V is the chunk of L_u^-1 k(Z, X) the forward
+// substitution leaves: column-major, V(t, k) at V[t + k ldv], t = data point of the chunk, k = inducing index.  Output tile
+// (ti, tj) of b's tile-major workspace takes
 //     C(k1, k2) += sum_t V(t, k1) V(t, k2),      rhs tile row: row 0 += sum_t r_t V(t, k)
-// so, unlike downdate_kernel, the contraction index t is the CONTIGUOUS one of both operands and the output indices are the
-// strided ones: an operand tile of one stage is 128 inducing rows x 128 bytes of consecutive t (16 doubles / 32 floats).
-// Staging: LDS-DMA, 16 bytes per lane.  A DMA writes LDS lane-linearly, so the stage image is [row][8 chunks of 16 bytes] with
-// no room for padding; read as it lies, the 16 rows of an MFMA operand (one element per lane, row = lane & 15, k = lane >> 4)
-// would sit 128 bytes apart -- two banks' worth for sixteen lanes.  The image is therefore swizzled: chunk c of row i lies in
-// slot c ^ ((i >> 1) & 7) of its row.  The permutation is applied on the SOURCE address of the DMA (lane l of an instruction
-// fills slot l & 7 of row l >> 3, so it fetches chunk (l & 7) ^ swz(row); the eight lanes of a row still cover one whole
-// 128-byte line) and again on the fragment read.  16 rows x one chunk then cover sixteen different 16-byte groups of the 256
-// bytes the banks serve per cycle: the reads are conflict-free in both types (fp64: half a wave reads the two halves of one
-// chunk; fp32: the four k of a wave are the four floats of one chunk).
-// Which t an MFMA step contracts is the same for both operands, so their order inside a stage is free: step kk takes chunk
-// 2 kk + (l4 >> 1), element l4 & 1 (fp64) or chunk kk, element l4 (fp32).
-// One workgroup = one 128 x 128 output tile x one strip of the chunk's rows; tile list, strip partials and the thin rhs / diagonal
-// tiles are downdate_kernel's, and so are the accumulator layout and the two-stage software pipeline.
-// The rhs operand Rz is 16 rows x ldr (row 0 = r of the chunk, rows 1 .. 15 zero): only the first 16-row group of an rhs tile
-// is computed.
+// so the contraction index t is the contiguous one of both operands.  The rhs operand is 16 rows x ldr (row 0 = r of the chunk,
+// rows 1 .. 15 zero).  One workgroup = one output tile x one strip of the chunk's rows x one slot.
 // ---------------------------------------------------------------------------------------------
 template <typename T>
-struct SparseAccArgs {
-    T* C; int R;                 // b's workspace (slot 0 base) of R = Mt + 1 tile rows
-    const T* V; long ldv;        // V(t, k) at V[t + k ldv]
-    const T* Rz; long ldr;       // 16 x ldr, row-contiguous in t: row 0 = r
-    int Mt;                      // tile rows of inducing points
-    int ntri;                    // Mt (Mt + 1) / 2: tiles 0 .. ntri-1 = the lower triangle (column-major), then the rhs row's Mt tiles
-    int ntiles;                  // ntri + Mt
-    int kstrip;                  // data points per strip (multiple of 128)
-    int K;                       // padded data points of the chunk (multiple of 128)
-    T* P;                        // [strip][tile][128 x 128] partial tiles; null: C += directly
-    long c_bstride, v_bstride, r_bstride, p_bstride;      // elements between the slots (blockIdx.z) of C, V, Rz and P
+struct SparseAccArgs : ContractArgs<T> {
+    long ldr;                    // leading dimension of the rhs operand Z
 };
-
-constexpr int SPA_OPND = TB * 128;             // bytes of one operand image of a stage: 128 rows x 128 bytes
-constexpr int SPA_STAGE = 2 * SPA_OPND;
-constexpr size_t SPA_LDS = 2 * SPA_STAGE;      // two stages, 64 KiB: two workgroups per CU
 
 template <typename T>
 __global__ __launch_bounds__(256, 2) void sparse_accumulate_kernel(SparseAccArgs<T> g) {
-    constexpr int FI = 4, FJ = 4;
-    extern __shared__ double smem_raw[];
-    char* smem = reinterpret_cast<char*>(smem_raw);
-    typedef typename Num<T>::acc_t acc_t;
-    constexpr int GK = 128 / (int)sizeof(T);       // data points per stage
-    constexpr int CE = 16 / (int)sizeof(T);        // elements per 16-byte chunk
-    constexpr bool F64 = sizeof(T) == 8;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int uw = __builtin_amdgcn_readfirstlane(wave);
-    const int wi = uw & 1, wj = uw >> 1;
-    const int t = blockIdx.x, split = blockIdx.y;
-    int ti, tj;
-    if (t < g.ntri) tri_decode(t, g.Mt, ti, tj);
-    else { ti = g.Mt; tj = t - g.ntri; }
-    ti = __builtin_amdgcn_readfirstlane(ti);
-    tj = __builtin_amdgcn_readfirstlane(tj);
-    const long k0 = (long)split * g.kstrip;
-    const long klen = (g.K - k0 < g.kstrip) ? g.K - k0 : g.kstrip;
-    const bool rhs = ti == g.Mt;
-    const long lda = rhs ? g.ldr : g.ldv, ldb = g.ldv;
-    // this lane's share of a DMA instruction: slot lane & 7 of row lane >> 3 of the instruction's eight rows
-    const int lr = lane >> 3, lp = lane & 7;
-    const long slot = blockIdx.z;
-    const T* Vs = g.V + slot * g.v_bstride;
-    const T* a_run = (rhs ? g.Rz + slot * g.r_bstride : Vs + (long)ti * TB * g.ldv) + k0;
-    const T* b_run = Vs + (long)tj * TB * g.ldv + k0;
-    auto stage = [&](int st) {
-        char* Is = smem + st * SPA_STAGE;
-        char* Js = Is + SPA_OPND;
-        const T* Ag = a_run;
-        const T* Bg = b_run;
-        a_run += GK;
-        b_run += GK;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const int q = uw + 4 * s;             // instruction index 0..15 within the stage: rows 8 q .. 8 q + 7
-            const int row = 8 * q + lr;
-            const int c = lp ^ ((row >> 1) & 7);
-            if (!rhs || q < 2)                    // (an rhs tile reads the first 16 rows of its I image only)
-                __builtin_amdgcn_global_load_lds((glb_void*)(Ag + (long)row * lda + c * CE), (lds_void*)(Is + q * 1024), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((glb_void*)(Bg + (long)row * ldb + c * CE), (lds_void*)(Js + q * 1024), 16, 0, 0);
-        }
-    };
-    const bool direct = g.P == nullptr;
-    // lane holds i = wi*64 + y*16 + (lane&15), j = wj*64 + x*16 + drow(lane>>4, r) of the tile (column-major, ld 128)
-    const long toff = (long)(wj * 16 * FJ) * TB + wi * (16 * FI) + (lane & 15);
-    T* Cg = g.C + slot * g.c_bstride + tile_index(ti, tj, g.R) * TS + toff;
-    T* Pg = direct ? nullptr : g.P + slot * g.p_bstride + ((long)split * g.ntiles + t) * TS + toff;
-    const int l4 = lane >> 4, l15 = lane & 15;
-    const int nk = (int)(klen / GK);
-    // rows this wave computes (wave-uniform), as in downdate_kernel: ONE 16-row group of an rhs tile, nothing of the strictly-upper
-    // quadrant of a diagonal tile
-    int ny = FI;
-    if (rhs) ny = wi == 0 ? 1 : 0;
-    else if (ti == tj && wi == 0 && wj == 1) ny = 0;
-    acc_t acc[FJ][FI];
-    // byte offset of this lane's element of row (16 f + l15) of a 64-row half, MFMA step kk: the rows' swizzle term is l15 >> 1
-    const int swz = l15 >> 1;
-    auto frag_off = [&](int row, int kk) {
-        const int c = F64 ? 2 * kk + (l4 >> 1) : kk, e = F64 ? (l4 & 1) : l4;
-        return (row * 8 + (c ^ swz)) * 16 + e * (int)sizeof(T);
-    };
-    auto load_frags = [&](int buf, int kk, T* fi, T* fj) {
-        const char* Is = smem + buf * SPA_STAGE;
-        const char* Js = Is + SPA_OPND;
-#pragma unroll
-        for (int f = 0; f < FI; ++f) fi[f] = *reinterpret_cast<const T*>(Is + frag_off(wi * (16 * FI) + f * 16 + l15, kk));
-#pragma unroll
-        for (int f = 0; f < FJ; ++f) fj[f] = *reinterpret_cast<const T*>(Js + frag_off(wj * (16 * FJ) + f * 16 + l15, kk));
-    };
-    auto pin_frags = [&](T* fi, T* fj) {
-#pragma unroll
-        for (int f = 0; f < FI; ++f) asm volatile("" : "+v"(fi[f]));
-#pragma unroll
-        for (int f = 0; f < FJ; ++f) asm volatile("" : "+v"(fj[f]));
-    };
-    auto pipeline = [&](auto nyc) {
-        constexpr int NY = decltype(nyc)::value;
-        constexpr int NKK = GK / 4;
-        auto mfma_block = [&](const T* fi, const T* fj) {
-#pragma unroll
-            for (int x = 0; x < FJ; ++x)
-#pragma unroll
-                for (int y = 0; y < NY; ++y) acc[x][y] = Num<T>::mfma(fj[x], fi[y], acc[x][y]);
-        };
-        T fa[2][FI], fb[2][FJ];
-        stage(0);
-#pragma unroll
-        for (int x = 0; x < FJ; ++x)
-#pragma unroll
-            for (int y = 0; y < FI; ++y) {
-                if (!direct || y >= NY) {
-                    acc[x][y] = (acc_t){0, 0, 0, 0};
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) acc[x][y][r] = Cg[(long)(x * 16 + Num<T>::drow(l4, r)) * TB + y * 16];
-                }
-            }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (NY > 0) load_frags(0, 0, fa[0], fb[0]);
-        for (int kb = 0; kb < nk; ++kb) {
-            const int cur = kb & 1;
-            if (kb + 1 < nk) stage(cur ^ 1);
-            if (NY > 0) {
-#pragma unroll
-                for (int kk = 0; kk + 1 < NKK; ++kk) {
-                    pin_frags(fa[kk & 1], fb[kk & 1]);
-                    __builtin_amdgcn_sched_barrier(0);
-                    load_frags(cur, kk + 1, fa[(kk + 1) & 1], fb[(kk + 1) & 1]);
-                    __builtin_amdgcn_sched_barrier(0);
-                    mfma_block(fa[kk & 1], fb[kk & 1]);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                pin_frags(fa[(NKK - 1) & 1], fb[(NKK - 1) & 1]);
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            if (NY > 0) {
-                if (kb + 1 < nk) load_frags(cur ^ 1, 0, fa[0], fb[0]);
-                __builtin_amdgcn_sched_barrier(0);
-                mfma_block(fa[(NKK - 1) & 1], fb[(NKK - 1) & 1]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        T* out = direct ? Cg : Pg;
-#pragma unroll
-        for (int x = 0; x < FJ; ++x)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                T* cp = out + (long)(x * 16 + Num<T>::drow(l4, r)) * TB;
-#pragma unroll
-                for (int y = 0; y < NY; ++y) cp[y * 16] = acc[x][y][r];
-            }
-    };
-    if (ny == FI) pipeline(std::integral_constant<int, FI>{});
-    else if (ny == 1) pipeline(std::integral_constant<int, 1>{});
-    else pipeline(std::integral_constant<int, 0>{});
-}
-
-// C += P[0] + P[1] + .. + P[nsplit-1], elementwise, strips in order (fp64 sums).  grid = (ntiles, 16, slots), 256 threads x 4 elements.
-// Only what sparse_accumulate_kernel wrote: the first 16 rows of an rhs tile, a diagonal tile without its strictly-upper quadrant.
-template <typename T>
-__global__ __launch_bounds__(256) void sparse_reduce_kernel(T* __restrict__ C, int R, int ntri, int Mt, int ntiles,
-                                                            const T* __restrict__ P, int nsplit, long c_bstride, long p_bstride) {
-    const int t = blockIdx.x;
-    C += (long)blockIdx.z * c_bstride;
-    P += (long)blockIdx.z * p_bstride;
-    int ti, tj;
-    if (t < ntri) tri_decode(t, Mt, ti, tj);
-    else { ti = Mt; tj = t - ntri; }
-    T* Ct = C + tile_index(ti, tj, R) * TS;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const int e = (blockIdx.y * 4 + u) * 256 + threadIdx.x;          // element of the tile: row e % 128, column e / 128
-        const int i = e & 127, j = e >> 7;
-        if (ti == Mt && i >= 16) continue;
-        if (ti == tj && i < 64 && j >= 64) continue;
-        double s = 0.0;
-        for (int q = 0; q < nsplit; ++q) s += (double)P[((long)q * ntiles + t) * TS + e];
-        Ct[e] = (T)((double)Ct[e] + s);
-    }
+    strip_contract<T>(g, SwizzledK<T>{g.ldr}, JIdentity<T>{});
 }
 
 // fixed-order sum of the 256 values of a workgroup (one per thread); the result is valid in thread 0

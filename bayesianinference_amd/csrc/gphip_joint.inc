@@ -79,8 +79,7 @@ int joint_mean_kss(gphip_ctx* h, int64_t M, int64_t mpad, double* out) {
     return GPHIP_OK;
 }
 
-// C -= [V; z^T] V^T on the child's workspace.  Split rule: while the output tiles (incl. the rhs row) are fewer than two per CU,
-// the contraction is cut into strips of whole 128-columns so that tiles x strips >= 2 per CU; strips are equal but the last.
+// C -= [V; z^T] V^T on the child's workspace, in the strips of strip_split (gp_contract.h).
 // SEG (the sparse object): h->dV holds [V1 | V2], the contraction runs over the stacked index of 2 x h->Npad columns and sn2
 // scales the second segment (gp_joint.h); split > 0 forces that many strips; *nsplit_out: the strips used.
 template <typename T, bool SEG>
@@ -90,12 +89,8 @@ int queue_downdate_any(gphip_ctx* h, gphip_ctx* c, int64_t mpad, int split, int*
     g.V = (const T*)h->dV.p; g.ldv = (long)mpad; g.Z = (const T*)h->dJZ.p;
     g.Mt = (int)(mpad / TB); g.ntri = g.Mt * (g.Mt + 1) / 2; g.ntiles = g.ntri + g.Mt;
     g.K = (int)(SEG ? 2 * h->Npad : h->Npad);
-    const long target = 2l * std::max(h->ncu, 1);
-    const int kt = (int)(SEG ? 2 * h->Nt : h->Nt);
-    int nsplit = g.ntiles >= target ? 1 : (int)std::min<long>(kt, (target + g.ntiles - 1) / g.ntiles);
-    if (split > 0) nsplit = std::min(split, kt);
-    const int strip_tiles = (kt + nsplit - 1) / nsplit;
-    nsplit = (kt + strip_tiles - 1) / strip_tiles;
+    int strip_tiles;
+    const int nsplit = strip_split(g.ntiles, (int)(SEG ? 2 * h->Nt : h->Nt), split, h->ncu, &strip_tiles);
     g.kstrip = strip_tiles * TB;
     *nsplit_out = nsplit;
     if (nsplit > 1) {
@@ -110,10 +105,10 @@ int queue_downdate_any(gphip_ctx* h, gphip_ctx* c, int64_t mpad, int split, int*
     {
         // algorithmic flops M (M + 1) N (the lower triangle and the rhs row of an M x M downdate of contraction length N)
         ProfScope ps(c, 4, (double)mpad * (mpad + 1) * (double)(SEG ? 2 * h->N : h->N), (double)sizeof(T) * (mpad + TB) * (double)g.K);
-        hipLaunchKernelGGL((downdate_kernel<T, SEG>), dim3((unsigned)g.ntiles, (unsigned)nsplit), dim3(256), GEMM_LDS, c->stream, g);
+        hipLaunchKernelGGL((downdate_kernel<T, SEG>), dim3((unsigned)g.ntiles, (unsigned)nsplit), dim3(256), StridedK<T>::LDS, c->stream, g);
         if (nsplit > 1)
-            hipLaunchKernelGGL(downdate_reduce_kernel<T>, dim3((unsigned)g.ntiles, 16), dim3(256), 0, c->stream, (T*)c->dA.p, (int)c->R,
-                               g.ntri, g.Mt, g.ntiles, (const T*)g.P, nsplit);
+            hipLaunchKernelGGL(strip_reduce_kernel<T>, dim3((unsigned)g.ntiles, 16), dim3(256), 0, c->stream, g.C, g.R, g.ntri, g.Mt,
+                               g.ntiles, (const T*)g.P, nsplit, -1.0, 0l, 0l);
     }
     return GPHIP_OK;
 }

@@ -152,7 +152,7 @@ struct SparseScope {
 template <typename T>
 int sparse_func_attrs(gphip_sparse_ctx* h) {
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(sparse_accumulate_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)SPA_LDS));
+                               (int)SwizzledK<T>::LDS));
 #define ZG_ATTR(DW)                                                                                                              \
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(sparse_zgrad_kernel<T, DW, false, false>),                          \
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)sparse_zgrad_lds<T, DW, false>(1)));             \
@@ -221,24 +221,19 @@ int sparse_ensure_par(gphip_sparse_ctx* h, int nb) {
 }
 
 // C += V^T V, rhs row += r^T V for the chunk of mpad rows in u->dV, for every one of nb slots by ONE launch (slot s: V at
-// dV + s mpad Npad, C = b's workspace slot s).  Split rule (queue_downdate's, counting WORKGROUPS): while output tiles x slots
-// are fewer than two per CU the chunk is cut into strips of whole 128-rows so that tiles x slots x strips >= 2 per CU.
+// dV + s mpad Npad, C = b's workspace slot s), in the strips of strip_split (gp_contract.h) for output tiles x slots workgroups.
 template <typename T>
 int sparse_queue_accumulate(gphip_sparse_ctx* h, int64_t mpad, int nb = 1) {
     gphip_ctx *u = h->u, *b = h->b;
     SparseAccArgs<T> g{};
     g.C = (T*)b->dA.p; g.R = (int)b->R;
     g.V = (const T*)u->dV.p; g.ldv = (long)mpad;
-    g.Rz = (const T*)h->dRz.p; g.ldr = (long)h->rcap;
+    g.Z = (const T*)h->dRz.p; g.ldr = (long)h->rcap;
     g.Mt = (int)u->Nt; g.ntri = g.Mt * (g.Mt + 1) / 2; g.ntiles = g.ntri + g.Mt;
     g.K = (int)mpad;
-    g.c_bstride = (long)b->slot_elems; g.v_bstride = (long)mpad * u->Npad; g.r_bstride = 16l * h->rcap;
-    const long target = 2l * std::max(u->ncu, 1), wgs = (long)g.ntiles * nb;
-    const int kt = (int)(mpad / TB);
-    int nsplit = wgs >= target ? 1 : (int)std::min<long>(kt, (target + wgs - 1) / wgs);
-    if (h->split > 0) nsplit = std::min(h->split, kt);
-    const int strip_tiles = (kt + nsplit - 1) / nsplit;
-    nsplit = (kt + strip_tiles - 1) / strip_tiles;
+    g.c_bstride = (long)b->slot_elems; g.v_bstride = (long)mpad * u->Npad; g.z_bstride = 16l * h->rcap;
+    int strip_tiles;
+    const int nsplit = strip_split((long)g.ntiles * nb, (int)(mpad / TB), h->split, u->ncu, &strip_tiles);
     g.kstrip = strip_tiles * TB;
     h->last_nsplit = nsplit;
     if (nsplit > 1) {
@@ -246,10 +241,11 @@ int sparse_queue_accumulate(gphip_sparse_ctx* h, int64_t mpad, int nb = 1) {
         HIPCHK(h->dAccP.grow((size_t)nb * g.p_bstride * sizeof(T)));
         g.P = (T*)h->dAccP.p;
     }
-    hipLaunchKernelGGL(sparse_accumulate_kernel<T>, dim3((unsigned)g.ntiles, (unsigned)nsplit, (unsigned)nb), dim3(256), SPA_LDS, u->stream, g);
+    hipLaunchKernelGGL(sparse_accumulate_kernel<T>, dim3((unsigned)g.ntiles, (unsigned)nsplit, (unsigned)nb), dim3(256), SwizzledK<T>::LDS,
+                       u->stream, g);
     if (nsplit > 1)
-        hipLaunchKernelGGL(sparse_reduce_kernel<T>, dim3((unsigned)g.ntiles, 16, (unsigned)nb), dim3(256), 0, u->stream, (T*)b->dA.p, (int)b->R,
-                           g.ntri, g.Mt, g.ntiles, (const T*)g.P, nsplit, g.c_bstride, g.p_bstride);
+        hipLaunchKernelGGL(strip_reduce_kernel<T>, dim3((unsigned)g.ntiles, 16, (unsigned)nb), dim3(256), 0, u->stream, g.C, g.R, g.ntri, g.Mt,
+                           g.ntiles, (const T*)g.P, nsplit, 1.0, g.c_bstride, g.p_bstride);
     return GPHIP_OK;
 }
 

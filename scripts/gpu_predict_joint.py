@@ -2,7 +2,7 @@
 call (every call returns host data, so it ends device-synchronised), the downdate's strip count, and -- with the library's
 profile option -- the time the child context's downdate launch took.  One JSON line per case; with an argument, the lines
 also go to that file.  The downdate kernel's own time is best read from a `rocprofv3 --kernel-trace --stats` run of this
-script (downdate_kernel / downdate_reduce_kernel rows)."""
+script (downdate_kernel / strip_reduce_kernel rows)."""
 import json
 import os
 import sys

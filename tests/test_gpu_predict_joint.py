@@ -82,19 +82,38 @@ def test_cov_matches_numpy_and_predict(kname, d, n, ms):
     h.close()
 
 
-def test_split_and_unsplit_downdate_agree():
-    """The K-split (strip partials added in order) and the single-strip downdate compute the same Sigma."""
-    X, y = syn.make_dataset(4096, 3)
+# (n, m, dtype, strips forced for the split call; 0: the library's own count).  300 x 130 is the smallest shape with every kind
+# of tile: three contraction tiles, so two strips are two tiles and ONE tile wide (an uneven last strip); two tile rows, so a
+# diagonal tile, an off-diagonal tile, a second diagonal tile and two rhs tiles.
+SPLIT_CASES = [(4096, 300, 64, 0), (300, 130, 64, 2), (300, 130, 32, 2)]
+
+
+@pytest.mark.parametrize("n,m,dtype,forced", SPLIT_CASES)
+def test_split_and_unsplit_downdate_agree(n, m, dtype, forced):
+    """The K-split (strip partials added in order) and the single-strip downdate compute the same Sigma: fp64 to 1e-12 of each
+    other and 1e-9 of numpy; fp32 both within the file's fp32 bar of numpy (the two orders of summation differ legitimately
+    there, and no bound on that difference has been derived).  Every call repeats its bytes and Sigma is exactly symmetric."""
+    X, y = syn.make_dataset(n, 3)
     th = _theta("se_ard", 3)
-    Xs = syn.make_test_points(300, 3)
-    h = _handle("se_ard", X, y)
+    Xs = syn.make_test_points(m, 3)
+    _, S_ref, _ = reference("se_ard", th, X, y, Xs)
+    h = _handle("se_ard", X, y, dtype=dtype)
     assert h.fit(th) == 0
-    _, auto = h.predict_cov(Xs)
-    assert h.get_option("last_joint_nsplit") > 1
-    h.set_option("joint_split", 1)
-    _, one = h.predict_cov(Xs)
-    assert h.get_option("last_joint_nsplit") == 1
-    np.testing.assert_allclose(auto, one, rtol=0, atol=1e-12)
+    covs = []
+    for split in (forced, 1):
+        h.set_option("joint_split", split)
+        _, cov = h.predict_cov(Xs)
+        nsplit = h.get_option("last_joint_nsplit")
+        assert (nsplit == split) if split else (nsplit > 1)
+        _, again = h.predict_cov(Xs)
+        assert np.array_equal(cov, again)
+        assert np.array_equal(cov, cov.T)
+        err = np.abs(cov - S_ref).max()
+        print(f"fp{dtype} n={n} m={m} strips={nsplit}: max |error| = {err:.3e} x sf^2")
+        assert err <= (1e-9 if dtype == 64 else 2e-3)
+        covs.append(cov)
+    if dtype == 64:
+        np.testing.assert_allclose(covs[0], covs[1], rtol=0, atol=1e-12)
     h.close()
 
 

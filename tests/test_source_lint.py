@@ -101,6 +101,24 @@ def test_sparse_bound_has_one_forward_pass_and_owned_phase_records():
     assert all(re.fullmatch(r"\w+\.harvest\(\)", m) for m in re.findall(r"[\w.>-]*\bharvest\b(?:\(\))?", rest)), "harvest outside the owner"
 
 
+def test_strip_split_contraction_exists_once():
+    # The joint downdate and the sparse accumulation are one device algorithm (gp_contract.h): tile-list
+    # decode, thin-tile rule, two-stage software pipeline and the reduction of the strip partials.  A hand copy in a caller's
+    # header means every fix to the barrier / wait placement or to the thin-tile rule has to be made and proved twice.
+    joint, sparse, contract = (_code(os.path.join(CSRC, n)) for n in ("gp_joint.h", "gp_sparse.h", "gp_contract.h"))
+    thin = (r"\bi\s*>=\s*16\b", r"\bj\s*>=\s*64\b")           # the reduce kernel's skip conditions
+    for code in (joint, sparse):
+        assert "sched_barrier" not in code and "pin_frags" not in code
+        assert "tri_decode" not in code
+        assert not any(re.search(t, code) for t in thin)
+    assert all(len(re.findall(t, contract)) == 1 for t in thin)
+    assert len(re.findall(r"__global__[^;{]*\bvoid\s+\w*reduce_kernel\b", joint + sparse)) == 0
+    # the two entry kernels are its only users: downdate_kernel calls it on either side of `if constexpr (SEG)`
+    users = {name: len(re.findall(r"\bstrip_contract\b", _code(os.path.join(CSRC, name)))) for name in os.listdir(CSRC)}
+    users = {name: n for name, n in users.items() if n and name != "gp_contract.h"}
+    assert users == {"gp_joint.h": 2, "gp_sparse.h": 1}, users
+
+
 def test_gfx950_only_no_compat_layers():
     for name in os.listdir(CSRC):
         code = _code(os.path.join(CSRC, name))
