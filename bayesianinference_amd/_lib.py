@@ -138,6 +138,12 @@ _SIGNATURES = {
     "gphip_sparse_fit": (C.c_int, [_h, _dp, C.c_int, C.c_double, _ip]),
     "gphip_sparse_predict": (C.c_int, [_h, C.c_void_p, C.c_int64, C.c_int, _dp, _dp]),
     "gphip_sparse_predict_samples": (C.c_int, [_h, _dp, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_int64, C.c_int, _dp, _dp, _dp, _ip]),
+    "gphip_sparse_bound_pw": (C.c_int, [_h, _dp, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _ip]),
+    "gphip_sparse_bound_batch_pw": (C.c_int, [_h, _dp, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _ip]),
+    "gphip_sparse_fit_pw": (C.c_int, [_h, _dp, C.c_int, C.c_double, _dp, _dp, _ip]),
+    "gphip_sparse_predict_pw": (C.c_int, [_h, C.c_void_p, C.c_int64, C.c_int, _dp, _dp, _dp, _dp]),
+    "gphip_sparse_predict_samples_pw": (C.c_int, [_h, _dp, C.c_int, C.c_int, C.c_double, _dp, _dp, C.c_void_p, C.c_int64, C.c_int, _dp, _dp,
+                                                  _dp, _dp, _dp, _ip]),
     "gphip_sparse_predict_cov": (C.c_int, [_h, C.c_void_p, C.c_int64, C.c_int, _dp, _dp]),
     "gphip_sparse_predict_draws": (C.c_int, [_h, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_uint64, _dp, C.c_double, _dp, _ip]),
     "gphip_sparse_predict_logpdf": (C.c_int, [_h, C.c_void_p, C.c_int64, _dp, _dp, _ip]),
@@ -228,6 +234,19 @@ def ns_crude_weights(points, loglik, pool: int):
     if rc != OK:
         raise GphipError(rc, "gphip_ns_crude_weights")
     return order, logx, logw, z.value
+
+
+def num_params(kernel, d: int, mean: str) -> int:
+    """Length of theta for a kernel (a name of the grammar or a CustomKernel) on d dimensions with the mean "zero" / "const":
+    the kernel's parameters, sigma_n and, for the constant mean, mu.  Host logic (gphip_kernel_parse): no device is touched."""
+    if isinstance(kernel, CustomKernel):
+        count = kernel.nparams
+    else:
+        spec = (C.c_int * 8)()
+        if load().gphip_kernel_parse(str(kernel).encode(), int(d), spec) != OK:
+            raise GphipError(1, f"{kernel!r} is not a kernel of the library")
+        count = spec[7]                                # the 0-based position of sigma_n
+    return count + 1 + (1 if mean == "const" else 0)
 
 
 class CustomKernel:
@@ -848,6 +867,86 @@ class SparseHandle:
         F = np.zeros(S) if bound else None
         self._check(self._lib.gphip_sparse_predict_samples(self._h, _d(Th), S, p, float(jitter), Xs.ctypes.data, M, int(bool(latent)),
                                                            _d(mean), _d(var), _d(F) if bound else None, info.ctypes.data_as(_ip)))
+        return (mean, var, info, F) if bound else (mean, var, info)
+
+    # ---- a mean and a noise variance that depend on the point (gphip_sparse_*_pw)
+    @staticmethod
+    def _pw_array(a, rows, cols, what):
+        """None, or the contiguous fp64 [rows, cols] array of a point-dependent quantity (one row may be given 1-D)."""
+        if a is None:
+            return None
+        a = np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+        if a.size != rows * cols:
+            raise GphipError(2, f"{what} needs {rows} x {cols} values, got an array of shape {a.shape}")
+        return a.reshape(rows, cols)
+
+    def bound_pw(self, theta, jitter: float = -1.0, mean_train=None, nugget_train=None, parts: bool = False):
+        """gphip_sparse_bound_pw: (F, info) -- with parts=True (F, parts[6], info) -- with the mean m_i and the noise VARIANCE
+        nu_i at the N training points as arrays (None: the constant of theta).  parts = (log det B, c'c, r'W r, tr(V W V'),
+        sum_i k_ii / nu_i, sum_i log nu_i) with W = diag(1 / nu) and B = I + V W V'.  The fit stays resident."""
+        th = np.ascontiguousarray(np.asarray(theta, dtype=np.float64).ravel())
+        mt = self._pw_array(mean_train, 1, self.N, "mean_train")
+        nt = self._pw_array(nugget_train, 1, self.N, "nugget_train")
+        out, info, pr = C.c_double(0.0), C.c_int(0), np.zeros(6)
+        self._check(self._lib.gphip_sparse_bound_pw(self._h, _d(th), th.size, float(jitter), None if mt is None else _d(mt),
+                                                    None if nt is None else _d(nt), C.byref(out), _d(pr) if parts else None, C.byref(info)))
+        return (out.value, pr, info.value) if parts else (out.value, info.value)
+
+    def bound_batch_pw(self, Theta, jitter: float = -1.0, mean_train=None, nugget_train=None, parts: bool = False):
+        """gphip_sparse_bound_batch_pw: (F[B], info[B]) -- with parts=True also parts[B, 6] -- for the rows of Theta [B, p] with
+        the arrays mean_train / nugget_train [B, N] (row s for row s of Theta; None: the constant of theta) in ONE call."""
+        Th = np.ascontiguousarray(np.asarray(Theta, dtype=np.float64))
+        if Th.ndim == 1:
+            Th = Th.reshape(1, -1)
+        B, p = Th.shape
+        mt = self._pw_array(mean_train, B, self.N, "mean_train")
+        nt = self._pw_array(nugget_train, B, self.N, "nugget_train")
+        out, info = np.zeros(B), np.zeros(B, dtype=np.int32)
+        pr = np.zeros((B, 6)) if parts else None
+        self._check(self._lib.gphip_sparse_bound_batch_pw(self._h, _d(Th), B, p, float(jitter), None if mt is None else _d(mt),
+                                                          None if nt is None else _d(nt), _d(out), _d(pr) if parts else None,
+                                                          info.ctypes.data_as(_ip)))
+        return (out, info, pr) if parts else (out, info)
+
+    def fit_pw(self, theta, jitter: float = -1.0, mean_train=None, nugget_train=None) -> int:
+        th = np.ascontiguousarray(np.asarray(theta, dtype=np.float64).ravel())
+        mt = self._pw_array(mean_train, 1, self.N, "mean_train")
+        nt = self._pw_array(nugget_train, 1, self.N, "nugget_train")
+        info = C.c_int(0)
+        self._check(self._lib.gphip_sparse_fit_pw(self._h, _d(th), th.size, float(jitter), None if mt is None else _d(mt),
+                                                  None if nt is None else _d(nt), C.byref(info)))
+        return info.value
+
+    def predict_pw(self, Xs, latent: bool = False, mean_test=None, nugget_test=None):
+        """gphip_sparse_predict_pw: (mean[M], var[M]) at Xs from the resident fit with m(x*) and nu(x*) at the test points as
+        arrays (None: the constant of the fit's theta); nugget_test is not read for a latent prediction."""
+        Xs = self._test_points(Xs)
+        M = Xs.shape[0]
+        mt = self._pw_array(mean_test, 1, M, "mean_test")
+        nt = self._pw_array(nugget_test, 1, M, "nugget_test")
+        mean, var = np.zeros(M), np.zeros(M)
+        self._check(self._lib.gphip_sparse_predict_pw(self._h, Xs.ctypes.data, M, 1 if latent else 0, None if mt is None else _d(mt),
+                                                      None if nt is None else _d(nt), _d(mean), _d(var)))
+        return mean, var
+
+    def predict_samples_pw(self, Thetas, Xs, jitter: float = -1.0, latent: bool = False, mean_train=None, nugget_train=None,
+                           mean_test=None, nugget_test=None, bound: bool = False):
+        """gphip_sparse_predict_samples_pw: `predict_samples` with the training arrays [S, N] and the test arrays [S, M] of a
+        point-dependent mean and noise variance (None: the constant of the row's theta)."""
+        Th = np.ascontiguousarray(np.asarray(Thetas, dtype=np.float64))
+        if Th.ndim == 1:
+            Th = Th.reshape(1, -1)
+        Xs = self._test_points(Xs)
+        S, p = Th.shape
+        M = Xs.shape[0]
+        arrs = [self._pw_array(mean_train, S, self.N, "mean_train"), self._pw_array(nugget_train, S, self.N, "nugget_train"),
+                self._pw_array(mean_test, S, M, "mean_test"), self._pw_array(nugget_test, S, M, "nugget_test")]
+        ptr = [None if a is None else _d(a) for a in arrs]
+        mean, var, info = np.zeros((S, M)), np.zeros((S, M)), np.zeros(S, dtype=np.int32)
+        F = np.zeros(S) if bound else None
+        self._check(self._lib.gphip_sparse_predict_samples_pw(self._h, _d(Th), S, p, float(jitter), ptr[0], ptr[1], Xs.ctypes.data, M,
+                                                              int(bool(latent)), ptr[2], ptr[3], _d(mean), _d(var),
+                                                              _d(F) if bound else None, info.ctypes.data_as(_ip)))
         return (mean, var, info, F) if bound else (mean, var, info)
 
     def _test_points(self, Xs):

@@ -3,7 +3,7 @@
 //
 //   strip_contract       device skeleton: one 128 x 128 output tile x one strip of the contraction index per workgroup
 //   StridedK / SwizzledK operand policies: the contraction index is the strided / the contiguous one of the operands
-//   JNegate / JSegment / JIdentity    what a J fragment takes before the MFMA
+//   JNegate / JSegment / JIdentity / JWeight    what a J fragment takes before the MFMA
 //   strip_reduce_kernel  C -/+= the strip partials, strips added in a fixed order
 //   strip_split          host: how many strips a launch is cut into
 #pragma once
@@ -174,18 +174,19 @@ struct SwizzledK {
 };
 
 // ---------------------------------------------------------------------------------------------
-// J-scale policy: at(k) is called once per stage with the stage's first contraction index, then (*this)(fj, direct) on every J
-// fragment of the stage.  direct: the accumulators started at C (no partial tiles).
+// J-scale policy: at(k) is called once per stage with the stage's first contraction index, then (*this)(fj, direct, kk) on every J
+// fragment of MFMA step kk of the stage (a lane's fragment of step kk is contraction index k + 4 kk + (lane >> 4) in both operand
+// policies).  direct: the accumulators started at C (no partial tiles).
 // ---------------------------------------------------------------------------------------------
 template <typename T>
 struct JIdentity {               // C += I J^T
     __device__ __forceinline__ void at(long) {}
-    __device__ __forceinline__ T operator()(T fj, bool) const { return fj; }
+    __device__ __forceinline__ T operator()(T fj, bool, int) const { return fj; }
 };
 template <typename T>
 struct JNegate {                 // C -= I J^T: accumulators that start at C take the negated fragment, a partial tile the product itself
     __device__ __forceinline__ void at(long) {}
-    __device__ __forceinline__ T operator()(T fj, bool direct) const { return direct ? -fj : fj; }
+    __device__ __forceinline__ T operator()(T fj, bool direct, int) const { return direct ? -fj : fj; }
 };
 template <typename T>
 struct JSegment {                // factor s1 for k < kseg, s2 from there on; a stage lies in one segment (GK divides 128 divides kseg)
@@ -193,7 +194,29 @@ struct JSegment {                // factor s1 for k < kseg, s2 from there on; a 
     T s1, s2, sc;
     __device__ __forceinline__ JSegment(int kseg_, T s1_, T s2_) : kseg(kseg_), s1(s1_), s2(s2_), sc(s1_) {}
     __device__ __forceinline__ void at(long k) { sc = k < kseg ? s1 : s2; }
-    __device__ __forceinline__ T operator()(T fj, bool) const { return sc * fj; }
+    __device__ __forceinline__ T operator()(T fj, bool, int) const { return sc * fj; }
+};
+// C += I diag(w) J^T: a weight per contraction index, w [kend] in the operands' type (zero where an operand is padding).  A lane
+// needs one weight per MFMA step: NKK values per stage, held in registers.  Those of the NEXT stage are requested in at(), next to
+// the staging loads of that stage, and the pipeline's wait before its barrier covers them, so no MFMA waits for a weight.
+template <typename T, int GK>
+struct JWeight {
+    static constexpr int NKK = GK / 4;
+    const T* w;                  // + (lane >> 4): this lane's weight of step kk of the stage at k is w[k + 4 kk]
+    long kend;
+    T cur[NKK], nxt[NKK];
+    __device__ __forceinline__ void fetch(long k) {
+#pragma unroll
+        for (int kk = 0; kk < NKK; ++kk) nxt[kk] = k < kend ? w[k + 4 * kk] : (T)0;
+    }
+    // w_: the weights of the workgroup's slot; k0: where its strip starts; kend_: the contraction length (a multiple of GK)
+    __device__ __forceinline__ JWeight(const T* w_, long k0, long kend_) : w(w_ + (threadIdx.x >> 4 & 3)), kend(kend_) { fetch(k0); }
+    __device__ __forceinline__ void at(long k) {
+#pragma unroll
+        for (int kk = 0; kk < NKK; ++kk) cur[kk] = nxt[kk];
+        fetch(k + GK);
+    }
+    __device__ __forceinline__ T operator()(T fj, bool, int kk) const { return cur[kk] * fj; }
 };
 
 template <typename T, class Opnd, class JScale>
@@ -235,10 +258,10 @@ __device__ __forceinline__ void strip_contract(const ContractArgs<T>& g, Opnd op
     auto pipeline = [&](auto nyc) {
         constexpr int NY = decltype(nyc)::value;
         constexpr int NKK = GK / 4;
-        auto mfma_block = [&](const T* fi, const T* fj) {
+        auto mfma_block = [&](const T* fi, const T* fj, int kk) {
             T nj[FJ];
 #pragma unroll
-            for (int f = 0; f < FJ; ++f) nj[f] = js(fj[f], direct);
+            for (int f = 0; f < FJ; ++f) nj[f] = js(fj[f], direct, kk);
 #pragma unroll
             for (int x = 0; x < FJ; ++x)
 #pragma unroll
@@ -271,7 +294,7 @@ __device__ __forceinline__ void strip_contract(const ContractArgs<T>& g, Opnd op
                     __builtin_amdgcn_sched_barrier(0);
                     op.load_frags(smem_raw, cur, kk + 1, fa[(kk + 1) & 1], fb[(kk + 1) & 1], w);
                     __builtin_amdgcn_sched_barrier(0);
-                    mfma_block(fa[kk & 1], fb[kk & 1]);
+                    mfma_block(fa[kk & 1], fb[kk & 1], kk);
                     __builtin_amdgcn_sched_barrier(0);
                 }
                 pin_frags(fa[(NKK - 1) & 1], fb[(NKK - 1) & 1]);
@@ -281,7 +304,7 @@ __device__ __forceinline__ void strip_contract(const ContractArgs<T>& g, Opnd op
             if (NY > 0) {
                 if (kb + 1 < nk) op.load_frags(smem_raw, cur ^ 1, 0, fa[0], fb[0], w);
                 __builtin_amdgcn_sched_barrier(0);
-                mfma_block(fa[(NKK - 1) & 1], fb[(NKK - 1) & 1]);
+                mfma_block(fa[(NKK - 1) & 1], fb[(NKK - 1) & 1], NKK - 1);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }

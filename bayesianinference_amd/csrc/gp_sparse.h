@@ -4,6 +4,8 @@
 //   (the first four kernels and strip_reduce_kernel carry a slot dimension for gphip_sparse_bound_batch: one theta per workspace
 //    slot, slot = the grid's last index, every operand addressed as slot-0 base + slot x stride; the one-theta calls run them with one slot)
 //   sparse_resid_kernel          r = y - mu of a chunk into row 0 of the rhs operand + per-block partial sums of r^2
+//   sparse_resid_pw_kernel       point-dependent mean and noise: r = y - m_i, the weight row w = 1 / nu_i, partial sums of r^2 w, log nu, w
+//   sparse_scale_rows_kernel     option "sparse_pw_fused" = 0 (the default): V(t, .) and r_t times sqrt(w_t) in place, ahead of the unweighted accumulation
 //   sparse_blocksum_kernel       per-block partial sums of a double vector (k(x_i, x_i) of a run-time compiled kernel)
 //   sparse_diag_kernel           tr(V V^T) from C's diagonal, then + sn^2 on it (identity on the pad)
 //   sparse_predict_finish_kernel mean and variance of a chunk of test points from the strip partials of v1 and v2, per slot
@@ -15,7 +17,8 @@
 
 namespace gphip {
 
-constexpr int SPARSE_PAR = 4;                  // doubles per slot of the sparse object's own scalars: mu, sn^2, k(x, x), unused
+constexpr int SPARSE_PAR = 4;                  // doubles per slot of the sparse object's own scalars: mu, sn^2 of B, k(x, x), the noise of theta
+constexpr int SPARSE_PAR_NOISE = 3;            // (par[1] is the sn^2 of B = sn^2 I + V V^T: 1 once the data are whitened by 1 / nu_i)
 
 // ---------------------------------------------------------------------------------------------
 // Accumulation: strip_contract (gp_contract.h) with the contiguous-k operands.  V is the chunk of L_u^-1 k(Z, X) the forward
@@ -25,14 +28,25 @@ constexpr int SPARSE_PAR = 4;                  // doubles per slot of the sparse
 // so the contraction index t is the contiguous one of both operands.  The rhs operand is 16 rows x ldr (row 0 = r of the chunk,
 // rows 1 .. 15 zero).  One workgroup = one output tile x one strip of the chunk's rows x one slot.
 // ---------------------------------------------------------------------------------------------
+// Weighted form (point-dependent noise): C(k1, k2) += sum_t V(t, k1) w_t V(t, k2), rhs row 0 +=
+// sum_t r_t w_t V(t, k), w = 1 / nu the weight row of the chunk (W: one row of ldw elements per slot, zero on the pad).  The weight
+// is the J-scale policy of the one contraction, chosen at compile time: the constant form's instantiation does not know of it.
+// (Option "sparse_pw_fused" = 1; the default is the scaling pass of sparse_scale_rows_kernel, see the measurement in DESIGN.md 8i.)
 template <typename T>
 struct SparseAccArgs : ContractArgs<T> {
     long ldr;                    // leading dimension of the rhs operand Z
+    const T* W; long ldw;        // weighted form: the weight rows
 };
 
-template <typename T>
+template <typename T, bool WEIGHTED>
+__device__ __forceinline__ auto sparse_jscale(const SparseAccArgs<T>& g) {
+    if constexpr (WEIGHTED) return JWeight<T, SwizzledK<T>::GK>(g.W + (long)blockIdx.z * g.ldw, (long)blockIdx.y * g.kstrip, g.K);
+    else return JIdentity<T>{};
+}
+
+template <typename T, bool WEIGHTED>
 __global__ __launch_bounds__(256, 2) void sparse_accumulate_kernel(SparseAccArgs<T> g) {
-    strip_contract<T>(g, SwizzledK<T>{g.ldr}, JIdentity<T>{});
+    strip_contract<T>(g, SwizzledK<T>{g.ldr}, sparse_jscale<T, WEIGHTED>(g));
 }
 
 // fixed-order sum of the 256 values of a workgroup (one per thread); the result is valid in thread 0
@@ -64,14 +78,69 @@ __global__ __launch_bounds__(256) void sparse_resid_kernel(const T* __restrict__
     if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
-// part[block] = sum of v[t], t < n, over the block's 256 entries.  grid = (blocks, slots): slot s reads v + s v_bstride
+// The point-dependent form of sparse_resid_kernel.  mean / nug: this chunk's slice of the group's arrays (fp64, slot s at
+// + s a_bstride); a null array is the slot's constant par[0] (mu) / par[SPARSE_PAR_NOISE] (sn^2), broadcast.
+//   rz[t] = y[t] - m_t, wz[t] = 1 / nu_t for t < n, both 0 for n <= t < npad (the handle's arithmetic type)
+//   part[block], part[2 pn + block], part[3 pn + block] = the block's sums of r^2 w, log nu and w in fp64 (w as the kernel uses it;
+//   part[pn + block] is sparse_blocksum_kernel's)
+// grid = (ceil(npad / 256), slots).
+template <typename T>
+__global__ __launch_bounds__(256) void sparse_resid_pw_kernel(const T* __restrict__ y, int n, int npad, const double* __restrict__ par,
+                                                              const double* __restrict__ mean, const double* __restrict__ nug, long a_bstride,
+                                                              T* __restrict__ rz, long r_bstride, T* __restrict__ wz, long w_bstride,
+                                                              double* __restrict__ part, long p_bstride, long pn) {
+    __shared__ double red[256];
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    const long slot = blockIdx.y;
+    par += SPARSE_PAR * slot;
+    rz += slot * r_bstride;
+    wz += slot * w_bstride;
+    part += slot * p_bstride;
+    T r = (T)0, w = (T)0;
+    double lognu = 0.0;
+    if (t < n) {
+        const double m = mean ? mean[slot * a_bstride + t] : par[0];
+        const double nu = nug ? nug[slot * a_bstride + t] : par[SPARSE_PAR_NOISE];
+        r = (T)(y[t] - (T)m);
+        w = (T)(1.0 / nu);
+        lognu = log(nu);
+    }
+    if (t < npad) { rz[t] = r; wz[t] = w; }
+    double s = sparse_block_sum((double)r * (double)r * (double)w, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+    __syncthreads();
+    s = sparse_block_sum(lognu, red);
+    if (threadIdx.x == 0) part[2 * pn + blockIdx.x] = s;
+    __syncthreads();
+    s = sparse_block_sum((double)w, red);
+    if (threadIdx.x == 0) part[3 * pn + blockIdx.x] = s;
+}
+
+// V(t, k) *= sqrt(w_t) for the npad rows x ncols columns of every slot's chunk, and r_t *= sqrt(w_t): after it the unweighted
+// accumulation gives the weighted sums.  grid = (npad / 256, ncols + 1, slots); column ncols is the residual row.
+template <typename T>
+__global__ __launch_bounds__(256) void sparse_scale_rows_kernel(T* __restrict__ V, long ldv, long v_bstride, int ncols, T* __restrict__ rz,
+                                                                long r_bstride, const T* __restrict__ wz, long w_bstride, int npad) {
+    const int t = blockIdx.x * 256 + threadIdx.x, k = blockIdx.y;
+    const long slot = blockIdx.z;
+    if (t >= npad) return;
+    const T s = (T)sqrt((double)wz[slot * w_bstride + t]);
+    T* p = k < ncols ? V + slot * v_bstride + (long)k * ldv + t : rz + slot * r_bstride + t;
+    *p *= s;
+}
+
+// part[block] = sum of v[t] (w: v[t] w[t]), t < n, over the block's 256 entries.  grid = (blocks, slots): slot s reads
+// v + s v_bstride and w + s w_bstride
+template <typename W>
 __global__ __launch_bounds__(256) void sparse_blocksum_kernel(const double* __restrict__ v, long v_bstride, int n, double* __restrict__ part,
-                                                              long p_bstride) {
+                                                              long p_bstride, const W* __restrict__ w, long w_bstride) {
     __shared__ double red[256];
     const int t = blockIdx.x * 256 + threadIdx.x;
     v += (long)blockIdx.y * v_bstride;
     part += (long)blockIdx.y * p_bstride;
-    const double s = sparse_block_sum(t < n ? v[t] : 0.0, red);
+    double x = t < n ? v[t] : 0.0;
+    if (w && t < n) x *= (double)w[(long)blockIdx.y * w_bstride + t];
+    const double s = sparse_block_sum(x, red);
     if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
@@ -105,11 +174,14 @@ __global__ __launch_bounds__(256) void sparse_diag_kernel(T* __restrict__ C, lon
 // strip s of slot q at part1[q p1_bstride + s p1_sstride + t] (predict_partial_kernel's norm rows of u, or what
 // sparse_handover_kernel leaves); part2: predict_partial_kernel's [slot][strip][2][mpad] for v2 = L_B^-1 v1 against c (dots and
 // norms).  par: [slot][SPARSE_PAR] = mu, sn^2 and the scalar k(x, x) of the slot's theta; kss [slot][mpad] (run-time compiled
-// kernels): k(x*, x*) per point in its place.  mean, var: [slot][mpad].
-//     mean = mu + v2^T c        var = k(x*, x*) [+ sn2] - |v1|^2 + sn2 |v2|^2
+// kernels): k(x*, x*) per point in its place.  mean, var: [slot][mpad].  par[1] is the sn^2 of B = sn^2 I + V V^T (1 for a whitened
+// fit), par[3] the noise variance at a test point; mean_t / nug_t ([slot][mpad] or null): m(x*) / nu(x*) per point in their place.
+//     mean = mu + v2^T c        var = k(x*, x*) [+ noise] - |v1|^2 + sn2 |v2|^2
 __global__ void sparse_predict_finish_kernel(const double* __restrict__ part1, int nstrips1, long p1_sstride, long p1_bstride,
                                              const double* __restrict__ part2, int nstrips2, long mpad, int mc,
-                                             const double* __restrict__ par, const double* __restrict__ kss, int latent, double* __restrict__ mean, double* __restrict__ var) {
+                                             const double* __restrict__ par, const double* __restrict__ kss, int latent,
+                                             const double* __restrict__ mean_t, const double* __restrict__ nug_t,
+                                             double* __restrict__ mean, double* __restrict__ var) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     const int slot = blockIdx.y;
     if (t >= mc) return;
@@ -123,8 +195,9 @@ __global__ void sparse_predict_finish_kernel(const double* __restrict__ part1, i
         n2 += part2[((long)s * 2 + 1) * mpad + t];
     }
     const long o = (long)slot * mpad + t;
-    mean[o] = mu + dot;
-    var[o] = (kss ? kss[o] : par[SPARSE_PAR * slot + 2]) + (latent ? 0.0 : sn2) - n1 + sn2 * n2;
+    const double noise = nug_t ? nug_t[o] : par[SPARSE_PAR * slot + SPARSE_PAR_NOISE];
+    mean[o] = (mean_t ? mean_t[o] : mu) + dot;
+    var[o] = (kss ? kss[o] : par[SPARSE_PAR * slot + 2]) + (latent ? 0.0 : noise) - n1 + sn2 * n2;
 }
 
 // gphip_sparse_predict_samples: V1 = L_u^-1 k(Z, X*) of every slot of a group goes from u's dV into b's, and the norms |v1|^2 are

@@ -66,7 +66,9 @@ struct gphip_sparse_ctx {
     std::vector<std::pair<std::string, double>> forwarded;    // options handed on to u and b (replayed after gphip_sparse_set_inducing)
     Buf dXt, dY;                               // typed [d][Npad], [Npad]: the data, resident
     Buf dRz; int64_t rcap = 0; int rz_slots = 0;   // typed [slot][16][rcap]: row 0 = r of the current chunk, the other rows zero
-    Buf dPar, hPar;                            // double [slot][SPARSE_PAR]: mu, sn^2 and k(x, x) of every slot's theta (device; pinned staging copy)
+    Buf dPar, hPar;                            // double [slot][SPARSE_PAR]: mu, B's sn^2, k(x, x) and the noise of every slot's theta (device; pinned staging copy)
+    Buf dWz;                                   // typed [slot][rcap]: the weight row 1 / nu of the current chunk (point-dependent noise), zero on the pad
+    Buf dPwTrain, dPwTest;                     // double: a group's rows of mean_train | nugget_train ([2][slot][N]); a chunk's of mean_test | nugget_test ([2][slot][mpad])
     Buf dAccP;                                 // typed [slot][strip][tile][128 x 128]: strip partials of the accumulation
     Buf dSum; std::vector<double> hSum;        // double, per slot: [0] tr(V V^T), then the per-block partial sums of r^2 and of k(x_i, x_i)
     Buf dBc, dS, dH;                           // gradient, typed: B's tiles before its factorisation; S; the inner matrix of H (mpad x mpad)
@@ -79,6 +81,8 @@ struct gphip_sparse_ctx {
     int batch_slots = 0;                       // gphip_sparse_bound_batch / _predict_samples: most thetas per group (0 = by the group rule)
     int samples_chunk = 0;                     // gphip_sparse_predict_samples: test points per pass (0 = by the rule)
     int samples_handover = 1;                  // gphip_sparse_predict_samples: 1 = sparse_handover_kernel, 0 = copy + norm launch (measurement)
+    int pw_fused = 0;                          // the _pw calls: 1 = the weight inside the contraction, 0 = sparse_scale_rows_kernel + the unweighted one
+                                               // (the default since the measurement of DESIGN.md section 8i: fused lost at the largest size)
     // read-only results of the last call
     int last_nsplit = 0;
     int joint_nsplit = 0;                      // strips the last joint prediction's downdate used
@@ -93,6 +97,7 @@ struct gphip_sparse_ctx {
                                                // prediction over samples: V1, the handover to b, V2, the reductions
     // the resident fit
     bool fitted = false;
+    bool pw_fit = false;                       // the fit was made with a point-dependent array: B = I + V W V^T, no joint prediction
     double sn2_fit = 0, mu_fit = 0, kxx_fit = 0;
     std::string err;
 };
@@ -151,7 +156,9 @@ struct SparseScope {
 
 template <typename T>
 int sparse_func_attrs(gphip_sparse_ctx* h) {
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(sparse_accumulate_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(sparse_accumulate_kernel<T, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)SwizzledK<T>::LDS));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(sparse_accumulate_kernel<T, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)SwizzledK<T>::LDS));
 #define ZG_ATTR(DW)                                                                                                              \
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(sparse_zgrad_kernel<T, DW, false, false>),                          \
@@ -222,13 +229,15 @@ int sparse_ensure_par(gphip_sparse_ctx* h, int nb) {
 
 // C += V^T V, rhs row += r^T V for the chunk of mpad rows in u->dV, for every one of nb slots by ONE launch (slot s: V at
 // dV + s mpad Npad, C = b's workspace slot s), in the strips of strip_split (gp_contract.h) for output tiles x slots workgroups.
+// weighted: C += V^T W V, rhs row += r^T W V with the slots' weight rows in dWz (the kernel's other instantiation).
 template <typename T>
-int sparse_queue_accumulate(gphip_sparse_ctx* h, int64_t mpad, int nb = 1) {
+int sparse_queue_accumulate(gphip_sparse_ctx* h, int64_t mpad, int nb, bool weighted) {
     gphip_ctx *u = h->u, *b = h->b;
     SparseAccArgs<T> g{};
     g.C = (T*)b->dA.p; g.R = (int)b->R;
     g.V = (const T*)u->dV.p; g.ldv = (long)mpad;
     g.Z = (const T*)h->dRz.p; g.ldr = (long)h->rcap;
+    g.W = weighted ? (const T*)h->dWz.p : nullptr; g.ldw = (long)h->rcap;
     g.Mt = (int)u->Nt; g.ntri = g.Mt * (g.Mt + 1) / 2; g.ntiles = g.ntri + g.Mt;
     g.K = (int)mpad;
     g.c_bstride = (long)b->slot_elems; g.v_bstride = (long)mpad * u->Npad; g.z_bstride = 16l * h->rcap;
@@ -241,8 +250,8 @@ int sparse_queue_accumulate(gphip_sparse_ctx* h, int64_t mpad, int nb = 1) {
         HIPCHK(h->dAccP.grow((size_t)nb * g.p_bstride * sizeof(T)));
         g.P = (T*)h->dAccP.p;
     }
-    hipLaunchKernelGGL(sparse_accumulate_kernel<T>, dim3((unsigned)g.ntiles, (unsigned)nsplit, (unsigned)nb), dim3(256), SwizzledK<T>::LDS,
-                       u->stream, g);
+    void (*const kernel)(SparseAccArgs<T>) = weighted ? sparse_accumulate_kernel<T, true> : sparse_accumulate_kernel<T, false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)g.ntiles, (unsigned)nsplit, (unsigned)nb), dim3(256), SwizzledK<T>::LDS, u->stream, g);
     if (nsplit > 1)
         hipLaunchKernelGGL(strip_reduce_kernel<T>, dim3((unsigned)g.ntiles, 16, (unsigned)nb), dim3(256), 0, u->stream, g.C, g.R, g.ntri, g.Mt,
                            g.ntiles, (const T*)g.P, nsplit, 1.0, g.c_bstride, g.p_bstride);
@@ -255,6 +264,45 @@ int sparse_queue_resid(gphip_sparse_ctx* h, int64_t c0, int64_t mc, int64_t mpad
     hipLaunchKernelGGL(sparse_resid_kernel<T>, dim3((unsigned)((mpad + 255) / 256), (unsigned)nb), dim3(256), 0, h->u->stream,
                        (const T*)h->dY.p + c0, (int)mc, (int)mpad, (const double*)h->dPar.as<double>(), SPARSE_PAR, (T*)h->dRz.p, 16l * h->rcap, part,
                        pstride);
+    return GPHIP_OK;
+}
+
+// The point-dependent mean and noise of a call (gphip_sparse_*_pw), a property of the group evaluation.  mean / nugget: the
+// group's rows, row s = slot s, N values each; a null array is the constant of theta, broadcast.
+struct SparsePw {
+    const double *mean = nullptr, *nugget = nullptr;
+    bool any() const { return mean || nugget; }
+    SparsePw rows_from(int64_t s0, int64_t N) const { return SparsePw{mean ? mean + s0 * N : nullptr, nugget ? nugget + s0 * N : nullptr}; }
+};
+
+// r = y - m_i and the weight row 1 / nu_i of the chunk for nb slots from the group's arrays in dPwTrain (pw's null array: the
+// slot's constant in dPar); slot s's partial sums of r^2 w, log nu and w go to part + s pstride + {0, 2 pn, 3 pn}
+template <typename T>
+int sparse_queue_resid_pw(gphip_sparse_ctx* h, const SparsePw& pw, int64_t c0, int64_t mc, int64_t mpad, double* part, int nb, long pstride,
+                          long pn) {
+    const double* dm = h->dPwTrain.as<double>() + c0;
+    hipLaunchKernelGGL(sparse_resid_pw_kernel<T>, dim3((unsigned)((mpad + 255) / 256), (unsigned)nb), dim3(256), 0, h->u->stream,
+                       (const T*)h->dY.p + c0, (int)mc, (int)mpad, (const double*)h->dPar.as<double>(), pw.mean ? dm : nullptr,
+                       pw.nugget ? dm + (size_t)nb * h->N : nullptr, (long)h->N, (T*)h->dRz.p, 16l * h->rcap, (T*)h->dWz.p, (long)h->rcap, part,
+                       pstride, pn);
+    return GPHIP_OK;
+}
+
+// option "sparse_pw_fused" = 0: the chunk of V and the residual row of nb slots times sqrt(w) in place
+template <typename T>
+int sparse_queue_scale_rows(gphip_sparse_ctx* h, int64_t mpad, int nb) {
+    gphip_ctx* u = h->u;
+    hipLaunchKernelGGL(sparse_scale_rows_kernel<T>, dim3((unsigned)(mpad / 256 + 1), (unsigned)u->Npad + 1, (unsigned)nb), dim3(256), 0, u->stream,
+                       (T*)u->dV.p, (long)mpad, (long)mpad * u->Npad, (int)u->Npad, (T*)h->dRz.p, 16l * h->rcap, (const T*)h->dWz.p, (long)h->rcap,
+                       (int)mpad);
+    return GPHIP_OK;
+}
+
+// per-block partial sums of k(x_i, x_i) of the chunk (u->dKss) for nb slots; weighted: of k(x_i, x_i) / nu_i
+template <typename T>
+int sparse_queue_kk(gphip_sparse_ctx* h, int64_t mc, int64_t mpad, double* part, int nb, long pstride, bool weighted) {
+    hipLaunchKernelGGL(sparse_blocksum_kernel<T>, dim3((unsigned)((mpad + 255) / 256), (unsigned)nb), dim3(256), 0, h->u->stream,
+                       h->u->dKss.as<double>(), (long)mpad, (int)mc, part, pstride, weighted ? (const T*)h->dWz.p : nullptr, (long)h->rcap);
     return GPHIP_OK;
 }
 
@@ -568,10 +616,31 @@ struct SparseSlot {
     bool ok = false;                           // theta and its jitter are usable (else stand-in values were staged)
     bool evaluated = false;                    // B was factored and F formed (SparseKeep::fit stops before that on a failure)
     int info = 0, uinfo = 0;                   // the row's info as gphip_loglik's; that of K_uu's factorisation alone
+    bool pw = false;                           // whitened by a point-dependent array: B = I + V W V^T and the sums below carry w = 1 / nu
     double sn2 = 0, mu = 0, kxx = 0, jit = 0;
-    double F = 0, logdet = 0, ctc = 0, rtr = 0, trvv = 0, skk = 0;
+    double sb2 = 0;                            // the sn^2 of B = sn^2 I + V V^T: theta's, or 1 when whitened
+    double F = 0, logdet = 0, ctc = 0, rtr = 0, trvv = 0, skk = 0, slognu = 0;
     void put_parts(double* out) const { out[0] = logdet; out[1] = ctc; out[2] = rtr; out[3] = trvv; out[4] = skk; }
+    // the six parts of the _pw calls, B = I + V W V^T: what a whitened slot holds; a constant slot's five converted
+    void put_parts_pw(double* out, int64_t N, int64_t m) const {
+        if (pw) { put_parts(out); out[5] = slognu; return; }
+        out[0] = logdet - (double)m * std::log(sn2); out[1] = ctc / sn2; out[2] = rtr / sn2; out[3] = trvv / sn2; out[4] = skk / sn2;
+        out[5] = (double)N * std::log(sn2);
+    }
 };
+
+// a row of a point-dependent array is usable: every mean value finite, every noise variance finite and > 0
+bool sparse_pw_row_ok(const SparsePw& pw, int s, int64_t N) {
+    if (pw.mean)
+        for (int64_t i = 0; i < N; ++i)
+            if (!std::isfinite(pw.mean[(size_t)s * N + i])) return false;
+    if (pw.nugget)
+        for (int64_t i = 0; i < N; ++i) {
+            const double v = pw.nugget[(size_t)s * N + i];
+            if (!std::isfinite(v) || !(v > 0.0)) return false;
+        }
+    return true;
+}
 
 // the chunk's mpad rows of every slot: V <- L_u^-1 k(Z, X).  Resident: the fitted factor's route.  Batch: ONE dataflow launch
 // (slot = row) where gphip_predict_samples would take it and every slot of the group has a factor (a slot whose factorisation
@@ -588,8 +657,12 @@ void sparse_queue_forward(gphip_ctx* u, int64_t mpad, int nb, SparseKeep keep, b
 // once.  A row that fails keeps its slot (a non-finite theta is staged as stage_theta's stand-in values with a unit nugget, so
 // its slot factors) and only its own res[s] tells -- unless keep says that it ends the call.  keepB (null: not wanted): slot
 // 0's B before its factorisation overwrites it.
+// pw (DESIGN.md section 8i): the group's rows of a point-dependent mean and noise.  The data are whitened by w = 1 / nu_i: the
+// residual kernel's pw form leaves the weight row, the accumulation runs its weighted instantiation, and the slot's B is
+// I + V W V^T -- sn^2 = 1 for sparse_diag_kernel, b's nugget and b's pivot tolerance.  A row whose arrays are unusable is staged
+// with the stand-in arrays m = 0, nu = 1 and fails like a non-finite theta.
 int sparse_group(gphip_sparse_ctx* h, const double* Theta, int nb, int p, double jitter, int64_t rows, SparseKeep keep, Buf* keepB,
-                 SparsePhases& ph, SparseSlot* res) {
+                 const SparsePw& pw, SparsePhases& ph, SparseSlot* res) {
     gphip_ctx *u = h->u, *b = h->b;
     const bool resident = keep == SparseKeep::fit;
     int rc;
@@ -600,9 +673,15 @@ int sparse_group(gphip_sparse_ctx* h, const double* Theta, int nb, int p, double
         r.ok = stage_theta(u, s, Theta + (size_t)s * p);
         const double* sp = u->hSlotp.as<double>() + (size_t)s * SLOTP;
         r.sn2 = sp[1]; r.mu = sp[2]; r.kxx = sp[SP_KXX]; r.jit = jitter;
+        r.pw = pw.any();
+        r.sb2 = r.pw ? 1.0 : r.sn2;
         double* ps = par + (size_t)SPARSE_PAR * s;
-        ps[0] = r.mu; ps[1] = r.sn2; ps[2] = r.kxx; ps[3] = 0.0;
+        ps[0] = r.mu; ps[1] = r.sb2; ps[2] = r.kxx; ps[SPARSE_PAR_NOISE] = r.sn2;
     }
+    std::vector<char> pw_ok((size_t)nb, 1);
+    if (pw.any())
+        for (int s = 0; s < nb; ++s)
+            if (!sparse_pw_row_ok(pw, s, h->N)) { pw_ok[(size_t)s] = 0; res[s].ok = false; }
     if (jitter < 0.0) {                        // default: joint_jitter_rel x the row's k(x, x) (run-time compiled kernels: its mean of k(z, z))
         std::vector<double> scale((size_t)nb);
         for (int s = 0; s < nb; ++s) scale[(size_t)s] = res[s].kxx;
@@ -628,6 +707,24 @@ int sparse_group(gphip_sparse_ctx* h, const double* Theta, int nb, int p, double
     if ((rc = copy_theta(u, nb))) return sfail(h, rc, u->err);
     HIPCHK(hipMemsetAsync(u->dInfo.p, 0, (size_t)nb * 4, u->stream));
     if ((rc = sparse_copy_par(h, nb))) return rc;
+    std::vector<double> standin;               // (outlives the uploads: the call ends with a synchronisation of u's stream)
+    if (pw.any()) {                            // the group's rows, once: every chunk reads its slice
+        HIPCHK(h->dPwTrain.grow((size_t)2 * nb * h->N * 8));
+        HIPCHK(h->dWz.grow((size_t)h->rz_slots * h->rcap * h->es));
+        const double* src[2] = {pw.mean, pw.nugget};
+        for (int a = 0; a < 2; ++a) {
+            if (!src[a]) continue;
+            double* dst = h->dPwTrain.as<double>() + (size_t)a * nb * h->N;
+            bool all = true;
+            for (int s = 0; s < nb; ++s) all = all && pw_ok[(size_t)s];
+            if (all) { HIPCHK(hipMemcpyAsync(dst, src[a], (size_t)nb * h->N * 8, hipMemcpyHostToDevice, u->stream)); continue; }
+            standin.assign((size_t)2 * h->N, 0.0);
+            std::fill(standin.begin() + h->N, standin.end(), 1.0);
+            for (int s = 0; s < nb; ++s)
+                HIPCHK(hipMemcpyAsync(dst + (size_t)s * h->N, pw_ok[(size_t)s] ? src[a] + (size_t)s * h->N : standin.data() + (size_t)a * h->N,
+                                      (size_t)h->N * 8, hipMemcpyHostToDevice, u->stream));
+        }
+    }
     {
         SparseScope ps(ph, PH_KUU_FACTOR, u->stream);
         rc = sparse_factor(h, u, nb, true, true, "sparse GP: the factorisation of K_uu timed out (set option dataflow=0 and report)");
@@ -642,7 +739,7 @@ int sparse_group(gphip_sparse_ctx* h, const double* Theta, int nb, int p, double
     }
     // b: empty bordered workspaces; the nugget scalar of slot s is sn_s^2, its pivot tolerance relative to sn_s^2 (B >= sn_s^2 I)
     for (int s = 0; s < nb; ++s) {
-        const double sn2 = res[s].sn2, thb[3] = {1.0, 1.0, std::sqrt(sn2)};
+        const double sn2 = res[s].sb2, thb[3] = {1.0, 1.0, std::sqrt(sn2)};
         (void)stage_theta(b, s, thb);
         double* spb = b->hSlotp.as<double>() + (size_t)s * SLOTP;
         spb[1] = sn2; spb[3] = pivot_tol_rel(b) * sn2; spb[4] = 0.0; spb[SP_MFMA] = 0.0;
@@ -652,7 +749,8 @@ int sparse_group(gphip_sparse_ctx* h, const double* Theta, int nb, int p, double
     HIPCHK(hipMemsetAsync(b->dA.p, 0, (size_t)nb * b->slot_elems * h->es, u->stream));
     // partial sums per slot: [0] the trace, then one per 256 data points of every chunk for r^2, then the same for k(x_i, x_i)
     const int64_t nchunks = (h->N + rows - 1) / rows;
-    const size_t nblk = (size_t)(h->Npad / 256 + nchunks + 1), ss = 1 + 2 * nblk;
+    // (whitened: two more, for log nu_i and for w_i = 1 / nu_i, and the other two carry w)
+    const size_t nblk = (size_t)(h->Npad / 256 + nchunks + 1), ss = 1 + (pw.any() ? 4 : 2) * nblk;
     HIPCHK(h->dSum.grow((size_t)nb * ss * 8));
     double* d_r2 = h->dSum.as<double>() + 1;
     double* d_kk = d_r2 + nblk;
@@ -668,16 +766,18 @@ int sparse_group(gphip_sparse_ctx* h, const double* Theta, int nb, int p, double
             SparseScope ps(ph, PH_FORWARD, u->stream);
             sparse_queue_forward(u, mpad, nb, keep, all_factored);
         }
-        DISPATCH(h, sparse_queue_resid, h, c0, mc, mpad, d_r2 + used, nb, (long)ss);
+        if (pw.any()) DISPATCH(h, sparse_queue_resid_pw, h, pw, c0, mc, mpad, d_r2 + used, nb, (long)ss, (long)nblk);
+        else DISPATCH(h, sparse_queue_resid, h, c0, mc, mpad, d_r2 + used, nb, (long)ss);
         if (h->custom) {                       // k(x_i, x_i) per point and slot (u->dXsT still holds the chunk)
             if ((rc = queue_custom_kss(u, mc, mpad, nb))) return sfail(h, rc, u->err);
-            hipLaunchKernelGGL(sparse_blocksum_kernel, dim3((unsigned)((mpad + 255) / 256), (unsigned)nb), dim3(256), 0, u->stream,
-                               u->dKss.as<double>(), (long)mpad, (int)mc, d_kk + used, (long)ss);
+            DISPATCH(h, sparse_queue_kk, h, mc, mpad, d_kk + used, nb, (long)ss, pw.any());
         }
         used += (size_t)((mpad + 255) / 256);
         {
             SparseScope ps(ph, PH_ACCUMULATE, u->stream);
-            if ((rc = DISPATCH(h, sparse_queue_accumulate, h, mpad, nb))) return rc;
+            const bool fused = pw.any() && h->pw_fused;
+            if (pw.any() && !fused) DISPATCH(h, sparse_queue_scale_rows, h, mpad, nb);
+            if ((rc = DISPATCH(h, sparse_queue_accumulate, h, mpad, nb, fused))) return rc;
         }
     }
     // a slot without a factor of K_uu accumulated whatever its V held: B = sn^2 I in its place, so that b factors numbers
@@ -702,17 +802,20 @@ int sparse_group(gphip_sparse_ctx* h, const double* Theta, int nb, int p, double
         const double* hs = h->hSum.data() + (size_t)s * ss;
         r.logdet = b->hRes.as<double>()[2 * s]; r.ctc = b->hRes.as<double>()[2 * s + 1];
         for (size_t k = 0; k < used; ++k) r.rtr += hs[1 + k];
+        double sw = 0.0;                       // whitened: sum_i log nu_i and sum_i w_i
+        if (r.pw) for (size_t k = 0; k < used; ++k) { r.slognu += hs[1 + 2 * nblk + k]; sw += hs[1 + 3 * nblk + k]; }
         if (h->custom) for (size_t k = 0; k < used; ++k) r.skk += hs[1 + nblk + k];
-        else r.skk = (double)h->N * r.kxx;
+        else r.skk = r.pw ? sw * r.kxx : (double)h->N * r.kxx;
         r.trvv = hs[0];
-        r.F = -0.5 * ((double)h->N * LOG_TWO_PI + (double)(h->N - h->m) * std::log(r.sn2) + r.logdet + (r.rtr - r.ctc) / r.sn2) -
-              (r.skk - r.trvv) / (2.0 * r.sn2);
+        // (whitened: log det Lambda in the place of (N - m) log sn^2 -- B = I + V W V^T carries no power of sn^2 -- and sb2 = 1)
+        r.F = -0.5 * ((double)h->N * LOG_TWO_PI + (r.pw ? r.slognu : (double)(h->N - h->m) * std::log(r.sn2)) + r.logdet + (r.rtr - r.ctc) / r.sb2) -
+              (r.skk - r.trvv) / (2.0 * r.sb2);
         r.info = r.uinfo != 0 ? r.uinfo : b->hInfo.as<int>()[s];        // (a failure of u comes first)
         if (!r.ok || (r.info == 0 && !std::isfinite(r.F))) r.info = GPHIP_INFO_NAN;
         r.evaluated = true;
     }
     if (resident) {
-        const double thb[3] = {1.0, 1.0, std::sqrt(res[0].sn2)};
+        const double thb[3] = {1.0, 1.0, std::sqrt(res[0].sb2)};
         record_fit(b, res[0].info == 0, thb, 3, res[0].logdet);
     }
     return GPHIP_OK;
@@ -721,8 +824,9 @@ int sparse_group(gphip_sparse_ctx* h, const double* Theta, int nb, int p, double
 // One evaluation: the group evaluator with one slot, the fit left resident.  out, parts: the bound (null = not wanted); grad
 // (null = not wanted): the analytic gradient in theta; gradZ (null = not wanted): the analytic gradient in the inducing
 // locations, row-major m x d.
+// pw (the _pw calls; no gradient): point-dependent arrays of N values.  six: parts are the six of gphip_sparse_bound_pw.
 int sparse_eval(gphip_sparse_ctx* h, const double* theta, int p, double jitter, double* out, double* parts, int* info,
-                double* grad = nullptr, double* gradZ = nullptr) {
+                double* grad = nullptr, double* gradZ = nullptr, const SparsePw& pw = SparsePw{}, bool six = false) {
     gphip_ctx *u = h->u, *b = h->b;
     int rc = sparse_check_args(h, p, jitter);
     if (rc) return rc;
@@ -730,7 +834,7 @@ int sparse_eval(gphip_sparse_ctx* h, const double* theta, int p, double jitter, 
     auto give_up = [&](int inf) {
         *info = inf;
         if (out) *out = qnan;
-        if (parts) for (int k = 0; k < 5; ++k) parts[k] = qnan;
+        if (parts) for (int k = 0; k < (six ? 6 : 5); ++k) parts[k] = qnan;
         return GPHIP_OK;
     };
     if (grad) for (int k = 0; k < p; ++k) grad[k] = qnan;
@@ -767,12 +871,14 @@ int sparse_eval(gphip_sparse_ctx* h, const double* theta, int p, double jitter, 
     SparsePhases ph(h);
     SparseSlot r;
     // (the gradient wants B itself, before its factorisation overwrites it: the B / (2 sn^2) term of H)
-    if ((rc = sparse_group(h, theta, 1, p, jitter, rows, SparseKeep::fit, wants_grad ? &h->dBc : nullptr, ph, &r))) return rc;
+    if ((rc = sparse_group(h, theta, 1, p, jitter, rows, SparseKeep::fit, wants_grad ? &h->dBc : nullptr, pw, ph, &r))) return rc;
     if (!r.evaluated) return give_up(r.info);
-    if (parts) r.put_parts(parts);
+    if (parts && six) r.put_parts_pw(parts, h->N, h->m);
+    else if (parts) r.put_parts(parts);
     if (out) *out = r.F;
     *info = r.info;
     h->fitted = *info == 0;
+    h->pw_fit = pw.any();
     h->sn2_fit = r.sn2; h->mu_fit = r.mu; h->kxx_fit = r.kxx;
     if (wants_grad && *info == 0) {
         const SparseGradIn in{theta, r.sn2, r.mu, r.rtr, r.ctc, r.trvv, r.skk, rows, (h->N + rows - 1) / rows};
@@ -781,6 +887,23 @@ int sparse_eval(gphip_sparse_ctx* h, const double* theta, int p, double jitter, 
         if (rc && gradZ) for (int64_t k = 0; k < h->m * h->d; ++k) gradZ[k] = qnan;
     }
     return rc;
+}
+
+// m(x*) and nu(x*) of test points [m0, m0 + mc) for nb slots (pwt: rows of M values; a null array stays null) into dPwTest as
+// [2][slot][mpad], on b's stream, for sparse_predict_finish_kernel.  The noise is not read for a latent prediction.
+int sparse_stage_test_arrays(gphip_sparse_ctx* h, const SparsePw& pwt, int64_t M, int64_t m0, int64_t mc, int64_t mpad, int nb, int latent,
+                             const double** d_mean, const double** d_nug) {
+    *d_mean = *d_nug = nullptr;
+    const double* src[2] = {pwt.mean, latent ? nullptr : pwt.nugget};
+    if (!src[0] && !src[1]) return GPHIP_OK;
+    HIPCHK(h->dPwTest.grow((size_t)2 * nb * mpad * 8));
+    for (int a = 0; a < 2; ++a) {
+        if (!src[a]) continue;
+        double* dst = h->dPwTest.as<double>() + (size_t)a * nb * mpad;
+        HIPCHK(hipMemcpy2DAsync(dst, (size_t)mpad * 8, src[a] + m0, (size_t)M * 8, (size_t)mc * 8, (size_t)nb, hipMemcpyHostToDevice, h->b->stream));
+        (a == 0 ? *d_mean : *d_nug) = dst;
+    }
+    return GPHIP_OK;
 }
 
 // The group and chunk rule of the batched calls (gphip_sparse_bound_batch, gphip_sparse_predict_samples) for B rows: *G rows per
@@ -821,7 +944,9 @@ int sparse_size_groups(gphip_sparse_ctx* h, int B, int* G_out, int64_t* rows_out
 
 // gphip_sparse_bound_batch (DESIGN.md section 8f): the bound for the B rows of Theta, one theta per workspace slot, the group
 // evaluator on group after group.  No fit is left resident; a row that fails has only its own info / out to show for it.
-int sparse_eval_batch(gphip_sparse_ctx* h, const double* Theta, int B, int p, double jitter, double* out, double* parts, int* info) {
+// pw: B x N point-dependent arrays, row s for row s of Theta.  six: parts are B x 6, those of gphip_sparse_bound_pw.
+int sparse_eval_batch(gphip_sparse_ctx* h, const double* Theta, int B, int p, double jitter, double* out, double* parts, int* info,
+                      const SparsePw& pw = SparsePw{}, bool six = false) {
     const double qnan = std::nan("");
     h->fitted = false;
     sparse_reset_phases(h, PH_KUU_FACTOR, PH_JOINT_V);
@@ -835,15 +960,18 @@ int sparse_eval_batch(gphip_sparse_ctx* h, const double* Theta, int B, int p, do
     for (int s0 = 0; s0 < B; s0 += G) {
         const int nb = std::min(G, B - s0);
         h->last_slots = nb;
-        if ((rc = sparse_group(h, Theta + (size_t)s0 * p, nb, p, jitter, rows, SparseKeep::nothing, nullptr, ph, res.data()))) return rc;
+        if ((rc = sparse_group(h, Theta + (size_t)s0 * p, nb, p, jitter, rows, SparseKeep::nothing, nullptr, pw.rows_from(s0, h->N), ph, res.data())))
+            return rc;
+        const int np = six ? 6 : 5;
         for (int s = 0; s < nb; ++s) {
             const SparseSlot& r = res[(size_t)s];
             info[s0 + s] = r.info;
             out[s0 + s] = r.info == 0 ? r.F : qnan;
             if (parts) {
-                double* ps = parts + (size_t)(s0 + s) * 5;
-                r.put_parts(ps);
-                if (r.info != 0) for (int k = 0; k < 5; ++k) ps[k] = qnan;
+                double* ps = parts + (size_t)(s0 + s) * np;
+                if (six) r.put_parts_pw(ps, h->N, h->m);
+                else r.put_parts(ps);
+                if (r.info != 0) for (int k = 0; k < np; ++k) ps[k] = qnan;
             }
         }
         ph.harvest();                          // (group by group: the events go back to the pool for the next one)
@@ -859,8 +987,9 @@ int sparse_eval_batch(gphip_sparse_ctx* h, const double* Theta, int B, int p, do
 //   b   (after an event of u's stream) the forward substitution of all slots, predict_partial_kernel, the finishing kernel
 // and one download per chunk.  A launch that spin-waits (the dataflow substitution) runs on a context only when every slot of
 // the group has a factor there: a slot whose factorisation was abandoned has no block inverses to hand to the launch's chain.
+// pw: S x N training arrays; pwt: S x M arrays of m(x*) and nu(x*), which take the place of mu and sn^2 in the finishing kernel.
 int sparse_predict_samples(gphip_sparse_ctx* h, const double* Thetas, int S, int p, double jitter, const double* X, int64_t M, int latent,
-                           double* mean, double* var, double* bound, int* info) {
+                           double* mean, double* var, double* bound, int* info, const SparsePw& pw = SparsePw{}, const SparsePw& pwt = SparsePw{}) {
     gphip_ctx *u = h->u, *b = h->b;
     const double qnan = std::nan("");
     h->fitted = false;
@@ -894,7 +1023,8 @@ int sparse_predict_samples(gphip_sparse_ctx* h, const double* Thetas, int S, int
     for (int s0 = 0; s0 < S; s0 += G) {
         const int nb = std::min(G, S - s0);
         h->last_slots = nb;
-        if ((rc = sparse_group(h, Thetas + (size_t)s0 * p, nb, p, jitter, rows, SparseKeep::group, nullptr, ph, res.data()))) return rc;
+        if ((rc = sparse_group(h, Thetas + (size_t)s0 * p, nb, p, jitter, rows, SparseKeep::group, nullptr, pw.rows_from(s0, h->N), ph, res.data())))
+            return rc;
         bool u_factored = true, b_factored = true;
         for (int s = 0; s < nb; ++s) {
             const SparseSlot& r = res[(size_t)s];
@@ -935,10 +1065,12 @@ int sparse_predict_samples(gphip_sparse_ctx* h, const double* Thetas, int S, int
             {
                 SparseScope ps(ph, PH_SAMPLES_REDUCE, b->stream);
                 if ((rc = DISPATCH(b, sparse_queue_partial, b, mpad, &ns2, nb))) return sfail(h, rc, b->err);
+                const double *d_mt = nullptr, *d_nt = nullptr;
+                if ((rc = sparse_stage_test_arrays(h, pwt.rows_from(s0, M), M, m0, mc, mpad, nb, latent, &d_mt, &d_nt))) return rc;
                 hipLaunchKernelGGL(sparse_predict_finish_kernel, dim3((unsigned)((mc + 255) / 256), (unsigned)nb), dim3(256), 0, b->stream,
                                    u->dPart.as<double>() + p1_off, ns1, p1_sstride, (long)ns1 * p1_sstride, b->dPart.as<double>(), ns2,
                                    (long)mpad, (int)mc, h->dPar.as<double>(), h->custom ? u->dKss.as<double>() : nullptr, latent ? 1 : 0,
-                                   b->dMean.as<double>(), b->dVar.as<double>());
+                                   d_mt, d_nt, b->dMean.as<double>(), b->dVar.as<double>());
             }
             hm.resize((size_t)nb * mpad);
             hv.resize((size_t)nb * mpad);
@@ -1007,6 +1139,7 @@ int sparse_joint_dim_check(gphip_sparse_ctx* h, int64_t M) {
 
 int sparse_joint_state_check(gphip_sparse_ctx* h) {
     if (!h->fitted || !has_fit(h->u) || !has_fit(h->b)) return sfail(h, GPHIP_ERR_STATE, "joint prediction before a successful gphip_sparse_fit");
+    if (h->pw_fit) return sfail(h, GPHIP_ERR_UNSUPPORTED, "no joint prediction after a fit with a point-dependent mean or noise");
     return GPHIP_OK;
 }
 
@@ -1150,6 +1283,30 @@ int gphip_sparse_bound_batch(gphip_sparse_handle h, const double* Theta, int B, 
     return sparse_eval_batch(h, Theta, B, p, jitter, out, parts, info);
 }
 
+int gphip_sparse_bound_pw(gphip_sparse_handle h, const double* theta, int p, double jitter, const double* mean_train,
+                          const double* nugget_train, double* out, double* parts, int* info) {
+    if (!h || !theta || !out || !info) return sfail(h, GPHIP_ERR_ARG, "null argument");
+    std::lock_guard<std::recursive_mutex> lk(h->mu);
+    // (no array: the constant call itself -- the same bytes in out and info -- with its five parts converted on the host)
+    return sparse_eval(h, theta, p, jitter, out, parts, info, nullptr, nullptr, SparsePw{mean_train, nugget_train}, true);
+}
+
+int gphip_sparse_bound_batch_pw(gphip_sparse_handle h, const double* Theta, int B, int p, double jitter, const double* mean_train,
+                                const double* nugget_train, double* out, double* parts, int* info) {
+    if (!h || !Theta || !out || !info) return sfail(h, GPHIP_ERR_ARG, "null argument");
+    std::lock_guard<std::recursive_mutex> lk(h->mu);
+    if (const int rc = sparse_check_args(h, p, jitter)) return rc;
+    if (B <= 0) return GPHIP_OK;
+    return sparse_eval_batch(h, Theta, B, p, jitter, out, parts, info, SparsePw{mean_train, nugget_train}, true);
+}
+
+int gphip_sparse_fit_pw(gphip_sparse_handle h, const double* theta, int p, double jitter, const double* mean_train, const double* nugget_train,
+                        int* info) {
+    if (!h || !theta || !info) return sfail(h, GPHIP_ERR_ARG, "null argument");
+    std::lock_guard<std::recursive_mutex> lk(h->mu);
+    return sparse_eval(h, theta, p, jitter, nullptr, nullptr, info, nullptr, nullptr, SparsePw{mean_train, nugget_train});
+}
+
 int gphip_sparse_nested_sampling(gphip_sparse_handle h, double jitter, const double* box, const int* prior_kind, gphip_logprior_fn logprior,
                                  void* user, const gphip_ns_options* opts, const double* start, int64_t cap, double* points, double* loglik,
                                  double* logprior_out, double* accept_rate, int64_t* n_samples, double* log_evidence, int64_t* n_evals) {
@@ -1228,6 +1385,11 @@ int gphip_sparse_fit(gphip_sparse_handle h, const double* theta, int p, double j
 }
 
 int gphip_sparse_predict(gphip_sparse_handle h, const void* Xs, int64_t M, int latent, double* mean, double* var) {
+    return gphip_sparse_predict_pw(h, Xs, M, latent, nullptr, nullptr, mean, var);
+}
+
+int gphip_sparse_predict_pw(gphip_sparse_handle h, const void* Xs, int64_t M, int latent, const double* mean_test, const double* nugget_test,
+                            double* mean, double* var) {
     if (!h || !Xs || !mean || !var) return sfail(h, GPHIP_ERR_ARG, "null argument");
     if (M < 1) return sfail(h, GPHIP_ERR_DIM, "M < 1");
     std::lock_guard<std::recursive_mutex> lk(h->mu);
@@ -1254,10 +1416,12 @@ int gphip_sparse_predict(gphip_sparse_handle h, const void* Xs, int64_t M, int l
         HIPCHK(hipMemcpyAsync(b->dV.p, u->dV.p, (size_t)mpad * u->Npad * h->es, hipMemcpyDeviceToDevice, b->stream));
         queue_forward_fit(b, mpad);
         if ((rc = DISPATCH(b, sparse_queue_partial, b, mpad, &ns2))) return sfail(h, rc, b->err);
-        // (one slot of the finishing kernel: u's norm rows; mu, sn^2 and k(x, x) of the fit are slot 0 of dPar since the evaluation)
+        const double *d_mt = nullptr, *d_nt = nullptr;
+        if ((rc = sparse_stage_test_arrays(h, SparsePw{mean_test, nugget_test}, M, m0, mc, mpad, 1, latent, &d_mt, &d_nt))) return rc;
+        // (one slot of the finishing kernel: u's norm rows; mu, B's sn^2, k(x, x) and the noise of the fit are slot 0 of dPar since the evaluation)
         hipLaunchKernelGGL(sparse_predict_finish_kernel, dim3((unsigned)((mc + 255) / 256), 1u), dim3(256), 0, b->stream,
                            u->dPart.as<double>() + mpad, ns1, 2l * mpad, 0l, b->dPart.as<double>(), ns2, (long)mpad, (int)mc,
-                           h->dPar.as<double>(), h->custom ? u->dKss.as<double>() : nullptr, latent ? 1 : 0, b->dMean.as<double>(),
+                           h->dPar.as<double>(), h->custom ? u->dKss.as<double>() : nullptr, latent ? 1 : 0, d_mt, d_nt, b->dMean.as<double>(),
                            b->dVar.as<double>());
         HIPCHK(hipMemcpyAsync(mean + m0, b->dMean.p, (size_t)mc * 8, hipMemcpyDeviceToHost, b->stream));
         HIPCHK(hipMemcpyAsync(var + m0, b->dVar.p, (size_t)mc * 8, hipMemcpyDeviceToHost, b->stream));
@@ -1273,6 +1437,17 @@ int gphip_sparse_predict_samples(gphip_sparse_handle h, const double* Thetas, in
     if (const int rc = sparse_check_args(h, p, jitter)) return rc;
     if (S < 1 || M < 1) return sfail(h, GPHIP_ERR_DIM, "S < 1 or M < 1");
     return sparse_predict_samples(h, Thetas, S, p, jitter, static_cast<const double*>(Xs), M, latent, mean, var, bound, info);
+}
+
+int gphip_sparse_predict_samples_pw(gphip_sparse_handle h, const double* Thetas, int S, int p, double jitter, const double* mean_train,
+                                    const double* nugget_train, const void* Xs, int64_t M, int latent, const double* mean_test,
+                                    const double* nugget_test, double* mean, double* var, double* bound, int* info) {
+    if (!h || !Thetas || !Xs || !mean || !var || !info) return sfail(h, GPHIP_ERR_ARG, "null argument");
+    std::lock_guard<std::recursive_mutex> lk(h->mu);
+    if (const int rc = sparse_check_args(h, p, jitter)) return rc;
+    if (S < 1 || M < 1) return sfail(h, GPHIP_ERR_DIM, "S < 1 or M < 1");
+    return sparse_predict_samples(h, Thetas, S, p, jitter, static_cast<const double*>(Xs), M, latent, mean, var, bound, info,
+                                  SparsePw{mean_train, nugget_train}, SparsePw{mean_test, nugget_test});
 }
 
 int gphip_sparse_predict_cov(gphip_sparse_handle h, const void* Xs, int64_t M, int latent, double* mean, double* cov) {
@@ -1330,6 +1505,7 @@ int gphip_sparse_set_option(gphip_sparse_handle h, const char* name, double valu
     if (!strcmp(name, "sparse_batch_slots")) { if (v < 0) return sfail(h, GPHIP_ERR_ARG, "sparse_batch_slots < 0"); h->batch_slots = v; return GPHIP_OK; }
     if (!strcmp(name, "sparse_samples_chunk")) { if (v < 0) return sfail(h, GPHIP_ERR_ARG, "sparse_samples_chunk < 0"); h->samples_chunk = v; return GPHIP_OK; }
     if (!strcmp(name, "sparse_samples_handover")) { h->samples_handover = v != 0; return GPHIP_OK; }
+    if (!strcmp(name, "sparse_pw_fused")) { h->pw_fused = v != 0; return GPHIP_OK; }
     int rc = gphip_set_option(h->u, name, value);
     if (!rc) rc = gphip_set_option(h->b, name, value);
     if (rc) return sfail(h, rc, "unknown option");
@@ -1357,6 +1533,7 @@ int gphip_sparse_get_option(gphip_sparse_handle h, const char* name, double* val
     if (!strcmp(name, "sparse_samples_chunk")) { *value = h->samples_chunk; return GPHIP_OK; }
     if (!strcmp(name, "last_sparse_samples_chunk")) { *value = (double)h->last_samples_chunk; return GPHIP_OK; }
     if (!strcmp(name, "sparse_samples_handover")) { *value = h->samples_handover; return GPHIP_OK; }
+    if (!strcmp(name, "sparse_pw_fused")) { *value = h->pw_fused; return GPHIP_OK; }
     if (!strcmp(name, "sparse_joint_split")) { *value = h->joint_split; return GPHIP_OK; }
     if (!strcmp(name, "last_sparse_joint_nsplit")) { *value = h->joint_nsplit; return GPHIP_OK; }
     const int rc = gphip_get_option(h->u, name, value);

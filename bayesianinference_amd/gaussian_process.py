@@ -820,10 +820,15 @@ def selectInducingPoints(X, m: int, seed: int = 0):
     return X[idx[:m]].copy()
 
 
-def make_sparse_log_likelihood(handle: "_lib.SparseHandle", jitter: float = -1.0):
+def make_sparse_log_likelihood(handle: "_lib.SparseHandle", jitter: float = -1.0, nugget_fn=None, mean_fn=None, X=None):
     """The closure for "LogLikelihoodFunction" of a sparse object: theta -> F(theta), the collapsed lower bound on the log
     marginal likelihood; $MachineLogZero on numerical failure (info != 0), B x p -> B for a batch, like make_log_likelihood.
-    A batch is ONE device call (SparseHandle.bound_batch), so every Metropolis step of nestedSampling is one call."""
+    A batch is ONE device call (SparseHandle.bound_batch), so every Metropolis step of nestedSampling is one call.
+    nugget_fn / mean_fn: point-dependent nugget[x] / meanFunction[x] (callables f(X, theta) -> values[N], as
+    make_log_likelihood takes them), evaluated here on the host for every theta; a 1-D or 2-D theta then is one
+    SparseHandle.bound_batch_pw call."""
+    pw = nugget_fn is not None or mean_fn is not None
+
     def one(theta):
         val, info = handle.bound(theta, jitter)
         if info != 0 or not math.isfinite(val):
@@ -832,13 +837,17 @@ def make_sparse_log_likelihood(handle: "_lib.SparseHandle", jitter: float = -1.0
 
     def log_likelihood(theta):
         theta = np.asarray(theta, dtype=np.float64)
-        if theta.ndim == 2:
-            if theta.shape[0] == 0:
+        if theta.ndim == 2 or pw:
+            if theta.ndim == 2 and theta.shape[0] == 0:
                 return np.zeros(0, dtype=np.float64)
-            val, info = handle.bound_batch(theta, jitter)
+            if pw:
+                val, info = handle.bound_batch_pw(theta, jitter, _pointwise(mean_fn, X, theta), _pointwise(nugget_fn, X, theta))
+            else:
+                val, info = handle.bound_batch(theta, jitter)
             val = np.asarray(val, dtype=np.float64)
             bad = (np.asarray(info) != 0) | ~np.isfinite(val)
-            return np.where(bad, MACHINE_LOG_ZERO, np.clip(np.where(bad, 0.0, val), MACHINE_LOG_ZERO, -MACHINE_LOG_ZERO))
+            res = np.where(bad, MACHINE_LOG_ZERO, np.clip(np.where(bad, 0.0, val), MACHINE_LOG_ZERO, -MACHINE_LOG_ZERO))
+            return res if theta.ndim == 2 else float(res[0])
         return one(theta)
     return log_likelihood
 
@@ -846,14 +855,16 @@ def make_sparse_log_likelihood(handle: "_lib.SparseHandle", jitter: float = -1.0
 def defineSparseGaussianProcess(data, kernel, inducing, nugget="Constant", meanFunction=None, variables=(),
                                 variablePrior="Uniform", **rules) -> inferenceObject:
     """defineGaussianProcess for a sparse inducing-point GP: `inducing` = an int m (-> selectInducingPoints(X, m)) or an array
-    [m, d]; the other arguments, parameter specs, priors and pre-processors are defineGaussianProcess's (constant nugget, zero or
-    constant mean).  Extra rules: Jitter (default -1: the library's), Device, Precision, Seed (of the inducing-point choice).
+    [m, d]; the other arguments, parameter specs, priors and pre-processors are defineGaussianProcess's: nugget = "Constant" or
+    a callable f(X, theta) -> variances[N], meanFunction = None / 0, "Constant" or a callable f(X, theta) -> means[N] (the
+    handle then has the zero mean).  Extra rules: Jitter (default -1: the library's), Device, Precision, Seed (of the inducing-point choice).
     "LogLikelihoodFunction" of the returned object is the collapsed bound F(theta) <= log p(y | X, theta), so nestedSampling,
     laplace.selectHyperparameters(Criterion="MarginalLikelihood") and approximateEvidence run on it unchanged.
     "LogLikelihoodGradientFunction" returns (F, dF/dtheta) from the device's analytic gradient (gphip_sparse_bound_grad: one
     evaluation plus one more pass over the data, the jitter held fixed); rule Gradient="Differences" keeps the difference
     quotient instead: central differences of F with the step eps^(1/3) max(|theta_k|, 1e-2), 2p + 1 evaluations of the bound.
-    Also carries "InducingPoints" and "Jitter"; no leave-one-out keys."""
+    With a callable nugget or mean it is always the difference quotient (the library cannot differentiate a host function of
+    the point).  Also carries "InducingPoints" and "Jitter"; no leave-one-out keys."""
     if normalizedDataQ(data) and isinstance(data, Mapping) and "Input" in data:
         rules.setdefault("DataPreProcessors", {k: {"Function": v["Function"], "InverseFunction": v["InverseFunction"]}
                                                for k, v in data.items()})
@@ -864,16 +875,19 @@ def defineSparseGaussianProcess(data, kernel, inducing, nugget="Constant", meanF
     X, Y = norm
     if Y.shape[1] != 1 or len(X) != len(Y):
         return inferenceObject(None)
-    if not (isinstance(nugget, str) and nugget.lower() == "constant"):
-        raise ValueError('a sparse GP takes the constant nugget only (nugget="Constant")')
-    if callable(meanFunction):
-        raise ValueError("a sparse GP takes the zero or the constant mean only")
+    if isinstance(nugget, str) and nugget.lower() != "constant":
+        raise ValueError('nugget must be "Constant" (Function[sn^2]) or a callable f(X, theta) -> variances[N]')
+    if not (isinstance(nugget, str) or callable(nugget)):
+        raise ValueError('nugget must be "Constant" (Function[sn^2]) or a callable f(X, theta) -> variances[N]')
+    nugget_fn = nugget if callable(nugget) else None
+    mean_fn = meanFunction if callable(meanFunction) else None
+    pointwise = nugget_fn is not None or mean_fn is not None
     kname = _resolve_kernel(kernel)
     if isinstance(kname, str) and kname == "null":
         raise ValueError("a sparse GP needs a covariance function (the null kernel has nothing to approximate)")
-    mean = "zero" if meanFunction in (None, 0, "Zero", "zero") else "const"
+    mean = "zero" if (mean_fn is not None or meanFunction in (None, 0, "Zero", "zero")) else "const"
     if mean == "const" and str(meanFunction).lower() not in ("constant", "const"):
-        raise ValueError("meanFunction must be None/0 or 'Constant'")
+        raise ValueError("meanFunction must be None/0, 'Constant' or a callable f(X, theta) -> means[N]")
     params = [tuple(v) for v in variables]
     if not params or any(len(v) != 3 for v in params):
         return inferenceObject(None)
@@ -892,13 +906,15 @@ def defineSparseGaussianProcess(data, kernel, inducing, nugget="Constant", meanF
         Z = np.atleast_2d(np.asarray(inducing, dtype=np.float64))
         if Z.ndim != 2 or Z.shape[1] != X.shape[1] or len(Z) < 1:
             return inferenceObject(None)
+    # the number of hyper-parameters is host logic (the kernel grammar / the CustomKernel, + sigma_n [+ mu]): a wrong count is
+    # refused before any device is touched
+    need = _lib.num_params(kname, X.shape[1], mean)
+    if need != len(params):
+        raise ValueError(f"kernel {kname!r} with mean {mean!r} on d={X.shape[1]} needs {need} "
+                         f"hyper-parameters (l.., sigma_f, sigma_n[, mu]); got {len(params)}")
     handle = _lib.SparseHandle(X, Y[:, 0], Z, kname, mean, dtype=64 if precision == "double" else 32,
                                device=device)                     # raises loudly without the library / GPU
-    if handle.p != len(params):
-        handle.close()
-        raise ValueError(f"kernel {kname!r} with mean {mean!r} on d={X.shape[1]} needs {handle.p} "
-                         f"hyper-parameters (l.., sigma_f, sigma_n[, mu]); got {len(params)}")
-    loglik = make_sparse_log_likelihood(handle, jitter)
+    loglik = make_sparse_log_likelihood(handle, jitter, nugget_fn, mean_fn, X)
 
     def log_likelihood_gradient(theta):
         """(F, dF/dtheta) from the device (gphip_sparse_bound_grad; F is the value "LogLikelihoodFunction" returns); sentinel and
@@ -938,13 +954,14 @@ def defineSparseGaussianProcess(data, kernel, inducing, nugget="Constant", meanF
             "ModelFunctions": {
                 "KernelFunction": ((kname.name, kname.body) if isinstance(kname, _lib.CustomKernel)
                                    else (kname, wl_kernel_expression(kname))),
-                "NuggetFunction": WL_NUGGET_EXPRESSION,
-                "MeanFunction": mean,
+                "NuggetFunction": nugget_fn if nugget_fn is not None else WL_NUGGET_EXPRESSION,
+                "MeanFunction": mean_fn if mean_fn is not None else mean,
             },
             "HIPHandle": handle,
         },
         **rules,
-        "LogLikelihoodGradientFunction": log_likelihood_gradient if gradient == "analytic" else log_likelihood_gradient_differences,
+        "LogLikelihoodGradientFunction": (log_likelihood_gradient if gradient == "analytic" and not pointwise
+                                          else log_likelihood_gradient_differences),
         "LogLikelihoodFunction": loglik,
     })
 
@@ -1012,6 +1029,13 @@ def optimizeInducingPoints(obj, theta, Joint: bool = False, MaxIterations: int =
                                                 "Evaluations": count[0], "Message": msg}})
 
 
+def _sparse_pointwise_functions(obj):
+    """(nugget_fn, mean_fn) of a sparse object: its callables, None where the object has the constant form"""
+    mf = obj["SparseGaussianProcessData"]["ModelFunctions"]
+    return (mf["NuggetFunction"] if callable(mf["NuggetFunction"]) else None,
+            mf["MeanFunction"] if callable(mf["MeanFunction"]) else None)
+
+
 def predictFromSparseGaussianProcess(obj, pts, theta=None):
     """Prediction from a sparse object: for one theta, or (theta=None) the posterior mixture of a sampled object -- one Normal
     per posterior sample, mixed with the CrudePosteriorWeights.  Returns the dict of predictFromGaussianProcess: "Points" [M,d],
@@ -1030,17 +1054,27 @@ def predictFromSparseGaussianProcess(obj, pts, theta=None):
     if P is None or isinstance(P, tuple):
         return None
     handle = obj["SparseGaussianProcessData"]["HIPHandle"]
+    nugget_fn, mean_fn = _sparse_pointwise_functions(obj)
+    pw = nugget_fn is not None or mean_fn is not None
     if theta is not None:
         points, weights = np.atleast_2d(np.asarray(theta, dtype=np.float64)), np.ones(1)
         mean = np.full((len(points), len(P)), np.nan)
         var = np.full((len(points), len(P)), np.nan)
         for s, th in enumerate(points):
-            if handle.fit(th, obj["Jitter"]) == 0:
+            if pw:                                                # the functions at the training and at the test points
+                if handle.fit_pw(th, obj["Jitter"], _pointwise(mean_fn, X, th), _pointwise(nugget_fn, X, th)) == 0:
+                    mean[s], var[s] = handle.predict_pw(P, False, _pointwise(mean_fn, P, th), _pointwise(nugget_fn, P, th))
+            elif handle.fit(th, obj["Jitter"]) == 0:
                 mean[s], var[s] = handle.predict(P)
     elif "Samples" in obj:
         points = np.array([s["Point"] for s in obj["Samples"]], dtype=np.float64)
         weights = np.array([s["CrudePosteriorWeight"] for s in obj["Samples"]], dtype=np.float64)
-        mean, var, info = handle.predict_samples(points, P, obj["Jitter"])
+        if pw:
+            mean, var, info = handle.predict_samples_pw(points, P, obj["Jitter"], False, _pointwise(mean_fn, X, points),
+                                                        _pointwise(nugget_fn, X, points), _pointwise(mean_fn, P, points),
+                                                        _pointwise(nugget_fn, P, points))
+        else:
+            mean, var, info = handle.predict_samples(points, P, obj["Jitter"])
         mean[info != 0] = np.nan
         var[info != 0] = np.nan
     else:
@@ -1060,6 +1094,8 @@ def predictJointFromSparseGaussianProcess(obj, pts, theta):
     P = dataNormalForm(pts)
     if P is None or isinstance(P, tuple):
         return None
+    if any(f is not None for f in _sparse_pointwise_functions(obj)):
+        raise ValueError("no joint prediction from a sparse GP object with a point-dependent nugget or mean function")
     _, first = np.unique(P, axis=0, return_index=True)
     P = P[np.sort(first)]
     handle = obj["SparseGaussianProcessData"]["HIPHandle"]
@@ -1081,6 +1117,8 @@ def sparsePredictiveLogDensity(obj, heldout, theta):
     ys = np.asarray(heldout[1], dtype=np.float64).ravel()
     if ys.shape != (len(P),):
         return None
+    if any(f is not None for f in _sparse_pointwise_functions(obj)):
+        raise ValueError("no joint predictive density from a sparse GP object with a point-dependent nugget or mean function")
     handle = obj["SparseGaussianProcessData"]["HIPHandle"]
     if handle.fit(np.asarray(theta, dtype=np.float64).ravel(), obj["Jitter"]) != 0:
         return None

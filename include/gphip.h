@@ -470,7 +470,8 @@ int gphip_factor_bytes(gphip_handle h, int member, double* bytes);
  *     mean = m(x*) + v2^T c            var = k(x*, x*) [+ sn^2 unless latent] - |v1|^2 + sn^2 |v2|^2
  *
  * A separate opaque type: no other entry point of this header takes a sparse object.  Every named and composed kernel and the
- * run-time compiled ones (gphip_sparse_create_custom: arguments as gphip_create_custom), zero and constant mean, fp64 and fp32;
+ * run-time compiled ones (gphip_sparse_create_custom: arguments as gphip_create_custom), zero and constant mean (a mean and a
+ * noise that depend on the point: the _pw calls below), fp64 and fp32;
  * one device.  m > N is allowed.  Statuses, all decided before any device work: NULL arguments GPHIP_ERR_ARG; N < 1, d < 1,
  * m < 1, m > GPHIP_SPARSE_MAX_M, wrong p GPHIP_ERR_DIM; the null kernel GPHIP_ERR_UNSUPPORTED, unknown ids GPHIP_ERR_ARG;
  * gphip_sparse_predict before a successful fit GPHIP_ERR_STATE; non-finite jitter GPHIP_ERR_ARG.  Non-finite theta is
@@ -582,6 +583,32 @@ int gphip_factor_bytes(gphip_handle h, int member, double* bytes);
  * the rows of every output bit for bit while the group sizes stay the same.  Against fit + predict of the same theta a row differs
  * by rounding (the factorisations of several slots take another schedule).  One device.
  *
+ * gphip_sparse_bound_pw / _bound_batch_pw / _fit_pw / _predict_pw / _predict_samples_pw: the calls above for a noise variance and a
+ * mean that are functions of the point (the reference's nugget[x] and meanFunction[x]; the conventions of gphip_loglik_batch_pw).
+ * mean_train / nugget_train: fp64 host arrays of the values at the N training points (the batched calls: row-major B x N / S x N,
+ * row s for row s of Theta), read during the call only; nugget values are VARIANCES nu_i.  theta keeps its layout; the entries an
+ * array replaces are not used.  A NULL array keeps the constant read from theta (sn^2; mu or 0), broadcast.  The jitter rule is
+ * unchanged.  With Lambda = diag(nu), r = y - m:
+ *     B = I + V Lambda^-1 V^T = L_B L_B^T,   c = L_B^-1 V Lambda^-1 r
+ *     F = -1/2 [N log 2 pi + sum_i log nu_i + log det B + r^T Lambda^-1 r - c^T c] - 1/2 sum_i (k(x_i, x_i) - |v_i|^2) / nu_i
+ * -- the model above with sn^2 = 1 on data whitened by 1 / nu_i; with nu_i = sn^2 it is that model (B there = sn^2 B here).
+ * parts (NULL or 6 doubles; batch: B x 6) = {log det B, c^T c, r^T Lambda^-1 r, tr(V Lambda^-1 V^T), sum_i k(x_i, x_i) / nu_i,
+ * sum_i log nu_i} with this B.  With both training arrays NULL the call IS the constant one: out and info are the same bytes, and
+ * the six parts are its five converted on the host.  A row whose mean array holds a non-finite value, or whose noise array a value
+ * that is non-finite or <= 0, gets info GPHIP_INFO_NAN and NaN outputs like a non-finite theta; it disturbs no other row of a batch.
+ * The weights 1 / nu_i enter the accumulation either inside its kernel (a weight per contraction index ahead of the MFMA) or
+ * through a scaling pass ahead of it (option "sparse_pw_fused"); every sum runs in
+ * a fixed order without atomics: two calls return the same bytes, and permuting rows and arrays of a batch permutes the outputs
+ * bit for bit while the group sizes stay the same.
+ * gphip_sparse_predict_pw: mean_test / nugget_test (NULL or M values) are m(x*) and nu(x*) at the test points: mean = m(x*) + v2^T c,
+ * var = k(x*, x*) [+ nu(x*) unless latent] - |v1|^2 + s |v2|^2, s = 1 after a _pw fit with an array and sn^2 otherwise.  It works
+ * after any successful fit; nugget_test is not read when latent = 1.  gphip_sparse_predict after a _pw fit uses theta's sn^2 and mu
+ * at the test points, as gphip_predict does after gphip_fit_pw.  gphip_sparse_predict_samples_pw: training arrays S x N, test
+ * arrays S x M, any of them NULL.  gphip_sparse_predict_cov / _draws / _logpdf after a fit made with a non-NULL training array
+ * return GPHIP_ERR_UNSUPPORTED, as the exact joint calls do.  Statuses before any device work are those of the calls they extend.
+ * There is no _pw form of the gradients or of the native sampler: the library cannot differentiate or call a host function of the
+ * point.
+ *
  * Options (gphip_sparse_set_option / gphip_sparse_get_option):
  *   "sparse_chunk"  data points per pass over V (rounded up to 128); 0 (default) = as many as keep the chunk of V within ~8 GiB,
  *                   at least 2048, halved while it does not fit.  "last_sparse_chunk" (read-only): what the last call used.
@@ -597,6 +624,11 @@ int gphip_factor_bytes(gphip_handle h, int member, double* bytes);
  *   "sparse_samples_handover"  1 (default): V1 reaches the context of B through sparse_handover_kernel (one read, one write, the
  *                   norms on the way); 0: through a device-to-device copy and a separate norm launch, the form it replaced (kept
  *                   for measurement, scripts/gpu_sparse_samples_time.py).
+ *   "sparse_pw_fused"  how the _pw calls apply the weights 1 / nu_i.  1: inside the accumulation kernel, a weight per contraction
+ *                   index ahead of the MFMA; 0 (default): a plain kernel scales the chunk of V and the residual row by
+ *                   sqrt(1 / nu_i) in place and the unweighted accumulation follows.  The fused form is the faster one at four of the
+ *                   five measured sizes and the slower one at (N, m) = (262144, 2048), which decides the default (DESIGN.md section
+ *                   8i, scripts/gpu_sparse_pw_time.py); the two agree to rounding.
  *   "profile"       0 / 1: time the phases of gphip_sparse_bound / _fit with HIP events; read-only milliseconds of the last call:
  *                   "ms_kuu_factor", "ms_cross", "ms_forward", "ms_accumulate", "ms_b_factor"; of gphip_sparse_bound_grad also
  *                   "ms_grad_small" (the m x m work and the vector w), "ms_grad_weights" (sparse_weight_kernel alone),
@@ -636,6 +668,20 @@ int gphip_sparse_predict(gphip_sparse_handle h, const void* Xs, int64_t M, int l
 int gphip_sparse_predict_samples(gphip_sparse_handle h, const double* Thetas, int S, int p, double jitter, const void* Xs, int64_t M,
                                  int latent, double* mean /* S x M */, double* var /* S x M */, double* bound /* NULL or S */,
                                  int* info /* S */);
+int gphip_sparse_bound_pw(gphip_sparse_handle h, const double* theta, int p, double jitter, const double* mean_train /* N or NULL */,
+                          const double* nugget_train /* N or NULL */, double* out, double* parts /* NULL or 6 */, int* info);
+int gphip_sparse_bound_batch_pw(gphip_sparse_handle h, const double* Theta, int B, int p, double jitter,
+                                const double* mean_train /* B x N or NULL */, const double* nugget_train /* B x N or NULL */,
+                                double* out /* B */, double* parts /* NULL or B x 6 */, int* info /* B */);
+int gphip_sparse_fit_pw(gphip_sparse_handle h, const double* theta, int p, double jitter, const double* mean_train,
+                        const double* nugget_train, int* info);
+int gphip_sparse_predict_pw(gphip_sparse_handle h, const void* Xs, int64_t M, int latent, const double* mean_test /* M or NULL */,
+                            const double* nugget_test /* M or NULL */, double* mean, double* var);
+int gphip_sparse_predict_samples_pw(gphip_sparse_handle h, const double* Thetas, int S, int p, double jitter,
+                                    const double* mean_train /* S x N or NULL */, const double* nugget_train /* S x N or NULL */,
+                                    const void* Xs, int64_t M, int latent, const double* mean_test /* S x M or NULL */,
+                                    const double* nugget_test /* S x M or NULL */, double* mean /* S x M */, double* var /* S x M */,
+                                    double* bound /* NULL or S */, int* info /* S */);
 int gphip_sparse_predict_cov(gphip_sparse_handle h, const void* Xs, int64_t M, int latent, double* mean /* M */, double* cov /* M x M */);
 int gphip_sparse_predict_draws(gphip_sparse_handle h, const void* Xs, int64_t M, int latent, int S, uint64_t seed,
                                const double* z /* NULL or S x M */, double jitter, double* out /* S x M */, int* info);
