@@ -1727,6 +1727,16 @@ bool queue_forward_fit(gphip_ctx* h, int64_t mpad) {
     return df;
 }
 
+// The forward substitution of the mpad rows of nb slots in dV.  resident: slot 0 with the fitted factor's route above.  Else the
+// slots were factored by this call with their 128-block inverses: ONE dataflow launch (slot = its last grid index) where
+// samples_forward_df takes it and all_factored says that every slot has a factor (a slot whose factorisation was abandoned has no
+// block inverses to hand to the launch's chain of waits), else the batched GEMM substitution, which has no waits.
+void queue_forward_slots(gphip_ctx* h, int64_t mpad, int nb, bool resident, bool all_factored) {
+    if (resident) queue_forward_fit(h, mpad);
+    else if (all_factored && samples_forward_df(h, nb, mpad)) launch_dataflow_inverse<double, 64>(h, mpad, false, nb, h->dW64s.p);
+    else DISPATCH(h, queue_forward_rows, h, mpad, nb);
+}
+
 // V <- V L^-1 (backward substitution, block columns from last to first), "NN" GEMM role:
 //   X_b = Y_b W_b ;  Y_c -= X_b L(b,c) for c < b.   Two-level as above.  rows: the mpad x Npad block to work on (null: dV).
 // Ld / res given: every diagonal solve is REFINED once in the working precision, X_b += (Y_b - X_b L_bb) W_b.  A product with
@@ -1862,20 +1872,39 @@ int queue_custom_kss(gphip_ctx* h, int64_t mc, int64_t mpad, int nslots) {
     return GPHIP_OK;
 }
 
+// The strips of a pass over the mpad rows x Npad columns of nslots slots of dV (the exact prediction, the sparse prediction and its
+// hand-over): the columns per strip, their number in *nstrips.
+int predict_strips(const gphip_ctx* h, int64_t mpad, int nslots, int* nstrips) {
+    const int Mt = (int)(mpad / TB), Nt = (int)h->Nt;
+    int ns = (2048 + Mt * nslots - 1) / (Mt * nslots);               // enough workgroups to fill 256 CUs several times
+    if (ns > Nt) ns = Nt;
+    if (ns > 64) ns = 64;
+    if (ns < 1) ns = 1;
+    int js = (Nt + ns - 1) / ns * TB;
+    if (js > 4096) js = 4096;
+    *nstrips = (int)((h->Npad + js - 1) / js);
+    return js;
+}
+
+// The strip partials of the mpad rows of nslots slots in dV against each slot's z: dPart [slot][strip][2][mpad], dots then
+// squared norms.  z_gathered: z is read from dZ (predict_streamed gathered it there while the panels streamed by), not from the
+// workspace's rhs row.  The library's one launch of predict_partial_kernel.
+template <typename T>
+int queue_predict_partial(gphip_ctx* h, int64_t mpad, int nslots, bool z_gathered, int* nstrips) {
+    const int js = predict_strips(h, mpad, nslots, nstrips);
+    HIPCHK(h->dPart.grow((size_t)nslots * *nstrips * 2 * mpad * 8));
+    hipLaunchKernelGGL(predict_partial_kernel<T>, dim3((unsigned)(mpad / TB), (unsigned)*nstrips, (unsigned)nslots), dim3(256),
+                       (size_t)js * 8 + 8 * TB * 8, h->stream, (const T*)h->dV.p, (long)mpad, (long)mpad * h->Npad, (int)h->N,
+                       z_gathered ? (const T*)h->dZ.p : (const T*)h->dA.p, z_gathered ? 0 : (int)h->R, (long)h->slot_elems, js,
+                       h->dPart.as<double>(), *nstrips);
+    return GPHIP_OK;
+}
+
 // mu*, var* from V and z: V streamed once (HBM bound) -- strips of columns x 128 test points per workgroup,
-// then the strips are added in order.  Profile class 6: bytes = V once.  z_gathered: z is read from dZ (predict_streamed gathered
-// it there while the panels streamed by), not from the workspace's rhs row.
+// then the strips are added in order.  Profile class 6: bytes = V once.
 template <typename T>
 int queue_predict_reduce(gphip_ctx* h, int64_t mc, int64_t mpad, int nslots, bool z_gathered = false) {
-    const int Mt = (int)(mpad / TB), Nt = (int)h->Nt;
-    int nstrips = (2048 + Mt * nslots - 1) / (Mt * nslots);          // enough workgroups to fill 256 CUs several times
-    if (nstrips > Nt) nstrips = Nt;
-    if (nstrips > 64) nstrips = 64;
-    if (nstrips < 1) nstrips = 1;
-    int js = (Nt + nstrips - 1) / nstrips * TB;
-    if (js > 4096) js = 4096;
-    nstrips = (int)((h->Npad + js - 1) / js);
-    HIPCHK(h->dPart.grow((size_t)nslots * nstrips * 2 * mpad * 8));
+    int nstrips = 0;
     const double* kss = nullptr;
     if (h->custom) {                               // k(x*, x*) is a function of the test point for a general covariance function
         const int rc = queue_custom_kss(h, mc, mpad, nslots);
@@ -1884,10 +1913,7 @@ int queue_predict_reduce(gphip_ctx* h, int64_t mc, int64_t mpad, int nslots, boo
     }
     {
         ProfScope ps(h, 6, 4.0 * (double)mpad * h->Npad * nslots, (double)sizeof(T) * mpad * h->Npad * nslots);
-        hipLaunchKernelGGL(predict_partial_kernel<T>, dim3((unsigned)Mt, (unsigned)nstrips, (unsigned)nslots), dim3(256),
-                           (size_t)js * 8 + 8 * TB * 8, h->stream, (const T*)h->dV.p, (long)mpad, (long)mpad * h->Npad, (int)h->N,
-                           z_gathered ? (const T*)h->dZ.p : (const T*)h->dA.p, z_gathered ? 0 : (int)h->R, (long)h->slot_elems, js,
-                           h->dPart.as<double>(), nstrips);
+        if (const int rc = queue_predict_partial<T>(h, mpad, nslots, z_gathered, &nstrips)) return rc;
         hipLaunchKernelGGL(predict_finish_kernel, dim3((unsigned)((mc + 255) / 256), (unsigned)nslots), dim3(256), 0, h->stream,
                            h->dPart.as<double>(), nstrips, (long)mpad, h->dSlotp.as<double>(), (int)mc, (long)mpad,
                            h->dMean.as<double>(), h->dVar.as<double>(), h->pw_mean_test ? h->dPwMeanT.as<double>() : nullptr,
@@ -3288,9 +3314,8 @@ int gphip_predict_samples(gphip_handle h, const double* Thetas, int S, int p, co
             const int64_t mpad = stage_test_chunk(h, X, m0, mc, nb, s0, xt, &rc);
             if (rc) return rc;
             // few test points per sample: the forward substitutions of ALL samples as ONE dataflow launch (slot = sample) instead
-            // of two launches per tile column (samples_forward_df)
-            if (samples_forward_df(h, nb, mpad)) launch_dataflow_inverse<double, 64>(h, mpad, false, nb, h->dW64s.p);
-            else DISPATCH(h, queue_forward_rows, h, mpad, nb);
+            // of two launches per tile column (queue_forward_slots; the guard for a slot without a factor is not applied here)
+            queue_forward_slots(h, mpad, nb, false, true);
             DISPATCH(h, queue_predict_reduce, h, mc, mpad, nb);
             hm.resize((size_t)nb * mpad);
             hv.resize((size_t)nb * mpad);

@@ -8,9 +8,9 @@
 // substitutes with the factors each group leaves; DESIGN.md sections 8f and 8h list what the mode decides.  Per slot:
 //   u (a context whose TRAINING points are Z, y = 0; its nugget slot scalar carries the jitter j)
 //        queue_build + queue_factor        L_u L_u^T = k(Z, Z) + j I, direct-difference kernel build
-//        per chunk of data points, treated as test points of u:
-//        queue_cross + sparse_queue_forward   the chunk of V = L_u^-1 k(Z, X) in u->dV, V(t, k) at V[t + k ld]
-//        sparse_resid_kernel               r = y - mu of the chunk (row 0 of the rhs operand), partial sums of r^2
+//        per chunk of data points, treated as test points of u, sparse_chunk_head (the gradient's recomputed chunks share it):
+//        queue_cross + queue_forward_slots the chunk of V = L_u^-1 k(Z, X) in u->dV, V(t, k) at V[t + k ld]
+//        sparse_resid[_pw]_kernel          r = y - mu of the chunk (row 0 of the rhs operand), partial sums of r^2
 //        sparse_accumulate_kernel          b's workspace: lower tiles += V^T V, rhs tile row += r^T V  (chunks in order)
 //   b (a context of m points whose workspace is filled by hand)
 //        sparse_diag_kernel                tr(V V^T), then B = sn^2 I + V V^T
@@ -24,11 +24,12 @@
 // Gradient in the inducing locations (gphip_sparse_bound_grad_inducing, DESIGN.md section 8e): the same pass; sparse_zgrad_kernel
 //   contracts -2 H (rows = Z) and every chunk's -2 G (rows = the chunk's points) per COLUMN with the coordinate differences,
 //   sparse_zgrad_finish_kernel adds the strip partials, H first and then chunk after chunk, into the m x d accumulator dZacc
-// Prediction: v1 = L_u^-1 k(Z, x*) by u's forward substitution, v2 = L_B^-1 v1 by b's, predict_partial_kernel on both and one
-// finishing kernel.  Everything of one evaluation up to B runs on u's stream; b's stream takes over after a host synchronisation.
-// Prediction over samples (gphip_sparse_predict_samples, DESIGN.md section 8h): the same per chunk of test points for all slots of
-//   a group at once; sparse_handover_kernel takes V1 from u's dV to b's and the norms |v1|^2 on the way, b's stream waits for an
-//   event of u's.
+// Everything of one evaluation up to B runs on u's stream; b's stream takes over after a host synchronisation.
+// Prediction exists once, in sparse_predict_pass (DESIGN.md section 8h): per chunk of test points and for all slots at once,
+//   v1 = L_u^-1 k(Z, x*) by u's forward substitution, sparse_handover_kernel takes V1 from u's dV to b's and the norms |v1|^2 on
+//   the way, b's stream waits for an event of u's, v2 = L_B^-1 v1 by b's substitution, the exact path's partial launch against c
+//   and one finishing kernel.  gphip_sparse_predict[_pw] is the pass for the ONE slot of the resident fit,
+//   gphip_sparse_predict_samples[_pw] the pass after every group.
 // Joint prediction (gphip_sparse_predict_cov / _draws / _logpdf, DESIGN.md section 8g): all M rows of V1 = L_u^-1 k(Z, X*) and
 //   V2 = L_B^-1 V1 side by side in u's dV, the rhs-row operand -c / sn^2 in u's dJZ; u owns the child context of the exact
 //   path (u->joint, gphip_joint.inc: training points X*, K(X*, X*) by the direct build) and the two-segment downdate_kernel turns
@@ -38,7 +39,8 @@
 
 // The phases timed by HIP events while option "profile" is on, and the options that read them (gphip_sparse_get_option).
 // PH_KUU_FACTOR .. PH_GRAD_INDUCING are reset by every evaluation of the bound, PH_JOINT_V .. PH_JOINT_FACTOR by every joint
-// prediction, PH_SAMPLES_VU .. by every gphip_sparse_predict_samples (which also evaluates the bound).
+// prediction, PH_SAMPLES_VU .. by every prediction pass: gphip_sparse_predict and gphip_sparse_predict_samples (which also
+// evaluates the bound).
 enum SparsePhaseId {
     PH_KUU_FACTOR, PH_CROSS, PH_FORWARD, PH_ACCUMULATE, PH_B_FACTOR,                               // the bound
     PH_GRAD_SMALL, PH_GRAD_WEIGHTS, PH_GRAD_BACKWARD, PH_GRAD_REDUCE, PH_GRAD_INDUCING,            // its gradients
@@ -79,16 +81,16 @@ struct gphip_sparse_ctx {
     int chunk = 0, split = 0, profile = 0;
     int joint_split = 0;                       // joint prediction: strips of the stacked contraction (0 = by the split rule)
     int batch_slots = 0;                       // gphip_sparse_bound_batch / _predict_samples: most thetas per group (0 = by the group rule)
-    int samples_chunk = 0;                     // gphip_sparse_predict_samples: test points per pass (0 = by the rule)
-    int samples_handover = 1;                  // gphip_sparse_predict_samples: 1 = sparse_handover_kernel, 0 = copy + norm launch (measurement)
+    int samples_chunk = 0;                     // the prediction pass: most test points per chunk (0 = by the caller's rule)
+    int samples_handover = 1;                  // the prediction pass: 1 = sparse_handover_kernel, 0 = copy + norm launch (measurement)
     int pw_fused = 0;                          // the _pw calls: 1 = the weight inside the contraction, 0 = sparse_scale_rows_kernel + the unweighted one
                                                // (the default since the measurement of DESIGN.md section 8i: fused lost at the largest size)
     // read-only results of the last call
     int last_nsplit = 0;
     int joint_nsplit = 0;                      // strips the last joint prediction's downdate used
     int last_slots = 0;                        // thetas in the last group of the last gphip_sparse_bound_batch
-    int64_t last_chunk = 0;
-    int64_t last_samples_chunk = 0;            // test points per pass of the last gphip_sparse_predict_samples
+    int last_chunk = 0;                        // data points per chunk of the last evaluation
+    int last_samples_chunk = 0;           // test points per chunk of the last prediction pass
     double last_jitter = 0.0;
     int grad_analytic = 0;                     // the last gphip_sparse_bound_grad: 1 = the analytic route, 0 = central differences
     double ms[PH_COUNT] = {};                  // K_uu factor, cross build, forward substitution, accumulation, B factor;
@@ -260,7 +262,7 @@ int sparse_queue_accumulate(gphip_sparse_ctx* h, int64_t mpad, int nb, bool weig
 
 // r = y - mu_s of the chunk for nb slots (mu_s from dPar); slot s's partial sums go to part + s pstride
 template <typename T>
-int sparse_queue_resid(gphip_sparse_ctx* h, int64_t c0, int64_t mc, int64_t mpad, double* part, int nb = 1, long pstride = 0) {
+int sparse_queue_resid(gphip_sparse_ctx* h, int64_t c0, int64_t mc, int64_t mpad, double* part, int nb, long pstride) {
     hipLaunchKernelGGL(sparse_resid_kernel<T>, dim3((unsigned)((mpad + 255) / 256), (unsigned)nb), dim3(256), 0, h->u->stream,
                        (const T*)h->dY.p + c0, (int)mc, (int)mpad, (const double*)h->dPar.as<double>(), SPARSE_PAR, (T*)h->dRz.p, 16l * h->rcap, part,
                        pstride);
@@ -329,46 +331,40 @@ int sparse_factor(gphip_sparse_ctx* h, gphip_ctx* c, int nb, bool build, bool wa
     return rc ? sfail(h, rc, c->err) : GPHIP_OK;
 }
 
-// the strips of a pass over the mpad rows x Npad columns of nb slots of c->dV (queue_predict_reduce's rule): columns per strip
-int sparse_partial_strips(const gphip_ctx* h, int64_t mpad, int nb, int* nstrips_out) {
-    const int Mt = (int)(mpad / TB), Nt = (int)h->Nt;
-    int nstrips = (2048 + Mt * nb - 1) / (Mt * nb);
-    if (nstrips > Nt) nstrips = Nt;
-    if (nstrips > 64) nstrips = 64;
-    if (nstrips < 1) nstrips = 1;
-    int js = (Nt + nstrips - 1) / nstrips * TB;
-    if (js > 4096) js = 4096;
-    *nstrips_out = (int)((h->Npad + js - 1) / js);
-    return js;
-}
-
-// strip partials of predict_partial_kernel for the mpad rows of nb slots in c->dV against each slot's rhs row
-// (queue_predict_reduce's first stage): c->dPart [slot][strip][2][mpad]
-template <typename T>
-int sparse_queue_partial(gphip_ctx* h, int64_t mpad, int* nstrips_out, int nb = 1) {
-    int nstrips = 0;
-    const int js = sparse_partial_strips(h, mpad, nb, &nstrips);
-    HIPCHK(h->dPart.grow((size_t)nb * nstrips * 2 * mpad * 8));
-    hipLaunchKernelGGL(predict_partial_kernel<T>, dim3((unsigned)(mpad / TB), (unsigned)nstrips, (unsigned)nb), dim3(256),
-                       (size_t)js * 8 + 8 * TB * 8, h->stream, (const T*)h->dV.p, (long)mpad, (long)mpad * h->Npad, (int)h->N,
-                       (const T*)h->dA.p, (int)h->R, (long)h->slot_elems, js, h->dPart.as<double>(), nstrips);
-    *nstrips_out = nstrips;
-    return GPHIP_OK;
-}
-
-// gphip_sparse_predict_samples: the mpad rows of V1 of nb slots from u's dV into b's, the strip partials of |v1|^2 into u->dPart
-// [slot][strip][mpad] on the way (sparse_handover_kernel), on u's stream
+// prediction: the mpad rows of V1 of nb slots from u's dV into b's, the strip partials of |v1|^2 into u->dPart [slot][strip][mpad]
+// on the way (sparse_handover_kernel, in the strips of the exact path's predict_strips), on u's stream
 template <typename T>
 int sparse_queue_handover(gphip_sparse_ctx* h, int64_t mpad, int nb, int* nstrips_out) {
     gphip_ctx *u = h->u, *b = h->b;
     int nstrips = 0;
-    const int js = sparse_partial_strips(u, mpad, nb, &nstrips);
+    const int js = predict_strips(u, mpad, nb, &nstrips);
     HIPCHK(u->dPart.grow((size_t)nb * nstrips * mpad * 8));
     hipLaunchKernelGGL(sparse_handover_kernel<T>, dim3((unsigned)(mpad / TB), (unsigned)nstrips, (unsigned)nb), dim3(256), 0, u->stream,
                        (const T*)u->dV.p, (T*)b->dV.p, (long)mpad, (long)mpad * u->Npad, (int)u->N, (int)u->Npad, js, u->dPart.as<double>(),
                        nstrips);
     *nstrips_out = nstrips;
     return GPHIP_OK;
+}
+
+// The head of the data chunk [c0, c0 + mc) for nb slots, on u's stream: the chunk's points into u's test-point block, its mpad rows
+// of V = L_u^-1 k(Z, X) into u->dV (queue_forward_slots: resident = slot 0 with the fitted factor, all_factored = its guard) and
+// the residual rows into dRz -- with pw the weight rows into dWz as well.  Slot s's partial sums go to part + s pstride (pw: pn
+// apart per sum).  The chunk loop of the group evaluator and the gradient's recomputed chunks both come through here, so a
+// recomputed chunk's V, residual and weights are the evaluation's.
+int sparse_chunk_head(gphip_sparse_ctx* h, int64_t c0, int64_t mc, int64_t mpad, int nb, bool resident, bool all_factored, const SparsePw& pw,
+                      double* part, long pstride, long pn, SparsePhases& ph) {
+    gphip_ctx* u = h->u;
+    {
+        SparseScope ps(ph, PH_CROSS, u->stream);
+        if (const int rc = sparse_load_points(h, h->dXt.p, h->Npad, c0, mpad)) return rc;
+        DISPATCH(u, queue_cross, u, mc, mpad, nb);
+    }
+    {
+        SparseScope ps(ph, PH_FORWARD, u->stream);
+        queue_forward_slots(u, mpad, nb, resident, all_factored);
+    }
+    if (pw.any()) return DISPATCH(h, sparse_queue_resid_pw, h, pw, c0, mc, mpad, part, nb, pstride, pn);
+    return DISPATCH(h, sparse_queue_resid, h, c0, mc, mpad, part, nb, pstride);
 }
 
 // mean of k(z, z) over the inducing points of a run-time compiled kernel (the default jitter's scale) for the thetas of the
@@ -441,6 +437,7 @@ int sparse_queue_zgrad(gphip_sparse_ctx* h, const void* W, long ldw, const void*
 // what the evaluation hands on to the gradient phase
 struct SparseGradIn {
     const double* theta;
+    SparsePw pw;                               // the evaluation's arrays, for the head of a recomputed chunk (no entry point has a gradient with them yet)
     double sn2, mu, rtr, ctc, trvv, skk;
     int64_t rows, nchunks;
 };
@@ -514,18 +511,9 @@ int sparse_grad_phase(gphip_sparse_ctx* h, const SparseGradIn& in, SparsePhases&
     for (int64_t c0 = 0; c0 < h->N; c0 += in.rows) {
         const int64_t mc = std::min(in.rows, h->N - c0), mpad = (mc + TB - 1) / TB * TB;
         const unsigned nb = (unsigned)((mpad + 255) / 256);
-        if (in.nchunks > 1) {
-            {
-                SparseScope ps(ph, PH_CROSS, u->stream);
-                if ((rc = sparse_load_points(h, h->dXt.p, h->Npad, c0, mpad))) return rc;
-                queue_cross<T>(u, mc, mpad, 1);
-            }
-            {
-                SparseScope ps(ph, PH_FORWARD, u->stream);
-                queue_forward_fit(u, mpad);
-            }
-            sparse_queue_resid<T>(h, c0, mc, mpad, h->dSum.as<double>() + 1);       // (mu is still in dPar; its sums of r^2 are not read again)
-        }
+        // (the evaluation's chunk again: mu is still in dPar, and its partial sums, which are not read again, go where chunk 0's went)
+        if (in.nchunks > 1 && (rc = sparse_chunk_head(h, c0, mc, mpad, 1, true, true, in.pw, h->dSum.as<double>() + 1, 0l, (long)nblk, ph)))
+            return rc;
         {
             SparseScope ps(ph, PH_GRAD_SMALL, u->stream);
             hipLaunchKernelGGL(sparse_vta_kernel<T>, dim3(nb, (unsigned)Mt), dim3(256), 0, u->stream, (const T*)u->dV.p, (long)mpad,
@@ -642,15 +630,6 @@ bool sparse_pw_row_ok(const SparsePw& pw, int s, int64_t N) {
     return true;
 }
 
-// the chunk's mpad rows of every slot: V <- L_u^-1 k(Z, X).  Resident: the fitted factor's route.  Batch: ONE dataflow launch
-// (slot = row) where gphip_predict_samples would take it and every slot of the group has a factor (a slot whose factorisation
-// was abandoned has no block inverses to hand to the launch's chain), else the batched GEMM substitution, which has no waits
-void sparse_queue_forward(gphip_ctx* u, int64_t mpad, int nb, SparseKeep keep, bool all_factored) {
-    if (keep == SparseKeep::fit) queue_forward_fit(u, mpad);
-    else if (all_factored && samples_forward_df(u, nb, mpad)) launch_dataflow_inverse<double, 64>(u, mpad, false, nb, u->dW64s.p);
-    else DISPATCH(u, queue_forward_rows, u, mpad, nb);
-}
-
 // The bound for the nb rows of Theta in slots 0 .. nb - 1 of u and b, `rows` data points per chunk (the callers size u's dV, dRz
 // and dPar for nb slots of them).  u builds and factors nb K_uu at once; every chunk of data points is loaded once and crossed,
 // substituted, reduced and accumulated for all nb slots by launches whose last grid index is the slot; b factors nb matrices B at
@@ -757,17 +736,7 @@ int sparse_group(gphip_sparse_ctx* h, const double* Theta, int nb, int p, double
     size_t used = 0;
     for (int64_t c0 = 0; c0 < h->N; c0 += rows) {
         const int64_t mc = std::min(rows, h->N - c0), mpad = (mc + TB - 1) / TB * TB;
-        {
-            SparseScope ps(ph, PH_CROSS, u->stream);
-            if ((rc = sparse_load_points(h, h->dXt.p, h->Npad, c0, mpad))) return rc;
-            DISPATCH(u, queue_cross, u, mc, mpad, nb);
-        }
-        {
-            SparseScope ps(ph, PH_FORWARD, u->stream);
-            sparse_queue_forward(u, mpad, nb, keep, all_factored);
-        }
-        if (pw.any()) DISPATCH(h, sparse_queue_resid_pw, h, pw, c0, mc, mpad, d_r2 + used, nb, (long)ss, (long)nblk);
-        else DISPATCH(h, sparse_queue_resid, h, c0, mc, mpad, d_r2 + used, nb, (long)ss);
+        if ((rc = sparse_chunk_head(h, c0, mc, mpad, nb, resident, all_factored, pw, d_r2 + used, (long)ss, (long)nblk, ph))) return rc;
         if (h->custom) {                       // k(x_i, x_i) per point and slot (u->dXsT still holds the chunk)
             if ((rc = queue_custom_kss(u, mc, mpad, nb))) return sfail(h, rc, u->err);
             DISPATCH(h, sparse_queue_kk, h, mc, mpad, d_kk + used, nb, (long)ss, pw.any());
@@ -865,7 +834,7 @@ int sparse_eval(gphip_sparse_ctx* h, const double* theta, int p, double jitter, 
         }
         if (rc) { (void)hipGetLastError(); return sfail(h, rc, "no device memory for the gradient's weights: " + b->err); }
     }
-    h->last_chunk = rows;
+    h->last_chunk = (int)rows;
     if ((rc = sparse_ensure_rz(h, 1, rows))) return rc;
     if ((rc = sparse_ensure_par(h, 1))) return rc;
     SparsePhases ph(h);
@@ -881,7 +850,7 @@ int sparse_eval(gphip_sparse_ctx* h, const double* theta, int p, double jitter, 
     h->pw_fit = pw.any();
     h->sn2_fit = r.sn2; h->mu_fit = r.mu; h->kxx_fit = r.kxx;
     if (wants_grad && *info == 0) {
-        const SparseGradIn in{theta, r.sn2, r.mu, r.rtr, r.ctc, r.trvv, r.skk, rows, (h->N + rows - 1) / rows};
+        const SparseGradIn in{theta, pw, r.sn2, r.mu, r.rtr, r.ctc, r.trvv, r.skk, rows, (h->N + rows - 1) / rows};
         rc = DISPATCH(h, sparse_grad_phase, h, in, ph, grad, gradZ);
         if (rc && grad) for (int k = 0; k < p; ++k) grad[k] = qnan;
         if (rc && gradZ) for (int64_t k = 0; k < h->m * h->d; ++k) gradZ[k] = qnan;
@@ -935,7 +904,7 @@ int sparse_size_groups(gphip_sparse_ctx* h, int B, int* G_out, int64_t* rows_out
         rc = ensure_vbuf(u, (int64_t)G * rows);
     }
     if (rc) { (void)hipGetLastError(); return sfail(h, rc, "no device memory for a chunk of V: " + u->err); }
-    h->last_chunk = rows;
+    h->last_chunk = (int)rows;
     if ((rc = sparse_ensure_rz(h, G, rows))) return rc;
     if ((rc = sparse_ensure_par(h, G))) return rc;
     *G_out = G; *rows_out = rows;
@@ -979,15 +948,89 @@ int sparse_eval_batch(gphip_sparse_ctx* h, const double* Theta, int B, int p, do
     return GPHIP_OK;
 }
 
-// gphip_sparse_predict_samples (DESIGN.md section 8h): mean and variance at the M test points for the S rows of Thetas.  Group
-// after group (sparse_eval_batch's rule) the group evaluator leaves the factors of every slot of u and b (SparseKeep::group);
-// the test points then go through in chunks of MC points, every launch with the slot as its last grid index:
+// The prediction pass of gphip_sparse_predict[_pw] and gphip_sparse_predict_samples[_pw] (DESIGN.md section 8h): mean and variance
+// at the M test points X for the nb slots whose factors u and b hold, MC points at a time, every launch with the slot as its last
+// grid index:
 //   u   stage_test_chunk (k_s(X*, Z) of all slots), the forward substitution of all slots, k_s(x*, x*) of a run-time compiled
-//       kernel, sparse_handover_kernel: V1 into b's dV and the strip partials of |v1|^2
-//   b   (after an event of u's stream) the forward substitution of all slots, predict_partial_kernel, the finishing kernel
-// and one download per chunk.  A launch that spin-waits (the dataflow substitution) runs on a context only when every slot of
-// the group has a factor there: a slot whose factorisation was abandoned has no block inverses to hand to the launch's chain.
-// pw: S x N training arrays; pwt: S x M arrays of m(x*) and nu(x*), which take the place of mu and sn^2 in the finishing kernel.
+//       kernel, the hand-over: V1 into b's dV and the strip partials of |v1|^2 (sparse_handover_kernel; option
+//       "sparse_samples_handover" = 0: a copy and the exact path's partial launch on u, whose dots nobody reads)
+//   b   (its stream waits for an event of u's, not the host) the forward substitution of all slots, the partial launch against c,
+//       the finishing kernel
+// and one staged download per chunk, which the host scatters: row s to mean / var + s stride.  resident: the factors are the fit's
+// (one slot).  Else u_factored / b_factored: every slot has a factor there -- a launch that spin-waits (the dataflow substitution)
+// runs on a context only then (queue_forward_slots).  pwt: nb rows of M values of m(x*) and nu(x*), which take the place of mu and
+// sn^2 in the finishing kernel.  info (null: every row is good): a row whose info is not 0 gets NaN.
+int sparse_predict_pass(gphip_sparse_ctx* h, const double* X, int64_t M, int64_t MC, int nb, bool resident, bool u_factored, bool b_factored,
+                        const SparsePw& pwt, int latent, double* mean, double* var, int64_t stride, const int* info, SparsePhases& ph) {
+    gphip_ctx *u = h->u, *b = h->b;
+    const double qnan = std::nan("");
+    const int64_t mpm = u->Npad;
+    int rc = GPHIP_OK;
+    std::vector<double> xt, hm, hv;
+    struct Handed { gphip_ctx* u; hipEvent_t e; ~Handed() { u->pool.push_back(e); } } handed{u, get_event(u)};
+    for (int64_t m0 = 0; m0 < M; m0 += MC) {
+        const int64_t mc = std::min(MC, M - m0);
+        int64_t mpad = 0;
+        int ns1 = 0, ns2 = 0;
+        {
+            SparseScope ps(ph, PH_SAMPLES_VU, u->stream);
+            // (ranged = false: u builds k(x*, Z) with the direct form, kbuild_mfma = 0 -- no verdict of the MFMA kernel build to guard)
+            mpad = stage_test_chunk(u, X, m0, mc, nb, 0, xt, &rc, false);
+            if (rc) return sfail(h, rc, u->err);
+            queue_forward_slots(u, mpad, nb, resident, u_factored);
+            if (h->custom && (rc = queue_custom_kss(u, mc, mpad, nb))) return sfail(h, rc, u->err);
+        }
+        long p1_sstride = (long)mpad, p1_off = 0;
+        {
+            SparseScope ps(ph, PH_SAMPLES_HANDOVER, u->stream);
+            if (h->samples_handover) {
+                if ((rc = DISPATCH(h, sparse_queue_handover, h, mpad, nb, &ns1))) return rc;
+            } else {                           // the two launches it replaces; the norm rows are the second of each strip's two
+                HIPCHK(hipMemcpyAsync(b->dV.p, u->dV.p, (size_t)nb * mpad * mpm * h->es, hipMemcpyDeviceToDevice, u->stream));
+                if ((rc = DISPATCH(u, queue_predict_partial, u, mpad, nb, false, &ns1))) return sfail(h, rc, u->err);
+                p1_sstride = 2l * mpad; p1_off = (long)mpad;
+            }
+        }
+        HIPCHK(hipEventRecord(handed.e, u->stream));
+        HIPCHK(hipStreamWaitEvent(b->stream, handed.e, 0));
+        {
+            SparseScope ps(ph, PH_SAMPLES_VB, b->stream);
+            queue_forward_slots(b, mpad, nb, resident, b_factored);
+        }
+        {
+            SparseScope ps(ph, PH_SAMPLES_REDUCE, b->stream);
+            if ((rc = DISPATCH(b, queue_predict_partial, b, mpad, nb, false, &ns2))) return sfail(h, rc, b->err);
+            const double *d_mt = nullptr, *d_nt = nullptr;
+            if ((rc = sparse_stage_test_arrays(h, pwt, M, m0, mc, mpad, nb, latent, &d_mt, &d_nt))) return rc;
+            // (mu, B's sn^2, k(x, x) and the noise of every slot are in dPar since the evaluation)
+            hipLaunchKernelGGL(sparse_predict_finish_kernel, dim3((unsigned)((mc + 255) / 256), (unsigned)nb), dim3(256), 0, b->stream,
+                               u->dPart.as<double>() + p1_off, ns1, p1_sstride, (long)ns1 * p1_sstride, b->dPart.as<double>(), ns2,
+                               (long)mpad, (int)mc, h->dPar.as<double>(), h->custom ? u->dKss.as<double>() : nullptr, latent ? 1 : 0,
+                               d_mt, d_nt, b->dMean.as<double>(), b->dVar.as<double>());
+        }
+        hm.resize((size_t)nb * mpad);
+        hv.resize((size_t)nb * mpad);
+        HIPCHK(hipMemcpyAsync(hm.data(), b->dMean.p, hm.size() * 8, hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(hipMemcpyAsync(hv.data(), b->dVar.p, hv.size() * 8, hipMemcpyDeviceToHost, b->stream));
+        if ((rc = complete_call(b))) return sfail(h, rc, b->err);      // (b's stream waited for u's: both are idle)
+        if ((rc = complete_call(u))) return sfail(h, rc, u->err);      // (the abort word of u's substitution)
+        for (int s = 0; s < nb; ++s) {
+            const bool good = !info || info[s] == 0;
+            double* ms = mean + (size_t)s * stride + m0;
+            double* vs = var + (size_t)s * stride + m0;
+            for (int64_t t = 0; t < mc; ++t) {
+                ms[t] = good ? hm[(size_t)s * mpad + t] : qnan;
+                vs[t] = good ? hv[(size_t)s * mpad + t] : qnan;
+            }
+        }
+    }
+    return GPHIP_OK;
+}
+
+// gphip_sparse_predict_samples (DESIGN.md section 8h): mean and variance at the M test points for the S rows of Thetas.  Group
+// after group (sparse_eval_batch's rule) the group evaluator leaves the factors of every slot of u and b (SparseKeep::group) and
+// the prediction pass substitutes with them.
+// pw: S x N training arrays; pwt: S x M arrays of m(x*) and nu(x*).
 int sparse_predict_samples(gphip_sparse_ctx* h, const double* Thetas, int S, int p, double jitter, const double* X, int64_t M, int latent,
                            double* mean, double* var, double* bound, int* info, const SparsePw& pw = SparsePw{}, const SparsePw& pwt = SparsePw{}) {
     gphip_ctx *u = h->u, *b = h->b;
@@ -1014,12 +1057,9 @@ int sparse_predict_samples(gphip_sparse_ctx* h, const double* Thetas, int S, int
         MC = (MC / 2 + TB - 1) / TB * TB;
     }
     if (rc) { (void)hipGetLastError(); return sfail(h, rc, "no device memory for the test points' V of a group"); }
-    h->last_samples_chunk = MC;
+    h->last_samples_chunk = (int)MC;
     SparsePhases ph(h);
     std::vector<SparseSlot> res((size_t)G);
-    std::vector<double> xt, hm, hv;
-    hipEvent_t handed = get_event(u);          // u's part of a chunk is queued: b's stream waits for it, not the host
-    struct Back { gphip_ctx* u; hipEvent_t e; ~Back() { u->pool.push_back(e); } } back{u, handed};
     for (int s0 = 0; s0 < S; s0 += G) {
         const int nb = std::min(G, S - s0);
         h->last_slots = nb;
@@ -1033,61 +1073,9 @@ int sparse_predict_samples(gphip_sparse_ctx* h, const double* Thetas, int S, int
             if (r.uinfo != 0) u_factored = false;
             if (b->hInfo.as<int>()[s] != 0) b_factored = false;
         }
-        for (int64_t m0 = 0; m0 < M; m0 += MC) {
-            const int64_t mc = std::min(MC, M - m0);
-            int64_t mpad = 0;
-            int ns1 = 0, ns2 = 0;
-            {
-                SparseScope ps(ph, PH_SAMPLES_VU, u->stream);
-                mpad = stage_test_chunk(u, X, m0, mc, nb, 0, xt, &rc, false);
-                if (rc) return sfail(h, rc, u->err);
-                sparse_queue_forward(u, mpad, nb, SparseKeep::nothing, u_factored);
-                if (h->custom && (rc = queue_custom_kss(u, mc, mpad, nb))) return sfail(h, rc, u->err);
-            }
-            long p1_sstride = (long)mpad, p1_off = 0;
-            {
-                SparseScope ps(ph, PH_SAMPLES_HANDOVER, u->stream);
-                if (h->samples_handover) {
-                    if ((rc = DISPATCH(h, sparse_queue_handover, h, mpad, nb, &ns1))) return rc;
-                } else {                       // the two launches it replaces: a copy, and predict_partial_kernel on u for its norm rows
-                    HIPCHK(hipMemcpyAsync(b->dV.p, u->dV.p, (size_t)nb * mpad * mpm * h->es, hipMemcpyDeviceToDevice, u->stream));
-                    if ((rc = DISPATCH(u, sparse_queue_partial, u, mpad, &ns1, nb))) return sfail(h, rc, u->err);
-                    p1_sstride = 2l * mpad; p1_off = (long)mpad;
-                }
-            }
-            HIPCHK(hipEventRecord(handed, u->stream));
-            HIPCHK(hipStreamWaitEvent(b->stream, handed, 0));
-            {
-                SparseScope ps(ph, PH_SAMPLES_VB, b->stream);
-                if (b_factored && samples_forward_df(b, nb, mpad)) launch_dataflow_inverse<double, 64>(b, mpad, false, nb, b->dW64s.p);
-                else DISPATCH(b, queue_forward_rows, b, mpad, nb);
-            }
-            {
-                SparseScope ps(ph, PH_SAMPLES_REDUCE, b->stream);
-                if ((rc = DISPATCH(b, sparse_queue_partial, b, mpad, &ns2, nb))) return sfail(h, rc, b->err);
-                const double *d_mt = nullptr, *d_nt = nullptr;
-                if ((rc = sparse_stage_test_arrays(h, pwt.rows_from(s0, M), M, m0, mc, mpad, nb, latent, &d_mt, &d_nt))) return rc;
-                hipLaunchKernelGGL(sparse_predict_finish_kernel, dim3((unsigned)((mc + 255) / 256), (unsigned)nb), dim3(256), 0, b->stream,
-                                   u->dPart.as<double>() + p1_off, ns1, p1_sstride, (long)ns1 * p1_sstride, b->dPart.as<double>(), ns2,
-                                   (long)mpad, (int)mc, h->dPar.as<double>(), h->custom ? u->dKss.as<double>() : nullptr, latent ? 1 : 0,
-                                   d_mt, d_nt, b->dMean.as<double>(), b->dVar.as<double>());
-            }
-            hm.resize((size_t)nb * mpad);
-            hv.resize((size_t)nb * mpad);
-            HIPCHK(hipMemcpyAsync(hm.data(), b->dMean.p, hm.size() * 8, hipMemcpyDeviceToHost, b->stream));
-            HIPCHK(hipMemcpyAsync(hv.data(), b->dVar.p, hv.size() * 8, hipMemcpyDeviceToHost, b->stream));
-            if ((rc = complete_call(b))) return sfail(h, rc, b->err);      // (b's stream waited for u's: both are idle)
-            if ((rc = complete_call(u))) return sfail(h, rc, u->err);      // (the abort word of u's substitution)
-            for (int s = 0; s < nb; ++s) {
-                const bool good = info[s0 + s] == 0;
-                double* ms = mean + (size_t)(s0 + s) * M + m0;
-                double* vs = var + (size_t)(s0 + s) * M + m0;
-                for (int64_t t = 0; t < mc; ++t) {
-                    ms[t] = good ? hm[(size_t)s * mpad + t] : qnan;
-                    vs[t] = good ? hv[(size_t)s * mpad + t] : qnan;
-                }
-            }
-        }
+        if ((rc = sparse_predict_pass(h, X, M, MC, nb, false, u_factored, b_factored, pwt.rows_from(s0, M), latent, mean + (size_t)s0 * M,
+                                      var + (size_t)s0 * M, M, info + s0, ph)))
+            return rc;
         ph.harvest();                          // (group by group: the events go back to the pool for the next one)
     }
     return GPHIP_OK;
@@ -1216,6 +1204,27 @@ struct SparseFactorEvents {
         if (on) ph.recs.push_back(SparsePhase{PH_JOINT_FACTOR, ev[0], ev[1]});
     }
 };
+
+// One table for gphip_sparse_set_option / gphip_sparse_get_option (as option_slot is for the exact path): the object's own integer
+// options -- OPT_NONNEG: a negative value is refused, OPT_FLAG: stored as 0 / 1 -- and, OPT_RESULT, the results of the last call,
+// which can be read only (setting one goes where every name the object does not own goes: to u and b).
+enum { OPT_NONNEG = 1, OPT_FLAG = 2, OPT_RESULT = 4 };
+struct SparseOption { const char* name; int gphip_sparse_ctx::*field; int kind; };
+const SparseOption* sparse_option(const char* name) {
+    static const SparseOption table[] = {
+        {"sparse_chunk", &gphip_sparse_ctx::chunk, OPT_NONNEG}, {"sparse_split", &gphip_sparse_ctx::split, OPT_NONNEG},
+        {"profile", &gphip_sparse_ctx::profile, 0}, {"sparse_joint_split", &gphip_sparse_ctx::joint_split, OPT_NONNEG},
+        {"sparse_batch_slots", &gphip_sparse_ctx::batch_slots, OPT_NONNEG}, {"sparse_samples_chunk", &gphip_sparse_ctx::samples_chunk, OPT_NONNEG},
+        {"sparse_samples_handover", &gphip_sparse_ctx::samples_handover, OPT_FLAG}, {"sparse_pw_fused", &gphip_sparse_ctx::pw_fused, OPT_FLAG},
+        {"grad_analytic", &gphip_sparse_ctx::grad_analytic, OPT_RESULT}, {"last_sparse_chunk", &gphip_sparse_ctx::last_chunk, OPT_RESULT},
+        {"last_sparse_nsplit", &gphip_sparse_ctx::last_nsplit, OPT_RESULT}, {"last_sparse_slots", &gphip_sparse_ctx::last_slots, OPT_RESULT},
+        {"last_sparse_samples_chunk", &gphip_sparse_ctx::last_samples_chunk, OPT_RESULT},
+        {"last_sparse_joint_nsplit", &gphip_sparse_ctx::joint_nsplit, OPT_RESULT},
+    };
+    for (const SparseOption& o : table)
+        if (!strcmp(name, o.name)) return &o;
+    return nullptr;
+}
 
 }  // namespace
 
@@ -1396,38 +1405,18 @@ int gphip_sparse_predict_pw(gphip_sparse_handle h, const void* Xs, int64_t M, in
     gphip_ctx *u = h->u, *b = h->b;
     if (!h->fitted || !has_fit(u) || !has_fit(b)) return sfail(h, GPHIP_ERR_STATE, "gphip_sparse_predict before a successful gphip_sparse_fit");
     HIPCHK(hipSetDevice(h->device));
-    const double* X = static_cast<const double*>(Xs);
-    int64_t MC = 0;
-    int rc = ensure_vchunk(u, std::min<int64_t>(32768, (M + TB - 1) / TB * TB), &MC);
+    // test points per pass: ensure_vchunk's rule on u up to 32768, at most the option; b's dV takes the same rows
+    int64_t MC = std::min<int64_t>(32768, (M + TB - 1) / TB * TB);
+    if (h->samples_chunk > 0) MC = std::min(MC, ((int64_t)h->samples_chunk + TB - 1) / TB * TB);
+    int rc = ensure_vchunk(u, MC, &MC);
     if (rc) { (void)hipGetLastError(); return sfail(h, rc, "no device memory for the test points' V: " + u->err); }
     if ((rc = ensure_vbuf(b, MC))) { (void)hipGetLastError(); return sfail(h, rc, "no device memory for the test points' V: " + b->err); }
-    std::vector<double> xt;
-    for (int64_t m0 = 0; m0 < M; m0 += MC) {
-        const int64_t mc = std::min(MC, M - m0);
-        // (ranged = false: u builds k(x*, Z) with the direct form, kbuild_mfma = 0 -- no verdict of the MFMA kernel build to guard)
-        const int64_t mpad = stage_test_chunk(u, X, m0, mc, 1, 0, xt, &rc, false);
-        if (rc) return sfail(h, rc, u->err);
-        queue_forward_fit(u, mpad);
-        int ns1 = 0, ns2 = 0;
-        if ((rc = DISPATCH(u, sparse_queue_partial, u, mpad, &ns1))) return sfail(h, rc, u->err);
-        if (h->custom && (rc = queue_custom_kss(u, mc, mpad, 1))) return sfail(h, rc, u->err);
-        if ((rc = complete_call(u))) return sfail(h, rc, u->err);
-        // v2 = L_B^-1 v1: the same rows through b's factor
-        HIPCHK(hipMemcpyAsync(b->dV.p, u->dV.p, (size_t)mpad * u->Npad * h->es, hipMemcpyDeviceToDevice, b->stream));
-        queue_forward_fit(b, mpad);
-        if ((rc = DISPATCH(b, sparse_queue_partial, b, mpad, &ns2))) return sfail(h, rc, b->err);
-        const double *d_mt = nullptr, *d_nt = nullptr;
-        if ((rc = sparse_stage_test_arrays(h, SparsePw{mean_test, nugget_test}, M, m0, mc, mpad, 1, latent, &d_mt, &d_nt))) return rc;
-        // (one slot of the finishing kernel: u's norm rows; mu, B's sn^2, k(x, x) and the noise of the fit are slot 0 of dPar since the evaluation)
-        hipLaunchKernelGGL(sparse_predict_finish_kernel, dim3((unsigned)((mc + 255) / 256), 1u), dim3(256), 0, b->stream,
-                           u->dPart.as<double>() + mpad, ns1, 2l * mpad, 0l, b->dPart.as<double>(), ns2, (long)mpad, (int)mc,
-                           h->dPar.as<double>(), h->custom ? u->dKss.as<double>() : nullptr, latent ? 1 : 0, d_mt, d_nt, b->dMean.as<double>(),
-                           b->dVar.as<double>());
-        HIPCHK(hipMemcpyAsync(mean + m0, b->dMean.p, (size_t)mc * 8, hipMemcpyDeviceToHost, b->stream));
-        HIPCHK(hipMemcpyAsync(var + m0, b->dVar.p, (size_t)mc * 8, hipMemcpyDeviceToHost, b->stream));
-        if ((rc = complete_call(b))) return sfail(h, rc, b->err);
-    }
-    return GPHIP_OK;
+    h->last_samples_chunk = (int)MC;
+    sparse_reset_phases(h, PH_SAMPLES_VU, PH_COUNT);
+    SparsePhases ph(h);
+    // (the fit's one slot: mu, B's sn^2, k(x, x) and the noise of the fit are slot 0 of dPar since the evaluation)
+    return sparse_predict_pass(h, static_cast<const double*>(Xs), M, MC, 1, true, true, true, SparsePw{mean_test, nugget_test}, latent, mean, var,
+                               M, nullptr, ph);
 }
 
 int gphip_sparse_predict_samples(gphip_sparse_handle h, const double* Thetas, int S, int p, double jitter, const void* Xs, int64_t M,
@@ -1498,14 +1487,12 @@ int gphip_sparse_set_option(gphip_sparse_handle h, const char* name, double valu
     if (!h || !name) return GPHIP_ERR_ARG;
     std::lock_guard<std::recursive_mutex> lk(h->mu);
     const int v = (int)value;
-    if (!strcmp(name, "sparse_chunk")) { if (v < 0) return sfail(h, GPHIP_ERR_ARG, "sparse_chunk < 0"); h->chunk = v; return GPHIP_OK; }
-    if (!strcmp(name, "sparse_split")) { if (v < 0) return sfail(h, GPHIP_ERR_ARG, "sparse_split < 0"); h->split = v; return GPHIP_OK; }
-    if (!strcmp(name, "profile")) { h->profile = v; return GPHIP_OK; }
-    if (!strcmp(name, "sparse_joint_split")) { if (v < 0) return sfail(h, GPHIP_ERR_ARG, "sparse_joint_split < 0"); h->joint_split = v; return GPHIP_OK; }
-    if (!strcmp(name, "sparse_batch_slots")) { if (v < 0) return sfail(h, GPHIP_ERR_ARG, "sparse_batch_slots < 0"); h->batch_slots = v; return GPHIP_OK; }
-    if (!strcmp(name, "sparse_samples_chunk")) { if (v < 0) return sfail(h, GPHIP_ERR_ARG, "sparse_samples_chunk < 0"); h->samples_chunk = v; return GPHIP_OK; }
-    if (!strcmp(name, "sparse_samples_handover")) { h->samples_handover = v != 0; return GPHIP_OK; }
-    if (!strcmp(name, "sparse_pw_fused")) { h->pw_fused = v != 0; return GPHIP_OK; }
+    const SparseOption* o = sparse_option(name);
+    if (o && !(o->kind & OPT_RESULT)) {
+        if ((o->kind & OPT_NONNEG) && v < 0) return sfail(h, GPHIP_ERR_ARG, std::string(name) + " < 0");
+        h->*(o->field) = (o->kind & OPT_FLAG) ? (v != 0) : v;
+        return GPHIP_OK;
+    }
     int rc = gphip_set_option(h->u, name, value);
     if (!rc) rc = gphip_set_option(h->b, name, value);
     if (rc) return sfail(h, rc, "unknown option");
@@ -1521,21 +1508,8 @@ int gphip_sparse_get_option(gphip_sparse_handle h, const char* name, double* val
     std::lock_guard<std::recursive_mutex> lk(h->mu);
     for (int k = 0; k < PH_COUNT; ++k)
         if (!strcmp(name, SPARSE_PHASE_OPTION[k])) { *value = h->ms[k]; return GPHIP_OK; }
-    if (!strcmp(name, "sparse_chunk")) { *value = h->chunk; return GPHIP_OK; }
-    if (!strcmp(name, "sparse_split")) { *value = h->split; return GPHIP_OK; }
-    if (!strcmp(name, "profile")) { *value = h->profile; return GPHIP_OK; }
-    if (!strcmp(name, "last_jitter")) { *value = h->last_jitter; return GPHIP_OK; }
-    if (!strcmp(name, "grad_analytic")) { *value = h->grad_analytic; return GPHIP_OK; }
-    if (!strcmp(name, "last_sparse_chunk")) { *value = (double)h->last_chunk; return GPHIP_OK; }
-    if (!strcmp(name, "last_sparse_nsplit")) { *value = h->last_nsplit; return GPHIP_OK; }
-    if (!strcmp(name, "sparse_batch_slots")) { *value = h->batch_slots; return GPHIP_OK; }
-    if (!strcmp(name, "last_sparse_slots")) { *value = h->last_slots; return GPHIP_OK; }
-    if (!strcmp(name, "sparse_samples_chunk")) { *value = h->samples_chunk; return GPHIP_OK; }
-    if (!strcmp(name, "last_sparse_samples_chunk")) { *value = (double)h->last_samples_chunk; return GPHIP_OK; }
-    if (!strcmp(name, "sparse_samples_handover")) { *value = h->samples_handover; return GPHIP_OK; }
-    if (!strcmp(name, "sparse_pw_fused")) { *value = h->pw_fused; return GPHIP_OK; }
-    if (!strcmp(name, "sparse_joint_split")) { *value = h->joint_split; return GPHIP_OK; }
-    if (!strcmp(name, "last_sparse_joint_nsplit")) { *value = h->joint_nsplit; return GPHIP_OK; }
+    if (const SparseOption* o = sparse_option(name)) { *value = h->*(o->field); return GPHIP_OK; }
+    if (!strcmp(name, "last_jitter")) { *value = h->last_jitter; return GPHIP_OK; }         // (the one result that is no integer)
     const int rc = gphip_get_option(h->u, name, value);
     return rc ? sfail(h, rc, "unknown option") : GPHIP_OK;
 }

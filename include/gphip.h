@@ -468,6 +468,9 @@ int gphip_factor_bytes(gphip_handle h, int member, double* bytes);
  *
  * prediction at x* with v1 = L_u^-1 k(Z, x*), v2 = L_B^-1 v1:
  *     mean = m(x*) + v2^T c            var = k(x*, x*) [+ sn^2 unless latent] - |v1|^2 + sn^2 |v2|^2
+ * gphip_sparse_predict runs the prediction pass of gphip_sparse_predict_samples (below) on the one slot of
+ * the resident fit: per chunk of test points one kernel hands V1 to the context of B and takes |v1|^2 on the way, B's stream waits
+ * for an event, not the host, and one download is scattered into mean and var.
  *
  * A separate opaque type: no other entry point of this header takes a sparse object.  Every named and composed kernel and the
  * run-time compiled ones (gphip_sparse_create_custom: arguments as gphip_create_custom), zero and constant mean (a mean and a
@@ -617,13 +620,16 @@ int gphip_factor_bytes(gphip_handle h, int member, double* bytes);
  *                   strips of the last chunk of the last call (of its last group).
  *   "sparse_batch_slots"  most rows gphip_sparse_bound_batch / gphip_sparse_predict_samples evaluate together in one group; 0
  *                   (default) = by the group rule above.  "last_sparse_slots" (read-only): rows in the last group of the last call.
- *   "sparse_samples_chunk"  test points per pass of gphip_sparse_predict_samples; 0 (default) = by the rule: at most 2048, the
- *                   group's slots x points x m_pad elements within ~8 GiB in both contexts, halved while the buffers do not fit;
- *                   n = n points rounded up to 128, within the same caps.  "last_sparse_samples_chunk" (read-only): what the
- *                   last call used.
- *   "sparse_samples_handover"  1 (default): V1 reaches the context of B through sparse_handover_kernel (one read, one write, the
- *                   norms on the way); 0: through a device-to-device copy and a separate norm launch, the form it replaced (kept
- *                   for measurement, scripts/gpu_sparse_samples_time.py).
+ *   "sparse_samples_chunk"  test points per chunk of the prediction pass, which gphip_sparse_predict[_pw] (the one slot of the
+ *                   resident fit) and gphip_sparse_predict_samples[_pw] (the slots of a group) both run; 0 (default) = by the
+ *                   caller's rule.  predict_samples: at most 2048, the group's slots x points x m_pad elements within ~8 GiB in
+ *                   both contexts, halved while the buffers do not fit.  predict: at most 32768, points x m_pad elements within
+ *                   ~8 GiB, at least 2048, halved while they do not fit.  n = n points rounded up to 128, within the same caps.
+ *                   "last_sparse_samples_chunk" (read-only): what the last of these calls used.
+ *   "sparse_samples_handover"  for both calls.  1 (default): V1 reaches the context of B through sparse_handover_kernel (one
+ *                   read, one write, the norms on the way); 0: through a device-to-device copy and a separate norm launch, the
+ *                   form it replaced (kept for measurement, scripts/gpu_sparse_samples_time.py).  The two return the same bytes.
+ *                   Either way B's stream waits for an event of K_uu's stream, not the host.
  *   "sparse_pw_fused"  how the _pw calls apply the weights 1 / nu_i.  1: inside the accumulation kernel, a weight per contraction
  *                   index ahead of the MFMA; 0 (default): a plain kernel scales the chunk of V and the residual row by
  *                   sqrt(1 / nu_i) in place and the unweighted accumulation follows.  The fused form is the faster one at four of the
@@ -636,9 +642,10 @@ int gphip_factor_bytes(gphip_handle h, int member, double* bytes);
  *                   of gphip_sparse_bound_grad_inducing also "ms_grad_inducing" (the column-wise reductions for dF/dZ).
  *                   of the joint prediction calls "ms_joint_v" (V1 and V2), "ms_joint_build" (K(X*, X*)), "ms_joint_downdate" (the
  *                   two-segment downdate and its strip reduction) and "ms_joint_factor" (Sigma's factorisation; draws / logpdf).
- *                   of gphip_sparse_predict_samples, next to the bound's five, "ms_samples_v1" (k(X*, Z) and u's substitution),
- *                   "ms_samples_handover" (V1 to b and |v1|^2), "ms_samples_v2" (b's substitution) and "ms_samples_reduce"
- *                   (the dots and norms of v2 and the finishing kernel), summed over groups and chunks.
+ *                   of gphip_sparse_predict[_pw] and gphip_sparse_predict_samples[_pw] (there next to the bound's five)
+ *                   "ms_samples_v1" (k(X*, Z) and u's substitution), "ms_samples_handover" (V1 to b and |v1|^2), "ms_samples_v2"
+ *                   (b's substitution) and "ms_samples_reduce" (the dots and norms of v2 and the finishing kernel), summed over
+ *                   groups and chunks; each of these calls resets the four, no other call touches them.
  *   "sparse_joint_split"  strips the joint prediction's downdate cuts the stacked index of 2 m_pad columns into; 0 (default) = by
  *                   gphip_predict_cov's split rule (output tiles x strips >= 2 per CU, strips of whole 128-columns; a strip may
  *                   span the V1 / V2 boundary), n = n strips.  "last_sparse_joint_nsplit" (read-only): strips of the last call.

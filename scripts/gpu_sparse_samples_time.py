@@ -60,6 +60,7 @@ def main():
             return mu, var
 
         def loop():
+            h.set_option("sparse_samples_handover", 1)          # (the one-theta call runs the same pass and reads the option too)
             mu, var = np.empty((S, M)), np.empty((S, M))
             for s, th in enumerate(Th):
                 assert h.fit(th, JITTER) == 0

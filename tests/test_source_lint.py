@@ -101,6 +101,27 @@ def test_sparse_bound_has_one_forward_pass_and_owned_phase_records():
     assert all(re.fullmatch(r"\w+\.harvest\(\)", m) for m in re.findall(r"[\w.>-]*\bharvest\b(?:\(\))?", rest)), "harvest outside the owner"
 
 
+def test_sparse_prediction_pass_and_chunk_head_exist_once():
+    # Prediction from a sparse object is one pass (sparse_predict_pass: the one-theta call and the call over samples are its two
+    # callers) and a chunk of data points has one head (sparse_chunk_head: the group evaluator and the gradient's recomputed
+    # chunks), DESIGN.md sections 8d and 8h.  What they share with the exact path belongs to the exact path: the strip rule, the
+    # launch of predict_partial_kernel and the choice between the dataflow launch and the batched GEMM substitution.
+    host = {name: _code(os.path.join(CSRC, name)) for name in sorted(os.listdir(CSRC)) if name.endswith((".hip", ".inc"))}
+    everything = "\n".join(host.values())
+    assert len(re.findall(r"\bpredict_partial_kernel\b", everything)) == 1               # (defined in gp_kernels.h)
+    assert len(re.findall(r"hipLaunchKernelGGL\(\s*predict_partial_kernel\b", host["gphip.hip"])) == 1
+    assert len(re.findall(r"2048 \+", everything)) == 1                                  # the strip rule's literal
+    assert len(re.findall(r"\bsamples_forward_df\(", everything)) == 2                   # its definition and one call
+    code = host["gphip_sparse.inc"]
+    assert len(re.findall(r"\bsparse_predict_finish_kernel\b", code)) == 1               # (defined in gp_sparse.h)
+    for fn in ("sparse_stage_test_arrays", "sparse_queue_handover", "sparse_queue_resid", "sparse_queue_resid_pw"):
+        uses = re.findall(r"\b%s\b.{0,24}" % fn, code)              # its definition `int fn(gphip_sparse_ctx* h, ..` and its call sites
+        sites = [u for u in uses if not u.startswith(fn + "(gphip_sparse_ctx*")]
+        assert len(uses) == 2 and len(sites) == 1, (fn, uses)
+    for gone in ("sparse_partial_strips", "sparse_queue_partial", "sparse_queue_forward"):
+        assert gone not in everything, gone
+
+
 def test_strip_split_contraction_exists_once():
     # The joint downdate and the sparse accumulation are one device algorithm (gp_contract.h): tile-list
     # decode, thin-tile rule, two-stage software pipeline and the reduction of the strip partials.  A hand copy in a caller's
