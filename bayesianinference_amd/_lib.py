@@ -96,6 +96,7 @@ _SIGNATURES = {
     "gphip_predict_cov": (C.c_int, [_h, C.c_void_p, C.c_int64, C.c_int, _dp, _dp]),
     "gphip_predict_draws": (C.c_int, [_h, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_uint64, _dp, C.c_double, _dp, _ip]),
     "gphip_predict_logpdf": (C.c_int, [_h, C.c_void_p, C.c_int64, _dp, _dp, _ip]),
+    "gphip_predict_grad": (C.c_int, [_h, C.c_void_p, C.c_int64, _dp, _dp, _dp, _dp]),
     "gphip_loglik_batch_pw": (C.c_int, [_h, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _ip]),
     "gphip_fit_pw": (C.c_int, [_h, _dp, C.c_int, _dp, _dp, _ip]),
     "gphip_predict_pw": (C.c_int, [_h, C.c_void_p, C.c_int64, _dp, _dp, _dp, _dp]),
@@ -137,6 +138,7 @@ _SIGNATURES = {
     "gphip_sparse_bound_grad_inducing": (C.c_int, [_h, _dp, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _ip]),
     "gphip_sparse_fit": (C.c_int, [_h, _dp, C.c_int, C.c_double, _ip]),
     "gphip_sparse_predict": (C.c_int, [_h, C.c_void_p, C.c_int64, C.c_int, _dp, _dp]),
+    "gphip_sparse_predict_grad": (C.c_int, [_h, C.c_void_p, C.c_int64, _dp, _dp, _dp, _dp]),
     "gphip_sparse_predict_samples": (C.c_int, [_h, _dp, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_int64, C.c_int, _dp, _dp, _dp, _ip]),
     "gphip_sparse_bound_pw": (C.c_int, [_h, _dp, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _ip]),
     "gphip_sparse_bound_batch_pw": (C.c_int, [_h, _dp, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _ip]),
@@ -555,6 +557,17 @@ class Handle:
         self._check(self._lib.gphip_predict_logpdf(self._h, Xs.ctypes.data, M, _d(ys), C.byref(out), C.byref(info)))
         return out.value, info.value
 
+    def predict_grad(self, Xs, variance: bool = True):
+        """Gradients of the prediction in the test inputs (gphip_predict_grad): (mean[M], var[M], dmean[M, d], dvar[M, d]);
+        variance=False skips the backward substitution and returns dvar = None."""
+        Xs = self._test_points(Xs)
+        M = Xs.shape[0]
+        mean, var, dmean = np.zeros(M), np.zeros(M), np.zeros((M, self.d))
+        dvar = np.zeros((M, self.d)) if variance else None
+        self._check(self._lib.gphip_predict_grad(self._h, Xs.ctypes.data, M, _d(mean), _d(var), _d(dmean),
+                                                 _d(dvar) if variance else None))
+        return mean, var, dmean, dvar
+
     def covariance(self, theta):
         """theta[p] -> K[N, N]; Theta[B, p] -> K[B, N, N] (the Listable form, BGP:59)."""
         th = np.ascontiguousarray(np.asarray(theta, dtype=np.float64))
@@ -687,6 +700,7 @@ SPARSE_GRAD_PHASES = ("ms_grad_small", "ms_grad_weights", "ms_grad_backward", "m
 SPARSE_ZGRAD_PHASES = ("ms_grad_inducing",)
 SPARSE_JOINT_PHASES = ("ms_joint_v", "ms_joint_build", "ms_joint_downdate", "ms_joint_factor")
 SPARSE_SAMPLES_PHASES = ("ms_samples_v1", "ms_samples_handover", "ms_samples_v2", "ms_samples_reduce")
+SPARSE_PGRAD_PHASES = ("ms_pgrad_backward", "ms_pgrad_reduce")
 
 
 class SparseHandle:
@@ -851,6 +865,17 @@ class SparseHandle:
         mean, var = np.zeros(M), np.zeros(M)
         self._check(self._lib.gphip_sparse_predict(self._h, Xs.ctypes.data, M, 1 if latent else 0, _d(mean), _d(var)))
         return mean, var
+
+    def predict_grad(self, Xs, variance: bool = True):
+        """Gradients of the resident fit's prediction in the test inputs (gphip_sparse_predict_grad): (mean[M], var[M],
+        dmean[M, d], dvar[M, d]); var is that of a noisy observation; variance=False returns dvar = None."""
+        Xs = self._test_points(Xs)
+        M = Xs.shape[0]
+        mean, var, dmean = np.zeros(M), np.zeros(M), np.zeros((M, self.d))
+        dvar = np.zeros((M, self.d)) if variance else None
+        self._check(self._lib.gphip_sparse_predict_grad(self._h, Xs.ctypes.data, M, _d(mean), _d(var), _d(dmean),
+                                                        _d(dvar) if variance else None))
+        return mean, var, dmean, dvar
 
     def predict_samples(self, Thetas, Xs, jitter: float = -1.0, latent: bool = False, bound: bool = False):
         """gphip_sparse_predict_samples: (mean[S, M], var[S, M], info[S]) -- with bound=True also F[S] -- at Xs for the rows of

@@ -283,6 +283,13 @@ struct gphip_ctx {
     Buf dJOut;                                        // double: dense covariance + mean / the draws' mean
     int joint_split = 0;                              // option: strips of the downdate's contraction (0 = by the split rule)
     int joint_nsplit = 0;                             // read-only: strips the last downdate used
+    // gradients in the test inputs (gphip_xgrad.inc)
+    Buf dXgPart;                                      // double: the strip partials of predict_xgrad_kernel
+    Buf dXgOut;                                       // double [2][mpad d]: dmean, dvar of the current chunk
+    int predict_grad_split = 0;                       // option: strips over the contraction points (0 = by the strip rule)
+    int predict_grad_nsplit = 0;                      // read-only: strips the last reduction used
+    int predict_grad_chunk = 0;                       // option: test points per chunk (0 = by the chunk rule)
+    int predict_grad_chunk_last = 0;                  // read-only: rows per chunk of the last call
 };
 
 namespace {
@@ -3726,6 +3733,8 @@ int* option_slot(gphip_ctx* h, const char* name) {
         {"bcast_chunks", &gphip_ctx::bcast_chunks}, {"bcast_two_hop", &gphip_ctx::bcast_two_hop}, {"dist_panel_df", &gphip_ctx::dist_panel_df}, {"dist_owner_yield", &gphip_ctx::dist_owner_yield},
         {"debug_fail_alloc", &gphip_ctx::debug_fail_alloc}, {"debug_fail_hip", &gphip_ctx::debug_fail_hip},
         {"debug_abort_word", &gphip_ctx::debug_abort_word}, {"joint_split", &gphip_ctx::joint_split}, {"last_joint_nsplit", &gphip_ctx::joint_nsplit},
+        {"predict_grad_split", &gphip_ctx::predict_grad_split}, {"last_predict_grad_nsplit", &gphip_ctx::predict_grad_nsplit},
+        {"predict_grad_chunk", &gphip_ctx::predict_grad_chunk}, {"last_predict_grad_chunk", &gphip_ctx::predict_grad_chunk_last},
     };
     // fault injection ("debug_*") exists for the test-suite only: the names resolve in a process that was started with
     // GPHIP_TEST_HOOKS=1 and nowhere else (not through GPHIP_OPTIONS either: apply_env_options skips them)
@@ -3833,4 +3842,5 @@ int gphip_sync(gphip_handle h) {
 #include "gphip_sampler.inc"
 #include "gphip_joint.inc"
 #include "gphip_loo.inc"
+#include "gphip_xgrad.inc"
 #include "gphip_sparse.inc"

@@ -30,6 +30,9 @@
 //   the way, b's stream waits for an event of u's, v2 = L_B^-1 v1 by b's substitution, the exact path's partial launch against c
 //   and one finishing kernel.  gphip_sparse_predict[_pw] is the pass for the ONE slot of the resident fit,
 //   gphip_sparse_predict_samples[_pw] the pass after every group.
+// Gradients in the test inputs (gphip_sparse_predict_grad, DESIGN.md section 8j): the pass for the one slot of the resident fit
+//   with one more step per chunk (sparse_queue_pgrad): b substitutes V2 backward and forms V1 - sn^2 (that), an event hands it to u,
+//   u substitutes backward with L_u and runs the exact path's reduction kernel (queue_xgrad) against the scaled Z.
 // Joint prediction (gphip_sparse_predict_cov / _draws / _logpdf, DESIGN.md section 8g): all M rows of V1 = L_u^-1 k(Z, X*) and
 //   V2 = L_B^-1 V1 side by side in u's dV, the rhs-row operand -c / sn^2 in u's dJZ; u owns the child context of the exact
 //   path (u->joint, gphip_joint.inc: training points X*, K(X*, X*) by the direct build) and the two-segment downdate_kernel turns
@@ -39,20 +42,22 @@
 
 // The phases timed by HIP events while option "profile" is on, and the options that read them (gphip_sparse_get_option).
 // PH_KUU_FACTOR .. PH_GRAD_INDUCING are reset by every evaluation of the bound, PH_JOINT_V .. PH_JOINT_FACTOR by every joint
-// prediction, PH_SAMPLES_VU .. by every prediction pass: gphip_sparse_predict and gphip_sparse_predict_samples (which also
-// evaluates the bound).
+// prediction, PH_SAMPLES_VU .. by every prediction pass: gphip_sparse_predict, gphip_sparse_predict_grad (the only one that fills
+// PH_PGRAD_*) and gphip_sparse_predict_samples (which also evaluates the bound).
 enum SparsePhaseId {
     PH_KUU_FACTOR, PH_CROSS, PH_FORWARD, PH_ACCUMULATE, PH_B_FACTOR,                               // the bound
     PH_GRAD_SMALL, PH_GRAD_WEIGHTS, PH_GRAD_BACKWARD, PH_GRAD_REDUCE, PH_GRAD_INDUCING,            // its gradients
     PH_JOINT_V, PH_JOINT_BUILD, PH_JOINT_DOWNDATE, PH_JOINT_FACTOR,                                // joint prediction
     PH_SAMPLES_VU, PH_SAMPLES_HANDOVER, PH_SAMPLES_VB, PH_SAMPLES_REDUCE,                          // prediction over samples
+    PH_PGRAD_BACKWARD, PH_PGRAD_REDUCE,                                                            // gradients in the test inputs
     PH_COUNT
 };
 static const char* const SPARSE_PHASE_OPTION[] = {
     "ms_kuu_factor", "ms_cross", "ms_forward", "ms_accumulate", "ms_b_factor",
     "ms_grad_small", "ms_grad_weights", "ms_grad_backward", "ms_grad_reduce", "ms_grad_inducing",
     "ms_joint_v", "ms_joint_build", "ms_joint_downdate", "ms_joint_factor",
-    "ms_samples_v1", "ms_samples_handover", "ms_samples_v2", "ms_samples_reduce"};
+    "ms_samples_v1", "ms_samples_handover", "ms_samples_v2", "ms_samples_reduce",
+    "ms_pgrad_backward", "ms_pgrad_reduce"};
 static_assert(sizeof SPARSE_PHASE_OPTION / sizeof SPARSE_PHASE_OPTION[0] == PH_COUNT, "one option name per phase");
 
 struct gphip_sparse_ctx {
@@ -83,6 +88,7 @@ struct gphip_sparse_ctx {
     int batch_slots = 0;                       // gphip_sparse_bound_batch / _predict_samples: most thetas per group (0 = by the group rule)
     int samples_chunk = 0;                     // the prediction pass: most test points per chunk (0 = by the caller's rule)
     int samples_handover = 1;                  // the prediction pass: 1 = sparse_handover_kernel, 0 = copy + norm launch (measurement)
+    int pgrad_refine = 1;                      // gphip_sparse_predict_grad: 1 = the backward substitution with L_u refines its diagonal solves
     int pw_fused = 0;                          // the _pw calls: 1 = the weight inside the contraction, 0 = sparse_scale_rows_kernel + the unweighted one
                                                // (the default since the measurement of DESIGN.md section 8i: fused lost at the largest size)
     // read-only results of the last call
@@ -96,7 +102,8 @@ struct gphip_sparse_ctx {
     double ms[PH_COUNT] = {};                  // K_uu factor, cross build, forward substitution, accumulation, B factor;
                                                // gradient: small m x m work, weights, backward substitution, reductions, the reduction in Z;
                                                // joint prediction: V1 and V2, K(X*, X*), the downdate, the factorisation of Sigma;
-                                               // prediction over samples: V1, the handover to b, V2, the reductions
+                                               // prediction over samples: V1, the handover to b, V2, the reductions;
+                                               // gradients in the test inputs: the backward substitutions, the reduction
     // the resident fit
     bool fitted = false;
     bool pw_fit = false;                       // the fit was made with a point-dependent array: B = I + V W V^T, no joint prediction
@@ -948,6 +955,76 @@ int sparse_eval_batch(gphip_sparse_ctx* h, const double* Theta, int B, int p, do
     return GPHIP_OK;
 }
 
+// Gradients in the test inputs (gphip_sparse_predict_grad, DESIGN.md section 8j): what the prediction pass adds per chunk for the
+// ONE slot of the resident fit.  dmean / dvar: the call's row-major M x d outputs (dvar null: not wanted).
+struct SparseXGrad { double* dmean; double* dvar; };
+
+// a_mu = L_u^-T L_B^-T c into u->dAlpha, once per call: b's single-vector backward launch (queue_alpha: c sits in b's rhs row), then
+// u's on that vector (the row route where the launch is unavailable); b hands over through an event.
+template <typename T>
+int sparse_queue_amu(gphip_sparse_ctx* h) {
+    gphip_ctx *u = h->u, *b = h->b;
+    const int64_t mpm = u->Npad;
+    int rc;
+    HIPCHK(b->dAlpha.grow((size_t)mpm * sizeof(T)));
+    HIPCHK(u->dAlpha.grow((size_t)mpm * sizeof(T)));
+    if ((rc = queue_alpha<T>(b))) return sfail(h, rc, b->err);
+    hipEvent_t e = get_event(u);
+    const hipError_t e1 = hipEventRecord(e, b->stream), e2 = hipStreamWaitEvent(u->stream, e, 0);
+    u->pool.push_back(e);                      // (the wait holds what was recorded)
+    HIPCHK(e1);
+    HIPCHK(e2);
+    if (trsv_ok(u, 1)) {
+        T *z = trsv_input<T>(u), *x = nullptr;
+        HIPCHK(hipMemcpyAsync(z, b->dAlpha.p, (size_t)mpm * sizeof(T), hipMemcpyDeviceToDevice, u->stream));
+        rc = queue_trsv_fill<T>(u, 1, 1);
+        if (!rc) rc = queue_trsv<T>(u, z, 0, 1, true, &x);
+        if (rc) return sfail(h, rc, u->err);
+        HIPCHK(hipMemcpyAsync(u->dAlpha.p, x, (size_t)mpm * sizeof(T), hipMemcpyDeviceToDevice, u->stream));
+        return GPHIP_OK;
+    }
+    HIPCHK(hipMemsetAsync(u->dV.p, 0, (size_t)TB * mpm * sizeof(T), u->stream));
+    HIPCHK(hipMemcpy2DAsync(u->dV.p, (size_t)TB * sizeof(T), b->dAlpha.p, sizeof(T), sizeof(T), (size_t)mpm, hipMemcpyDeviceToDevice, u->stream));
+    queue_backward_rows<T>(u, TB);
+    HIPCHK(hipMemcpy2DAsync(u->dAlpha.p, sizeof(T), u->dV.p, (size_t)TB * sizeof(T), sizeof(T), (size_t)mpm, hipMemcpyDeviceToDevice, u->stream));
+    return GPHIP_OK;
+}
+
+// One chunk of the gradients, after the pass has left V1 in u's dV and V2 in b's: b's stream takes V2 to L_B^-T V2 and forms
+// V1 - sn^2 (that) in place, hands it to u through the event `back`, u's stream substitutes with L_u (W = L_u^-T (..), refined
+// unless option "sparse_pgrad_refine" = 0), reduces against the scaled Z and downloads the chunk's rows.
+template <typename T>
+int sparse_queue_pgrad(gphip_sparse_ctx* h, const SparseXGrad& xg, int64_t m0, int64_t mc, int64_t mpad, hipEvent_t back, SparsePhases& ph) {
+    gphip_ctx *u = h->u, *b = h->b;
+    int rc;
+    if (xg.dvar) {
+        {
+            SparseScope ps(ph, PH_PGRAD_BACKWARD, b->stream);
+            if ((rc = queue_backward_rows<T>(b, mpad))) return sfail(h, rc, b->err);
+            const long n = (long)mpad * u->Npad;
+            hipLaunchKernelGGL(sparse_xgrad_combine_kernel<T>, dim3((unsigned)std::min<long>((n + 255) / 256, 4096)), dim3(256), 0, b->stream,
+                               (const T*)u->dV.p, (T*)b->dV.p, n, h->sn2_fit);
+        }
+        HIPCHK(hipEventRecord(back, b->stream));
+        HIPCHK(hipStreamWaitEvent(u->stream, back, 0));
+        {
+            SparseScope ps(ph, PH_PGRAD_BACKWARD, u->stream);
+            rc = h->pgrad_refine ? queue_backward_rows<T>(u, mpad, b->dV.p, h->dLd.p, h->dRes.p) : queue_backward_rows<T>(u, mpad, b->dV.p);
+            if (rc) return sfail(h, rc, u->err);
+        }
+    }
+    {
+        SparseScope ps(ph, PH_PGRAD_REDUCE, u->stream);
+        if ((rc = queue_xgrad<T>(u, b->dV.p, u->dAlpha.p, mc, mpad, xg.dvar != nullptr, u->predict_grad_split, &u->predict_grad_nsplit)))
+            return sfail(h, rc, u->err);
+    }
+    const int64_t d = u->d;
+    const double* out = u->dXgOut.as<double>();
+    HIPCHK(hipMemcpyAsync(xg.dmean + m0 * d, out, (size_t)(mc * d) * 8, hipMemcpyDeviceToHost, u->stream));
+    if (xg.dvar) HIPCHK(hipMemcpyAsync(xg.dvar + m0 * d, out + mpad * d, (size_t)(mc * d) * 8, hipMemcpyDeviceToHost, u->stream));
+    return GPHIP_OK;
+}
+
 // The prediction pass of gphip_sparse_predict[_pw] and gphip_sparse_predict_samples[_pw] (DESIGN.md section 8h): mean and variance
 // at the M test points X for the nb slots whose factors u and b hold, MC points at a time, every launch with the slot as its last
 // grid index:
@@ -959,15 +1036,17 @@ int sparse_eval_batch(gphip_sparse_ctx* h, const double* Theta, int B, int p, do
 // and one staged download per chunk, which the host scatters: row s to mean / var + s stride.  resident: the factors are the fit's
 // (one slot).  Else u_factored / b_factored: every slot has a factor there -- a launch that spin-waits (the dataflow substitution)
 // runs on a context only then (queue_forward_slots).  pwt: nb rows of M values of m(x*) and nu(x*), which take the place of mu and
-// sn^2 in the finishing kernel.  info (null: every row is good): a row whose info is not 0 gets NaN.
+// sn^2 in the finishing kernel.  info (null: every row is good): a row whose info is not 0 gets NaN.  xg (gphip_sparse_predict_grad,
+// the resident slot only): every chunk goes on to the gradients in its test points (sparse_queue_pgrad) before it is downloaded.
 int sparse_predict_pass(gphip_sparse_ctx* h, const double* X, int64_t M, int64_t MC, int nb, bool resident, bool u_factored, bool b_factored,
-                        const SparsePw& pwt, int latent, double* mean, double* var, int64_t stride, const int* info, SparsePhases& ph) {
+                        const SparsePw& pwt, int latent, double* mean, double* var, int64_t stride, const int* info, SparsePhases& ph,
+                        const SparseXGrad* xg = nullptr) {
     gphip_ctx *u = h->u, *b = h->b;
     const double qnan = std::nan("");
     const int64_t mpm = u->Npad;
     int rc = GPHIP_OK;
     std::vector<double> xt, hm, hv;
-    struct Handed { gphip_ctx* u; hipEvent_t e; ~Handed() { u->pool.push_back(e); } } handed{u, get_event(u)};
+    struct Handed { gphip_ctx* u; hipEvent_t e; ~Handed() { if (e) u->pool.push_back(e); } } handed{u, get_event(u)}, back{u, xg ? get_event(u) : nullptr};
     for (int64_t m0 = 0; m0 < M; m0 += MC) {
         const int64_t mc = std::min(MC, M - m0);
         int64_t mpad = 0;
@@ -1012,6 +1091,7 @@ int sparse_predict_pass(gphip_sparse_ctx* h, const double* X, int64_t M, int64_t
         hv.resize((size_t)nb * mpad);
         HIPCHK(hipMemcpyAsync(hm.data(), b->dMean.p, hm.size() * 8, hipMemcpyDeviceToHost, b->stream));
         HIPCHK(hipMemcpyAsync(hv.data(), b->dVar.p, hv.size() * 8, hipMemcpyDeviceToHost, b->stream));
+        if (xg && (rc = DISPATCH(h, sparse_queue_pgrad, h, *xg, m0, mc, mpad, back.e, ph))) return rc;
         if ((rc = complete_call(b))) return sfail(h, rc, b->err);      // (b's stream waited for u's: both are idle)
         if ((rc = complete_call(u))) return sfail(h, rc, u->err);      // (the abort word of u's substitution)
         for (int s = 0; s < nb; ++s) {
@@ -1216,6 +1296,7 @@ const SparseOption* sparse_option(const char* name) {
         {"profile", &gphip_sparse_ctx::profile, 0}, {"sparse_joint_split", &gphip_sparse_ctx::joint_split, OPT_NONNEG},
         {"sparse_batch_slots", &gphip_sparse_ctx::batch_slots, OPT_NONNEG}, {"sparse_samples_chunk", &gphip_sparse_ctx::samples_chunk, OPT_NONNEG},
         {"sparse_samples_handover", &gphip_sparse_ctx::samples_handover, OPT_FLAG}, {"sparse_pw_fused", &gphip_sparse_ctx::pw_fused, OPT_FLAG},
+        {"sparse_pgrad_refine", &gphip_sparse_ctx::pgrad_refine, OPT_FLAG},
         {"grad_analytic", &gphip_sparse_ctx::grad_analytic, OPT_RESULT}, {"last_sparse_chunk", &gphip_sparse_ctx::last_chunk, OPT_RESULT},
         {"last_sparse_nsplit", &gphip_sparse_ctx::last_nsplit, OPT_RESULT}, {"last_sparse_slots", &gphip_sparse_ctx::last_slots, OPT_RESULT},
         {"last_sparse_samples_chunk", &gphip_sparse_ctx::last_samples_chunk, OPT_RESULT},
@@ -1417,6 +1498,32 @@ int gphip_sparse_predict_pw(gphip_sparse_handle h, const void* Xs, int64_t M, in
     // (the fit's one slot: mu, B's sn^2, k(x, x) and the noise of the fit are slot 0 of dPar since the evaluation)
     return sparse_predict_pass(h, static_cast<const double*>(Xs), M, MC, 1, true, true, true, SparsePw{mean_test, nugget_test}, latent, mean, var,
                                M, nullptr, ph);
+}
+
+int gphip_sparse_predict_grad(gphip_sparse_handle h, const void* Xs, int64_t M, double* mean, double* var, double* dmean, double* dvar) {
+    if (!h || !Xs || !dmean) return sfail(h, GPHIP_ERR_ARG, "null argument");
+    if (M < 1) return sfail(h, GPHIP_ERR_DIM, "M < 1");
+    std::lock_guard<std::recursive_mutex> lk(h->mu);
+    gphip_ctx *u = h->u, *b = h->b;
+    if (!h->fitted || !has_fit(u) || !has_fit(b)) return sfail(h, GPHIP_ERR_STATE, "gphip_sparse_predict_grad before a successful gphip_sparse_fit");
+    if (h->custom) return sfail(h, GPHIP_ERR_UNSUPPORTED, "no gradient in the test inputs for a run-time compiled covariance function");
+    if (h->pw_fit) return sfail(h, GPHIP_ERR_UNSUPPORTED, "gphip_sparse_predict_grad after a fit with a point-dependent nugget / mean array");
+    HIPCHK(hipSetDevice(h->device));
+    int64_t MC = 0;                            // the exact call's chunk rule on u; b's dV takes the same rows
+    int rc = xgrad_chunk(u, M, &MC);
+    if (rc) { (void)hipGetLastError(); return sfail(h, rc, "no device memory for the test points' V: " + u->err); }
+    if ((rc = ensure_vbuf(b, MC))) { (void)hipGetLastError(); return sfail(h, rc, "no device memory for the test points' V: " + b->err); }
+    h->last_samples_chunk = (int)MC;
+    HIPCHK(h->dLd.grow((size_t)u->Nt * TS * h->es));
+    HIPCHK(h->dRes.grow((size_t)MC * TB * h->es));
+    sparse_reset_phases(h, PH_SAMPLES_VU, PH_COUNT);
+    SparsePhases ph(h);
+    if ((rc = DISPATCH(h, sparse_queue_amu, h))) return rc;
+    std::vector<double> own_mean, own_var;     // (the pass always downloads both)
+    if (!mean) { own_mean.resize((size_t)M); mean = own_mean.data(); }
+    if (!var) { own_var.resize((size_t)M); var = own_var.data(); }
+    const SparseXGrad xg{dmean, dvar};
+    return sparse_predict_pass(h, static_cast<const double*>(Xs), M, MC, 1, true, true, true, SparsePw{}, 0, mean, var, M, nullptr, ph, &xg);
 }
 
 int gphip_sparse_predict_samples(gphip_sparse_handle h, const double* Thetas, int S, int p, double jitter, const void* Xs, int64_t M,

@@ -554,6 +554,60 @@ def predictJointFromGaussianProcess(examples, pts, kernel, theta, meanFunction=N
     return {"Points": P, "Mean": mean, "Covariance": cov}
 
 
+def predictGradientFromGaussianProcess(obj_or_examples, pts, kernel=None, theta=None, meanFunction=None):
+    """How the prediction changes when the test point moves (gphip_predict_grad; no reference counterpart).  The two forms of
+    predictFromGaussianProcess:
+      predictGradientFromGaussianProcess((X, Y), pts, kernel, theta[, meanFunction])      duplicates in pts are removed first;
+          {"Points" [M,d], "Mean" [M], "StandardDeviation" [M], "MeanGradient" [M,d], "VarianceGradient" [M,d]}
+      predictGradientFromGaussianProcess(obj, pts)     obj has "GaussianProcessData" and "Samples": the same arrays per
+          posterior sample ([S,M] / [S,M,d]) with "Weights" [S], from a host loop of fit + predict_grad over the samples
+          (samples whose covariance matrix does not factor give NaN rows).
+    Values are in the handle's units, as predictFromGaussianProcess returns them; the variance is that of a noisy observation
+    (its gradient is that of the latent variance).  None on bad data, a theta that does not factor, and for objects with a
+    callable nugget or mean function (dm/dx of a host function is unknown)."""
+    if isinstance(obj_or_examples, inferenceObject):
+        obj = obj_or_examples
+        if obj.failed or "GaussianProcessData" not in obj or "Samples" not in obj:
+            return None
+        mf = obj["GaussianProcessData"]["ModelFunctions"]
+        if callable(mf["NuggetFunction"]) or callable(mf["MeanFunction"]):
+            return None
+        P = dataNormalForm(pts)
+        if P is None or isinstance(P, tuple):
+            return None
+        handle = obj["GaussianProcessData"]["HIPHandle"]
+        points = np.array([s["Point"] for s in obj["Samples"]], dtype=np.float64)
+        weights = np.array([s["CrudePosteriorWeight"] for s in obj["Samples"]], dtype=np.float64)
+        return _predict_grad_samples(handle.fit, handle.predict_grad, points, weights, P)
+    P = dataNormalForm(pts)
+    if P is None or isinstance(P, tuple):
+        return None
+    _, first = np.unique(P, axis=0, return_index=True)
+    P = P[np.sort(first)]
+    handle = _direct_handle(obj_or_examples, kernel, theta, meanFunction)
+    if handle is None:
+        return None
+    try:
+        mean, var, dmean, dvar = handle.predict_grad(P)
+    finally:
+        handle.close()
+    with np.errstate(invalid="ignore"):
+        return {"Points": P, "Mean": mean, "StandardDeviation": np.sqrt(var), "MeanGradient": dmean, "VarianceGradient": dvar}
+
+
+def _predict_grad_samples(fit, predict_grad, points, weights, P):
+    """the per-sample arrays of the two predictGradient functions: fit(theta) -> info, predict_grad(P) -> the four arrays"""
+    S, (M, d) = len(points), P.shape
+    mean, var = np.full((S, M), np.nan), np.full((S, M), np.nan)
+    dmean, dvar = np.full((S, M, d), np.nan), np.full((S, M, d), np.nan)
+    for s, th in enumerate(points):
+        if fit(th) == 0:
+            mean[s], var[s], dmean[s], dvar[s] = predict_grad(P)
+    with np.errstate(invalid="ignore"):
+        return {"Points": P, "Weights": weights, "Mean": mean, "StandardDeviation": np.sqrt(var), "MeanGradient": dmean,
+                "VarianceGradient": dvar}
+
+
 def predictiveLogDensity(examples, heldout, kernel, theta, meanFunction=None):
     """log N(ys | mean, Covariance) of held-out data heldout = (Xs, ys) under the GP of (X, Y) at theta: the joint predictive
     log density (the correlations between the held-out points included).  None on bad data or a failed factorisation."""
@@ -1103,6 +1157,33 @@ def predictJointFromSparseGaussianProcess(obj, pts, theta):
         return None
     mean, cov = handle.predict_cov(P, latent=False)
     return {"Points": P, "Mean": mean, "Covariance": cov}
+
+
+def predictGradientFromSparseGaussianProcess(obj, pts, theta=None):
+    """predictGradientFromGaussianProcess for a sparse object (gphip_sparse_predict_grad): for one theta the direct form's dict,
+    or (theta=None) the per-sample arrays of a sampled object with "Weights", from a host loop of fit + predict_grad.  None
+    where the object is not a sparse GP object (or unsampled without a theta), on bad points, a theta whose fit fails, and for
+    objects with a callable nugget or mean function."""
+    if not isinstance(obj, inferenceObject) or obj.failed or "SparseGaussianProcessData" not in obj:
+        return None
+    if any(f is not None for f in _sparse_pointwise_functions(obj)):
+        return None
+    P = dataNormalForm(pts)
+    if P is None or isinstance(P, tuple):
+        return None
+    handle = obj["SparseGaussianProcessData"]["HIPHandle"]
+    fit = lambda th: handle.fit(np.asarray(th, dtype=np.float64).ravel(), obj["Jitter"])       # noqa: E731
+    if theta is not None:
+        out = _predict_grad_samples(fit, handle.predict_grad, np.atleast_2d(np.asarray(theta, dtype=np.float64))[:1], np.ones(1), P)
+        if not np.all(np.isfinite(out["Mean"][0])):
+            return None
+        return {"Points": P, "Mean": out["Mean"][0], "StandardDeviation": out["StandardDeviation"][0],
+                "MeanGradient": out["MeanGradient"][0], "VarianceGradient": out["VarianceGradient"][0]}
+    if "Samples" not in obj:
+        return None
+    points = np.array([s["Point"] for s in obj["Samples"]], dtype=np.float64)
+    weights = np.array([s["CrudePosteriorWeight"] for s in obj["Samples"]], dtype=np.float64)
+    return _predict_grad_samples(fit, handle.predict_grad, points, weights, P)
 
 
 def sparsePredictiveLogDensity(obj, heldout, theta):

@@ -219,6 +219,32 @@ int gphip_predict_draws(gphip_handle h, const void* Xs, int64_t M, int latent, i
 /* log N(ystar | mean, Sigma) with the noisy-observation Sigma (latent = 0): the joint predictive log density of held-out
  * data.  *info as gphip_loglik's (*out undefined if *info != 0). */
 int gphip_predict_logpdf(gphip_handle h, const void* Xs, int64_t M, const double* ystar, double* out, int* info);
+/* ---- Gradients of the predictive mean and variance in the TEST inputs (no reference counterpart): how the prediction of the
+ * current fit changes when x* moves -- what maximising an acquisition function, finding the optimum of the fitted surface and
+ * sensitivity analysis need.  With alpha = K^-1 (y - m), k*_i = k(x*, x_i) and w = K^-1 k* (an N-vector per test point):
+ *     dmean[t][c] = dmu /dx*_c  =     sum_i alpha_i dk(x*_t, x_i)/dx*_c
+ *     dvar [t][c] = dvar/dx*_c  = -2  sum_i w_i     dk(x*_t, x_i)/dx*_c        (dk(x*, x*)/dx* = 0: every family is stationary)
+ *     dk(a, b)/da_c = -sf^2 m2dg(r^2) (a_c - b_c) / l_c^2 per term, m2dg = -2 dg/dr^2; sums and products by the product rule.
+ * The constant mean and the noise sn^2 contribute nothing, so the gradient of the latent variance is the same: there is no
+ * `latent` argument.  Xs: row-major M x d fp64; dmean, dvar: row-major M x d.  mean, var (length M, each may be NULL) are
+ * gphip_predict's, to rounding.  dvar == NULL skips the backward substitution and the matrix-weighted sums: the call then costs
+ * what gphip_predict costs; dmean is the same bytes either way.
+ * On the device, per chunk of test points: V = L^-1 k(X, X*) as gphip_predict, mean / var from it when asked for, then V L^-1 in
+ * place by the route of gphip_solve (dvar only), then ONE reduction kernel evaluates every (test point, training point) pair
+ * once and accumulates both gradients in fp64 (csrc/gp_xgrad.h); alpha comes once per call from a single-vector backward
+ * substitution.  The strips over the training points are added in a fixed order, no atomics: two calls return the same bytes.
+ * The call never invalidates the fit (gphip_predict returns the same bytes before and after it) and works after anything that
+ * leaves a fit resident (gphip_fit, gphip_loglik_grad, gphip_loo).  fp64 and fp32 handles; the null kernel is answered on the
+ * host with zeros; a multi-device handle whose first device holds the whole factor computes there.
+ * Options: "predict_grad_split" n (0 = by the strip rule: at least two workgroups per compute unit while there are slabs of 64
+ * training points) forces n strips; "last_predict_grad_nsplit" (read-only) the strips the last reduction used;
+ * "predict_grad_chunk" n (0 = gphip_predict's chunk rule, halved beyond 2048 rows) = n test points per chunk, rounded up to
+ * 128; "last_predict_grad_chunk" (read-only).
+ * Statuses, all decided before any device work: NULL h / Xs / dmean GPHIP_ERR_ARG; M < 1 GPHIP_ERR_DIM; no successful fit
+ * GPHIP_ERR_STATE; GPHIP_ERR_UNSUPPORTED for a run-time compiled covariance function (it would need its dual-number program
+ * seeded in the coordinates, as gphip_sparse_bound_grad_inducing says), for a fit made by gphip_fit_pw with a non-NULL array
+ * (dm/dx of a host function is unknown) and for a sharded fit with replicate_factor = 0. */
+int gphip_predict_grad(gphip_handle h, const void* Xs, int64_t M, double* mean, double* var, double* dmean, double* dvar);
 /* ---- Leave-one-out cross-validation (Rasmussen & Williams, GPML section 5.4.2; no reference counterpart): how well the model
  * at theta predicts every training point from the other N - 1, from ONE factorisation.  With alpha = K^-1 (y - m) and
  * k_i = [K^-1]_ii:
@@ -428,7 +454,8 @@ int gphip_get_option(gphip_handle h, const char* name, double* value);
  * creates (for hosts that bind only the evaluation entry points, e.g. the LibraryLink shim). */
 
 /* Per-kernel-class timing, measured with HIP events on the handle's stream while "profile"=1.
- * class: 0 kbuild, 1 potrf, 2 trsm, 3 gemm (in-panel), 4 gemm/syrk (trailing), 5 total eval, 6 prediction epilogue.
+ * class: 0 kbuild, 1 potrf, 2 trsm, 3 gemm (in-panel), 4 gemm/syrk (trailing), 5 total eval, 6 prediction epilogue (the
+ * reductions of gphip_predict and the gradient reduction of gphip_predict_grad).
  * Returns accumulated milliseconds, launches, algorithmic flops and bytes since the last reset (class 4: flops =
  * m (m+1) nb per launch, SURVEY.md §8d -- not the tile-granular count the MFMA pipe executes). */
 #define GPHIP_NCLASS 7
@@ -612,6 +639,23 @@ int gphip_factor_bytes(gphip_handle h, int member, double* bytes);
  * There is no _pw form of the gradients or of the native sampler: the library cannot differentiate or call a host function of the
  * point.
  *
+ * gphip_sparse_predict_grad: the gradients of gphip_sparse_predict's mean and variance in the test inputs, the sparse form of
+ * gphip_predict_grad (same arguments, outputs and NULLs; var is that of a noisy observation, whose gradient is the latent one's).
+ * With v1 = L_u^-1 k(Z, x*), v2 = L_B^-1 v1 and s = sn^2:
+ *     a_mu = L_u^-T L_B^-T c   (an m-vector, once per call)        W = L_u^-T (V1 - s L_B^-T V2)   (m x M)
+ *     dmean[t][c] = sum_k (a_mu)_k dk(x*_t, z_k)/dx*_c             dvar[t][c] = -2 sum_k W_kt dk(x*_t, z_k)/dx*_c
+ * On the device it is the prediction pass of gphip_sparse_predict with one more step per chunk: B's stream substitutes V2
+ * backward and forms V1 - s (that) in place, hands the block to K_uu's stream through an event (not the host), which substitutes
+ * backward with L_u -- every diagonal solve refined once, as the substitutions of gphip_sparse_bound_grad_inducing are, because
+ * the difference cancels as cond(K_uu) grows (option "sparse_pgrad_refine" = 0: unrefined, for measurement) -- and runs the
+ * reduction kernel of gphip_predict_grad with the scaled Z as its contraction points.  a_mu comes from two single-vector
+ * backward substitutions.  dvar == NULL skips everything but a_mu and the mean-weighted sums.  Fixed summation order, no
+ * atomics: two calls return the same bytes; the fit stays (gphip_sparse_predict and gphip_sparse_bound return the same bytes
+ * before and after).  Options "predict_grad_split" / "predict_grad_chunk" and their read-only results are gphip_predict_grad's
+ * (they are handed on to the context of K_uu).  Statuses, before any device work: NULL h / Xs / dmean GPHIP_ERR_ARG; M < 1
+ * GPHIP_ERR_DIM; no successful fit (also after gphip_sparse_bound_batch or gphip_sparse_set_inducing) GPHIP_ERR_STATE; a run-time
+ * compiled covariance function and a fit made with a non-NULL training array GPHIP_ERR_UNSUPPORTED.
+ *
  * Options (gphip_sparse_set_option / gphip_sparse_get_option):
  *   "sparse_chunk"  data points per pass over V (rounded up to 128); 0 (default) = as many as keep the chunk of V within ~8 GiB,
  *                   at least 2048, halved while it does not fit.  "last_sparse_chunk" (read-only): what the last call used.
@@ -635,6 +679,9 @@ int gphip_factor_bytes(gphip_handle h, int member, double* bytes);
  *                   sqrt(1 / nu_i) in place and the unweighted accumulation follows.  The fused form is the faster one at four of the
  *                   five measured sizes and the slower one at (N, m) = (262144, 2048), which decides the default (DESIGN.md section
  *                   8i, scripts/gpu_sparse_pw_time.py); the two agree to rounding.
+ *   "sparse_pgrad_refine"  gphip_sparse_predict_grad's backward substitution with L_u.  1 (default): every diagonal 128-block solve
+ *                   refined once (the form gphip_sparse_bound_grad_inducing uses); 0: the bare product with the block inverses, kept
+ *                   for measurement (equal errors on the pinned one-tile case, 17 - 26 % of the call).
  *   "profile"       0 / 1: time the phases of gphip_sparse_bound / _fit with HIP events; read-only milliseconds of the last call:
  *                   "ms_kuu_factor", "ms_cross", "ms_forward", "ms_accumulate", "ms_b_factor"; of gphip_sparse_bound_grad also
  *                   "ms_grad_small" (the m x m work and the vector w), "ms_grad_weights" (sparse_weight_kernel alone),
@@ -646,6 +693,8 @@ int gphip_factor_bytes(gphip_handle h, int member, double* bytes);
  *                   "ms_samples_v1" (k(X*, Z) and u's substitution), "ms_samples_handover" (V1 to b and |v1|^2), "ms_samples_v2"
  *                   (b's substitution) and "ms_samples_reduce" (the dots and norms of v2 and the finishing kernel), summed over
  *                   groups and chunks; each of these calls resets the four, no other call touches them.
+ *                   of gphip_sparse_predict_grad next to those four "ms_pgrad_backward" (the backward substitutions with L_B and
+ *                   L_u and the kernel between them) and "ms_pgrad_reduce" (the reduction kernel and its finish).
  *   "sparse_joint_split"  strips the joint prediction's downdate cuts the stacked index of 2 m_pad columns into; 0 (default) = by
  *                   gphip_predict_cov's split rule (output tiles x strips >= 2 per CU, strips of whole 128-columns; a strip may
  *                   span the V1 / V2 boundary), n = n strips.  "last_sparse_joint_nsplit" (read-only): strips of the last call.
@@ -672,6 +721,8 @@ int gphip_sparse_bound_grad_inducing(gphip_sparse_handle h, const double* theta,
                                      double* grad /* p, may be NULL */, double* gradZ /* row-major m x d */, double* parts, int* info);
 int gphip_sparse_fit(gphip_sparse_handle h, const double* theta, int p, double jitter, int* info);
 int gphip_sparse_predict(gphip_sparse_handle h, const void* Xs, int64_t M, int latent, double* mean, double* var);
+int gphip_sparse_predict_grad(gphip_sparse_handle h, const void* Xs, int64_t M, double* mean /* M or NULL */, double* var /* M or NULL */,
+                              double* dmean /* row-major M x d */, double* dvar /* row-major M x d or NULL */);
 int gphip_sparse_predict_samples(gphip_sparse_handle h, const double* Thetas, int S, int p, double jitter, const void* Xs, int64_t M,
                                  int latent, double* mean /* S x M */, double* var /* S x M */, double* bound /* NULL or S */,
                                  int* info /* S */);
