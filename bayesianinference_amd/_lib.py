@@ -96,6 +96,7 @@ _SIGNATURES = {
     "gphip_predict_cov": (C.c_int, [_h, C.c_void_p, C.c_int64, C.c_int, _dp, _dp]),
     "gphip_predict_draws": (C.c_int, [_h, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_uint64, _dp, C.c_double, _dp, _ip]),
     "gphip_predict_logpdf": (C.c_int, [_h, C.c_void_p, C.c_int64, _dp, _dp, _ip]),
+    "gphip_extend": (C.c_int, [_h, C.c_void_p, _dp, C.c_int64, C.POINTER(_h), _dp, _ip]),
     "gphip_predict_grad": (C.c_int, [_h, C.c_void_p, C.c_int64, _dp, _dp, _dp, _dp]),
     "gphip_loglik_batch_pw": (C.c_int, [_h, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _ip]),
     "gphip_fit_pw": (C.c_int, [_h, _dp, C.c_int, _dp, _dp, _ip]),
@@ -556,6 +557,26 @@ class Handle:
         out, info = C.c_double(0.0), C.c_int(0)
         self._check(self._lib.gphip_predict_logpdf(self._h, Xs.ctypes.data, M, _d(ys), C.byref(out), C.byref(info)))
         return out.value, info.value
+
+    def extend(self, X_new, y_new):
+        """gphip_extend: the observations (X_new[M, d], y_new[M]) into the resident fit without refactoring it.  Returns
+        (Handle on the N + M points with the fit of the same theta resident, or None; log p(y_new | X_new, X, y, theta) -- the
+        bytes of predict_logpdf(X_new, y_new); info).  info != 0 (Sigma not positive definite under the pivot rule, non-finite
+        data): no handle, logp = NaN.  This handle is untouched; the new one is closed on its own."""
+        Xn = self._test_points(X_new)
+        M = Xn.shape[0]
+        yn = np.ascontiguousarray(np.asarray(y_new, dtype=np.float64).ravel())
+        if yn.shape != (M,):
+            raise GphipError(2, f"y_new must have length {M}")
+        out, logp, info = _h(), C.c_double(0.0), C.c_int(0)
+        self._check(self._lib.gphip_extend(self._h, Xn.ctypes.data, _d(yn), M, C.byref(out), C.byref(logp), C.byref(info)))
+        if not out.value:
+            return None, logp.value, info.value
+        new = Handle.__new__(Handle)
+        new._lib, new._h = self._lib, out
+        new.N, new.d = self.N + M, self.d
+        new.kernel, new.mean, new.dtype, new.p = self.kernel, self.mean, self.dtype, self.p
+        return new, logp.value, info.value
 
     def predict_grad(self, Xs, variance: bool = True):
         """Gradients of the prediction in the test inputs (gphip_predict_grad): (mean[M], var[M], dmean[M, d], dvar[M, d]);

@@ -144,6 +144,8 @@ struct gphip_ctx {
     Buf dInvEll2, hInvEll2;            // double
     Buf dNullMu, dNullOut;                                  // double: null-kernel path: per-theta mu and the two sums
     Buf dXt, dY;                                            // typed: [d][Npad], [Npad]
+    std::vector<double> hostX, hostY;                       // the fp64 host values the context was created with, row-major N x d and N
+                                                            // (gphip_extend creates its N + M point context from these, not from the typed copies)
     Buf dExp2;                                              // double [EXP_TAB] 2^(j/512): the kernel build's exp table
     // Kernel build with the distance cross term on the matrix pipe (kbuild_mfma_kernel): mid-range and half range of the
     // training inputs per dimension.  A theta's slot goes to that kernel while sum_k (half_k / l_k)^2 <= kbuild_mfma_bound
@@ -290,6 +292,9 @@ struct gphip_ctx {
     int predict_grad_nsplit = 0;                      // read-only: strips the last reduction used
     int predict_grad_chunk = 0;                       // option: test points per chunk (0 = by the chunk rule)
     int predict_grad_chunk_last = 0;                  // read-only: rows per chunk of the last call
+    // gphip_extend (gphip_extend.inc), read-only on the parent: microseconds of the last call's phases -- the joint log density
+    // (host clock), the new context and its buffers (host clock), the assembly kernel and the block inverses (events)
+    int extend_logpdf_us = 0, extend_create_us = 0, extend_assemble_us = 0, extend_derive_us = 0;
 };
 
 namespace {
@@ -604,6 +609,17 @@ bool use_dataflow(const gphip_ctx* h, int nslots);
 inline int few_slots(const gphip_ctx* h) { return h->dataflow_max_slots < 0 ? 8 : h->dataflow_max_slots; }   // "a few thetas": schedule choices made for latency
 hipEvent_t sync_event(gphip_ctx* h);
 
+// run-time compiled covariance function: prior variance scale -> pivot tolerance, per slot (device: only it can evaluate k)
+void queue_custom_prep(gphip_ctx* h, int nslots) {
+    if (!h->custom) return;
+    const void* x = h->dXt.p;
+    int npad = (int)h->Npad, n = (int)h->N, d = (int)h->d, ncp = std::max(h->ncp, 1);
+    const double* cp = h->dCustomP.as<double>();
+    double* sp = h->dSlotp.as<double>();
+    void* params[] = {&x, &npad, &n, &d, &cp, &ncp, &sp};
+    (void)hipModuleLaunchKernel(h->f_cprep, (unsigned)nslots, 1, 1, 256, 1, 1, 0, h->cs, params, nullptr);
+}
+
 // queue k_scale + kbuild for nslots slots (theta already staged in dInvEll / dSlotp)
 template <typename T>
 int queue_build(gphip_ctx* h, int nslots) {
@@ -623,14 +639,7 @@ int queue_build(gphip_ctx* h, int nslots) {
     if (h->nl2 > 0)
         hipLaunchKernelGGL(k_scale<T>, dim3(gx, nslots), dim3(256), 0, h->cs, (const T*)h->dXt.p, (T*)h->dXs2.p, h->dInvEll2.as<double>(),
                            (int)h->d, (int)h->Npad);
-    if (h->custom) {                               // prior variance scale -> pivot tolerance, per slot (device: only it can evaluate k)
-        const void* x = h->dXt.p;
-        int npad = (int)h->Npad, n = (int)h->N, d = (int)h->d, ncp = std::max(h->ncp, 1);
-        const double* cp = h->dCustomP.as<double>();
-        double* sp = h->dSlotp.as<double>();
-        void* params[] = {&x, &npad, &n, &d, &cp, &ncp, &sp};
-        (void)hipModuleLaunchKernel(h->f_cprep, (unsigned)nslots, 1, 1, 256, 1, 1, 0, h->cs, params, nullptr);
-    }
+    queue_custom_prep(h, nslots);
     KBuildArgs<T> a{};
     a.ks = h->ks; a.xi2 = a.xj2 = (const T*)h->dXs2.p;
     a.out = (T*)h->dA.p; a.ld = TB; a.bstride = h->slot_elems;
@@ -2420,6 +2429,7 @@ static int ctx_replace_points(gphip_ctx* h, const double* X) {
         for (int64_t j = 0; j < d; ++j) xt[(size_t)j * h->Npad + i] = X[i * d + j];
     invalidate_fit(h);
     h->test_ratio = 0.0;
+    h->hostX.assign(X, X + (size_t)N * (size_t)d);
     if (const int rc = DISPATCH(h, upload, h, h->dXt.p, xt, h->stream)) return rc;
     return ctx_point_ranges(h, xt);
 }
@@ -2519,6 +2529,8 @@ static int create_ctx(const void* X, const void* y, int64_t N, int64_t d, int ke
         for (int64_t j = 0; j < d; ++j) xt[(size_t)j * h->Npad + i] = Xd[i * d + j];
         yp[i] = yd[i];
     }
+    h->hostX.assign(Xd, Xd + (size_t)N * (size_t)d);
+    h->hostY.assign(yd, yd + (size_t)N);
     if (h->dXt.grow(xt.size() * h->es) != hipSuccess) return bail(GPHIP_ERR_HIP);
     if (h->dY.grow(yp.size() * h->es) != hipSuccess) return bail(GPHIP_ERR_HIP);
     {
@@ -3735,6 +3747,8 @@ int* option_slot(gphip_ctx* h, const char* name) {
         {"debug_abort_word", &gphip_ctx::debug_abort_word}, {"joint_split", &gphip_ctx::joint_split}, {"last_joint_nsplit", &gphip_ctx::joint_nsplit},
         {"predict_grad_split", &gphip_ctx::predict_grad_split}, {"last_predict_grad_nsplit", &gphip_ctx::predict_grad_nsplit},
         {"predict_grad_chunk", &gphip_ctx::predict_grad_chunk}, {"last_predict_grad_chunk", &gphip_ctx::predict_grad_chunk_last},
+        {"last_extend_logpdf_us", &gphip_ctx::extend_logpdf_us}, {"last_extend_create_us", &gphip_ctx::extend_create_us},
+        {"last_extend_assemble_us", &gphip_ctx::extend_assemble_us}, {"last_extend_derive_us", &gphip_ctx::extend_derive_us},
     };
     // fault injection ("debug_*") exists for the test-suite only: the names resolve in a process that was started with
     // GPHIP_TEST_HOOKS=1 and nowhere else (not through GPHIP_OPTIONS either: apply_env_options skips them)
@@ -3841,6 +3855,7 @@ int gphip_sync(gphip_handle h) {
 #include "gphip_hostlogic.inc"
 #include "gphip_sampler.inc"
 #include "gphip_joint.inc"
+#include "gphip_extend.inc"
 #include "gphip_loo.inc"
 #include "gphip_xgrad.inc"
 #include "gphip_sparse.inc"

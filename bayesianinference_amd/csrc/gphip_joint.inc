@@ -57,6 +57,8 @@ int joint_child(gphip_ctx* h, const double* Xs, int64_t M, const double* y) {
             for (int64_t j = 0; j < h->d; ++j) xt[(size_t)j * c->Npad + i] = Xs[i * h->d + j];
             yp[(size_t)i] = y[i];
         }
+        c->hostX.assign(Xs, Xs + (size_t)M * (size_t)h->d);       // (the host copy stays what the device holds)
+        c->hostY.assign(y, y + (size_t)M);
         int rc = DISPATCH(c, upload, c, c->dXt.p, xt, c->stream);
         if (!rc) rc = DISPATCH(c, upload, c, c->dY.p, yp, c->stream);
         if (rc) return fail(h, rc, c->err.c_str());

@@ -627,6 +627,20 @@ def predictiveLogDensity(examples, heldout, kernel, theta, meanFunction=None):
     return value if info == 0 else None
 
 
+def extendGaussianProcess(handle, new_examples):
+    """The observe step of a sequential design loop (gphip_extend; no reference counterpart): new_examples = (X_new, y_new) in
+    any form dataNormalForm takes, one output column, into the fit resident in `handle` (a _lib.Handle after fit) without
+    refactoring it.  Returns a new _lib.Handle on all the points with the fit of the same theta resident -- predict,
+    predict_grad, solve, extend again, .. work on it as after fit; `handle` itself is untouched and both are closed on their own --
+    or None on bad data, non-finite outputs and new points whose predictive covariance does not factor (duplicates at a tiny
+    noise level)."""
+    norm = dataNormalForm(new_examples)
+    if norm is None or not isinstance(norm, tuple) or norm[1].shape[1] != 1 or norm[0].shape[1] != handle.d or len(norm[0]) < 1:
+        return None
+    new, _, info = handle.extend(norm[0], norm[1][:, 0])
+    return new if info == 0 else None
+
+
 def gaussianProcessFunctionSamples(obj, pts, n: int, seed: int = 0, latent: bool = True):
     """n draws of the function values at pts from the posterior MIXTURE of a sampled GP object: each draw picks a theta from
     "Samples" by CrudePosteriorWeight (numpy generator seeded by `seed`), then the values come from the joint predictive

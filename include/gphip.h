@@ -219,6 +219,41 @@ int gphip_predict_draws(gphip_handle h, const void* Xs, int64_t M, int latent, i
 /* log N(ystar | mean, Sigma) with the noisy-observation Sigma (latent = 0): the joint predictive log density of held-out
  * data.  *info as gphip_loglik's (*out undefined if *info != 0). */
 int gphip_predict_logpdf(gphip_handle h, const void* Xs, int64_t M, const double* ystar, double* out, int* info);
+/* ---- New observations into a resident fit without refactoring it (no reference counterpart): the observe step of a sequential
+ * design loop (fit, maximise an acquisition with gphip_predict_grad, observe, repeat).  After the joint log density of the new
+ * points everything the factor of the N + M points consists of is resident:
+ *     L' = [ L    0   ]     z' = [ z ; z_new ]     log det K' = log det K + log det Sigma
+ *          [ V^T  L_S ]     V = L^-1 k(X, X_new),  L_S = chol(Sigma),  Sigma = k(X_new, X_new) + sn^2 I - V^T V,
+ *                           z_new = L_S^-1 (y_new - mu)
+ * so conditioning on M more points costs the forward substitution of M rows, an M x M downdate, its factorisation and one
+ * streaming pass over the factor: O(N^2 M) instead of the N^3 / 3 of a new handle and gphip_fit.
+ *
+ * A NEW handle on the N + M points [X; X_new], [y; y_new] whose fit at the parent's fitted theta is resident, made from the
+ * parent's factor without refactoring it.  *logp = log p(y_new | X_new, X, y, theta) -- the same bytes
+ * gphip_predict_logpdf(h, X_new, M, y_new, ..) returns -- so loglik(extended) = loglik(parent) + *logp.
+ * The parent is untouched (its fit stays; gphip_predict returns the same bytes before and after).
+ * The new handle is an ordinary single-device handle of the parent's kernel (named, composed or run-time compiled), mean and
+ * dtype on the device that holds the parent's whole factor, with default options plus GPHIP_OPTIONS like a fresh handle; the
+ * caller destroys it with gphip_destroy, before or after the parent.  Every entry point works on it as on a handle created from
+ * the concatenated data after gphip_fit(theta), gphip_extend included: extensions chain.  Calls that rebuild K (gphip_loglik,
+ * _batch, gphip_fit, gphip_loglik_grad, gphip_loo, gphip_covariance) return the SAME BYTES as on a handle created from the
+ * concatenated host arrays: every handle keeps the fp64 host copy of the X and y it was created with (N (d + 1) 8 bytes) and
+ * the new one is created from those.  Calls that use the carried-over factor (gphip_predict*, gphip_solve, gphip_logdet,
+ * gphip_predict_cov / _draws / _logpdf, gphip_predict_grad) agree with a fresh fit to rounding: the operation order differs.
+ * Two calls with the same arguments give handles whose every result is the same bytes.
+ * *info as gphip_predict_logpdf's: GPHIP_INFO_NOT_SPD when Sigma (noisy, no jitter added) does not pass the factorisation's own
+ * pivot rule, GPHIP_INFO_NAN for a non-finite y_new entry or result; in both cases *out = NULL, *logp = NaN, the status is
+ * GPHIP_OK and the parent keeps its fit.
+ * Statuses, all decided before any device work: NULL h / X_new / y_new / out / info GPHIP_ERR_ARG; M < 1 or
+ * M > GPHIP_JOINT_MAX_M GPHIP_ERR_DIM; no resident fit GPHIP_ERR_STATE; a sharded fit with replicate_factor = 0 and a fit made by
+ * gphip_fit_pw with a non-NULL array GPHIP_ERR_UNSUPPORTED.  The null kernel is answered on the host.
+ * Read-only options on the PARENT after a call, microseconds: "last_extend_logpdf_us" (V, Sigma, its factorisation),
+ * "last_extend_create_us" (the new context and its buffers), "last_extend_assemble_us" (the copy kernel, csrc/gp_extend.h),
+ * "last_extend_derive_us" (the 128-block inverses of the new factor).
+ * Not offered: the sparse object (its refit is cheap and its update would need the unfactored B), an in-place form with reserved
+ * capacity, removing points, another theta, point-dependent fits, a multi-device result. */
+int gphip_extend(gphip_handle h, const void* X_new /* row-major M x d fp64 */, const double* y_new /* M */, int64_t M,
+                 gphip_handle* out, double* logp /* may be NULL */, int* info);
 /* ---- Gradients of the predictive mean and variance in the TEST inputs (no reference counterpart): how the prediction of the
  * current fit changes when x* moves -- what maximising an acquisition function, finding the optimum of the fitted surface and
  * sensitivity analysis need.  With alpha = K^-1 (y - m), k*_i = k(x*, x_i) and w = K^-1 k* (an N-vector per test point):
