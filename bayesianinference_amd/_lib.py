@@ -88,6 +88,7 @@ _SIGNATURES = {
     "gphip_loglik_batch": (C.c_int, [_h, _dp, C.c_int, C.c_int, _dp, _ip]),
     "gphip_loglik_parts": (C.c_int, [_h, _dp, C.c_int, _dp, _dp, _ip]),
     "gphip_loglik_grad": (C.c_int, [_h, _dp, C.c_int, _dp, _dp, _ip]),
+    "gphip_loglik_grad_batch": (C.c_int, [_h, _dp, C.c_int, C.c_int, _dp, _dp, _ip]),
     "gphip_loo": (C.c_int, [_h, _dp, C.c_int, _dp, _dp, _dp, _dp, _ip]),
     "gphip_loo_grad": (C.c_int, [_h, _dp, C.c_int, _dp, _dp, _ip]),
     "gphip_fit": (C.c_int, [_h, _dp, C.c_int, _ip]),
@@ -456,6 +457,18 @@ class Handle:
         grad = np.zeros(th.size)
         self._check(self._lib.gphip_loglik_grad(self._h, _d(th), th.size, C.byref(out), _d(grad), C.byref(info)))
         return out.value, grad, info.value
+
+    def loglik_grad_batch(self, Theta):
+        """gphip_loglik_grad_batch: (loglik[B], grad[B, p], info[B]) for the rows of Theta [B, p] (a 1-D theta is one row) in one
+        call; a failing row has its own info and a NaN grad row.  Drops any resident fit."""
+        Th = np.ascontiguousarray(np.atleast_2d(np.asarray(Theta, dtype=np.float64)))
+        if Th.ndim != 2 or Th.shape[1] != self.p:
+            raise GphipError(2, f"Theta has rows of {Th.shape[-1]} entries, the handle takes {self.p}")
+        B, p = Th.shape
+        out, grad = np.zeros(B), np.zeros((B, p))
+        info = np.zeros(B, dtype=np.int32)
+        self._check(self._lib.gphip_loglik_grad_batch(self._h, _d(Th), B, p, _d(out), _d(grad), info.ctypes.data_as(_ip)))
+        return out, grad, info
 
     def _theta(self, theta):
         th = np.ascontiguousarray(np.asarray(theta, dtype=np.float64).ravel())

@@ -3249,17 +3249,24 @@ __global__ void predict_finish_kernel(const double* __restrict__ part, int nstri
 // row `row` (0..127) of tile row Nt of the packed workspace (z = L^-1 r sits in row 0) -> out[j * ldo], j < npad
 template <typename T>
 __global__ void gather_rhs_row_kernel(const T* __restrict__ Abase, int R, int row, int npad, T* __restrict__ out, long ldo,
-                                      int j_first = 0) {
+                                      int j_first = 0, long a_bstride = 0, long out_bstride = 0) {
     const int j = j_first + blockIdx.x * blockDim.x + threadIdx.x;        // columns [j_first, npad)
+    Abase += (long)blockIdx.z * a_bstride;                                // (slot = blockIdx.z: gphip_loglik_grad_batch)
+    out += (long)blockIdx.z * out_bstride;
     if (j < npad) out[(long)j * ldo] = Abase[tile_index(R - 1, j >> 7, R) * TS + (long)(j & 127) * TB + row];
 }
 
 // alpha = U z for the explicit upper-triangular U = L^-T (column-major, leading dimension ld; zeros below the diagonal): the
 // gradient's alpha = K^-1 r = L^-T (L^-1 r) once U exists, as one pass over U instead of a backward substitution of ~2 launches
 // per tile column.  Fixed summation order: a partial sum per (row, chunk of `chunk` columns), then the chunks in order.
+// Several slots at once (blockIdx.z, gphip_loglik_grad_batch): u_ / z_ / part_ / out_bstride are the elements between their U, z, partial sums and results.
 template <typename T>
 __global__ __launch_bounds__(128) void utri_gemv_partial_kernel(const T* __restrict__ U, long ld, const T* __restrict__ z, int npad,
-                                                                int chunk, double* __restrict__ part) {
+                                                                int chunk, double* __restrict__ part, long u_bstride = 0,
+                                                                long z_bstride = 0, long part_bstride = 0) {
+    U += (long)blockIdx.z * u_bstride;
+    z += (long)blockIdx.z * z_bstride;
+    part += (long)blockIdx.z * part_bstride;
     const int r = blockIdx.x * TB + threadIdx.x;                                // one tile row of U per workgroup (128 threads)
     const int c1 = min((int)(blockIdx.y + 1) * chunk, npad);
     const int c0 = max((int)blockIdx.y * chunk, (int)(blockIdx.x * TB));        // (row r has nothing left of column r)
@@ -3279,9 +3286,12 @@ __global__ __launch_bounds__(128) void utri_gemv_partial_kernel(const T* __restr
     part[(long)blockIdx.y * npad + r] = (s0 + s1) + (s2 + s3);
 }
 template <typename T>
-__global__ void utri_gemv_finish_kernel(const double* __restrict__ part, int nchunks, int npad, T* __restrict__ out) {
+__global__ void utri_gemv_finish_kernel(const double* __restrict__ part, int nchunks, int npad, T* __restrict__ out,
+                                        long part_bstride = 0, long out_bstride = 0) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= npad) return;
+    part += (long)blockIdx.z * part_bstride;
+    out += (long)blockIdx.z * out_bstride;
     double s = 0.0;
     for (int y = 0; y < nchunks; ++y) s += part[(long)y * npad + r];
     out[r] = (T)s;
@@ -3305,8 +3315,9 @@ __global__ __launch_bounds__(256) void transpose_blocks64_kernel(const T* __rest
 }
 
 template <typename T>
-__global__ void identity_rows_kernel(T* __restrict__ V, long ldv, int npad, int c0, int mc) {
+__global__ void identity_rows_kernel(T* __restrict__ V, long ldv, int npad, int c0, int mc, long v_bstride = 0) {
     const long total = ldv * (long)npad;
+    V += (long)blockIdx.y * v_bstride;                                    // (slot = blockIdx.y: one slab per slot)
     for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
         const int t = (int)(idx % ldv), j = (int)(idx / ldv);
         V[idx] = (t < mc && j == c0 + t) ? (T)1 : (T)0;
@@ -3331,9 +3342,29 @@ __global__ void add_rows_kernel(T* __restrict__ x, const T* __restrict__ r, long
 }
 
 
+// A group of gradient reductions, one per workspace slot (gphip_loglik_grad_batch): the arguments of slot 0 and the elements
+// between the slots' K^-1 slabs, alpha vectors, scaled inputs (both terms), slot scalars, accumulators and per-workgroup rows.
+// Square reductions only (beta / xr / diag unset).  The one-theta kernels below take GradArgs as they always did; the *_slots
+// kernels run the same tile body on at(blockIdx.z).
+struct GradStride {
+    long kinv, alpha, xs, slotp, gacc, gpart;
+};
+template <typename T>
+struct GradSlots {
+    GradArgs<T> a;
+    GradStride s;
+    __host__ __device__ GradArgs<T> at(int slot) const {
+        GradArgs<T> r = a;
+        r.Kinv += slot * s.kinv; r.alpha += slot * s.alpha; r.xs += slot * s.xs; r.slotp += slot * s.slotp; r.gacc += slot * s.gacc;
+        if (r.xs2) r.xs2 += slot * s.xs;
+        if (r.gpart) r.gpart += slot * s.gpart;
+        return r;
+    }
+};
+
 // One 128 (rows of the block) x 128 (columns) tile per workgroup; thread = one row, 64 columns.
 template <typename T, int D, int KT>
-__global__ __launch_bounds__(256) void grad_reduce_kernel(GradArgs<T> a) {
+__device__ __forceinline__ void grad_reduce_tile(const GradArgs<T>& a) {
     extern __shared__ double lds_raw[];
     T* xjs = reinterpret_cast<T*>(lds_raw);      // [d][128] column points, then alpha_j [128]
     const int d = (D > 0) ? D : a.d;
@@ -3403,6 +3434,10 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(GradArgs<T> a) {
     out.put(acc_dg, d + 1);
     out.finish();
 }
+template <typename T, int D, int KT>
+__global__ __launch_bounds__(256) void grad_reduce_kernel(GradArgs<T> a) { grad_reduce_tile<T, D, KT>(a); }
+template <typename T, int D, int KT>
+__global__ __launch_bounds__(256) void grad_reduce_slots_kernel(GradSlots<T> b) { grad_reduce_tile<T, D, KT>(b.at((int)blockIdx.z)); }
 
 // The same reduction for the general covariance form (KSpec): w = wt (alpha_g alpha_j - Kinv_gj) contracted with every
 // dk/dtheta.  Accumulators (the host applies the chain-rule factors of its theta layout):
@@ -3414,7 +3449,7 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(GradArgs<T> a) {
 //   gacc[2 d + 5]      sum w                                              -> d/dc = 1/2 gacc
 // One 128 x 128 tile per workgroup, thread = one row x 64 columns; row and column points of both terms sit in LDS.
 template <typename T>
-__global__ __launch_bounds__(256) void grad_reduce_general_kernel(GradArgs<T> a) {
+__device__ __forceinline__ void grad_reduce_general_tile(const GradArgs<T>& a) {
     extern __shared__ double lds_raw[];
     const int d = a.d;
     // Beyond KB_LDS_MAXD dimensions the point tiles do not fit in LDS and 32 accumulators per term are all the registers
@@ -3522,11 +3557,19 @@ __global__ __launch_bounds__(256) void grad_reduce_general_kernel(GradArgs<T> a)
     }
     out.finish();
 }
+template <typename T>
+__global__ __launch_bounds__(256) void grad_reduce_general_kernel(GradArgs<T> a) { grad_reduce_general_tile<T>(a); }
+template <typename T>
+__global__ __launch_bounds__(256) void grad_reduce_general_slots_kernel(GradSlots<T> b) { grad_reduce_general_tile<T>(b.at((int)blockIdx.z)); }
 
 // adds the per-workgroup rows of a gradient reduction into gacc: block p = accumulator slot p, fixed summation order
-__global__ __launch_bounds__(256) void grad_finish_kernel(const double* __restrict__ part, long nwg, int np, double* __restrict__ gacc) {
+// (blockIdx.y = workspace slot of a group, part_ / gacc_bstride the doubles between the slots' rows and accumulators)
+__global__ __launch_bounds__(256) void grad_finish_kernel(const double* __restrict__ part, long nwg, int np, double* __restrict__ gacc,
+                                                          long part_bstride = 0, long gacc_bstride = 0) {
     __shared__ double s[256];
     const int p = blockIdx.x, tid = threadIdx.x;
+    part += (long)blockIdx.y * part_bstride;
+    gacc += (long)blockIdx.y * gacc_bstride;
     double v = 0.0;
     for (long w = tid; w < nwg; w += 256) v += part[w * np + p];
     s[tid] = v;

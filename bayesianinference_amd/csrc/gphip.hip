@@ -191,6 +191,10 @@ struct gphip_ctx {
     int fuse_option = 1;                         // allow the single-launch evaluation (option "fused_eval")
     int grad_potri = 1;                          // gradient: K^-1 = U U^T in one go when the memory is there (1: U = L^-T from the dataflow kernel's
                                                  // inverse launch where the factor came from one launch; 2: always from the multi-kernel forward pass)
+    int grad_batch_slots = 0;                    // gphip_loglik_grad_batch: at most this many rows per group (0: the group rule alone, gphip_gradbatch.inc)
+    int grad_batch_max_n = 7168;                 // .. more training points than this: the per-row loop (one theta fills the device there; 0: no limit)
+    int grad_batch_last = 0, grad_batch_route = 0;     // .. rows in the last group of the last call; 1: the batched route ran, 0: the per-row loop
+    Buf dKinvB;                                  // .. typed [group][Npad x Npad]: z and the alpha partial sums, then the lower tiles of K^-1, per slot
     int predict_df_max_nt = 256;                 // .. and, after a look-ahead-schedule fit, up to this many tile columns (N = 32768)
     int predict_df = 2048;                       // prediction after a single-launch fit: forward substitution as ONE dataflow launch up to this many (padded) test points
                                                  // (twice that up to N = 8192); 0 = never
@@ -1619,6 +1623,9 @@ int set_func_attrs(gphip_ctx* h) {
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(grad_reduce_general_kernel<T>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize,
                                    (int)((4 * h->d + 1) * TB * sizeof(T) + 8 + 4 * (2 * h->d + 6) * 8)));     // (+ GradEmit's staging area)
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(grad_reduce_general_slots_kernel<T>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)((4 * h->d + 1) * TB * sizeof(T) + 8 + 4 * (2 * h->d + 6) * 8)));
     }
 #define GEMM_ATTR(ROLE)                                                                                   \
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_kernel<T, ROLE, 2, 2, 2>),             \
@@ -1962,72 +1969,87 @@ int queue_finalize(gphip_ctx* h) {         // sharded evaluation: the corner til
     return 0;
 }
 
+// One launch of a gradient reduction: the one-theta kernel K1 on `a`, or (G > 1 slots of a group, gphip_gradbatch.inc) the per-slot
+// kernel KG with the slot as grid.z
+#define GRAD_LAUNCH(K1, KG)                                                                                         \
+    do {                                                                                                            \
+        if (G == 1) hipLaunchKernelGGL(K1, grid, dim3(256), lds, h->cs, a);                                         \
+        else hipLaunchKernelGGL(KG, dim3(grid.x, grid.y, (unsigned)G), dim3(256), lds, h->cs, GradSlots<T>{a, *st}); \
+    } while (0)
+
 template <typename T, int KT>
-void launch_grad_kt(gphip_ctx* h, const GradArgs<T>& a, dim3 grid, size_t lds) {
+void launch_grad_kt(gphip_ctx* h, const GradArgs<T>& a, dim3 grid, size_t lds, int G, const GradStride* st) {
 #define GR_CASE(DD)                                                                                   \
     case DD:                                                                                          \
-        hipLaunchKernelGGL((grad_reduce_kernel<T, DD, KT>), grid, dim3(256), lds, h->cs, a);          \
+        GRAD_LAUNCH((grad_reduce_kernel<T, DD, KT>), (grad_reduce_slots_kernel<T, DD, KT>));          \
         break;
     switch (a.d) {
         GR_CASE(1) GR_CASE(2) GR_CASE(3) GR_CASE(4) GR_CASE(5) GR_CASE(6) GR_CASE(7) GR_CASE(8) GR_CASE(16)
         default:
-            hipLaunchKernelGGL((grad_reduce_kernel<T, 0, KT>), grid, dim3(256), lds, h->cs, a);
+            GRAD_LAUNCH((grad_reduce_kernel<T, 0, KT>), (grad_reduce_slots_kernel<T, 0, KT>));
     }
 #undef GR_CASE
 }
 
 // where the accumulators of a gradient reduction go (GradEmit, gp_kernels.h): per-workgroup rows in dGpart + a [4][np] staging
 // area behind the kernel's own LDS -- or, when that area would be larger than 8 KiB or the rows cannot be allocated, the atomics
-// on gacc.  Returns the LDS bytes to launch with.
+// on gacc.  Returns the LDS bytes to launch with.  G slots: every slot its own rows, st->gpart doubles apart.
 template <typename T>
-size_t grad_rows(gphip_ctx* h, GradArgs<T>& a, dim3 grid, size_t lds) {
-    const size_t np = h->ngacc, nwg = (size_t)grid.x * grid.y, need = nwg * np * 8;
+size_t grad_rows(gphip_ctx* h, GradArgs<T>& a, dim3 grid, size_t lds, int G = 1, GradStride* st = nullptr) {
+    const size_t np = h->ngacc, nwg = (size_t)grid.x * grid.y, need = nwg * np * 8 * (size_t)G;
     a.gpart = nullptr; a.np = (int)np; a.ws_off = (int)((lds + 7) / 8);
+    if (st) st->gpart = (long)(nwg * np);
     if (np == 0 || 4 * np * 8 > 8192) return lds;
     if (h->dGpart.grow(need) != hipSuccess) { (void)hipGetLastError(); return lds; }
     a.gpart = h->dGpart.as<double>();
     return (size_t)a.ws_off * 8 + 4 * np * 8;
 }
 template <typename T>
-void grad_rows_finish(gphip_ctx* h, const GradArgs<T>& a, dim3 grid) {
+void grad_rows_finish(gphip_ctx* h, const GradArgs<T>& a, dim3 grid, int G = 1, const GradStride* st = nullptr) {
     if (a.gpart)
-        hipLaunchKernelGGL(grad_finish_kernel, dim3((unsigned)a.np), dim3(256), 0, h->cs, (const double*)a.gpart, (long)grid.x * grid.y, a.np, a.gacc);
+        hipLaunchKernelGGL(grad_finish_kernel, dim3((unsigned)a.np, (unsigned)G), dim3(256), 0, h->cs, (const double*)a.gpart,
+                           (long)grid.x * grid.y, a.np, a.gacc, st ? st->gpart : 0l, st ? st->gacc : 0l);
 }
 
+// G > 1: the reductions of G workspace slots in one launch, *st the elements between the slots' operands (st->gpart is filled in here)
 template <typename T>
-void launch_grad(gphip_ctx* h, GradArgs<T>& a, dim3 grid) {
+void launch_grad(gphip_ctx* h, GradArgs<T>& a, dim3 grid, int G = 1, GradStride* st = nullptr) {
     if (h->custom) {                               // the run-time compiled custom_grad_kernel<T> (dual-number instantiation)
-        const double* cp = h->dCustomP.as<double>();
-        int ncp = h->ncp;
-        const size_t lds = grad_rows<T>(h, a, grid, (size_t)((a.d > KB_LDS_MAXD ? 0 : a.d) + 1) * TB * sizeof(T));
-        void* params[] = {&a, &cp, &ncp};
-        (void)hipModuleLaunchKernel(h->f_cgrad, grid.x, grid.y, grid.z, 256, 1, 1, (unsigned)lds, h->cs, params, nullptr);
-        grad_rows_finish<T>(h, a, grid);
+        const size_t lds = grad_rows<T>(h, a, grid, (size_t)((a.d > KB_LDS_MAXD ? 0 : a.d) + 1) * TB * sizeof(T), G, st);
+        for (int s = 0; s < G; ++s) {              // (one launch per slot: the kernel's argument list belongs to the compiled text)
+            GradArgs<T> as = G == 1 ? a : GradSlots<T>{a, *st}.at(s);
+            const double* cp = h->dCustomP.as<double>() + (size_t)s * h->ncp;
+            int ncp = h->ncp;
+            void* params[] = {&as, &cp, &ncp};
+            (void)hipModuleLaunchKernel(h->f_cgrad, grid.x, grid.y, grid.z, 256, 1, 1, (unsigned)lds, h->cs, params, nullptr);
+        }
+        grad_rows_finish<T>(h, a, grid, G, st);
         return;
     }
     if (a.d > KB_LDS_MAXD) {
         // any form, more dimensions than the specialised kernels hold in LDS / registers: the general kernel reading the points
         // from global memory, one launch per window of 32 length-scale derivatives
         a.ks = h->ks; a.xs2 = (const T*)h->dXs2.p;
-        const size_t lds = grad_rows<T>(h, a, grid, (size_t)TB * sizeof(T));
+        const size_t lds = grad_rows<T>(h, a, grid, (size_t)TB * sizeof(T), G, st);
         for (a.d0 = 0; a.d0 < a.d; a.d0 += 32) {
-            hipLaunchKernelGGL(grad_reduce_general_kernel<T>, grid, dim3(256), lds, h->cs, a);
-            grad_rows_finish<T>(h, a, grid);
+            GRAD_LAUNCH(grad_reduce_general_kernel<T>, grad_reduce_general_slots_kernel<T>);
+            grad_rows_finish<T>(h, a, grid, G, st);
         }
         a.d0 = 0;
         return;
     }
     if (h->kt == 0 || h->kt == 1) {
-        const size_t lds = grad_rows<T>(h, a, grid, (size_t)(a.d + 1) * TB * sizeof(T));
-        if (h->kt == 0) launch_grad_kt<T, 0>(h, a, grid, lds);
-        else launch_grad_kt<T, 1>(h, a, grid, lds);
+        const size_t lds = grad_rows<T>(h, a, grid, (size_t)(a.d + 1) * TB * sizeof(T), G, st);
+        if (h->kt == 0) launch_grad_kt<T, 0>(h, a, grid, lds, G, st);
+        else launch_grad_kt<T, 1>(h, a, grid, lds, G, st);
     } else {
         a.ks = h->ks; a.xs2 = (const T*)h->dXs2.p;
-        const size_t lds = grad_rows<T>(h, a, grid, (size_t)(4 * a.d + 1) * TB * sizeof(T));
-        hipLaunchKernelGGL(grad_reduce_general_kernel<T>, grid, dim3(256), lds, h->cs, a);
+        const size_t lds = grad_rows<T>(h, a, grid, (size_t)(4 * a.d + 1) * TB * sizeof(T), G, st);
+        GRAD_LAUNCH(grad_reduce_general_kernel<T>, grad_reduce_general_slots_kernel<T>);
     }
-    grad_rows_finish<T>(h, a, grid);
+    grad_rows_finish<T>(h, a, grid, G, st);
 }
+#undef GRAD_LAUNCH
 
 // ---- substitutions with 1 .. TRSV_MAXR right-hand sides: one launch per triangle, L streamed once (gp_trsv.h) ----
 // The factor of slot 0 and its 128-block inverses (dW) must be resident.  false: not applicable / no memory (the caller keeps
@@ -3740,6 +3762,8 @@ int* option_slot(gphip_ctx* h, const char* name) {
         {"kbuild_mfma", &gphip_ctx::kbuild_mfma}, {"kbuild_mfma_bound", &gphip_ctx::kbuild_mfma_bound},
         {"kbuild_mfma_digits", &gphip_ctx::kbuild_mfma_digits}, {"trsv", &gphip_ctx::trsv}, {"predict_df_max_nt", &gphip_ctx::predict_df_max_nt}, {"last_issue_us", &gphip_ctx::last_issue_us}, {"last_dist_panel_df", &gphip_ctx::dist_df_mode},
         {"custom_grad", &gphip_ctx::custom_grad}, {"grad_analytic", &gphip_ctx::grad_analytic},
+        {"grad_batch_slots", &gphip_ctx::grad_batch_slots}, {"last_grad_batch_slots", &gphip_ctx::grad_batch_last},
+        {"last_grad_batch_route", &gphip_ctx::grad_batch_route}, {"grad_batch_max_n", &gphip_ctx::grad_batch_max_n},
         {"max_slots", &gphip_ctx::max_slots}, {"shard_min_n", &gphip_ctx::shard_min_n},
         {"replicate_factor", &gphip_ctx::replicate_factor}, {"share_local_panels", &gphip_ctx::share_local_panels},
         {"bcast_chunks", &gphip_ctx::bcast_chunks}, {"bcast_two_hop", &gphip_ctx::bcast_two_hop}, {"dist_panel_df", &gphip_ctx::dist_panel_df}, {"dist_owner_yield", &gphip_ctx::dist_owner_yield},
@@ -3857,5 +3881,6 @@ int gphip_sync(gphip_handle h) {
 #include "gphip_joint.inc"
 #include "gphip_extend.inc"
 #include "gphip_loo.inc"
+#include "gphip_gradbatch.inc"
 #include "gphip_xgrad.inc"
 #include "gphip_sparse.inc"

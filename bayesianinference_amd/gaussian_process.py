@@ -346,8 +346,18 @@ def defineGaussianProcess(data, kernel, nugget="Constant", meanFunction=None, va
         mean forms only (the library cannot differentiate a host function of the point)."""
         if pointwise:
             return loglik(theta), np.full(len(params), np.nan)
+        if np.ndim(theta) == 2:
+            # B x p -> (values[B], gradients[B, p]) from ONE device call (gphip_loglik_grad_batch); a failing row gets the
+            # substitution of the one-theta form
+            vals, grads, infos = handle.loglik_grad_batch(theta)
+            bad = infos != 0
+            vals[bad] = MACHINE_LOG_ZERO
+            grads[bad] = np.nan
+            return vals, grads
         ll, grad, info = handle.loglik_grad(theta)
         return (ll, grad) if info == 0 else (MACHINE_LOG_ZERO, np.full(len(params), np.nan))
+
+    log_likelihood_gradient.batched = not pointwise               # a 2-D theta is accepted (laplace.approximateEvidence asks)
 
     def log_pseudo_likelihood(theta):
         """The leave-one-out log pseudo-likelihood L_LOO(theta) (R&W GPML 5.4.2; gphip_loo): the alternative to the marginal

@@ -120,11 +120,22 @@ def approximateEvidence(obj, InitialGuess=None, Starts: int = 4, HessianStep: fl
     mean, maximum = np.clip(best.x, lo, hi), -float(best.fun)
     p = len(mean)
     H = np.zeros((p, p))
-    for k in range(p):                                       # Hessian = central difference of gradients
+    pts = np.tile(mean, (2 * p, 1))                          # Hessian = central difference of gradients: rows 2k, 2k + 1 = mean +- step_k
+    for k in range(p):
         step = HessianStep * max(abs(mean[k]), 1e-3 * (hi[k] - lo[k]))
-        a, b = mean.copy(), mean.copy()
-        a[k], b[k] = min(mean[k] + step, hi[k]), max(mean[k] - step, lo[k])
-        H[:, k] = (neg_post(a)[1] - neg_post(b)[1]) / (a[k] - b[k])
+        pts[2 * k, k], pts[2 * k + 1, k] = min(mean[k] + step, hi[k]), max(mean[k] - step, lo[k])
+    if getattr(value_grad, "batched", False):                # all 2p gradients from ONE call of the closure
+        lls, gs = value_grad(np.clip(pts, lo, hi))
+        grads = np.zeros((2 * p, p))
+        for r in range(2 * p):                               # (row by row what neg_post does with one theta)
+            theta = np.clip(pts[r], lo, hi)
+            lp = logprior(theta)
+            if not (lls[r] <= MACHINE_LOG_ZERO or lp <= MACHINE_LOG_ZERO or not np.all(np.isfinite(gs[r]))):
+                grads[r] = -(gs[r] + _prior_grad(logprior, theta, lo, hi))
+    else:
+        grads = np.array([neg_post(row)[1] for row in pts])
+    for k in range(p):
+        H[:, k] = (grads[2 * k] - grads[2 * k + 1]) / (pts[2 * k, k] - pts[2 * k + 1, k])
     precision = 0.5 * (H + H.T)                              # - Hessian of the log posterior (neg_post is already negated)
     out = {"Maximum": (maximum, mean), "Mean": mean, "PrecisionMatrix": precision,
            "Parameters": [p_[0] for p_ in params]}

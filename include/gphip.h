@@ -181,6 +181,31 @@ int gphip_loglik_parts(gphip_handle h, const double* theta, int p, double* out, 
  * 1/2 tr((alpha alpha^T - K^-1) dK/dtheta_p).  No reference counterpart (the
  * reference maximises without gradients, LaplaceApproximation.wl:177-238).  grad = NaN if *info != 0. */
 int gphip_loglik_grad(gphip_handle h, const double* theta, int p, double* out, double* grad, int* info);
+/* gphip_loglik_grad_batch: value and gradient for the B rows of the row-major B x p array Theta in one call.  Theta: row-major
+ * B x p; out, info: length B; grad: row-major B x p (layout of gphip_loglik_grad per row).  Row s has the semantics of
+ * gphip_loglik_grad(h, Theta + s p, p, out + s, grad + s p, info + s).  A row that fails -- non-finite theta, a K that does not
+ * factor -- sets only its own info[s] (GPHIP_INFO_NAN / GPHIP_INFO_NOT_SPD), its grad row is NaN and out[s] undefined, as in the
+ * one-theta call; the other rows of the call are not disturbed.  NULL h / Theta / out / grad / info are GPHIP_ERR_ARG, a wrong p
+ * GPHIP_ERR_DIM, B <= 0 returns GPHIP_OK and touches nothing: all decided before any device work.
+ * The rows are evaluated in groups, one theta per workspace slot: a group's K are built and factored together, U_s = L_s^-T of
+ * all slots comes from one multi-kernel forward pass over the identity (the route of "grad_potri" = 2), alpha_s = U_s z_s,
+ * K_s^-1 = U_s U_s^T and the gradient reductions are launches that carry the slot as a grid dimension, and the accumulators of
+ * the group come back in one download.  A group holds as many rows as the context gives workspace slots,
+ * as keep what is missing of the 2 (Npad + 16) Npad es bytes of scratch per slot within a quarter of the free device memory, and
+ * as option "grad_batch_slots" allows (0, the default: no limit of its own).  "last_grad_batch_slots" (read-only) gives the rows
+ * in the last group of the last call, "last_grad_batch_route" (read-only) 1 when that route ran.  It reads 0 when the rows went
+ * one by one through gphip_loglik_grad instead, with results bit-identical to the caller's own loop: not even two slots fit,
+ * "grad_potri" = 0, the handle has more training points than option "grad_batch_max_n" (default 7168, 0 = no limit: beyond it
+ * one theta fills the device and the batch measured no faster than the loop), a point-dependent nugget / mean is set, or the
+ * handle's run-time compiled covariance function has no
+ * gradient program (it does not compile with dual numbers, more than 64 parameters, "custom_grad" = 0: central differences).
+ * With a gradient program, custom_grad_kernel is launched once per slot behind the shared chain.  The null kernel is answered
+ * by the host; a multi-device handle runs the batch on its first device, as the one-theta gradient does.
+ * The call drops any resident fit, as gphip_loglik_batch does: a following gphip_predict is GPHIP_ERR_STATE.  Every row's sums
+ * run in a fixed order without atomics: two calls with the same arguments and options return the same bytes, and permuting the
+ * rows of Theta permutes out, grad and info bit for bit while the group sizes stay the same.  Against gphip_loglik_grad of the
+ * same theta a row differs by rounding (the factorisations of several slots take another schedule). */
+int gphip_loglik_grad_batch(gphip_handle h, const double* Theta, int B, int p, double* out, double* grad, int* info);
 
 /* Factor K(theta) and keep L and L^-1 r resident for predict / solve / logdet. */
 int gphip_fit(gphip_handle h, const double* theta, int p, int* info);
@@ -472,6 +497,10 @@ int gphip_ns_crude_weights(const double* points, const double* loglik, int64_t m
  *   "custom_grad"  0/1 (default 1): gphip_loglik_grad of a run-time compiled covariance function through forward-mode dual
  *                  numbers (one factorisation); 0 = central differences.  "grad_analytic" (read-only) = 1 after a gradient call
  *                  that took the one-factorisation route.
+ *   "grad_batch_slots" n: gphip_loglik_grad_batch evaluates at most n rows per group; 0 (default): its group rule alone.
+ *                  "grad_batch_max_n" (default 7168; 0 = no limit): handles with more training points send the rows one by one
+ *                  through gphip_loglik_grad.  "last_grad_batch_slots" / "last_grad_batch_route" (read-only): the rows in the
+ *                  last group of the last call / 1 when the batched route ran, 0 for the per-row loop.
  *   "debug_fail_alloc" / "debug_fail_hip" n: tests only -- the n-th device allocation of the next slot allocation / the n-th checked
  *                  HIP call of the next collective sequence fails (fault injection of the multi-process tests).  The names exist
  *                  only in a process started with GPHIP_TEST_HOOKS=1 in its environment ("unknown option" otherwise) and are
