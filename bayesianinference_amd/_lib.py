@@ -99,6 +99,12 @@ _SIGNATURES = {
     "gphip_predict_logpdf": (C.c_int, [_h, C.c_void_p, C.c_int64, _dp, _dp, _ip]),
     "gphip_extend": (C.c_int, [_h, C.c_void_p, _dp, C.c_int64, C.POINTER(_h), _dp, _ip]),
     "gphip_predict_grad": (C.c_int, [_h, C.c_void_p, C.c_int64, _dp, _dp, _dp, _dp]),
+    "gphip_rff_table": (C.c_int, [C.c_int, C.c_int64, _dp, C.c_int, C.c_int, C.c_uint64, C.POINTER(C.c_int64), _dp, _dp, _dp]),
+    "gphip_paths_create": (C.c_int, [_h, C.c_int, C.c_int, C.c_uint64, C.POINTER(_h), _ip]),
+    "gphip_paths_eval": (C.c_int, [_h, C.c_void_p, C.c_int64, _dp, _dp]),
+    "gphip_paths_shape": (C.c_int, [_h, _ip, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "gphip_paths_get": (C.c_int, [_h, _dp, _dp, _dp, _dp, _dp]),
+    "gphip_paths_destroy": (C.c_int, [_h]),
     "gphip_loglik_batch_pw": (C.c_int, [_h, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _ip]),
     "gphip_fit_pw": (C.c_int, [_h, _dp, C.c_int, _dp, _dp, _ip]),
     "gphip_predict_pw": (C.c_int, [_h, C.c_void_p, C.c_int64, _dp, _dp, _dp, _dp]),
@@ -267,6 +273,71 @@ class CustomKernel:
         return f"CustomKernel({self.name!r}, nparams={self.nparams})"
 
 
+def rff_table(kernel, d: int, theta, F: int, seed: int = 0):
+    """gphip_rff_table (host only): (omega[Ftot, d], phase[Ftot], amp[Ftot]) of a named kernel (a name or an id) at theta."""
+    lib = load()
+    kid = kernel if isinstance(kernel, int) else kernel_id(kernel)
+    th = np.ascontiguousarray(np.asarray(theta, dtype=np.float64).ravel())
+    ftot = C.c_int64(0)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    rc = lib.gphip_rff_table(kid, int(d), _d(th), th.size, int(F), seed, C.byref(ftot), None, None, None)
+    if rc != OK:
+        raise GphipError(rc, "gphip_rff_table: no feature table for this kernel, theta or F")
+    omega, phase, amp = np.zeros((ftot.value, int(d))), np.zeros(ftot.value), np.zeros(ftot.value)
+    rc = lib.gphip_rff_table(kid, int(d), _d(th), th.size, int(F), seed, C.byref(ftot), _d(omega), _d(phase), _d(amp))
+    if rc != OK:
+        raise GphipError(rc, "gphip_rff_table: no feature table for this kernel, theta or F")
+    return omega, phase, amp
+
+
+class Paths:
+    """Owns one gphip_paths_handle (Handle.sample_paths): S coherent draws of the latent posterior function.  Keeps its parent
+    Handle alive; close() it (or leave the with block) before the parent is closed."""
+
+    def __init__(self, parent, h):
+        self._parent, self._lib, self._q = parent, parent._lib, h
+        S, ftot, n, d = C.c_int(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._lib.gphip_paths_shape(self._q, C.byref(S), C.byref(ftot), C.byref(n), C.byref(d))
+        self.S, self.Ftot, self.N, self.d = S.value, ftot.value, n.value, d.value
+
+    def _check(self, rc: int):
+        if rc != OK:
+            raise GphipError(rc, (self._lib.gphip_last_error(self._parent._h) or b"").decode())
+
+    def eval(self, Xs, grad: bool = False):
+        """f_s(Xs): out[S, M]; grad=True: (out, dout[S, M, d]) with dout[s, t, c] = df_s/dx_tc.  out is the same bytes either way."""
+        Xs = self._parent._test_points(Xs)
+        M = Xs.shape[0]
+        out = np.zeros((self.S, M))
+        dout = np.zeros((self.S, M, self.d)) if grad else None
+        self._check(self._lib.gphip_paths_eval(self._q, Xs.ctypes.data, M, _d(out), _d(dout) if grad else None))
+        return (out, dout) if grad else out
+
+    def table(self):
+        """{"omega" [Ftot, d], "phase" [Ftot], "w" [S, Ftot], "eps" [S, N], "v" [S, N]}: what the draws were made from"""
+        t = {"omega": np.zeros((self.Ftot, self.d)), "phase": np.zeros(self.Ftot), "w": np.zeros((self.S, self.Ftot)),
+             "eps": np.zeros((self.S, self.N)), "v": np.zeros((self.S, self.N))}
+        self._check(self._lib.gphip_paths_get(self._q, _d(t["omega"]), _d(t["phase"]), _d(t["w"]), _d(t["eps"]), _d(t["v"])))
+        return t
+
+    def close(self):
+        if getattr(self, "_q", None):
+            self._lib.gphip_paths_destroy(self._q)
+            self._q = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Handle:
     """Owns one gphip_handle: training data resident on the device (gphip_create .. gphip_destroy)."""
 
@@ -353,7 +424,8 @@ class Handle:
 
     def close(self):
         if getattr(self, "_h", None):
-            self._lib.gphip_destroy(self._h)
+            if self._lib.gphip_destroy(self._h) == 4:        # live Paths objects: nothing was destroyed, the handle stays open
+                raise GphipError(4, (self._lib.gphip_last_error(self._h) or b"").decode())
             self._h = None
 
     def __del__(self):
@@ -590,6 +662,15 @@ class Handle:
         new.N, new.d = self.N + M, self.d
         new.kernel, new.mean, new.dtype, new.p = self.kernel, self.mean, self.dtype, self.p
         return new, logp.value, info.value
+
+    def sample_paths(self, S: int, F: int = 1024, seed: int = 0):
+        """gphip_paths_create: S pathwise draws of the latent posterior function of the resident fit, F random Fourier features
+        per term.  Returns a Paths (close it before this handle), or None when v is not finite (info = GPHIP_INFO_NAN)."""
+        out, info = _h(), C.c_int(0)
+        self._check(self._lib.gphip_paths_create(self._h, int(S), int(F), int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(out), C.byref(info)))
+        if not out.value:
+            return None
+        return Paths(self, out)
 
     def predict_grad(self, Xs, variance: bool = True):
         """Gradients of the prediction in the test inputs (gphip_predict_grad): (mean[M], var[M], dmean[M, d], dvar[M, d]);

@@ -71,8 +71,7 @@ __global__ void joint_cblock_kernel(const T* __restrict__ A, int R, int npad, do
 // Philox4x32-10 (Salmon et al., SC'11), counter (j, s, 0x4A4F494E, 0), key = the 64-bit seed: one standard normal per
 // (seed, s, j) by Box-Muller from two 53-bit uniforms.  Nothing depends on how a call is chunked or tiled.
 // ---------------------------------------------------------------------------------------------
-__host__ __device__ inline double philox_normal(uint64_t seed, uint32_t s, uint32_t j) {
-    uint32_t c0 = j, c1 = s, c2 = 0x4A4F494Eu, c3 = 0u;
+__host__ __device__ inline void philox_words(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t* out) {
     uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
     for (int r = 0; r < 10; ++r) {
         const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
@@ -81,10 +80,21 @@ __host__ __device__ inline double philox_normal(uint64_t seed, uint32_t s, uint3
         c0 = n0; c1 = n1; c2 = n2; c3 = n3;
         k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
     }
-    const uint64_t a = (((uint64_t)c0 << 32) | c1) >> 11, b = (((uint64_t)c2 << 32) | c3) >> 11;
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+__host__ __device__ inline double philox_normal(uint64_t seed, uint32_t s, uint32_t j) {
+    uint32_t c[4];
+    philox_words(seed, j, s, 0x4A4F494Eu, 0u, c);
+    const uint64_t a = (((uint64_t)c[0] << 32) | c[1]) >> 11, b = (((uint64_t)c[2] << 32) | c[3]) >> 11;
     const double u1 = ((double)a + 0.5) * 0x1.0p-53;                 // (0, 1)
     const double u2 = (double)b * 0x1.0p-53;                         // [0, 1)
     return sqrt(-2.0 * log(u1)) * cos(6.283185307179586476925286766559 * u2);
+}
+// a uniform on [0, 1) with 32 bits from the same counter space, third counter word 0x554E4946 ("UNIF"): never a normal's counter
+__host__ __device__ inline double philox_uniform(uint64_t seed, uint32_t s, uint32_t j) {
+    uint32_t c[4];
+    philox_words(seed, j, s, 0x554E4946u, 0u, c);
+    return (double)c[0] * 0x1.0p-32;
 }
 
 // Z[s][j] (ld ldz) for the draws s0 .. s0 + S - 1 of the call, j < M; zero for M <= j < ldz

@@ -299,6 +299,13 @@ struct gphip_ctx {
     // gphip_extend (gphip_extend.inc), read-only on the parent: microseconds of the last call's phases -- the joint log density
     // (host clock), the new context and its buffers (host clock), the assembly kernel and the block inverses (events)
     int extend_logpdf_us = 0, extend_create_us = 0, extend_assemble_us = 0, extend_derive_us = 0;
+    // pathwise function draws (gphip_paths.inc): live paths objects that borrow this context (gphip_destroy refuses while > 0)
+    int paths_live = 0;
+    int paths_split = 0;                              // option: strips of both contractions (0 = by the strip rule)
+    int paths_nsplit = 0;                             // read-only: strips the last evaluation's kernel contraction used
+    int paths_chunk = 0;                              // option: points per chunk of gphip_paths_eval (0 = by the chunk rule)
+    // read-only: host microseconds of the last gphip_paths_create (whole call; its feature pass; its substitutions) and _eval
+    int paths_create_us = 0, paths_feature_us = 0, paths_subst_us = 0, paths_eval_us = 0;
 };
 
 namespace {
@@ -2696,6 +2703,10 @@ int gphip_create_rank(const void* X, const void* y, int64_t N, int64_t d, int ke
 
 int gphip_destroy(gphip_handle h) {
     if (!h) return GPHIP_OK;
+    {                                          // (the count is written under h->mu by gphip_paths_create / _destroy)
+        std::lock_guard<std::recursive_mutex> lk(h->mu);
+        if (h->paths_live > 0) return fail(h, GPHIP_ERR_STATE, "gphip_destroy with live paths objects: gphip_paths_destroy them first");
+    }
     (void)hipSetDevice(h->device);
     if (h->cstream) (void)hipStreamSynchronize(h->cstream);
     if (h->pstream) (void)hipStreamSynchronize(h->pstream);
@@ -3773,6 +3784,9 @@ int* option_slot(gphip_ctx* h, const char* name) {
         {"predict_grad_chunk", &gphip_ctx::predict_grad_chunk}, {"last_predict_grad_chunk", &gphip_ctx::predict_grad_chunk_last},
         {"last_extend_logpdf_us", &gphip_ctx::extend_logpdf_us}, {"last_extend_create_us", &gphip_ctx::extend_create_us},
         {"last_extend_assemble_us", &gphip_ctx::extend_assemble_us}, {"last_extend_derive_us", &gphip_ctx::extend_derive_us},
+        {"paths_split", &gphip_ctx::paths_split}, {"last_paths_nsplit", &gphip_ctx::paths_nsplit}, {"paths_chunk", &gphip_ctx::paths_chunk},
+        {"last_paths_create_us", &gphip_ctx::paths_create_us}, {"last_paths_feature_us", &gphip_ctx::paths_feature_us},
+        {"last_paths_subst_us", &gphip_ctx::paths_subst_us}, {"last_paths_eval_us", &gphip_ctx::paths_eval_us},
     };
     // fault injection ("debug_*") exists for the test-suite only: the names resolve in a process that was started with
     // GPHIP_TEST_HOOKS=1 and nowhere else (not through GPHIP_OPTIONS either: apply_env_options skips them)
@@ -3876,11 +3890,12 @@ int gphip_sync(gphip_handle h) {
 
 }  // extern "C"
 
-#include "gphip_hostlogic.inc"
 #include "gphip_sampler.inc"
 #include "gphip_joint.inc"
+#include "gphip_hostlogic.inc"    // (behind gphip_joint.inc: gphip_rff_table uses gp_joint.h's Philox counters, and the device code keeps its order)
 #include "gphip_extend.inc"
 #include "gphip_loo.inc"
 #include "gphip_gradbatch.inc"
 #include "gphip_xgrad.inc"
 #include "gphip_sparse.inc"
+#include "gphip_paths.inc"

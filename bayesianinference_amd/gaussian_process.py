@@ -694,6 +694,110 @@ def gaussianProcessFunctionSamples(obj, pts, n: int, seed: int = 0, latent: bool
     return {"Points": P, "Sample": which, "Values": values}
 
 
+class posteriorFunctionSamples:
+    """What samplePathsFromGaussianProcess returns: n coherent draws of the latent posterior function.  f(pts) -> [n, M];
+    f.gradient(pts) -> [n, M, d]; f.sample [n] = the index into "Samples" each draw belongs to (zeros in the direct form).
+    Rows of a theta that does not factor are NaN.  close() (or the with block) releases the device objects."""
+
+    def __init__(self, parts, n, d, inverse, scale, owned=None):
+        self._parts, self.n, self.d = parts, int(n), int(d)             # parts: [(rows, _lib.Paths)]
+        self._inverse, self._scale, self._owned = inverse, scale, owned
+        self.sample = np.zeros(self.n, dtype=np.int64)
+
+    def _points(self, pts):
+        P = dataNormalForm(pts)
+        if P is None or isinstance(P, tuple) or P.shape[1] != self.d:
+            raise ValueError("pts must be M points of dimension %d" % self.d)
+        return P
+
+    def __call__(self, pts):
+        P = self._points(pts)
+        out = np.full((self.n, len(P)), np.nan)
+        for rows, paths in self._parts:
+            out[rows] = paths.eval(P)
+        return out if self._inverse is None else np.asarray(self._inverse(out), dtype=np.float64).reshape(out.shape)
+
+    def gradient(self, pts):
+        P = self._points(pts)
+        out = np.full((self.n, len(P), self.d), np.nan)
+        for rows, paths in self._parts:
+            out[rows] = paths.eval(P, grad=True)[1]
+        return out * self._scale
+
+    def close(self):
+        for _, paths in self._parts:
+            paths.close()
+        self._parts = []
+        if self._owned is not None:
+            self._owned.close()
+            self._owned = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def samplePathsFromGaussianProcess(obj_or_examples, n: int, kernel=None, theta=None, meanFunction=None, Features: int = 1024, seed: int = 0):
+    """n pathwise draws of the latent posterior function (gphip_paths_create; no reference counterpart) that can be evaluated at
+    any points, and differentiated, after they have been drawn: Thompson sampling, optimum-location sampling.  Two forms, as
+    predictFromGaussianProcess:
+      samplePathsFromGaussianProcess(obj, n)                         a sampled GP object: every draw picks a theta from "Samples" by
+          CrudePosteriorWeight (numpy generator seeded by `seed`, the assignment of gaussianProcessFunctionSamples), one fit and
+          one paths object per distinct theta used;
+      samplePathsFromGaussianProcess((X, Y), n, kernel, theta[, meanFunction])   the direct form.
+    Features: random Fourier features per kernel term (the prior is approximated with error O(1 / sqrt(Features))).  Values come
+    back in the units of the data ("DataPreProcessors" undone), gradients scaled accordingly.
+    On a GP object the paths objects live on the object's own "HIPHandle": until the result's close() (or the end of its `with`
+    block) that handle cannot be closed (Handle.close raises GphipError, status 4), and it is left fitted at the last theta
+    used here, not at the theta it held before the call.  The direct form owns a handle of its own and closes it with the result.
+    Returns a posteriorFunctionSamples, or None for bad arguments, an unsampled object, point-dependent nugget / mean functions
+    and a run-time compiled kernel."""
+    if int(n) < 1 or int(Features) < 1:
+        return None
+    if isinstance(obj_or_examples, inferenceObject):
+        obj = obj_or_examples
+        if obj.failed or "GaussianProcessData" not in obj or "Samples" not in obj:
+            return None
+        mf = obj["GaussianProcessData"]["ModelFunctions"]
+        if callable(mf["NuggetFunction"]) or callable(mf["MeanFunction"]):
+            return None
+        handle = obj["GaussianProcessData"]["HIPHandle"]
+        if isinstance(handle.kernel, _lib.CustomKernel):
+            return None
+        samples = obj["Samples"]
+        points = np.array([s["Point"] for s in samples], dtype=np.float64)
+        w = np.array([s["CrudePosteriorWeight"] for s in samples], dtype=np.float64)
+        which = np.random.default_rng(seed).choice(len(samples), size=int(n), p=w / w.sum())
+        parts = []
+        for k in np.unique(which):
+            rows = np.flatnonzero(which == k)
+            if handle.fit(points[k]) != 0:
+                continue
+            key = int(np.random.SeedSequence([int(seed) & (2**63 - 1), int(k)]).generate_state(1, np.uint64)[0])
+            paths = handle.sample_paths(len(rows), int(Features), key)
+            if paths is not None:
+                parts.append((rows, paths))
+        inverse, scale = _output_scale(obj)
+        res = posteriorFunctionSamples(parts, n, handle.d, inverse, scale)
+        res.sample = which
+        return res
+    norm = dataNormalForm(obj_or_examples)
+    if norm is None or not isinstance(norm, tuple) or norm[1].shape[1] != 1 or theta is None:
+        return None
+    k = _resolve_kernel(kernel)
+    if isinstance(k, _lib.CustomKernel):
+        return None
+    mean = "zero" if meanFunction in (None, 0, "Zero", "zero") else "const"
+    handle = _lib.Handle(norm[0], norm[1][:, 0], k, mean)
+    paths = handle.sample_paths(int(n), int(Features), int(seed)) if handle.fit(np.asarray(theta, dtype=np.float64).ravel()) == 0 else None
+    if paths is None:
+        handle.close()
+        return None
+    return posteriorFunctionSamples([(np.arange(int(n)), paths)], n, handle.d, None, 1.0, owned=handle)
+
+
 def _output_scale(obj):
     """(inverse, scale) of the "Output" pre-processor of an object defined on normalizeData(..) data: y = inverse(z), and the
     factor by which it stretches a standard deviation; (None, 1.0) for an object on raw data."""

@@ -305,6 +305,60 @@ int gphip_extend(gphip_handle h, const void* X_new /* row-major M x d fp64 */, c
  * seeded in the coordinates, as gphip_sparse_bound_grad_inducing says), for a fit made by gphip_fit_pw with a non-NULL array
  * (dm/dx of a host function is unknown) and for a sharded fit with replicate_factor = 0. */
 int gphip_predict_grad(gphip_handle h, const void* Xs, int64_t M, double* mean, double* var, double* dmean, double* dvar);
+/* ---- Pathwise posterior function draws (Matheron's rule; Wilson et al. 2020; no reference counterpart): S draws of the LATENT
+ * posterior function of the current fit that can be evaluated anywhere, and differentiated, after they have been drawn -- what
+ * Thompson sampling, optimum-location sampling and entropy-search estimators walk.  gphip_predict_draws fixes its M test points
+ * before the draw, pays N^2 M + M^3 / 3 per call, stops at GPHIP_JOINT_MAX_M and has no gradient.  With K = k(X, X) + sn^2 I and
+ * the constant mean m, draw s = 0 .. S - 1 is
+ *     f_s(x)  = m + f~_s(x) + k(x, X) v_s,      v_s = K^-1 (y - m - f~_s(X) - eps_s),   eps_s ~ N(0, sn^2 I)
+ *     f~_s(x) = sum_j a_j w_sj cos(Omega_j . x + b_j),   w_sj ~ N(0, 1),   b_j ~ U[0, 2 pi)        (random Fourier features)
+ * A noisy observation of f_s is the caller's business (add sn z).  Omega is in raw input units (length scales divided in).
+ * f~ approximates the PRIOR with error O(1 / sqrt(F)); given (Omega, b), f_s is exactly linear-Gaussian in (w, eps)
+ * (DESIGN.md section 8m has the frequency laws and measured errors).  After the one-off O(N^2 S) solve on the resident factor one
+ * evaluation costs O(N + Ftot) per point and draw; the draws of one object are coherent across calls.
+ *
+ * gphip_rff_table: host only, no device: the feature table of a named kernel at theta (p = its length, with or without the
+ * constant mean's entry).  omega: Ftot x d row-major; phase, amp: Ftot.  omega == NULL: the size query (*Ftot_out only).
+ * Ftot = F (one term, product), 2 F (sum), + 1 with the constant offset (Omega = 0, b = 0, a = sqrt(c)).  Deterministic in
+ * (kernel_id, d, theta, F, seed): Philox counters under documented keys (csrc/gphip_hostlogic.inc); the rows of F features are
+ * NOT a prefix of those of F' > F.  GPHIP_KERNEL_CUSTOM and GPHIP_KERNEL_NULL: GPHIP_ERR_UNSUPPORTED; a wrong p, F < 1, d < 1:
+ * GPHIP_ERR_DIM; an unknown id, a zero length scale, alpha <= 0, a negative offset, a missing array: GPHIP_ERR_ARG.
+ *
+ * gphip_paths_create works on a resident fit like gphip_predict_cov; it never invalidates the fit and gphip_predict returns the
+ * same bytes before and after it.  w_sj = philox_normal(seed, s, j), eps_si = sn philox_normal(seed ^ 0x2E2AC13EF8E8D8D2, s, i)
+ * (both evaluated on the device; the key of eps is 10 x 0x9E3779B97F4A7C15 mod 2^64, which no stream of the table uses: those
+ * are 1, 2, 5, 6 and 9 times that constant, so eps is independent of (Omega, b)), the table is gphip_rff_table(fitted theta, F, seed) byte for byte.  Prefix property: the first S
+ * rows of w and eps and the whole table equal those of a call with S' > S bit for bit; v and the outputs agree to rounding.
+ * The object owns device copies of everything that depends on theta or the draw (raw X, 1 / l, the slot scalars, Omega, b, a w,
+ * w, eps, v): it stays valid when the parent is fitted again at another theta.  It borrows the parent's device, stream and mutex
+ * (one call in flight) and must be destroyed before the parent: gphip_destroy of a parent with live paths objects returns
+ * GPHIP_ERR_STATE and destroys nothing.  Statuses, all decided before any device work: NULL h / out / info GPHIP_ERR_ARG; S < 1,
+ * F < 1, S > 2048, Ftot S > 2^26 GPHIP_ERR_DIM; no fit GPHIP_ERR_STATE; a run-time compiled covariance function, a fit made by
+ * gphip_fit_pw with a non-NULL array and a sharded fit with replicate_factor = 0 GPHIP_ERR_UNSUPPORTED.  *info = GPHIP_INFO_NAN
+ * on a non-finite v: *out = NULL, status GPHIP_OK.  The null kernel is answered on the host (f = m, gradients 0, Ftot = 0).  A
+ * multi-device handle whose first device holds the whole factor computes there.  fp64 and fp32 handles (the coordinates, phases
+ * and kernel values are fp64 in both; weights, matrix products and the solve are the handle's type).
+ *
+ * gphip_paths_eval: Xs row-major M x d fp64, any M >= 1 (chunks; no GPHIP_JOINT_MAX_M); out S x M; dout S x M x d
+ * (dout[s][t][c] = df_s/dx*_tc) or NULL.  out is the same bytes whether dout is asked for or not, and two calls return the same
+ * bytes (fixed-order sums, no atomics).  gphip_paths_get: every pointer may be NULL: omega Ftot x d, phase Ftot, w S x Ftot (the
+ * unit normals), eps S x N, v S x N.
+ * Options on the PARENT handle: "paths_split" n (0 = by the strip rule) forces n strips of both contractions;
+ * "last_paths_nsplit" (read-only) the strips of the last evaluation's contraction over the training points; "paths_chunk" n
+ * (0 = up to 16384) = n points per chunk, rounded up to 64; "last_paths_create_us" / "last_paths_feature_us" /
+ * "last_paths_subst_us" / "last_paths_eval_us" (read-only): host microseconds of the last create (whole call, its feature pass,
+ * its substitutions) and evaluation.
+ * Not offered: the sparse object, run-time compiled covariance functions, point-dependent fits, sharding over devices,
+ * conditioning a paths object on new data. */
+typedef struct gphip_paths* gphip_paths_handle;
+int gphip_rff_table(int kernel_id, int64_t d, const double* theta, int p, int F, uint64_t seed, int64_t* Ftot_out, double* omega,
+                    double* phase, double* amp);
+int gphip_paths_create(gphip_handle h, int S, int F, uint64_t seed, gphip_paths_handle* out, int* info);
+int gphip_paths_eval(gphip_paths_handle q, const void* Xs /* M x d fp64 */, int64_t M, double* out /* S x M */,
+                     double* dout /* S x M x d, or NULL */);
+int gphip_paths_shape(gphip_paths_handle q, int* S, int64_t* Ftot, int64_t* N, int64_t* d);
+int gphip_paths_get(gphip_paths_handle q, double* omega, double* phase, double* w, double* eps, double* v);
+int gphip_paths_destroy(gphip_paths_handle q);
 /* ---- Leave-one-out cross-validation (Rasmussen & Williams, GPML section 5.4.2; no reference counterpart): how well the model
  * at theta predicts every training point from the other N - 1, from ONE factorisation.  With alpha = K^-1 (y - m) and
  * k_i = [K^-1]_ii:
