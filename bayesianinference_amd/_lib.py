@@ -102,6 +102,7 @@ _SIGNATURES = {
     "gphip_rff_table": (C.c_int, [C.c_int, C.c_int64, _dp, C.c_int, C.c_int, C.c_uint64, C.POINTER(C.c_int64), _dp, _dp, _dp]),
     "gphip_paths_create": (C.c_int, [_h, C.c_int, C.c_int, C.c_uint64, C.POINTER(_h), _ip]),
     "gphip_paths_eval": (C.c_int, [_h, C.c_void_p, C.c_int64, _dp, _dp]),
+    "gphip_paths_eval_own": (C.c_int, [_h, C.c_void_p, C.c_int64, _dp, _dp]),
     "gphip_paths_shape": (C.c_int, [_h, _ip, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "gphip_paths_get": (C.c_int, [_h, _dp, _dp, _dp, _dp, _dp]),
     "gphip_paths_destroy": (C.c_int, [_h]),
@@ -311,6 +312,18 @@ class Paths:
         out = np.zeros((self.S, M))
         dout = np.zeros((self.S, M, self.d)) if grad else None
         self._check(self._lib.gphip_paths_eval(self._q, Xs.ctypes.data, M, _d(out), _d(dout) if grad else None))
+        return (out, dout) if grad else out
+
+    def eval_own(self, Xs, grad: bool = False):
+        """gphip_paths_eval_own: every draw at its own points.  Xs[S, M, d] -> out[S, M] with out[s, t] = f_s(Xs[s, t]); grad=True:
+        (out, dout[S, M, d]).  out is the same bytes either way.  A wrong shape raises ValueError before any library call."""
+        Xs = np.ascontiguousarray(np.asarray(Xs, dtype=np.float64))
+        if Xs.ndim != 3 or Xs.shape[0] != self.S or Xs.shape[1] < 1 or Xs.shape[2] != self.d:
+            raise ValueError("Xs must have shape [%d, M, %d] with M >= 1, got %s" % (self.S, self.d, list(Xs.shape)))
+        M = Xs.shape[1]
+        out = np.zeros((self.S, M))
+        dout = np.zeros((self.S, M, self.d)) if grad else None
+        self._check(self._lib.gphip_paths_eval_own(self._q, Xs.ctypes.data, M, _d(out), _d(dout) if grad else None))
         return (out, dout) if grad else out
 
     def table(self):

@@ -306,6 +306,8 @@ struct gphip_ctx {
     int paths_chunk = 0;                              // option: points per chunk of gphip_paths_eval (0 = by the chunk rule)
     // read-only: host microseconds of the last gphip_paths_create (whole call; its feature pass; its substitutions) and _eval
     int paths_create_us = 0, paths_feature_us = 0, paths_subst_us = 0, paths_eval_us = 0;
+    // read-only: gphip_paths_eval_own's strips of the contraction over the training points and host microseconds (last call)
+    int paths_own_nsplit = 0, paths_own_us = 0;
 };
 
 namespace {
@@ -3787,6 +3789,7 @@ int* option_slot(gphip_ctx* h, const char* name) {
         {"paths_split", &gphip_ctx::paths_split}, {"last_paths_nsplit", &gphip_ctx::paths_nsplit}, {"paths_chunk", &gphip_ctx::paths_chunk},
         {"last_paths_create_us", &gphip_ctx::paths_create_us}, {"last_paths_feature_us", &gphip_ctx::paths_feature_us},
         {"last_paths_subst_us", &gphip_ctx::paths_subst_us}, {"last_paths_eval_us", &gphip_ctx::paths_eval_us},
+        {"last_paths_own_nsplit", &gphip_ctx::paths_own_nsplit}, {"last_paths_own_us", &gphip_ctx::paths_own_us},
     };
     // fault injection ("debug_*") exists for the test-suite only: the names resolve in a process that was started with
     // GPHIP_TEST_HOOKS=1 and nowhere else (not through GPHIP_OPTIONS either: apply_env_options skips them)

@@ -1,6 +1,6 @@
-// gphip_paths.inc -- pathwise posterior function draws (include/gphip.h: gphip_paths_create / _eval / _shape / _get / _destroy;
-// DESIGN.md section 8m).  Included at the end of gphip.hip.  Exact object only.  Out of scope: the sparse object, run-time
-// compiled covariance functions, point-dependent fits, sharding over devices, conditioning a paths object on new data.
+// gphip_paths.inc -- pathwise posterior function draws (include/gphip.h: gphip_paths_create / _eval / _eval_own / _shape / _get /
+// _destroy; DESIGN.md sections 8m and 8n).  Included at the end of gphip.hip.  Exact object only.  Out of scope: the sparse object,
+// run-time compiled covariance functions, point-dependent fits, sharding over devices, conditioning a paths object on new data.
 //
 //   create   gphip_rff_table(fitted theta)             host: Omega, b, a
 //            paths_weights_kernel                      w_sj = philox_normal(seed, s, j), Wa = a_j w_sj
@@ -11,9 +11,13 @@
 //   eval     per chunk of points: paths_contract_kernel<GenFeature> over the features, <GenKernel> over the training points,
 //            paths_finish_kernel (mean + strips in order), one download; with dout the GRAD forms and paths_finish_grad_kernel.
 //            The values come from the value launches whether dout is asked for or not: the same bytes.
+//   eval_own per chunk of points per draw: paths_own_kernel (gp_paths_own.h; a thread owns one (draw, point) pair) over the
+//            features, then over the training points, paths_own_finish_kernel, one download.  With dout the GRAD form leaves the
+//            value and the d gradient components of a pair from one generator evaluation; the value is summed in the same order.
 // The object owns device copies of all it needs (raw X, 1 / l, slot scalars, Omega, b, Wa, w, eps, v): a later fit of the parent at
 // another theta does not touch it.  It borrows the parent's device, stream and mutex and must be destroyed before the parent.
 #include "gp_paths.h"
+#include "gp_paths_own.h"
 
 struct gphip_paths {
     gphip_ctx* h = nullptr;
@@ -49,23 +53,31 @@ int paths_strips(const gphip_ctx* h, long wgs, long ncon, int forced, int* strip
     return (int)((nslabs + *strip_slabs - 1) / *strip_slabs);
 }
 
-// One contraction: the points xt ([d][ldt], ntest of them) against the features (kernel = false) or the training points of q, into
-// part (grown here).  grad: the GRAD form, d components.  *nstrips_out: the strips used.
+// The contraction side of q for the points xt ([d][ldt], ntest of them): the features (kernel = false) or the training points
 template <typename T>
-int queue_paths_contract(gphip_paths* q, bool kernel, bool grad, const double* xt, long ldt, int64_t ntest, Buf& part, int split, int* nstrips_out) {
-    gphip_ctx* h = q->h;
+PathsArgs<T> paths_side(const gphip_paths* q, bool kernel, const double* xt, long ldt, int64_t ntest) {
     PathsArgs<T> a{};
-    const int d = (int)q->d;
     a.xt = xt; a.ldt = ldt;
     a.con = kernel ? q->dXt.as<double>() : q->dOmT.as<double>();
     a.ldc = kernel ? (long)q->Npad : (long)q->Ftot;
     a.phase = kernel ? nullptr : q->dPhase.as<double>();
     a.W = kernel ? (const T*)q->dV.p : (const T*)q->dWa.p; a.ldw = (long)q->Spad;
-    a.ntest = (int)ntest; a.ncon = (int)(kernel ? q->N : q->Ftot); a.S = q->S; a.d = d;
+    a.ntest = (int)ntest; a.ncon = (int)(kernel ? q->N : q->Ftot); a.S = q->S; a.d = (int)q->d;
     a.ie1 = kernel ? q->dIe1.as<double>() : nullptr;
     a.ie2 = (kernel && q->two) ? q->dIe2.as<double>() : nullptr;
     a.slotp = q->dSlotp.as<double>(); a.ks = q->ks;
-    a.mpad = ldt; a.ncomp = grad ? d : 1;
+    a.mpad = ldt;
+    return a;
+}
+
+// One contraction: the points xt ([d][ldt], ntest of them) against the features (kernel = false) or the training points of q, into
+// part (grown here).  grad: the GRAD form, d components.  *nstrips_out: the strips used.
+template <typename T>
+int queue_paths_contract(gphip_paths* q, bool kernel, bool grad, const double* xt, long ldt, int64_t ntest, Buf& part, int split, int* nstrips_out) {
+    gphip_ctx* h = q->h;
+    const int d = (int)q->d;
+    PathsArgs<T> a = paths_side<T>(q, kernel, xt, ldt, ntest);
+    a.ncomp = grad ? d : 1;
     const int SG = grad ? 64 : 128;
     const unsigned gz = (unsigned)((q->S + SG - 1) / SG) * (unsigned)(grad ? (d + PC_GW - 1) / PC_GW : 1);
     const unsigned gx = (unsigned)(ldt / PC_TP);
@@ -223,6 +235,105 @@ int paths_eval_device(gphip_paths* q, const double* X, int64_t M, double* out, d
     return GPHIP_OK;
 }
 
+// ---- gphip_paths_eval_own: every draw at its own points (gp_paths_own.h)
+
+// One contraction of the E pairs xt ([d][ldt], pair e = s mc + t at column e) against the features (kernel = false) or the
+// training points of q, into part (grown here): ncomp = 1 (values) or 1 + d (grad) components per pair and strip.  The strips
+// follow from the pairs alone, not from grad: the value is summed in the same order in both forms.
+template <typename T>
+int queue_paths_own(gphip_paths* q, bool kernel, bool grad, const double* xt, long ldt, int64_t E, int64_t mc, Buf& part, int split,
+                    int* nstrips_out) {
+    gphip_ctx* h = q->h;
+    const int d = (int)q->d;
+    PathsOwnArgs<T> o{};
+    o.a = paths_side<T>(q, kernel, xt, ldt, E);
+    PathsArgs<T>& a = o.a;
+    a.ncomp = grad ? d + 1 : 1;
+    o.mc = (int)mc;
+    o.span = (int)std::min<int64_t>(q->S, (PO_P - 1) / mc + 2);
+    const unsigned gx = (unsigned)(ldt / PO_P);
+    const bool glb = d > KB_LDS_MAXD;
+    // the strip rule counts 256-thread workgroups: two of this kernel's count as one
+    const int nstrips = paths_strips(h, ((long)gx + 1) / 2, a.ncon, split, &a.strip_slabs);
+    *nstrips_out = nstrips;
+    HIPCHK(part.grow((size_t)nstrips * a.ncomp * ldt * 8));
+    a.part = part.as<double>();
+    const dim3 grid(gx, (unsigned)nstrips, (unsigned)(grad && glb ? (d + PO_GW - 1) / PO_GW : 1));
+    // profile class 6 (prediction epilogue): flops = the FMAs of the dot products; bytes = the weight slabs once per workgroup
+    ProfScope ps(h, 6, 2.0 * a.ncomp * (double)E * a.ncon, (double)sizeof(T) * gx * a.ncon * o.span);
+#define PATHS_OWN_GO(GEN, GRAD, DW) \
+    hipLaunchKernelGGL((paths_own_kernel<T, GEN, GRAD, DW>), grid, dim3(PO_P), (paths_own_lds<T, DW>(o.span)), h->stream, o)
+#define PATHS_OWN_DW(GEN, GRAD)                                  \
+    do {                                                         \
+        if (d <= 8) PATHS_OWN_GO(GEN, GRAD, 8);                  \
+        else if (d <= 16) PATHS_OWN_GO(GEN, GRAD, 16);           \
+        else if (!glb) PATHS_OWN_GO(GEN, GRAD, 32);              \
+        else PATHS_OWN_GO(GEN, GRAD, 0);                         \
+    } while (0)
+    if (kernel) { if (grad) PATHS_OWN_DW(GenKernel, true); else PATHS_OWN_DW(GenKernel, false); }
+    else { if (grad) PATHS_OWN_DW(GenFeature, true); else PATHS_OWN_DW(GenFeature, false); }
+#undef PATHS_OWN_DW
+#undef PATHS_OWN_GO
+    return GPHIP_OK;
+}
+
+// points per draw and chunk: option paths_chunk n > 0 = n, else all M; halved while the staged points, the partials of both
+// contractions (the forced strips; the strip rule adds strips only while the pairs are few) and the outputs of the chunk would
+// pass 1 GiB.  Sized for the gradient form whether dout is asked for or not: the chunks, and with them the strips and the bytes
+// of out, do not depend on dout.
+int64_t paths_own_chunk_rows(const gphip_paths* q, int64_t M) {
+    const gphip_ctx* h = q->h;
+    int64_t mc = h->paths_chunk > 0 ? std::min<int64_t>(M, h->paths_chunk) : M;
+    const double per_pair = 8.0 * ((double)q->d + ((double)q->d + 1.0) * (2.0 * std::max(h->paths_split, 1) + 1.0));
+    while (mc > 1 && per_pair * (double)q->S * (double)mc > 1073741824.0) mc = (mc + 1) / 2;
+    return mc;
+}
+
+template <typename T>
+int paths_eval_own_device(gphip_paths* q, const double* X, int64_t M, double* out, double* dout) {
+    gphip_ctx* h = q->h;
+    const int64_t d = q->d;
+    const int S = q->S;
+    HIPCHK(hipSetDevice(h->device));
+    const int64_t MC = paths_own_chunk_rows(q, M);
+    const int64_t EPAD = ((int64_t)S * MC + PO_P - 1) / PO_P * PO_P;
+    HIPCHK(q->dXs.grow((size_t)d * EPAD * 8));
+    HIPCHK(q->dOut.grow((size_t)S * MC * 8));
+    if (dout) HIPCHK(q->dDout.grow((size_t)S * MC * d * 8));
+    std::vector<double> xt, ho, hd;
+    hipStream_t st = h->stream;
+    const bool grad = dout != nullptr;
+    for (int64_t m0 = 0; m0 < M; m0 += MC) {
+        const int64_t mc = std::min<int64_t>(MC, M - m0), E = (int64_t)S * mc, epad = (E + PO_P - 1) / PO_P * PO_P;
+        xt.assign((size_t)d * epad, 0.0);
+        for (int64_t s = 0; s < S; ++s)
+            for (int64_t i = 0; i < mc; ++i)
+                for (int64_t c = 0; c < d; ++c) xt[(size_t)c * epad + s * mc + i] = X[((int64_t)s * M + m0 + i) * d + c];
+        HIPCHK(hipMemcpyAsync(q->dXs.p, xt.data(), xt.size() * 8, hipMemcpyHostToDevice, st));
+        int nsf = 0, nsk = 0;
+        if (int rc = queue_paths_own<T>(q, false, grad, q->dXs.as<double>(), (long)epad, E, mc, q->dPartF, h->paths_split, &nsf)) return rc;
+        if (int rc = queue_paths_own<T>(q, true, grad, q->dXs.as<double>(), (long)epad, E, mc, q->dPartK, h->paths_split, &nsk)) return rc;
+        h->paths_own_nsplit = nsk;
+        const int ncomp = grad ? (int)d + 1 : 1;
+        const long nf = (long)E * ncomp;
+        hipLaunchKernelGGL(paths_own_finish_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, st, (const double*)q->dPartF.p, nsf,
+                           (const double*)q->dPartK.p, nsk, ncomp, (long)epad, (long)E, q->mu, q->dOut.as<double>(),
+                           grad ? q->dDout.as<double>() : nullptr);
+        ho.resize((size_t)E);
+        HIPCHK(hipMemcpyAsync(ho.data(), q->dOut.p, (size_t)E * 8, hipMemcpyDeviceToHost, st));
+        if (grad) {
+            hd.resize((size_t)(E * d));
+            HIPCHK(hipMemcpyAsync(hd.data(), q->dDout.p, (size_t)(E * d) * 8, hipMemcpyDeviceToHost, st));
+        }
+        if (int rc = complete_call(h)) return rc;
+        for (int s = 0; s < S; ++s) {
+            memcpy(out + (size_t)s * M + m0, ho.data() + (size_t)s * mc, (size_t)mc * 8);
+            if (grad) memcpy(dout + ((size_t)s * M + m0) * d, hd.data() + (size_t)s * mc * d, (size_t)(mc * d) * 8);
+        }
+    }
+    return GPHIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -292,6 +403,24 @@ int gphip_paths_eval(gphip_paths_handle q, const void* Xs, int64_t M, double* ou
     const auto t0 = std::chrono::steady_clock::now();
     const int rc = DISPATCH(h, paths_eval_device, q, static_cast<const double*>(Xs), M, out, dout);
     h->paths_eval_us = paths_us(t0);
+    return rc;
+}
+
+int gphip_paths_eval_own(gphip_paths_handle q, const void* Xs, int64_t M, double* out, double* dout) {
+    if (!q) return GPHIP_ERR_ARG;
+    gphip_ctx* h = q->h;
+    if (!Xs || !out) return fail(h, GPHIP_ERR_ARG, "null argument");
+    if (M < 1) return fail(h, GPHIP_ERR_DIM, "M < 1");
+    std::lock_guard<std::recursive_mutex> lk(h->mu);
+    if (q->null_k) {
+        for (int64_t e = 0; e < (int64_t)q->S * M; ++e) out[e] = q->mu;
+        if (dout)
+            for (int64_t e = 0; e < (int64_t)q->S * M * q->d; ++e) dout[e] = 0.0;
+        return GPHIP_OK;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    const int rc = DISPATCH(h, paths_eval_own_device, q, static_cast<const double*>(Xs), M, out, dout);
+    h->paths_own_us = paths_us(t0);
     return rc;
 }
 

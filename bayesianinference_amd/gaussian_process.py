@@ -696,7 +696,9 @@ def gaussianProcessFunctionSamples(obj, pts, n: int, seed: int = 0, latent: bool
 
 class posteriorFunctionSamples:
     """What samplePathsFromGaussianProcess returns: n coherent draws of the latent posterior function.  f(pts) -> [n, M];
-    f.gradient(pts) -> [n, M, d]; f.sample [n] = the index into "Samples" each draw belongs to (zeros in the direct form).
+    f.gradient(pts) -> [n, M, d]; f.own(pts[n, M, d]) -> [n, M] and f.own_gradient(..) -> [n, M, d]: every draw at its own points;
+    f.maximize(bounds) -> every draw's maximiser over a box; f.sample [n] = the index into "Samples" each draw belongs to (zeros
+    in the direct form).
     Rows of a theta that does not factor are NaN.  close() (or the with block) releases the device objects."""
 
     def __init__(self, parts, n, d, inverse, scale, owned=None):
@@ -723,6 +725,60 @@ class posteriorFunctionSamples:
         for rows, paths in self._parts:
             out[rows] = paths.eval(P, grad=True)[1]
         return out * self._scale
+
+    def _own(self, pts, grad):
+        """(f [n, M], df/dx [n, M, d] or None) of every draw at its own points, in the normalised output units: one eval_own call
+        per paths object on the rows of its draws; NaN rows for a theta that did not factor"""
+        P = np.asarray(pts, dtype=np.float64)
+        if P.ndim != 3 or P.shape[0] != self.n or P.shape[1] < 1 or P.shape[2] != self.d:
+            raise ValueError("pts must have shape [%d, M, %d] with M >= 1" % (self.n, self.d))
+        out = np.full(P.shape[:2], np.nan)
+        dout = np.full(P.shape, np.nan) if grad else None
+        for rows, paths in self._parts:
+            res = paths.eval_own(P[rows], grad=grad)
+            if grad:
+                out[rows], dout[rows] = res
+            else:
+                out[rows] = res
+        return out, dout
+
+    def own(self, pts):
+        """f_s(pts[s, t]) -> [n, M]: every draw at its own M points, pts[n, M, d] (gphip_paths_eval_own); units as __call__"""
+        out = self._own(pts, False)[0]
+        return out if self._inverse is None else np.asarray(self._inverse(out), dtype=np.float64).reshape(out.shape)
+
+    def own_gradient(self, pts):
+        """df_s/dx at pts[s, t] -> [n, M, d], scaled as gradient"""
+        return self._own(pts, True)[1] * self._scale
+
+    def maximize(self, bounds, candidates: int = 1024, starts: int = 4, iterations: int = 50, seed: int = 0):
+        """argmax of every draw over the box bounds [d, 2] (rows (lo, hi)): {"x" [n, d], "f" [n]} in data units; NaN for the draws
+        of a theta that did not factor.  `candidates` uniform points of numpy.random.default_rng(seed) are evaluated for all
+        draws in one shared call, the `starts` best of every draw are ascended in lock step (_ascend_batched: every iteration is
+        one eval_own call with gradients per paths object), and the best of a draw's starts is returned.  The work is done in
+        the normalised output units; under a decreasing output map the draws are minimised there."""
+        box = np.asarray(bounds, dtype=np.float64).reshape(-1, 2)
+        if box.shape[0] != self.d or not np.all(box[:, 1] >= box[:, 0]) or int(candidates) < 1 or int(starts) < 1 or int(iterations) < 1:
+            raise ValueError("bounds must be %d rows (lo, hi) with hi >= lo; candidates, starts and iterations at least 1" % self.d)
+        lo, hi = box[:, 0], box[:, 1]
+        sign = -1.0 if self._scale < 0 else 1.0
+        cand = lo + (hi - lo) * np.random.default_rng(seed).random((int(candidates), self.d))
+        vals = self(cand)                                                # data units: the map is monotone, the best are the best
+        vals = np.where(np.isnan(vals), -np.inf, vals)
+        best = np.argsort(-vals, axis=1, kind="stable")[:, :min(int(starts), len(cand))]
+
+        def fg(X):
+            f, g = self._own(X, True)
+            return sign * f, sign * g
+
+        X, f = _ascend_batched(fg, cand[best], lo, hi, int(iterations))
+        f = np.where(np.isnan(f), -np.inf, f)
+        k = np.argmax(f, axis=1)
+        rows = np.arange(self.n)
+        x, fz = X[rows, k], sign * f[rows, k]
+        dead = ~np.isfinite(fz)
+        x[dead], fz[dead] = np.nan, np.nan
+        return {"x": x, "f": fz if self._inverse is None else np.asarray(self._inverse(fz), dtype=np.float64).reshape(fz.shape)}
 
     def close(self):
         for _, paths in self._parts:
@@ -796,6 +852,56 @@ def samplePathsFromGaussianProcess(obj_or_examples, n: int, kernel=None, theta=N
         handle.close()
         return None
     return posteriorFunctionSamples([(np.arange(int(n)), paths)], n, handle.d, None, 1.0, owned=handle)
+
+
+def _ascend_batched(fg, X0, lo, hi, iterations, trace=None):
+    """Projected gradient ascent of n x R independent (function, point) pairs in lock step; pure numpy.  fg(X[n, R, d]) ->
+    (f[n, R], g[n, R, d]) is called exactly once per iteration, on all pairs.  One step length per pair: a trial
+    clip(x + step g) that lowers its pair's value is rejected and the pair's step is halved; an accepted trial sets the next
+    step by the Barzilai-Borwein quotient |s . s / s . y| of the pair (s, y = the change of the point and of the gradient;
+    doubled where the quotient does not exist).  The first iteration evaluates the projected start; the first step moves a
+    tenth of the widest side of the box along the largest gradient component.  No pair's value ever decreases.  A pair whose
+    values are NaN stays at its start.  Returns (X[n, R, d], f[n, R]); trace: a list that receives a copy of f per iteration."""
+    lo, hi = np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64)
+    X = np.clip(np.asarray(X0, dtype=np.float64), lo, hi)
+    f = g = step = None
+    for it in range(int(iterations)):
+        if it == 0:
+            f, g = fg(X)
+            f, g = np.array(f, dtype=np.float64), np.array(g, dtype=np.float64)
+            gmax = np.abs(g).max(axis=2)
+            width = float(np.max(hi - lo))
+            step = np.where(gmax > 0, 0.1 * (width if width > 0 else 1.0) / np.where(gmax > 0, gmax, 1.0), 1.0)
+        else:
+            Xt = np.clip(X + step[:, :, None] * g, lo, hi)
+            ft, gt = fg(Xt)
+            ok = ft >= f                                                 # (NaN: rejected)
+            s, y = Xt - X, gt - g
+            ss, sy = np.einsum("nrc,nrc->nr", s, s), np.einsum("nrc,nrc->nr", s, y)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                bb = np.abs(ss / sy)
+            grown = np.where(np.isfinite(bb) & (bb > 0), bb, np.where(ss > 0, 2.0 * step, step))     # (a pair held by the box keeps its step)
+            step = np.clip(np.where(ok, grown, 0.5 * step), 1e-300, 1e100)
+            X = np.where(ok[:, :, None], Xt, X)
+            g = np.where(ok[:, :, None], gt, g)
+            f = np.where(ok, ft, f)
+        if trace is not None:
+            trace.append(f.copy())
+    return X, f
+
+
+def thompsonSampleFromGaussianProcess(obj_or_examples, n: int, bounds, kernel=None, theta=None, meanFunction=None, Features: int = 1024,
+                                      seed: int = 0, **maximize_options):
+    """Thompson sampling in one call: n pathwise draws of the latent posterior function (samplePathsFromGaussianProcess, both
+    forms) and the maximiser of each over the box `bounds` (posteriorFunctionSamples.maximize(bounds, seed=seed,
+    **maximize_options)); the draws are released before it returns.  {"x" [n, d], "f" [n], "sample" [n]} in data units, or None
+    wherever samplePathsFromGaussianProcess returns None."""
+    draws = samplePathsFromGaussianProcess(obj_or_examples, n, kernel, theta, meanFunction, Features, seed)
+    if draws is None:
+        return None
+    with draws:
+        best = draws.maximize(bounds, seed=seed, **maximize_options)
+        return {"x": best["x"], "f": best["f"], "sample": np.array(draws.sample)}
 
 
 def _output_scale(obj):

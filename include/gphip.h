@@ -343,19 +343,37 @@ int gphip_predict_grad(gphip_handle h, const void* Xs, int64_t M, double* mean, 
  * (dout[s][t][c] = df_s/dx*_tc) or NULL.  out is the same bytes whether dout is asked for or not, and two calls return the same
  * bytes (fixed-order sums, no atomics).  gphip_paths_get: every pointer may be NULL: omega Ftot x d, phase Ftot, w S x Ftot (the
  * unit normals), eps S x N, v S x N.
+ * gphip_paths_eval_own: every draw at ITS OWN M points: Xs row-major S x M x d fp64, any M >= 1; out[s][t] = f_s(x_st), S x M;
+ * dout[s][t][c] = df_s/dx_c at x_st, S x M x d, or NULL.  f_s is the f_s of gphip_paths_eval (the object's table, draw and v);
+ * what Thompson sampling needs when every draw is refined from its own starting points, at 1 / S of the work and the download
+ * of gphip_paths_eval on the S M stacked points.  Against gphip_paths_eval at the same points the result agrees to rounding,
+ * NOT byte for byte: a thread sums one (draw, point) pair in fp64 in the order of the contraction index, gphip_paths_eval sums
+ * through the matrix pipe.  out is the same bytes whether dout is asked for or not, and two calls with the same arguments and
+ * options return the same bytes (fixed-order sums, no atomics).  The call chunks over t so that the staged points, partial sums
+ * and outputs of a chunk stay within 1 GiB ("paths_chunk" n = n points per draw and chunk, halved while above that budget;
+ * "paths_split" n forces n strips as for gphip_paths_eval); read-only "last_paths_own_nsplit" = the strips of the last call's
+ * contraction over the training points, "last_paths_own_us" = host microseconds of the last call.  Statuses, all decided before
+ * any device work: NULL q GPHIP_ERR_ARG; NULL Xs / out GPHIP_ERR_ARG; M < 1 GPHIP_ERR_DIM.  The null kernel is answered on the
+ * host (out = m, dout = 0).  fp64 and fp32 handles: coordinates, phases and kernel values are fp64 in both, the weights are read
+ * in the handle's type, and the accumulation is fp64 in both.  It borrows the parent's device, stream and mutex like
+ * gphip_paths_eval and never touches the fit or the bytes gphip_paths_eval returns.
  * Options on the PARENT handle: "paths_split" n (0 = by the strip rule) forces n strips of both contractions;
  * "last_paths_nsplit" (read-only) the strips of the last evaluation's contraction over the training points; "paths_chunk" n
  * (0 = up to 16384) = n points per chunk, rounded up to 64; "last_paths_create_us" / "last_paths_feature_us" /
  * "last_paths_subst_us" / "last_paths_eval_us" (read-only): host microseconds of the last create (whole call, its feature pass,
  * its substitutions) and evaluation.
- * Not offered: the sparse object, run-time compiled covariance functions, point-dependent fits, sharding over devices,
- * conditioning a paths object on new data. */
+ * Not offered: the sparse object (gphip_paths_eval_own reads only the object's contraction points, tables and weights, so a
+ * sparse paths object could use it as it is), run-time compiled covariance functions, point-dependent fits, sharding over
+ * devices, conditioning a paths object on new data, device-resident inputs and outputs. */
 typedef struct gphip_paths* gphip_paths_handle;
 int gphip_rff_table(int kernel_id, int64_t d, const double* theta, int p, int F, uint64_t seed, int64_t* Ftot_out, double* omega,
                     double* phase, double* amp);
 int gphip_paths_create(gphip_handle h, int S, int F, uint64_t seed, gphip_paths_handle* out, int* info);
 int gphip_paths_eval(gphip_paths_handle q, const void* Xs /* M x d fp64 */, int64_t M, double* out /* S x M */,
                      double* dout /* S x M x d, or NULL */);
+/* out[s][t] = f_s(x_{s,t}), dout[s][t][c] = df_s/dx_c at x_{s,t}: every draw at ITS OWN M points. */
+int gphip_paths_eval_own(gphip_paths_handle q, const void* Xs /* row-major S x M x d fp64 */, int64_t M,
+                         double* out /* S x M */, double* dout /* S x M x d, or NULL */);
 int gphip_paths_shape(gphip_paths_handle q, int* S, int64_t* Ftot, int64_t* N, int64_t* d);
 int gphip_paths_get(gphip_paths_handle q, double* omega, double* phase, double* w, double* eps, double* v);
 int gphip_paths_destroy(gphip_paths_handle q);
