@@ -161,6 +161,8 @@ _SIGNATURES = {
     "gphip_sparse_set_option": (C.c_int, [_h, C.c_char_p, C.c_double]),
     "gphip_sparse_get_option": (C.c_int, [_h, C.c_char_p, C.POINTER(C.c_double)]),
     "gphip_sparse_last_error": (C.c_char_p, [_h]),
+    "gphip_sparse_paths_create": (C.c_int, [_h, C.c_int, C.c_int, C.c_uint64, C.POINTER(_h), _ip]),
+    "gphip_sparse_paths_get": (C.c_int, [_h, _dp, _dp]),
     "gphip_last_error": (C.c_char_p, [_h]),
     "gphip_version": (C.c_char_p, []),
     "gphip_device_count": (C.c_int, [_ip]),
@@ -292,18 +294,21 @@ def rff_table(kernel, d: int, theta, F: int, seed: int = 0):
 
 
 class Paths:
-    """Owns one gphip_paths_handle (Handle.sample_paths): S coherent draws of the latent posterior function.  Keeps its parent
-    Handle alive; close() it (or leave the with block) before the parent is closed."""
+    """Owns one gphip_paths_handle (Handle.sample_paths, SparseHandle.sample_paths): S coherent draws of the latent posterior
+    function.  Keeps its parent handle alive; close() it (or leave the with block) before the parent is closed.  On a sparse
+    parent N reads m, the contraction points are Z and the error text comes from the sparse object."""
 
     def __init__(self, parent, h):
         self._parent, self._lib, self._q = parent, parent._lib, h
+        self._sparse = isinstance(parent, SparseHandle)
         S, ftot, n, d = C.c_int(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
         self._lib.gphip_paths_shape(self._q, C.byref(S), C.byref(ftot), C.byref(n), C.byref(d))
         self.S, self.Ftot, self.N, self.d = S.value, ftot.value, n.value, d.value
 
     def _check(self, rc: int):
         if rc != OK:
-            raise GphipError(rc, (self._lib.gphip_last_error(self._parent._h) or b"").decode())
+            last = self._lib.gphip_sparse_last_error if getattr(self, "_sparse", False) else self._lib.gphip_last_error
+            raise GphipError(rc, (last(self._parent._h) or b"").decode())
 
     def eval(self, Xs, grad: bool = False):
         """f_s(Xs): out[S, M]; grad=True: (out, dout[S, M, d]) with dout[s, t, c] = df_s/dx_tc.  out is the same bytes either way."""
@@ -327,10 +332,14 @@ class Paths:
         return (out, dout) if grad else out
 
     def table(self):
-        """{"omega" [Ftot, d], "phase" [Ftot], "w" [S, Ftot], "eps" [S, N], "v" [S, N]}: what the draws were made from"""
+        """{"omega" [Ftot, d], "phase" [Ftot], "w" [S, Ftot], "eps" [S, N], "v" [S, N]}: what the draws were made from.  A sparse
+        parent: N = m, "eps" = sqrt(jitter) zeta, and the unit normals "xi" [S, m] and "zeta" [S, m] as well."""
         t = {"omega": np.zeros((self.Ftot, self.d)), "phase": np.zeros(self.Ftot), "w": np.zeros((self.S, self.Ftot)),
              "eps": np.zeros((self.S, self.N)), "v": np.zeros((self.S, self.N))}
         self._check(self._lib.gphip_paths_get(self._q, _d(t["omega"]), _d(t["phase"]), _d(t["w"]), _d(t["eps"]), _d(t["v"])))
+        if getattr(self, "_sparse", False):
+            t["xi"], t["zeta"] = np.zeros((self.S, self.N)), np.zeros((self.S, self.N))
+            self._check(self._lib.gphip_sparse_paths_get(self._q, _d(t["xi"]), _d(t["zeta"])))
         return t
 
     def close(self):
@@ -874,8 +883,9 @@ class SparseHandle:
             raise GphipError(rc, (self._lib.gphip_sparse_last_error(self._h) or b"").decode())
 
     def close(self):
+        """gphip_sparse_destroy; refused (GphipError, status 4) while Paths objects of this handle are open"""
         if getattr(self, "_h", None):
-            self._lib.gphip_sparse_destroy(self._h)
+            self._check(self._lib.gphip_sparse_destroy(self._h))
             self._h = None
 
     def __del__(self):
@@ -883,6 +893,18 @@ class SparseHandle:
             self.close()
         except Exception:
             pass
+
+    def sample_paths(self, S: int, F: int = 1024, seed: int = 0):
+        """gphip_sparse_paths_create: S pathwise draws of the latent posterior function of the resident fit, F random Fourier
+        features per term.  Returns a Paths (close it before this handle), or None when v is not finite (info = GPHIP_INFO_NAN)."""
+        S, F = int(S), int(F)
+        if S < 1 or F < 1 or S > 2048:
+            raise ValueError("S must be 1 .. 2048 and F at least 1, got S = %d, F = %d" % (S, F))
+        out, info = _h(), C.c_int(0)
+        self._check(self._lib.gphip_sparse_paths_create(self._h, S, F, int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(out), C.byref(info)))
+        if not out.value:
+            return None
+        return Paths(self, out)
 
     def set_option(self, name: str, value: float):
         self._check(self._lib.gphip_sparse_set_option(self._h, name.encode(), float(value)))

@@ -3902,3 +3902,4 @@ int gphip_sync(gphip_handle h) {
 #include "gphip_xgrad.inc"
 #include "gphip_sparse.inc"
 #include "gphip_paths.inc"
+#include "gphip_sparse_paths.inc"  // (behind gphip_paths.inc: a sparse paths object is a gphip_paths)

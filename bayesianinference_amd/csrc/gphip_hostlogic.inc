@@ -165,7 +165,10 @@ int gphip_tab_prior_sample(const double* box, const double* tab, int p, int64_t 
 //     tag 8         b_j   = 2 pi philox_uniform(key, j, 0)              the phase
 //     tag 9         eps_si = sn philox_normal(key, s, i)                the observation noise of gphip_paths_create (RFF_TAG_EPS):
 //                   a tag the table never uses, so eps is independent of (Omega, b).  key = seed ^ 0x2E2AC13EF8E8D8D2.
-// gphip_paths_create draws w under the seed itself.  RFF_KEY is odd, so the keys of the tags 0 .. 9 and the seed are all distinct.
+//     tag 10        xi_si   = philox_normal(key, s, i)                  gphip_sparse_paths_create: the draw of the whitened inducing values
+//     tag 11        zeta_si = philox_normal(key, s, i)                  gphip_sparse_paths_create: the jitter's share of the prior at Z
+//                   (RFF_TAG_XI, RFF_TAG_ZETA in gphip_sparse_paths.inc: 11 and 12 times RFF_KEY, which no other stream uses)
+// gphip_paths_create draws w under the seed itself.  RFF_KEY is odd, so the keys of the tags 0 .. 11 and the seed are all distinct.
 //     SE          omega = z                          Matern-nu   omega = z sqrt(2 nu / u), u = the sum of 2 nu squared normals
 //     RQ(alpha)   omega = z sqrt(tau), tau ~ Gamma(shape alpha, scale 1 / alpha)  (Marsaglia-Tsang; alpha < 1: the U^(1/alpha) boost)
 // Omega_jc = omega_c / l_c.  Sum: the two terms' features side by side, a = sf_t sqrt(2 / F).  Product: Omega = Omega1 + Omega2 of

@@ -1,5 +1,6 @@
 // gphip_paths.inc -- pathwise posterior function draws (include/gphip.h: gphip_paths_create / _eval / _eval_own / _shape / _get /
-// _destroy; DESIGN.md sections 8m and 8n).  Included at the end of gphip.hip.  Exact object only.  Out of scope: the sparse object,
+// _destroy; DESIGN.md sections 8m and 8n).  Included at the end of gphip.hip.  gphip_paths_create serves the exact object; a sparse
+// object's draws are created in gphip_sparse_paths.inc and evaluated by the code here as they are (sp below).  Out of scope:
 // run-time compiled covariance functions, point-dependent fits, sharding over devices, conditioning a paths object on new data.
 //
 //   create   gphip_rff_table(fitted theta)             host: Omega, b, a
@@ -21,6 +22,7 @@
 
 struct gphip_paths {
     gphip_ctx* h = nullptr;
+    gphip_sparse_ctx* sp = nullptr;                 // a sparse paths object (gphip_sparse_paths.inc): h = sp->u, the contraction points are Z
     int S = 0, F = 0;
     int64_t Ftot = 0, N = 0, Npad = 0, d = 0, Spad = 0;
     uint64_t seed = 0;
@@ -34,6 +36,7 @@ struct gphip_paths {
     Buf dOmT, dPhase;                               // double [d][Ftot], [Ftot]
     Buf dWa;                                        // typed [Ftot][Spad]: a_j w_sj
     Buf dW, dEps;                                   // double [S][Ftot], [S][N]
+    Buf dXi, dZeta;                                 // double [S][N], [S][N]: the unit normals of a sparse paths object
     Buf dV;                                         // typed [Npad][Spad]: v
     Buf dPartF, dPartK, dXs, dOut, dDout, dFlag;    // scratch of a call
 };
@@ -42,6 +45,20 @@ namespace {
 
 constexpr int PATHS_MAX_S = 2048;
 constexpr int64_t PATHS_MAX_FS = (int64_t)1 << 26;
+
+// The mutexes of a call on q: the context's, and in front of it the sparse object's when q came from one (its calls hold theirs
+// while they work on the context of K_uu).
+struct PathsLock {
+    std::unique_lock<std::recursive_mutex> outer, inner;
+    explicit PathsLock(gphip_paths* q)
+        : outer(q->sp ? std::unique_lock<std::recursive_mutex>(q->sp->mu) : std::unique_lock<std::recursive_mutex>()), inner(q->h->mu) {}
+};
+
+// the status of a call on q; an error's text is readable through the sparse object too when q came from one
+int paths_ret(gphip_paths* q, int rc) {
+    if (rc && q->sp) q->sp->err = q->h->err;
+    return rc;
+}
 
 // strips of a contraction of ncon indices when the launch has wgs workgroups without them: whole slabs, wgs x strips >= 2 per CU
 // while there are slabs; forced > 0: that many (at most one per slab)
@@ -391,9 +408,9 @@ int gphip_paths_create(gphip_handle h, int S, int F, uint64_t seed, gphip_paths_
 int gphip_paths_eval(gphip_paths_handle q, const void* Xs, int64_t M, double* out, double* dout) {
     if (!q) return GPHIP_ERR_ARG;
     gphip_ctx* h = q->h;
-    if (!Xs || !out) return fail(h, GPHIP_ERR_ARG, "null argument");
-    if (M < 1) return fail(h, GPHIP_ERR_DIM, "M < 1");
-    std::lock_guard<std::recursive_mutex> lk(h->mu);
+    if (!Xs || !out) return paths_ret(q, fail(h, GPHIP_ERR_ARG, "null argument"));
+    if (M < 1) return paths_ret(q, fail(h, GPHIP_ERR_DIM, "M < 1"));
+    PathsLock lk(q);
     if (q->null_k) {
         for (int64_t e = 0; e < (int64_t)q->S * M; ++e) out[e] = q->mu;
         if (dout)
@@ -403,15 +420,15 @@ int gphip_paths_eval(gphip_paths_handle q, const void* Xs, int64_t M, double* ou
     const auto t0 = std::chrono::steady_clock::now();
     const int rc = DISPATCH(h, paths_eval_device, q, static_cast<const double*>(Xs), M, out, dout);
     h->paths_eval_us = paths_us(t0);
-    return rc;
+    return paths_ret(q, rc);
 }
 
 int gphip_paths_eval_own(gphip_paths_handle q, const void* Xs, int64_t M, double* out, double* dout) {
     if (!q) return GPHIP_ERR_ARG;
     gphip_ctx* h = q->h;
-    if (!Xs || !out) return fail(h, GPHIP_ERR_ARG, "null argument");
-    if (M < 1) return fail(h, GPHIP_ERR_DIM, "M < 1");
-    std::lock_guard<std::recursive_mutex> lk(h->mu);
+    if (!Xs || !out) return paths_ret(q, fail(h, GPHIP_ERR_ARG, "null argument"));
+    if (M < 1) return paths_ret(q, fail(h, GPHIP_ERR_DIM, "M < 1"));
+    PathsLock lk(q);
     if (q->null_k) {
         for (int64_t e = 0; e < (int64_t)q->S * M; ++e) out[e] = q->mu;
         if (dout)
@@ -421,7 +438,7 @@ int gphip_paths_eval_own(gphip_paths_handle q, const void* Xs, int64_t M, double
     const auto t0 = std::chrono::steady_clock::now();
     const int rc = DISPATCH(h, paths_eval_own_device, q, static_cast<const double*>(Xs), M, out, dout);
     h->paths_own_us = paths_us(t0);
-    return rc;
+    return paths_ret(q, rc);
 }
 
 int gphip_paths_shape(gphip_paths_handle q, int* S, int64_t* Ftot, int64_t* N, int64_t* d) {
@@ -436,7 +453,7 @@ int gphip_paths_shape(gphip_paths_handle q, int* S, int64_t* Ftot, int64_t* N, i
 int gphip_paths_get(gphip_paths_handle q, double* omega, double* phase, double* w, double* eps, double* v) {
     if (!q) return GPHIP_ERR_ARG;
     gphip_ctx* h = q->h;
-    std::lock_guard<std::recursive_mutex> lk(h->mu);
+    PathsLock lk(q);
     if (q->null_k) return GPHIP_OK;                 // no features, no weights: nothing to copy (Ftot = 0)
     if (omega) memcpy(omega, q->omega.data(), q->omega.size() * 8);
     if (phase) memcpy(phase, q->phase.data(), q->phase.size() * 8);
@@ -445,7 +462,7 @@ int gphip_paths_get(gphip_paths_handle q, double* omega, double* phase, double* 
     if (eps) HIPCHK(hipMemcpy(eps, q->dEps.p, (size_t)q->S * q->N * 8, hipMemcpyDeviceToHost));
     if (v) {
         std::vector<double> tmp;
-        if (int rc = DISPATCH(h, download, h, tmp, q->dV.p, (size_t)q->Npad * q->Spad, h->stream)) return rc;
+        if (int rc = DISPATCH(h, download, h, tmp, q->dV.p, (size_t)q->Npad * q->Spad, h->stream)) return paths_ret(q, rc);
         for (int s = 0; s < q->S; ++s)
             for (int64_t i = 0; i < q->N; ++i) v[(size_t)s * q->N + i] = tmp[(size_t)i * q->Spad + s];
     }
@@ -456,7 +473,7 @@ int gphip_paths_destroy(gphip_paths_handle q) {
     if (!q) return GPHIP_OK;
     gphip_ctx* h = q->h;
     {
-        std::lock_guard<std::recursive_mutex> lk(h->mu);
+        PathsLock lk(q);
         (void)hipSetDevice(h->device);
         if (h->stream) (void)hipStreamSynchronize(h->stream);
         --h->paths_live;

@@ -107,7 +107,7 @@ struct gphip_sparse_ctx {
     // the resident fit
     bool fitted = false;
     bool pw_fit = false;                       // the fit was made with a point-dependent array: B = I + V W V^T, no joint prediction
-    double sn2_fit = 0, mu_fit = 0, kxx_fit = 0;
+    double sn2_fit = 0, mu_fit = 0, kxx_fit = 0, jit_fit = 0;
     std::string err;
 };
 
@@ -855,7 +855,7 @@ int sparse_eval(gphip_sparse_ctx* h, const double* theta, int p, double jitter, 
     *info = r.info;
     h->fitted = *info == 0;
     h->pw_fit = pw.any();
-    h->sn2_fit = r.sn2; h->mu_fit = r.mu; h->kxx_fit = r.kxx;
+    h->sn2_fit = r.sn2; h->mu_fit = r.mu; h->kxx_fit = r.kxx; h->jit_fit = r.jit;
     if (wants_grad && *info == 0) {
         const SparseGradIn in{theta, pw, r.sn2, r.mu, r.rtr, r.ctc, r.trvv, r.skk, rows, (h->N + rows - 1) / rows};
         rc = DISPATCH(h, sparse_grad_phase, h, in, ph, grad, gradZ);
@@ -1327,6 +1327,11 @@ int gphip_sparse_create_custom(const void* X, const void* y, int64_t N, int64_t 
 
 int gphip_sparse_destroy(gphip_sparse_handle h) {
     if (!h) return GPHIP_OK;
+    {
+        std::lock_guard<std::recursive_mutex> lk(h->mu);
+        if (h->u && h->u->paths_live > 0)
+            return sfail(h, GPHIP_ERR_STATE, "gphip_sparse_destroy with live paths objects: gphip_paths_destroy them first");
+    }
     if (h->u) {
         (void)hipSetDevice(h->u->device);
         (void)hipStreamSynchronize(h->u->stream);
@@ -1343,7 +1348,11 @@ int gphip_sparse_set_inducing(gphip_sparse_handle h, const void* Z, int64_t m) {
     if (!h || !Z) return sfail(h, GPHIP_ERR_ARG, "null argument");
     if (m < 1 || m > SPARSE_MAX_M) return sfail(h, GPHIP_ERR_DIM, "m < 1 or above GPHIP_SPARSE_MAX_M");
     std::lock_guard<std::recursive_mutex> lk(h->mu);
-    if (m != h->m) return sparse_make_children(h, static_cast<const double*>(Z), m);
+    if (m != h->m) {                           // (new contexts: a paths object borrows the old one of K_uu)
+        if (h->u->paths_live > 0)
+            return sfail(h, GPHIP_ERR_STATE, "gphip_sparse_set_inducing with another m and live paths objects: gphip_paths_destroy them first");
+        return sparse_make_children(h, static_cast<const double*>(Z), m);
+    }
     // the same number of inducing points: both contexts keep their buffers, streams, options and compiled programs; the points
     // and what create_ctx derives from them are replaced, the fit is dropped
     h->fitted = false;

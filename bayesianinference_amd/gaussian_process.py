@@ -1439,3 +1439,66 @@ def sparsePredictiveLogDensity(obj, heldout, theta):
         return None
     value, info = handle.predict_logpdf(P, ys)
     return value if info == 0 else None
+
+
+def samplePathsFromSparseGaussianProcess(obj, n: int, theta=None, Features: int = 1024, seed: int = 0):
+    """samplePathsFromGaussianProcess for a sparse object (gphip_sparse_paths_create): n pathwise draws of the latent posterior
+    function under the collapsed bound's optimal q(u), which can be evaluated and differentiated after they have been drawn, at
+    a cost per point that does not depend on the number of data points.  Two forms:
+      samplePathsFromSparseGaussianProcess(obj, n, theta)   one fit at theta and one paths object of n draws under `seed`;
+      samplePathsFromSparseGaussianProcess(obj, n)          a sampled object: every draw picks a theta from "Samples" by
+          CrudePosteriorWeight with the assignment and the per-theta keys of samplePathsFromGaussianProcess, one fit and one
+          paths object per distinct theta used.
+    Every fit uses obj["Jitter"].  The paths objects live on the object's own "HIPHandle": until the result's close() (or the end
+    of its `with` block) that handle cannot be closed or given another number of inducing points, and it is left fitted at the
+    last theta used here.  Returns a posteriorFunctionSamples (values in the units of the data, gradients scaled accordingly),
+    or None for a non-sparse or failed object, an unsampled object without theta, bad arguments, point-dependent nugget / mean
+    functions and a run-time compiled kernel."""
+    if not isinstance(obj, inferenceObject) or obj.failed or "SparseGaussianProcessData" not in obj:
+        return None
+    if int(n) < 1 or int(Features) < 1:
+        return None
+    if any(f is not None for f in _sparse_pointwise_functions(obj)):
+        return None
+    handle = obj["SparseGaussianProcessData"]["HIPHandle"]
+    if isinstance(handle.kernel, _lib.CustomKernel):
+        return None
+    inverse, scale = _output_scale(obj)
+    if theta is not None:
+        if handle.fit(np.asarray(theta, dtype=np.float64).ravel(), obj["Jitter"]) != 0:
+            return None
+        paths = handle.sample_paths(int(n), int(Features), int(seed))
+        if paths is None:
+            return None
+        return posteriorFunctionSamples([(np.arange(int(n)), paths)], n, handle.d, inverse, scale)
+    if "Samples" not in obj:
+        return None
+    samples = obj["Samples"]
+    points = np.array([s["Point"] for s in samples], dtype=np.float64)
+    w = np.array([s["CrudePosteriorWeight"] for s in samples], dtype=np.float64)
+    which = np.random.default_rng(seed).choice(len(samples), size=int(n), p=w / w.sum())
+    parts = []
+    for k in np.unique(which):
+        rows = np.flatnonzero(which == k)
+        if handle.fit(points[k], obj["Jitter"]) != 0:
+            continue
+        key = int(np.random.SeedSequence([int(seed) & (2**63 - 1), int(k)]).generate_state(1, np.uint64)[0])
+        paths = handle.sample_paths(len(rows), int(Features), key)
+        if paths is not None:
+            parts.append((rows, paths))
+    res = posteriorFunctionSamples(parts, n, handle.d, inverse, scale)
+    res.sample = which
+    return res
+
+
+def thompsonSampleFromSparseGaussianProcess(obj, n: int, bounds, theta=None, Features: int = 1024, seed: int = 0, **maximize_options):
+    """thompsonSampleFromGaussianProcess for a sparse object: n pathwise draws (samplePathsFromSparseGaussianProcess, both forms)
+    and the maximiser of each over the box `bounds` (posteriorFunctionSamples.maximize(bounds, seed=seed, **maximize_options));
+    the draws are released before it returns.  {"x" [n, d], "f" [n], "sample" [n]} in data units, or None wherever
+    samplePathsFromSparseGaussianProcess returns None."""
+    draws = samplePathsFromSparseGaussianProcess(obj, n, theta, Features, seed)
+    if draws is None:
+        return None
+    with draws:
+        best = draws.maximize(bounds, seed=seed, **maximize_options)
+        return {"x": best["x"], "f": best["f"], "sample": np.array(draws.sample)}

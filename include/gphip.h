@@ -362,9 +362,9 @@ int gphip_predict_grad(gphip_handle h, const void* Xs, int64_t M, double* mean, 
  * (0 = up to 16384) = n points per chunk, rounded up to 64; "last_paths_create_us" / "last_paths_feature_us" /
  * "last_paths_subst_us" / "last_paths_eval_us" (read-only): host microseconds of the last create (whole call, its feature pass,
  * its substitutions) and evaluation.
- * Not offered: the sparse object (gphip_paths_eval_own reads only the object's contraction points, tables and weights, so a
- * sparse paths object could use it as it is), run-time compiled covariance functions, point-dependent fits, sharding over
- * devices, conditioning a paths object on new data, device-resident inputs and outputs. */
+ * The sparse object's draws are made by gphip_sparse_paths_create (below) and evaluated by the calls here.
+ * Not offered: run-time compiled covariance functions, point-dependent fits, sharding over devices, conditioning a paths object
+ * on new data, device-resident inputs and outputs. */
 typedef struct gphip_paths* gphip_paths_handle;
 int gphip_rff_table(int kernel_id, int64_t d, const double* theta, int p, int F, uint64_t seed, int64_t* Ftot_out, double* omega,
                     double* phase, double* amp);
@@ -883,6 +883,40 @@ int gphip_sparse_predict_logpdf(gphip_sparse_handle h, const void* Xs, int64_t M
 int gphip_sparse_set_option(gphip_sparse_handle h, const char* name, double value);
 int gphip_sparse_get_option(gphip_sparse_handle h, const char* name, double* value);
 const char* gphip_sparse_last_error(gphip_sparse_handle h);   /* owned by the library */
+
+/* ---- Pathwise posterior function draws of the sparse object: gphip_paths_create's draws for a resident
+ * gphip_sparse_fit / gphip_sparse_bound, so that Thompson sampling runs at the N the sparse object is for.  With
+ * K_uu = k(Z, Z) + j I = L_u L_u^T, B = sn^2 I + V V^T = L_B L_B^T and c = L_B^-1 V r as above, the collapsed bound's optimal q(u)
+ * has, for u' = L_u^-1 u, the mean L_B^-T c and the covariance sn^2 L_B^-T L_B^-1, and draw s = 0 .. S - 1 of the latent function is
+ *     f_s(x)  = m + f~_s(x) + k(x, Z) v_s
+ *     v_s     = L_u^-T [ L_B^-T (c + sn xi_s) - L_u^-1 (f~_s(Z) + sqrt(j) zeta_s) ],     xi_s, zeta_s ~ N(0, I_m)
+ * with f~ the random-Fourier-feature prior of gphip_paths_create.  sqrt(j) zeta is part of the model: K_uu holds the jitter, so
+ * the prior value that is conditioned on has covariance K_uu; without it the covariance is off by j |K_uu^-1 k(Z, x)|^2.  With an
+ * exact prior in the place of f~ the draws have the mean of gphip_sparse_predict and the latent covariance of
+ * gphip_sparse_predict_cov.  Neither N nor V appears: creation costs O(m^2 S + m Ftot S), an evaluation O(m + Ftot) per point and
+ * draw.
+ * The result is an ordinary gphip_paths_handle: gphip_paths_eval, _eval_own, _shape (N reads m), _get and _destroy serve it with
+ * the kernels of the exact object.  Its contraction points are Z; in gphip_paths_get eps (S x m) is sqrt(j) zeta and v (S x m) is
+ * v.  gphip_sparse_paths_get returns the unit normals xi and zeta (S x m each, either may be NULL); on a handle that
+ * gphip_paths_create made it returns GPHIP_ERR_ARG.  Streams: the table is gphip_rff_table(fitted theta, F, seed) byte for byte,
+ * w_sj = philox_normal(seed, s, j), xi_si = philox_normal(seed ^ 11 x 0x9E3779B97F4A7C15, s, i), zeta_si = philox_normal(seed ^
+ * 12 x 0x9E3779B97F4A7C15, s, i) (tags 10 and 11 of csrc/gphip_hostlogic.inc; products mod 2^64); the prefix property in S holds
+ * as for gphip_paths_create.  Fixed summation order, no atomics: two calls return the same bytes.  The fit is only read:
+ * gphip_sparse_predict and gphip_sparse_bound return the same bytes before and after.
+ * The object owns copies of everything that depends on theta, Z or the draw, so it survives a refit at another theta and a
+ * gphip_sparse_set_inducing with the same m.  It borrows the device and stream of the context of K_uu; every call on it takes the
+ * sparse object's mutex first.  While such objects live, gphip_sparse_destroy and a gphip_sparse_set_inducing that changes m
+ * return GPHIP_ERR_STATE and destroy nothing.  Errors of calls on it are readable through gphip_sparse_last_error.
+ * Statuses, all decided before any device work: NULL h / out / info GPHIP_ERR_ARG; S < 1, F < 1, S > 2048, Ftot S > 2^26
+ * GPHIP_ERR_DIM; no resident fit (also after gphip_sparse_bound_batch, gphip_sparse_predict_samples, gphip_sparse_set_inducing)
+ * GPHIP_ERR_STATE; a run-time compiled covariance function and a fit made by a _pw call with a non-NULL array
+ * GPHIP_ERR_UNSUPPORTED.  *info = GPHIP_INFO_NAN on a non-finite v: *out = NULL, status GPHIP_OK.  fp64 and fp32 objects, typed as
+ * gphip_paths_create's are; every named and composed kernel.  Options "paths_split", "paths_chunk" and the read-only
+ * "last_paths_*" names go through gphip_sparse_set_option / gphip_sparse_get_option to the context of K_uu.
+ * Not offered: run-time compiled covariance functions, point-dependent fits, draws over all posterior samples in one call,
+ * device-resident inputs and outputs. */
+int gphip_sparse_paths_create(gphip_sparse_handle h, int S, int F, uint64_t seed, gphip_paths_handle* out, int* info);
+int gphip_sparse_paths_get(gphip_paths_handle q, double* xi /* S x m or NULL */, double* zeta /* S x m or NULL */);
 
 /* Block until all work queued on the handle's stream is complete. */
 int gphip_sync(gphip_handle h);
