@@ -1626,15 +1626,18 @@ int set_func_attrs(gphip_ctx* h) {
     }
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trtri128_kernel<T>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)potrf_lds<T>()));
-    if (h->kt == 2 && h->d <= KB_LDS_MAXD) {   // general covariance form: both terms' row and column points in LDS
+    if (h->kt == 2) {   // general covariance form: both terms' row and column points in LDS
+        // The attribute belongs to the FUNCTION, not to the handle: sized for the largest request any handle can make (KB_LDS_MAXD
+        // dimensions), so that a second general-form handle of fewer dimensions cannot lower it under a live handle's launches.
+        constexpr int dmax = KB_LDS_MAXD;
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>((kbuild_kernel<T, 0, 2>)),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * h->d * TB * sizeof(T))));
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * dmax * TB * sizeof(T))));
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(grad_reduce_general_kernel<T>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)((4 * h->d + 1) * TB * sizeof(T) + 8 + 4 * (2 * h->d + 6) * 8)));     // (+ GradEmit's staging area)
+                                   (int)((4 * dmax + 1) * TB * sizeof(T) + 8 + 4 * (2 * dmax + 6) * 8)));     // (+ GradEmit's staging area)
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(grad_reduce_general_slots_kernel<T>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)((4 * h->d + 1) * TB * sizeof(T) + 8 + 4 * (2 * h->d + 6) * 8)));
+                                   (int)((4 * dmax + 1) * TB * sizeof(T) + 8 + 4 * (2 * dmax + 6) * 8)));
     }
 #define GEMM_ATTR(ROLE)                                                                                   \
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_kernel<T, ROLE, 2, 2, 2>),             \
