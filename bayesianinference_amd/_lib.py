@@ -106,6 +106,9 @@ _SIGNATURES = {
     "gphip_paths_shape": (C.c_int, [_h, _ip, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "gphip_paths_get": (C.c_int, [_h, _dp, _dp, _dp, _dp, _dp]),
     "gphip_paths_destroy": (C.c_int, [_h]),
+    "gphip_paths_create_samples": (C.c_int, [_h, _dp, C.c_int, C.c_int, _ip, C.POINTER(C.c_uint64), C.c_int, C.POINTER(_h), _ip]),
+    "gphip_paths_rows": (C.c_int, [_h, _ip, _ip]),
+    "gphip_paths_get_table": (C.c_int, [_h, C.c_int, _dp, _dp, _dp]),
     "gphip_loglik_batch_pw": (C.c_int, [_h, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _ip]),
     "gphip_fit_pw": (C.c_int, [_h, _dp, C.c_int, _dp, _dp, _ip]),
     "gphip_predict_pw": (C.c_int, [_h, C.c_void_p, C.c_int64, _dp, _dp, _dp, _dp]),
@@ -331,11 +334,28 @@ class Paths:
         self._check(self._lib.gphip_paths_eval_own(self._q, Xs.ctypes.data, M, _d(out), _d(dout) if grad else None))
         return (out, dout) if grad else out
 
-    def table(self):
+    def rows(self):
+        """gphip_paths_rows: (R, row_of_draw [S]) -- the hyper-parameter rows of the object and the row each draw belongs to; an
+        ordinary object has R = 1."""
+        R, row_of = C.c_int(0), np.zeros(self.S, dtype=np.int32)
+        self._check(self._lib.gphip_paths_rows(self._q, C.byref(R), row_of.ctypes.data_as(_ip)))
+        return R.value, row_of
+
+    def table(self, r=None):
         """{"omega" [Ftot, d], "phase" [Ftot], "w" [S, Ftot], "eps" [S, N], "v" [S, N]}: what the draws were made from.  A sparse
-        parent: N = m, "eps" = sqrt(jitter) zeta, and the unit normals "xi" [S, m] and "zeta" [S, m] as well."""
+        parent: N = m, "eps" = sqrt(jitter) zeta, and the unit normals "xi" [S, m] and "zeta" [S, m] as well.
+        r given: row r's {"omega", "phase", "amp" [Ftot]} (gphip_paths_get_table).  r=None on a mixture object (Handle.
+        sample_paths_samples): "w", "eps" and "v" only -- the tables are per row."""
+        if r is not None:
+            t = {"omega": np.zeros((self.Ftot, self.d)), "phase": np.zeros(self.Ftot), "amp": np.zeros(self.Ftot)}
+            self._check(self._lib.gphip_paths_get_table(self._q, int(r), _d(t["omega"]), _d(t["phase"]), _d(t["amp"])))
+            return t
         t = {"omega": np.zeros((self.Ftot, self.d)), "phase": np.zeros(self.Ftot), "w": np.zeros((self.S, self.Ftot)),
              "eps": np.zeros((self.S, self.N)), "v": np.zeros((self.S, self.N))}
+        if getattr(self, "info", None) is not None:                  # a mixture object: Handle.sample_paths_samples sets .info [R]
+            del t["omega"], t["phase"]
+            self._check(self._lib.gphip_paths_get(self._q, None, None, _d(t["w"]), _d(t["eps"]), _d(t["v"])))
+            return t
         self._check(self._lib.gphip_paths_get(self._q, _d(t["omega"]), _d(t["phase"]), _d(t["w"]), _d(t["eps"]), _d(t["v"])))
         if getattr(self, "_sparse", False):
             t["xi"], t["zeta"] = np.zeros((self.S, self.N)), np.zeros((self.S, self.N))
@@ -693,6 +713,36 @@ class Handle:
         if not out.value:
             return None
         return Paths(self, out)
+
+    def sample_paths_samples(self, Thetas, counts, seeds, F: int = 1024):
+        """gphip_paths_create_samples: ONE mixture paths object over the rows of Thetas [R, p]; row r gives counts[r] draws (>= 0),
+        draw q of row r being draw q of fit(Thetas[r]) + sample_paths(counts[r], F, seeds[r]).  The draws are ordered by row.  No
+        fit stays resident.  Returns a Paths whose .info [R] holds the rows' verdicts (the draws of a failed row are NaN), or None
+        when every row with draws failed; the verdicts are then in self.last_paths_info.  Wrong shapes raise ValueError before
+        any library call."""
+        Th = np.ascontiguousarray(np.asarray(Thetas, dtype=np.float64))
+        if Th.ndim == 1:
+            Th = Th.reshape(1, -1)
+        cnt = np.ascontiguousarray(np.asarray(counts, dtype=np.int64).ravel())
+        sd = np.ascontiguousarray(np.array([int(s) & 0xFFFFFFFFFFFFFFFF for s in np.ravel(np.asarray(seeds, dtype=object))], dtype=np.uint64))
+        if Th.ndim != 2 or Th.shape[0] < 1 or Th.shape[1] != self.p:
+            raise ValueError("Thetas must have shape [R, %d] with R >= 1, got %s" % (self.p, list(Th.shape)))
+        R = Th.shape[0]
+        if cnt.shape != (R,) or sd.shape != (R,):
+            raise ValueError("counts and seeds must have %d entries each, got %d and %d" % (R, cnt.size, sd.size))
+        if np.any(cnt < 0) or cnt.sum() < 1 or int(F) < 1:
+            raise ValueError("counts must be >= 0 with at least one draw in all, and F >= 1")
+        cnt = np.ascontiguousarray(cnt.astype(np.int32))
+        out, info = _h(), np.zeros(R, dtype=np.int32)
+        self.last_paths_info = info
+        self._check(self._lib.gphip_paths_create_samples(self._h, _d(Th), R, Th.shape[1], cnt.ctypes.data_as(_ip),
+                                                         sd.ctypes.data_as(C.POINTER(C.c_uint64)), int(F), C.byref(out),
+                                                         info.ctypes.data_as(_ip)))
+        if not out.value:
+            return None
+        paths = Paths(self, out)
+        paths.info = info
+        return paths
 
     def predict_grad(self, Xs, variance: bool = True):
         """Gradients of the prediction in the test inputs (gphip_predict_grad): (mean[M], var[M], dmean[M, d], dvar[M, d]);

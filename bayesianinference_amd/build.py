@@ -21,7 +21,8 @@ DEPS = [SRC, os.path.join(PKG, "csrc", "gp_kernels.h"), os.path.join(PKG, "csrc"
         os.path.join(PKG, "csrc", "gphip_extend.inc"), os.path.join(PKG, "csrc", "gp_extend.h"),
         os.path.join(PKG, "csrc", "gphip_gradbatch.inc"), os.path.join(PKG, "csrc", "gphip_paths.inc"), os.path.join(PKG, "csrc", "gp_paths.h"),
         os.path.join(PKG, "csrc", "gp_paths_own.h"), os.path.join(PKG, "csrc", "gphip_sparse_paths.inc"),
-        os.path.join(PKG, "csrc", "gp_sparse_paths.h"),
+        os.path.join(PKG, "csrc", "gp_sparse_paths.h"), os.path.join(PKG, "csrc", "gphip_paths_mix.inc"),
+        os.path.join(PKG, "csrc", "gp_paths_mix.h"),
         os.path.join(os.path.dirname(PKG), "include", "gphip.h")]
 LIB = os.path.join(PKG, "lib", "libgphip.so")
 

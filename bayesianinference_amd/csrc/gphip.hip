@@ -308,6 +308,11 @@ struct gphip_ctx {
     int paths_create_us = 0, paths_feature_us = 0, paths_subst_us = 0, paths_eval_us = 0;
     // read-only: gphip_paths_eval_own's strips of the contraction over the training points and host microseconds (last call)
     int paths_own_nsplit = 0, paths_own_us = 0;
+    // gphip_paths_create_samples (gphip_paths_mix.inc).  Options: rows per group (0 = by the slot rule of gphip_predict_samples);
+    // rows a workgroup of paths_mix_kernel may stage in LDS (-1 = by the staging rule, 0 = never: every workgroup reads its rows
+    // from global memory).  Read-only: the last call's rows per group, groups and host microseconds.
+    int paths_mix_slots = 0, paths_mix_stage = -1;
+    int paths_mix_slots_last = 0, paths_mix_groups = 0, paths_mix_create_us = 0;
 };
 
 namespace {
@@ -1774,15 +1779,20 @@ void queue_forward_slots(gphip_ctx* h, int64_t mpad, int nb, bool resident, bool
 
 // V <- V L^-1 (backward substitution, block columns from last to first), "NN" GEMM role:
 //   X_b = Y_b W_b ;  Y_c -= X_b L(b,c) for c < b.   Two-level as above.  rows: the mpad x Npad block to work on (null: dV).
+// nslots > 1 (gphip_paths_create_samples): the mpad x Npad blocks of nslots slots, one behind the other in rows, each with its
+// own slot's factor and block inverses (slot = the launches' second grid index, as in the forward substitution); the refined
+// form is for one slot.  nslots = 1: the launches are what they were, every slot stride zero.
 // Ld / res given: every diagonal solve is REFINED once in the working precision, X_b += (Y_b - X_b L_bb) W_b.  A product with
 // the explicit inverse W_b has a forward error of cond(L_bb) u but not the small residual of a substitution; one step restores
 // it (Skeel).  Ld: [Nt][128 x 128] scratch for the diagonal tiles with a zero upper triangle, res: mpad x 128 scratch.
 template <typename T>
-int queue_backward_rows(gphip_ctx* h, int64_t mpad, void* rows = nullptr, void* Ld = nullptr, void* res = nullptr) {
+int queue_backward_rows(gphip_ctx* h, int64_t mpad, void* rows = nullptr, void* Ld = nullptr, void* res = nullptr, int nslots = 1) {
     const int Nt = (int)h->Nt, Mt = (int)(mpad / TB), P = (Mt >= 8 && h->panel_wide) ? std::max(h->panel, 12) : h->panel;
     T *V = rows ? (T*)rows : (T*)h->dV.p, *W = (T*)h->dW.p, *L = (T*)Ld, *Rs = (T*)res;
-    const bool refine = L && Rs;
+    const bool refine = L && Rs, many = nslots > 1;
+    if (refine && many) return fail(h, GPHIP_ERR_ARG, "the refined backward substitution serves one slot");
     const long blk = (long)mpad * TB;            // elements of one block column of V
+    const long vs = many ? (long)mpad * h->Npad : 0l, lrs = many ? (long)Nt * TB * TB : 0l;      // elements between the slots' V and W
     if (refine)
         hipLaunchKernelGGL(diag_tiles_lower_kernel<T>, dim3((unsigned)Nt), dim3(256), 0, h->cs,
                            (const T*)(h->ws_override ? h->ws_override : h->dA.p), (int)h->R, L);
@@ -1791,7 +1801,7 @@ int queue_backward_rows(gphip_ctx* h, int64_t mpad, void* rows = nullptr, void* 
         for (int b = k1 - 1; b >= k0; --b) {
             T* Vb = V + (long)b * blk;
             if (refine) HIPCHK(hipMemcpyAsync(Rs, Vb, (size_t)blk * sizeof(T), hipMemcpyDeviceToDevice, h->cs));
-            launch_gemm<T>(h, 6, cm<T>(V, mpad, 0), cm<T>(Vb, mpad, 0), cm<T>(W, TB, 0), TB, 0, Mt, b, b + 1, 0, 1, 1);
+            launch_gemm<T>(h, 6, cm<T>(V, mpad, vs), cm<T>(Vb, mpad, vs), cm<T>(W, TB, lrs), TB, 0, Mt, b, b + 1, 0, nslots, 1);
             if (refine) {                       // res = Y_b - X_b L_bb ;  res <- res W_b ;  X_b += res
                 launch_gemm<T>(h, 6, cm<T>(Rs, mpad, 0), cm<T>(Vb, mpad, 0), cm<T>(L + (long)b * TS, TB, 0), TB, 0, Mt, 0, 1, 0, 1, 0);
                 launch_gemm<T>(h, 6, cm<T>(Rs, mpad, 0), cm<T>(Rs, mpad, 0), cm<T>(W + (long)b * TS, TB, 0), TB, 0, Mt, 0, 1, 0, 1, 1);
@@ -1800,12 +1810,12 @@ int queue_backward_rows(gphip_ctx* h, int64_t mpad, void* rows = nullptr, void* 
                 hipLaunchKernelGGL(add_rows_kernel<T>, dim3(gx), dim3(256), 0, h->cs, Vb, (const T*)Rs, blk);
             }
             if (b > k0)                         // (the J operand is L(b, c) read transposed: tile (b, c) of the workspace)
-                launch_gemm<T>(h, 6, cm<T>(V, mpad, 0), cm<T>(Vb, mpad, 0), tl<T>(h, b, false), TB, 0, Mt, k0, b,
-                               0, 1, 0);
+                launch_gemm<T>(h, 6, cm<T>(V, mpad, vs), cm<T>(Vb, mpad, vs), tl<T>(h, b, many), TB, 0, Mt, k0, b,
+                               0, nslots, 0);
         }
         if (k0 > 0)                             // Y_c -= X[:, k0..k1) L(k0..k1, c) for every c < k0
-            launch_gemm<T>(h, 6, cm<T>(V, mpad, 0), cm<T>(V + (long)k0 * TB * mpad, mpad, 0), tl<T>(h, k0, false), (k1 - k0) * TB, 0,
-                           Mt, 0, k0, 0, 1, 0);
+            launch_gemm<T>(h, 6, cm<T>(V, mpad, vs), cm<T>(V + (long)k0 * TB * mpad, mpad, vs), tl<T>(h, k0, many), (k1 - k0) * TB, 0,
+                           Mt, 0, k0, 0, nslots, 0);
     }
     return 0;
 }
@@ -3793,6 +3803,9 @@ int* option_slot(gphip_ctx* h, const char* name) {
         {"last_paths_create_us", &gphip_ctx::paths_create_us}, {"last_paths_feature_us", &gphip_ctx::paths_feature_us},
         {"last_paths_subst_us", &gphip_ctx::paths_subst_us}, {"last_paths_eval_us", &gphip_ctx::paths_eval_us},
         {"last_paths_own_nsplit", &gphip_ctx::paths_own_nsplit}, {"last_paths_own_us", &gphip_ctx::paths_own_us},
+        {"paths_mix_slots", &gphip_ctx::paths_mix_slots}, {"paths_mix_stage", &gphip_ctx::paths_mix_stage},
+        {"last_paths_mix_slots", &gphip_ctx::paths_mix_slots_last}, {"last_paths_mix_groups", &gphip_ctx::paths_mix_groups},
+        {"last_paths_mix_create_us", &gphip_ctx::paths_mix_create_us},
     };
     // fault injection ("debug_*") exists for the test-suite only: the names resolve in a process that was started with
     // GPHIP_TEST_HOOKS=1 and nowhere else (not through GPHIP_OPTIONS either: apply_env_options skips them)
@@ -3905,4 +3918,5 @@ int gphip_sync(gphip_handle h) {
 #include "gphip_xgrad.inc"
 #include "gphip_sparse.inc"
 #include "gphip_paths.inc"
+#include "gphip_paths_mix.inc"     // (behind gphip_paths.inc: a mixture object is a gphip_paths; its evaluation is declared there)
 #include "gphip_sparse_paths.inc"  // (behind gphip_paths.inc: a sparse paths object is a gphip_paths)

@@ -15,6 +15,8 @@
 //   eval_own per chunk of points per draw: paths_own_kernel (gp_paths_own.h; a thread owns one (draw, point) pair) over the
 //            features, then over the training points, paths_own_finish_kernel, one download.  With dout the GRAD form leaves the
 //            value and the d gradient components of a pair from one generator evaluation; the value is summed in the same order.
+// A mixture object (gphip_paths_create_samples, gphip_paths_mix.inc: draws over R hyper-parameter rows) is a gphip_paths too;
+// eval and eval_own hand it to paths_mix_eval, everything else here serves it as it is.
 // The object owns device copies of all it needs (raw X, 1 / l, slot scalars, Omega, b, Wa, w, eps, v): a later fit of the parent at
 // another theta does not touch it.  It borrows the parent's device, stream and mutex and must be destroyed before the parent.
 #include "gp_paths.h"
@@ -39,6 +41,13 @@ struct gphip_paths {
     Buf dXi, dZeta;                                 // double [S][N], [S][N]: the unit normals of a sparse paths object
     Buf dV;                                         // typed [Npad][Spad]: v
     Buf dPartF, dPartK, dXs, dOut, dDout, dFlag;    // scratch of a call
+    // a mixture object (gphip_paths_mix.inc): draw s belongs to hyper-parameter row row_of[s] of R; the tables and every buffer
+    // that depends on theta hold R rows (omega [R][Ftot][d], dOmT [R][d][Ftot], dIe1 [R][d], dSlotp [R][SLOTP], ..)
+    bool mix = false;
+    int R = 1;
+    std::vector<int> row_of;                        // [S], non-decreasing
+    std::vector<double> mu_r;                       // [R] m_r (NaN for a failed row of the null kernel)
+    Buf dRowOf, dMu;                                // int [S], double [R]
 };
 
 namespace {
@@ -119,6 +128,17 @@ int queue_paths_contract(gphip_paths* q, bool kernel, bool grad, const double* x
 #undef PATHS_DW
 #undef PATHS_GO
     return GPHIP_OK;
+}
+
+// a mixture object's evaluation (gphip_paths_mix.inc): shared = all draws at the same M points, else every draw at its own
+int paths_mix_eval(gphip_paths* q, const double* X, int64_t M, bool shared, double* out, double* dout);
+
+// the null kernel's answer, f = m (a mixture object: m of the draw's row), gradients 0
+void paths_null_eval(const gphip_paths* q, int64_t M, double* out, double* dout) {
+    for (int s = 0; s < q->S; ++s)
+        for (int64_t t = 0; t < M; ++t) out[(int64_t)s * M + t] = q->mix ? q->mu_r[(size_t)q->row_of[(size_t)s]] : q->mu;
+    if (dout)
+        for (int64_t e = 0; e < (int64_t)q->S * M * q->d; ++e) dout[e] = 0.0;
 }
 
 int paths_us(std::chrono::steady_clock::time_point t0) {
@@ -412,11 +432,10 @@ int gphip_paths_eval(gphip_paths_handle q, const void* Xs, int64_t M, double* ou
     if (M < 1) return paths_ret(q, fail(h, GPHIP_ERR_DIM, "M < 1"));
     PathsLock lk(q);
     if (q->null_k) {
-        for (int64_t e = 0; e < (int64_t)q->S * M; ++e) out[e] = q->mu;
-        if (dout)
-            for (int64_t e = 0; e < (int64_t)q->S * M * q->d; ++e) dout[e] = 0.0;
+        paths_null_eval(q, M, out, dout);
         return GPHIP_OK;
     }
+    if (q->mix) return paths_ret(q, paths_mix_eval(q, static_cast<const double*>(Xs), M, true, out, dout));
     const auto t0 = std::chrono::steady_clock::now();
     const int rc = DISPATCH(h, paths_eval_device, q, static_cast<const double*>(Xs), M, out, dout);
     h->paths_eval_us = paths_us(t0);
@@ -430,11 +449,10 @@ int gphip_paths_eval_own(gphip_paths_handle q, const void* Xs, int64_t M, double
     if (M < 1) return paths_ret(q, fail(h, GPHIP_ERR_DIM, "M < 1"));
     PathsLock lk(q);
     if (q->null_k) {
-        for (int64_t e = 0; e < (int64_t)q->S * M; ++e) out[e] = q->mu;
-        if (dout)
-            for (int64_t e = 0; e < (int64_t)q->S * M * q->d; ++e) dout[e] = 0.0;
+        paths_null_eval(q, M, out, dout);
         return GPHIP_OK;
     }
+    if (q->mix) return paths_ret(q, paths_mix_eval(q, static_cast<const double*>(Xs), M, false, out, dout));
     const auto t0 = std::chrono::steady_clock::now();
     const int rc = DISPATCH(h, paths_eval_own_device, q, static_cast<const double*>(Xs), M, out, dout);
     h->paths_own_us = paths_us(t0);
@@ -454,6 +472,7 @@ int gphip_paths_get(gphip_paths_handle q, double* omega, double* phase, double* 
     if (!q) return GPHIP_ERR_ARG;
     gphip_ctx* h = q->h;
     PathsLock lk(q);
+    if (q->mix && (omega || phase)) return fail(h, GPHIP_ERR_ARG, "a mixture object's tables are per row: gphip_paths_get_table");
     if (q->null_k) return GPHIP_OK;                 // no features, no weights: nothing to copy (Ftot = 0)
     if (omega) memcpy(omega, q->omega.data(), q->omega.size() * 8);
     if (phase) memcpy(phase, q->phase.data(), q->phase.size() * 8);

@@ -795,7 +795,8 @@ class posteriorFunctionSamples:
         self.close()
 
 
-def samplePathsFromGaussianProcess(obj_or_examples, n: int, kernel=None, theta=None, meanFunction=None, Features: int = 1024, seed: int = 0):
+def samplePathsFromGaussianProcess(obj_or_examples, n: int, kernel=None, theta=None, meanFunction=None, Features: int = 1024, seed: int = 0,
+                                   Batched: bool = False):
     """n pathwise draws of the latent posterior function (gphip_paths_create; no reference counterpart) that can be evaluated at
     any points, and differentiated, after they have been drawn: Thompson sampling, optimum-location sampling.  Two forms, as
     predictFromGaussianProcess:
@@ -805,6 +806,11 @@ def samplePathsFromGaussianProcess(obj_or_examples, n: int, kernel=None, theta=N
       samplePathsFromGaussianProcess((X, Y), n, kernel, theta[, meanFunction])   the direct form.
     Features: random Fourier features per kernel term (the prior is approximated with error O(1 / sqrt(Features))).  Values come
     back in the units of the data ("DataPreProcessors" undone), gradients scaled accordingly.
+    Batched=True on a sampled object: the same draw-to-sample assignment and per-theta keys, but the distinct thetas (ascending
+    sample index) go with their counts and keys into ONE Handle.sample_paths_samples call (gphip_paths_create_samples: the
+    thetas factored together, no fit per theta), and the result has a single part: every evaluation, and every iteration of
+    maximize, is one device call.  Draw i is the same function as draw i of Batched=False, to rounding; the draws of a theta
+    that does not factor are NaN; the handle is left without a fit.  Ignored in the direct form.
     On a GP object the paths objects live on the object's own "HIPHandle": until the result's close() (or the end of its `with`
     block) that handle cannot be closed (Handle.close raises GphipError, status 4), and it is left fitted at the last theta
     used here, not at the theta it held before the call.  The direct form owns a handle of its own and closes it with the result.
@@ -826,15 +832,21 @@ def samplePathsFromGaussianProcess(obj_or_examples, n: int, kernel=None, theta=N
         points = np.array([s["Point"] for s in samples], dtype=np.float64)
         w = np.array([s["CrudePosteriorWeight"] for s in samples], dtype=np.float64)
         which = np.random.default_rng(seed).choice(len(samples), size=int(n), p=w / w.sum())
+        used = np.unique(which)                                          # the distinct thetas, ascending sample index
+        keys = [int(np.random.SeedSequence([int(seed) & (2**63 - 1), int(k)]).generate_state(1, np.uint64)[0]) for k in used]
+        rows = [np.flatnonzero(which == k) for k in used]
         parts = []
-        for k in np.unique(which):
-            rows = np.flatnonzero(which == k)
-            if handle.fit(points[k]) != 0:
-                continue
-            key = int(np.random.SeedSequence([int(seed) & (2**63 - 1), int(k)]).generate_state(1, np.uint64)[0])
-            paths = handle.sample_paths(len(rows), int(Features), key)
+        if Batched:                                                      # one mixture object; its draws are ordered theta by theta
+            paths = handle.sample_paths_samples(points[used], [len(r) for r in rows], keys, int(Features))
             if paths is not None:
-                parts.append((rows, paths))
+                parts.append((np.concatenate(rows), paths))
+        else:
+            for k, key, r in zip(used, keys, rows):
+                if handle.fit(points[k]) != 0:
+                    continue
+                paths = handle.sample_paths(len(r), int(Features), key)
+                if paths is not None:
+                    parts.append((r, paths))
         inverse, scale = _output_scale(obj)
         res = posteriorFunctionSamples(parts, n, handle.d, inverse, scale)
         res.sample = which
@@ -891,12 +903,13 @@ def _ascend_batched(fg, X0, lo, hi, iterations, trace=None):
 
 
 def thompsonSampleFromGaussianProcess(obj_or_examples, n: int, bounds, kernel=None, theta=None, meanFunction=None, Features: int = 1024,
-                                      seed: int = 0, **maximize_options):
+                                      seed: int = 0, Batched: bool = False, **maximize_options):
     """Thompson sampling in one call: n pathwise draws of the latent posterior function (samplePathsFromGaussianProcess, both
     forms) and the maximiser of each over the box `bounds` (posteriorFunctionSamples.maximize(bounds, seed=seed,
     **maximize_options)); the draws are released before it returns.  {"x" [n, d], "f" [n], "sample" [n]} in data units, or None
-    wherever samplePathsFromGaussianProcess returns None."""
-    draws = samplePathsFromGaussianProcess(obj_or_examples, n, kernel, theta, meanFunction, Features, seed)
+    wherever samplePathsFromGaussianProcess returns None.  Batched=True on a sampled object: one mixture paths object over all
+    thetas used (samplePathsFromGaussianProcess), so one creation call and one evaluation call per ascent step."""
+    draws = samplePathsFromGaussianProcess(obj_or_examples, n, kernel, theta, meanFunction, Features, seed, Batched=Batched)
     if draws is None:
         return None
     with draws:

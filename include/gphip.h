@@ -377,6 +377,46 @@ int gphip_paths_eval_own(gphip_paths_handle q, const void* Xs /* row-major S x M
 int gphip_paths_shape(gphip_paths_handle q, int* S, int64_t* Ftot, int64_t* N, int64_t* d);
 int gphip_paths_get(gphip_paths_handle q, double* omega, double* phase, double* w, double* eps, double* v);
 int gphip_paths_destroy(gphip_paths_handle q);
+/* ---- Pathwise draws over all posterior samples in one object: a MIXTURE paths object is an ordinary
+ * gphip_paths_handle whose S draws each belong to one of R hyper-parameter rows, created in ONE call from the R x p array Thetas.
+ * S = sum counts; the draws are ordered by row (row 0's counts[0] draws first, then row 1's, ..).  Draw number q of row r is BY
+ * DEFINITION draw q of gphip_paths_create(h fitted at Thetas[r], counts[r], F, seeds[r]): the same table gphip_rff_table(theta_r,
+ * F, seeds[r]) byte for byte, the same w and eps bytes (Philox keyed by (seeds[r], q, j) and by the eps key of seeds[r]); v and
+ * every evaluated value agree with that object to rounding (several slots are factored by another schedule).  The rows with
+ * draws are factored together in groups that fit the workspace slots (as gphip_predict_samples; one factorisation per row, never
+ * one per draw), both substitutions run for all slots of a group at once.
+ * Rows: a row with counts[r] = 0 is not factored, info[r] = 0.  A row that fails (a non-finite theta, a K that does not factor:
+ * info[r] as gphip_loglik_batch's, or GPHIP_INFO_NAN for a non-finite v) sets only its own info[r]; its draws evaluate to NaN,
+ * values and gradients; the other rows' bytes are those of the call with a valid theta in its place.  *out is NULL (status
+ * GPHIP_OK) only when every row with draws failed.
+ * Statuses, all decided before any device work: GPHIP_ERR_ARG any NULL pointer; GPHIP_ERR_DIM a wrong p, R < 1, a negative
+ * count, S < 1, S > 2048, F < 1, Ftot S > 2^26, R Ftot d > 2^27 (1 GiB of per-row tables), S N >= 2^31; GPHIP_ERR_UNSUPPORTED a
+ * run-time compiled covariance function, a point-dependent nugget or mean array set on the handle.  The null kernel is answered
+ * on the host (f = m_r, gradients 0).  A multi-device handle computes on its first device.
+ * The call drops any resident fit, as gphip_predict_samples does (gphip_predict then returns GPHIP_ERR_STATE).  The object owns
+ * all it needs, so later fits do not touch it; it borrows the parent's device, stream and mutex and blocks gphip_destroy of the
+ * parent exactly as ordinary paths objects do.
+ * On a mixture object gphip_paths_eval (all draws at the same M points), gphip_paths_eval_own (S x M x d points), _shape (Ftot
+ * is the same for every row: it depends on the kernel's structure and F only) and _destroy work as on any paths object.  Both
+ * evaluations go through ONE kernel (paths_mix_kernel: a thread owns one (draw, point) pair, fp64 sums in the order of the
+ * contraction index, strips added in a fixed order, no atomics): out is the same bytes with and without dout, two calls return
+ * the same bytes, and gphip_paths_eval(P) returns the bytes of gphip_paths_eval_own on P broadcast to every draw.
+ * gphip_paths_get returns w, eps and v; asked for omega or phase it returns GPHIP_ERR_ARG: they are per row.
+ * gphip_paths_get_table(q, r, ..): row r's table, omega Ftot x d, phase Ftot, amp Ftot, each may be NULL; r outside [0, R)
+ * GPHIP_ERR_DIM.  gphip_paths_rows: R and, when row_of_draw is not NULL, the row of each of the S draws.  Both work on an
+ * ordinary (and a sparse-made) object too: R = 1, every draw in row 0.
+ * Options on the PARENT handle: "paths_mix_slots" n = at most n rows per group (0 = by the slot rule of gphip_predict_samples);
+ * "paths_mix_stage" n = at most n rows of a workgroup staged in LDS (-1 = by the staging rule of gp_paths_mix.h, 0 = every
+ * workgroup reads its rows from global memory; the same arithmetic on the same numbers); read-only "last_paths_mix_slots",
+ * "last_paths_mix_groups", "last_paths_mix_create_us" (rows per group, groups, host microseconds of the last creation);
+ * "paths_split" and "paths_chunk" act as for gphip_paths_eval_own, in both evaluations.
+ * Not offered: the sparse object, run-time compiled covariance functions, point-dependent fits, dealing rows to several devices,
+ * device-resident inputs and outputs, a device-resident ascent loop. */
+int gphip_paths_create_samples(gphip_handle h, const double* Thetas /* row-major R x p */, int R, int p,
+                               const int* counts /* R, each >= 0 */, const uint64_t* seeds /* R */, int F,
+                               gphip_paths_handle* out, int* info /* R */);
+int gphip_paths_rows(gphip_paths_handle q, int* R, int* row_of_draw /* S, or NULL */);
+int gphip_paths_get_table(gphip_paths_handle q, int r, double* omega /* Ftot x d */, double* phase, double* amp /* Ftot; each may be NULL */);
 /* ---- Leave-one-out cross-validation (Rasmussen & Williams, GPML section 5.4.2; no reference counterpart): how well the model
  * at theta predicts every training point from the other N - 1, from ONE factorisation.  With alpha = K^-1 (y - m) and
  * k_i = [K^-1]_ii:
