@@ -128,6 +128,7 @@ _SIGNATURES = {
                                         C.POINTER(C.c_int64), _dp, C.POINTER(C.c_int64)]),
     "gphip_ns_crude_weights": (C.c_int, [_dp, _dp, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64), _dp, _dp, _dp]),
     "gphip_factor_bytes": (C.c_int, [_h, C.c_int, _dp]),
+    "gphip_factor_get": (C.c_int, [_h, _dp, _dp, _dp]),
     "gphip_set_streams": (C.c_int, [_h, C.c_void_p, C.c_void_p]),
     "gphip_dist_num_panels": (C.c_int, [_h, _ip]),
     "gphip_dist_panel_shape": (C.c_int, [_h, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
@@ -843,6 +844,15 @@ class Handle:
         v = C.c_double(0.0)
         self._check(self._lib.gphip_factor_bytes(self._h, member, C.byref(v)))
         return v.value
+
+    def factor(self, winv: bool = False):
+        """gphip_factor_get (diagnostics): the resident factor as (L[N, N] lower triangular, z[N] = L^-1 (y - mean)); winv=True adds
+        W[Nt, 128, 128] with W[b, i, j] = element (i, j) of the inverse of the b-th 128 x 128 diagonal block of the padded factor
+        (the library keeps these blocks column-major; this is the transposed view of its bytes)."""
+        L, z = np.zeros((self.N, self.N)), np.zeros(self.N)
+        W = np.zeros(((self.N + 127) // 128, 128, 128)) if winv else None
+        self._check(self._lib.gphip_factor_get(self._h, _d(L), _d(z), _d(W) if winv else None))
+        return (L, z, W.transpose(0, 2, 1)) if winv else (L, z)
 
     # -- multi-GPU block-cyclic Cholesky steps (driven by dist_cholesky.py) ---------------
     def set_streams(self, main_stream: int, panel_stream: int):

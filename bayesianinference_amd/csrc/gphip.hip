@@ -268,6 +268,7 @@ struct gphip_ctx {
     int lay_rank = -1, lay_world = 0, lay_panel = 0, lay_full = -1;   // what dist_adj / dOwn were laid out for
     void* ws_override = nullptr;                 // tl<T>() / queue_panel address this base instead of dA (one owned panel; per call, Scoped)
     bool dist_fit = false;                       // the factor of theta_fit is spread over the ranks (owned panels only)
+    bool shard_fit = false;                      // the resident fit came from a sharded factorisation (whole here or not: gphip_factor_get)
     Buf dZ;                                      // typed [Npad]: z = L^-1 r gathered while the panels stream by (sharded prediction)
     bool null_fit = false;                       // fitted state of a null-kernel handle (no factor: K = diag(sn^2))
     // Point-dependent nugget / mean of the CURRENT call (gphip_*_pw, BGP:37, 113, 300, 408): host rows [B][N] (training
@@ -2395,7 +2396,7 @@ void stamp_fit(gphip_ctx* h) {
 void record_fit(gphip_ctx* h, bool ok, const double* theta, int p, double logdet) {
     h->fitted = ok;
     h->fit_pw = h->pw_mean_host || h->pw_nug_host;
-    h->dist_fit = false;
+    h->dist_fit = h->shard_fit = false;
     stamp_fit(h);
     h->theta_fit.assign(theta, theta + p);
     h->logdet_fit = logdet;
@@ -3458,7 +3459,7 @@ int gphip_solve(gphip_handle h, const double* rhs, int64_t nrhs, double* out) {
         if (info != 0) return fail(h, GPHIP_ERR_STATE, "the fitted theta no longer factors");
         h->fitted = true;                      // now a LOCAL fit of the same theta (logdet_fit / mu_fit / kappa_fit unchanged)
         stamp_fit(h);
-        h->dist_fit = false;
+        h->dist_fit = h->shard_fit = false;
     }
     if (h->null_fit) {                         // "Inverse" -> Function[Divide[#, matrixDiagonal]]  (BGP:156-159)
         for (int64_t i = 0; i < nrhs * h->N; ++i)
@@ -3895,6 +3896,35 @@ int gphip_factor_bytes(gphip_handle h, int member, double* bytes) {
     double b = (double)m->dA.bytes + (double)m->dOwn.bytes;
     for (const Buf& pk : m->packed) b += (double)pk.bytes;
     *bytes = b;
+    return GPHIP_OK;
+}
+
+// The resident factor of slot 0, its bordered row and its 128-block inverses (include/gphip.h): diagnostics, one download each.
+int gphip_factor_get(gphip_handle h, double* L, double* z, double* Winv) {
+    if (!h || !L) return fail(h, GPHIP_ERR_ARG, "null argument");
+    std::lock_guard<std::recursive_mutex> lk(h->mu);
+    if (!has_fit(h)) return fail(h, GPHIP_ERR_STATE, "gphip_factor_get before a successful gphip_fit");
+    if (h->null_fit || h->kernel_id == GPHIP_KERNEL_NULL) return fail(h, GPHIP_ERR_STATE, "gphip_factor_get: the null kernel has no factor");
+    if (h->dist_fit || h->shard_fit || h->dist_world != 0)
+        return fail(h, GPHIP_ERR_STATE, "gphip_factor_get: the factor of a sharded fit is not read out");
+    if (!h->dA.p || (Winv && !h->dW.p)) return fail(h, GPHIP_ERR_STATE, "gphip_factor_get: no resident workspace");
+    HIPCHK(hipSetDevice(h->device));
+    const int64_t N = h->N;
+    // the lower-triangle tiles of the packed workspace, exactly as gphip_covariance reads K (tile row Nt = the bordered rows)
+    std::vector<double> tmp;
+    int rc = DISPATCH(h, download, h, tmp, h->dA.p, (size_t)h->slot_elems, h->stream);
+    if (rc) return rc;
+    for (int64_t i = 0; i < N; ++i)
+        for (int64_t j = 0; j < N; ++j)
+            L[i * N + j] = j > i ? 0.0
+                                 : tmp[(size_t)tile_index((int)(i / TB), (int)(j / TB), (int)h->R) * TS + (size_t)(j % TB) * TB + (size_t)(i % TB)];
+    if (z)
+        for (int64_t j = 0; j < N; ++j) z[j] = tmp[(size_t)tile_index((int)h->Nt, (int)(j / TB), (int)h->R) * TS + (size_t)(j % TB) * TB];
+    if (Winv) {
+        rc = DISPATCH(h, download, h, tmp, h->dW.p, (size_t)h->Nt * TS, h->stream);
+        if (rc) return rc;
+        memcpy(Winv, tmp.data(), (size_t)h->Nt * TS * 8);
+    }
     return GPHIP_OK;
 }
 

@@ -635,6 +635,7 @@ int group_eval_run(gphip_ctx* h, const double* theta, int p, bool keep, double* 
             record_fit(m, true, theta, p, logdet);
             m->fit_id = g->fit_id;
             m->dist_fit = g->replicate == 0;
+            m->shard_fit = true;
             m->fit_rank = g->ranks[i]; m->fit_world = W;
         }
         g->in_sharded_fit = false;

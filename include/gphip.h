@@ -657,6 +657,21 @@ int gphip_dist_end(gphip_handle h, double* logdet_partial, double* quad, int* in
 /* Device memory (bytes) local rank `member` of the handle holds for factor storage right now: dense workspace slots +
  * compact own-panel storage + receive buffers (diagnostics: a sharded evaluation keeps ~1 / world of the workspace). */
 int gphip_factor_bytes(gphip_handle h, int member, double* bytes);
+/* The resident factor itself (diagnostics and tests, off every hot path: one download of slot 0 of the workspace, untiled on the
+ * host as gphip_covariance does; fp32 handles are widened).  After a successful fit -- gphip_fit[_pw], or a call that leaves the
+ * factor of its theta resident: gphip_loglik_grad, gphip_loo[_grad], gphip_extend's new handle --
+ *   L    row-major N x N: the Cholesky factor, L L^T = K(theta_fit); the strict upper triangle is written as zeros.
+ *   z    N values or NULL: the bordered row (tile row Nt of the workspace, row N_pad) as the factorisation left it,
+ *        z = L^-1 (y - mean).
+ *   Winv Nt x 128 x 128 values (Nt = ceil(N / 128)) or NULL: the inverses W_b = L_bb^-1 of the 128 x 128 diagonal blocks that the
+ *        substitutions multiply by, block b at Winv + b * 128 * 128, COLUMN-major inside the block as the device keeps them
+ *        (element (i, j) of W_b at j * 128 + i), the upper triangle zero.  The last block is that of the padded matrix: rows and
+ *        columns beyond N carry the identity.  Every route a local fit can take leaves these blocks resident (the 64-tile
+ *        launches rebuild them from L), so a non-NULL Winv is answered wherever L is.
+ * GPHIP_ERR_STATE: no successful fit is resident; the null kernel (no factor: K is diagonal); a fit whose factor is not whole in
+ * this context's dense workspace -- one sharded over a multi-device handle's ranks, whatever replicate_factor says, and anything
+ * between gphip_dist_begin and gphip_dist_end.  Takes the handle's mutex, uses the main stream only, leaves the fit valid. */
+int gphip_factor_get(gphip_handle h, double* L, double* z, double* Winv);
 
 /* ---- Sparse inducing-point GP: the collapsed variational bound of Titsias (2009), "SGPR"; no reference equivalent.
  * For data sizes the exact path cannot hold: m << N inducing points Z, a lower bound F(theta) <= log p(y | X, theta) that costs
